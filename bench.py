@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — candidate sites/sec (tensor build + inference) on synthetic ONT dRNA004 chr20 ~20x.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only.  --full adds the other figures of the line: the CPU baseline, the resident-input and other-precision
+rates, the per-kernel profile with its rooflines and, at N = 1, the other BASELINE.json configurations (each can be left out with its --no_* option).
+--dump-outputs DIR writes what the last timed step handed back, for comparing two builds output for output (dump_outputs).
 
 One "step" = one full pass of the hot path over one synthetic chr20 (BASELINE.json configs[1]), as SURVEY.md 8(d) defines
 the metric: from the contig's aligned-read records RESIDENT IN HOST MEMORY (flat c3r_read_t records, BAM-encoded CIGARs, 4-bit
@@ -130,6 +134,27 @@ def phase1_bytes(rs, channels, min_mq=5, excl_flags=2316):
     keep = ok[rid] & ((op == 0) | (op == 2) | (op == 7) | (op == 8)) & (ln > 0)
     aligned = union(start[keep], start[keep] + ln[keep])
     return float(in_bytes + 4 * channels * aligned), aligned, covered
+
+
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: array bytes per run (below 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, suffix, probs, pos=None, budget=DUMP_BYTES):
+    """--dump-outputs: the [n, 24] probabilities of one pass as <out_dir>/probs<suffix>.npy (float32) and, when given, their sites'
+    1-based positions as site_pos<suffix>.npy (float64).  Rows beyond `budget` bytes: a fixed seeded sample of them, kept in order,
+    whose row numbers go to sample_rows<suffix>.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    probs = np.asarray(probs, np.float32).reshape(-1, 24)
+    row_bytes = probs.itemsize * 24 + (8 if pos is not None else 0)
+    rows = None
+    if len(probs) * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(len(probs), budget // (row_bytes + 8), replace=False))
+        probs, pos = probs[rows], (None if pos is None else np.asarray(pos)[rows])
+    np.save(os.path.join(out_dir, "probs%s.npy" % suffix), probs)
+    if pos is not None:
+        np.save(os.path.join(out_dir, "site_pos%s.npy" % suffix), np.asarray(pos, np.float64))
+    if rows is not None:
+        np.save(os.path.join(out_dir, "sample_rows%s.npy" % suffix), rows.astype(np.float64))
 
 
 def chunk_list(contig_len, chunk=CHUNK):
@@ -409,25 +434,33 @@ def run_strong(args, rank, local_rank, world, one_gpu, emit=True):
         e.set_params(); e.load_weights(weights, 18); e.set_precision(args.precision)
         engs.append(e)
 
-    def run_steps(k):
-        total, pending, ne = 0, [None] * len(engs), len(engs)
+    outs = {}                  # contig index -> probabilities of the last step of a run_steps(k, keep=True)
+
+    def run_steps(k, keep=False):
+        total, pending, ne = 0, [None] * len(engs), len(engs)       # pending[j]: (step, contig, sites) of context j's unfetched pass
         i = 0
-        for _ in range(k):
-            for (_ci, ref, rs, chunks, _info) in data:
+
+        def fetch(j):
+            s, ci, n = pending[j]
+            p = engs[j].fetch_probs(n)
+            if keep and s == k - 1:
+                outs[ci] = p
+        for s in range(k):
+            for (ci, ref, rs, chunks, _info) in data:
                 j = i % ne; i += 1
                 e = engs[j]
                 if pending[j]:
-                    e.fetch_probs(pending[j])
+                    fetch(j)
                 e.set_reference(1, ref, upper_view=True)
                 e.load_reads(rs)
                 e.begin_batch(); n = e.scan_regions(chunks); e.end_batch()
                 if n:
                     e.infer(fetch=False)
-                pending[j] = n
+                pending[j] = (s, ci, n) if n else None
                 total += n
         for j in range(ne):
             if pending[j]:
-                engs[j].fetch_probs(pending[j])
+                fetch(j)
         return total
 
     def barrier():
@@ -441,11 +474,16 @@ def run_strong(args, rank, local_rank, world, one_gpu, emit=True):
     run_steps(max(args.warmup, 0))
     barrier()
     t0 = time.perf_counter()
-    sites = run_steps(args.steps)
+    sites = run_steps(args.steps, keep=bool(args.dump_outputs))
     for e in engs:
         e.synchronize()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # one file per contig (each rank writes its own); the byte budget is shared out by contig length
+        for ci in mine:
+            dump_outputs(args.dump_outputs, "_" + names[ci], outs.get(ci, np.zeros((0, 24), np.float32)),
+                         budget=DUMP_BYTES * lens[ci] // sum(lens))
     loads = [sum(lens[i] for i in p) for p in plan]
     my_reads = float(sum(info["n_reads"] for (_ci, _r, _rs, _ch, info) in data))
     reads_max, reads_sum = my_reads, my_reads
@@ -510,7 +548,13 @@ def main():
                     help="one context / one stream: tensor build and network strictly back to back")
     ap.add_argument("--precision", choices=["f16x3", "f32", "f16+f8", "auto"], default="f16x3",
                     help="network GEMM arithmetic: split-f16 (fp32-equivalent, default) or fp32 MFMA")
+    ap.add_argument("--full", action="store_true", help="also every additional measurement of the line (the --no_* options leave some out); "
+                                                        "without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the probabilities (and site positions) of the last "
+                                                          "timed step as DIR/*.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile = args.no_resident = args.no_f32 = args.no_fast = args.no_strong = args.no_extra = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -565,14 +609,14 @@ def main():
         return total
 
     host_inputs = [True]     # False: the `resident_inputs` measurement (read tables prepared once, outside the timed region)
+    last = {}                # the context that ran the latest pass and the probabilities it handed back (--dump-outputs)
 
     def one_step():
         # ... and go through the network in ONE launch per layer (batch mode); probabilities come back to the host
         if host_inputs[0]:
             eng.load_reads(rs_host)
         total = tensor_build(eng)
-        if total:
-            eng.infer()
+        last.update(eng=eng, probs=eng.infer() if total else None)
         return total
 
     # Two contexts = two HIP streams on the same GPU: while context A runs the network of pass i, context B builds the
@@ -601,9 +645,13 @@ def main():
                 e.infer(fetch=False)
             pending[j] = n
             total += n
+        if k:
+            last.update(eng=engs[(k - 1) % ne], probs=None)
         for j in range(ne):
             if pending[j]:
-                engs[j].fetch_probs(pending[j])
+                p = engs[j].fetch_probs(pending[j])
+                if engs[j] is last.get("eng"):
+                    last["probs"] = p
         return total
 
     def barrier():
@@ -621,12 +669,20 @@ def main():
     barrier()
     run_steps(max(args.warmup, 0))
     barrier()
+    last.clear()
     t0 = time.perf_counter()
     sites = run_steps(args.steps)
     for e in engs:
         e.synchronize()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        probs = last.get("probs")
+        if probs is None:
+            probs, pos = np.zeros((0, 24), np.float32), np.zeros(0)
+        else:
+            pos = last["eng"].sites()["pos"]          # the context's resident batch is still that of its last pass
+        dump_outputs(args.dump_outputs, "_rank%d" % rank if world > 1 else "", probs, pos, budget=DUMP_BYTES // world)
     if dist is not None:
         dist.barrier()
         from clair3_rna_amd import shard
@@ -764,7 +820,7 @@ def main():
     if world == 1 and not args.no_strong and args.steps > 0:
         try:
             sa = argparse.Namespace(**vars(args))
-            sa.genome_scale, sa.steps, sa.warmup = 0.25, 1, 0
+            sa.genome_scale, sa.steps, sa.warmup, sa.dump_outputs = 0.25, 1, 0, None
             so = run_strong(sa, rank, local_rank, world, one_gpu, emit=False)
             strong = dict(value=so["value"], unit="sites/s", ms_per_step=so["ms_per_step"], workload=so["config"]["workload"], inputs=so["config"]["inputs"],
                           genome_bp=so["config"]["genome_bp"], sites_per_step=so["config"]["sites_per_step"], streams=so["config"]["streams"],

@@ -313,7 +313,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
         port = so.getsockname()[1]
     env = dict(os.environ, C3R_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--contig_len", "4000000"]
+           "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--contig_len", "4000000", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
@@ -324,6 +324,42 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     per_rank = j["config"]["sites_per_step_per_rank"]
     assert abs(j["value"] - 2 * per_rank / (j["ms_per_step"] / 1e3)) / j["value"] < 1e-3        # whole-job aggregate over both ranks
     assert j["roofline"]["kernel"] == "k_lstm2" and j.get("cpu_baseline") is None      # the CPU baseline is an N = 1 leg
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(eng, tmp_path):
+    """A plain `bench.py` run measures the headline only, and --dump-outputs writes the probabilities and site positions of its last
+    timed step: bitwise what one pass over the same seeded contig and weights gives in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from clair3_rna_amd import capi, synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    L, out = 4000000, str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--contig_len", str(L), "--dump-outputs", out],
+                       cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "sites/s" and j["higher_is_better"] is True
+    n = j["config"]["sites_per_step_per_rank"]
+    assert abs(j["value"] - n / (j["ms_per_step"] / 1e3)) / j["value"] < 1e-3
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["resident_inputs"] is None and j["strong_1gpu"] is None
+    assert sorted(os.listdir(out)) == ["probs.npy", "site_pos.npy"]
+    probs, pos = np.load(os.path.join(out, "probs.npy")), np.load(os.path.join(out, "site_pos.npy"))
+    assert probs.dtype == np.float32 and pos.dtype == np.float64 and probs.shape == (n, 24) and n > 1000
+
+    ref, rs, _ = synth.generate_contig(contig_len=L, seed=synth.SEED, depth=20.0)
+    eng.params = capi.default_params()
+    eng.set_bed(0, None); eng.set_bed(1, None)
+    eng.set_params()
+    eng.load_reads(rs); eng.set_reference(1, ref); eng.load_weights(synth.random_weights(18), 18); eng.set_precision("f16x3")
+    eng.begin_batch(); m = eng.scan_regions(bench.chunk_list(L)); eng.end_batch()
+    assert m == n
+    assert np.array_equal(eng.sites()["pos"], pos)
+    assert np.array_equal(eng.infer(), probs)
 
 
 def test_depth_cap_between_separate_deep_loci(eng):

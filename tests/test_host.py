@@ -181,6 +181,31 @@ def test_bin_counter_layout_is_a_permutation_that_keeps_groups_and_separates_nei
     assert out.returncode == 0 and out.stdout.startswith("cnt_at ok") and "giant slices ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_bench_dump_outputs_samples_within_its_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 probabilities and float64 positions, whole when they fit the byte budget; beyond it
+    the same seeded sample of rows, in order, run after run, with the row numbers beside it."""
+    import bench
+    rng = np.random.default_rng(3)
+    probs, pos = rng.random((50000, 24)), np.arange(50000) * 3 + 11
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), "", probs, pos)
+    assert sorted(os.listdir(whole)) == ["probs.npy", "site_pos.npy"]
+    p = np.load(whole / "probs.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, probs.astype(np.float32))
+    assert np.load(whole / "site_pos.npy").dtype == np.float64
+    budget = 10 ** 6
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "_x", probs, pos, budget=budget)
+        assert sorted(os.listdir(tmp_path / d)) == ["probs_x.npy", "sample_rows_x.npy", "site_pos_x.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= budget + 3 * 256
+    rows = np.load(tmp_path / "a" / "sample_rows_x.npy")
+    assert rows.dtype == np.float64 and len(rows) > 5000 and (np.diff(rows) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "probs_x.npy"), probs[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "site_pos_x.npy"), pos[rows.astype(np.int64)])
+    for f in ("probs_x.npy", "sample_rows_x.npy", "site_pos_x.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def test_phase1_bytes_counts_aligned_and_covered_positions():
     """bench.phase1_bytes (SURVEY 8d, phase 1): input records + C * 4 B per position with an aligned base or a deletion of a passing read;
     positions that reads only span with a ref-skip are counted apart; filtered reads count for the input bytes only."""

@@ -1,19 +1,21 @@
 #!/bin/bash
 # A/B of several builds of libc3r.so on one GPU box:  bash tools/ab_bench.sh "<alt1.so> <alt2.so> ..." [bench args]
-# Runs bench.py (no CPU baseline) alternately with the in-tree library and with C3R_LIB=<alt.so>, ROUNDS (default 2) times each.
+# Runs bench.py --full (no CPU baseline) alternately with the in-tree library and with C3R_LIB=<alt.so>, ROUNDS (default 2) times each;
+# the lines go to build/ab/.
 ALTS=$1; shift
 R=${GRAFT_REPO_ROOT:-.}
-rm -rf $R/gpurun_out/ab; mkdir -p $R/gpurun_out/ab
+OUT=$R/build/ab
+rm -rf $OUT; mkdir -p $OUT
 for i in $(seq 1 ${ROUNDS:-2}); do
-  python3 $R/bench.py --no_cpu_baseline "$@" > $R/gpurun_out/ab/main_$i.json 2> $R/gpurun_out/ab/main_$i.err
+  python3 $R/bench.py --full --no_cpu_baseline "$@" > $OUT/main_$i.json 2> $OUT/main_$i.err
   for a in $ALTS; do
     t=$(basename $a .so)
-    C3R_LIB=$R/$a python3 $R/bench.py --no_cpu_baseline "$@" > $R/gpurun_out/ab/${t}_$i.json 2> $R/gpurun_out/ab/${t}_$i.err
+    C3R_LIB=$R/$a python3 $R/bench.py --full --no_cpu_baseline "$@" > $OUT/${t}_$i.json 2> $OUT/${t}_$i.err
   done
 done
 python3 - <<PY
 import json,glob
-for f in sorted(glob.glob("$R/gpurun_out/ab/*.json")):
+for f in sorted(glob.glob("$OUT/*.json")):
     try:
         d=json.loads(open(f).read().strip().splitlines()[-1])
         k=d.get("kernels_ms_per_step",{})

@@ -22,8 +22,8 @@ rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_
 # the additional configurations of the default line (configs[3] 30 channels, configs[4] 500x, the 20,000x locus): their kernels by full
 # template name (k_fused_tiles<30>, k_lstm1_rs<30, ...>) next to the 18-channel ones
 if [ "$PREC" = f16x3 ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_extra -- python3 $R/bench.py --steps 2 --warmup 1 --no_cpu_baseline --no_profile --no_fast --no_f32 --no_resident --no_overlap --no_strong --precision $PREC > $OUT/stats_extra.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_extra -- python3 $R/bench.py --full --steps 2 --warmup 1 --no_cpu_baseline --no_profile --no_fast --no_f32 --no_resident --no_overlap --no_strong --precision $PREC > $OUT/stats_extra.log 2>&1
 fi
 unset C3R_DEEP_SERIAL
-python3 $R/bench.py --precision $PREC > $OUT/bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --precision $PREC > $OUT/bench.json 2> $OUT/bench.err
 ls -R $OUT | head -40
