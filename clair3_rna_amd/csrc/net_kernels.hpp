@@ -36,6 +36,7 @@
 namespace c3r {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int NET_H1 = 128;
 constexpr int NET_H2 = 160;
@@ -44,16 +45,16 @@ constexpr int NET_SITES = 32;              // sites per MFMA column block
 constexpr int LSTM_SB = 2;                 // column blocks per wavefront in k_lstm
 constexpr int LSTM_SITES = NET_SITES * LSTM_SB;
 #ifndef C3R_W8_PD
-#define C3R_W8_PD 1          // prefetch distance (k-groups) of k_lstm2_w8's operand ring
+#define C3R_W8_PD 1          // prefetch distance (k-groups / units) of the layer-2 kernels' operand ring
 #endif
 #ifndef C3R_W8_MAP
-#define C3R_W8_MAP 0         // k_lstm2_w8: which wavefronts pair up on a SIMD — 0: w and w+4 (round-robin placement; measured 19.3 ms), 1: 2w and 2w+1 (20.5 ms)
+#define C3R_W8_MAP 0         // layer 2: which wavefronts pair up on a SIMD — 0: w and w+4 (round-robin placement; measured 19.3 ms), 1: 2w and 2w+1 (20.5 ms)
 #endif
 #ifndef C3R_W8_PRIO
 #define C3R_W8_PRIO 0        // 1: s_setprio 1 for the 3-tile wavefronts, 2: for the 2-tile wavefronts
 #endif
 #ifndef C3R_DIR_ILV
-#define C3R_DIR_ILV 1        // k_lstm1_rs / k_lstm2_w8: grid (2, groups) — the two directions of a site group are dispatched back to back
+#define C3R_DIR_ILV 1        // k_lstm1_rs / layer 2: grid (2, groups) — the two directions of a site group are dispatched back to back
 #endif
 constexpr int NET_FLAT = NET_T * 2 * NET_H2;   // 10560
 constexpr int NET_L4 = 128;
@@ -318,7 +319,7 @@ __device__ __forceinline__ void sched_interleave() {
 //         which returns out of order and forces vmcnt(0) lgkmcnt(0) drains)
 
 // ------------------------------------------------------------------------------------------------
-// Layer 2 (+ fused L4) with TWO wavefronts per SIMD: k_lstm2_w8, 512 threads, 64 sites x one direction per workgroup.
+// Layer 2 (+ fused L4) with TWO wavefronts per SIMD: 512 threads, 64 sites x one direction per workgroup (k_lstm2_w16, k_lstm2_mx).
 //
 // Round 1's kernel ran one wavefront per SIMD (its 160 accumulator registers + the L4 accumulators + the prefetch ring need the
 // whole 512-register file).  A wavefront issues in order, so everything that is not an MFMA — the weight and operand
@@ -336,7 +337,7 @@ __device__ __forceinline__ void sched_interleave() {
 //     double-buffered because a wavefront's cell update now runs while others still read h_{t-1}.  LDS: 2 x 42 KB (h hi/lo) + 64 KB (x tile) = 148 KB.
 //   Wp / W4p / bp / a4part: see "Operand layouts" above (the "quarter" sq = wave & 3 indexes them).
 #ifndef C3R_W8_ASYNC
-#define C3R_W8_ASYNC 1       // k_lstm2_w8: 1 = no workgroup barriers inside the time loop — the wavefronts meet through three LDS counters (x_t read by
+#define C3R_W8_ASYNC 1       // layer 2: 1 = no workgroup barriers inside the time loop — the wavefronts meet through three LDS counters (x_t read by
                              // all / x_{t+1} landed / h_t written by all), so that one wavefront's cell update runs under its SIMD partner's MFMAs
 #endif
 // Counters in LDS that only grow: arrive = release + one increment per wavefront, wait = spin until the count is reached, then acquire.
@@ -365,35 +366,59 @@ __device__ __forceinline__ void lds_wait(int *c, int target, int *tmo) {
 #ifndef C3R_PROBE_Y1
 #define C3R_PROBE_Y1 0
 #endif
+// ------------------------------------------------------------------------------------------------
+// Layer 2 (+ fused L4) on v_mfma_f32_16x16x32_f16: k_lstm2_w16.  The decomposition above (512 threads, 64 sites x one direction per
+// workgroup, tiles dealt 3 + 2 (+ L4) to the two wavefronts of a SIMD, x_t by LDS-DMA one step ahead, the three LDS counters, h
+// double-buffered in LDS) with the smaller MFMA shape: under the chip's power limit the matrix pipe holds a higher clock on 16x16x32 than
+// on 32x32x16 at equal cycles per flop (profiles/lstm2_mfma_shape_probe.txt: the same kernel with every 32x32x16 as two 16x16x32 ran in
+// 0.944x the time).
+//   * a 32-row gate tile is two 16-row subtiles st, the 64 sites four 16-site blocks sb; a k-group is 32 k wide.  A lane holds rows
+//     4q + m (q = lane / 16) of column lane % 16: with the rows of subtile st of tile T packed as  row 4q + m <-> gate m of unit
+//     8T + 2q + st  (pack_lstm2_w16) the four gates of a unit stay in one lane, and a lane's two subtiles are two consecutive units (its
+//     h_t writes are 4-byte stores);
+//   * the pipeline runs over (k-group G, subtile st) units — 26 of them, A operands of the same size as the 16-k groups of the
+//     32x32x16 layout, so the same two-slot ring; the B operands (four site blocks, hi and lo) are read once per k-group, one unit ahead, and serve both subtiles;
+//   * the accumulators start from the fp32 bias x 2^s (exact; kept in LDS) instead of a bias MFMA;
+//   * the fused L4's 32 rows of a quarter are two subtiles as well: a lane's 4 rows are 4 consecutive L4 outputs (float4 stores).
+//   Wp  : [dir][quarter(4)][u = 2G + st (26)][tile(5)][hi|lo][64 lanes] half8 — lane l: row l % 16 of subtile st, k = 32G + 8 (l / 16) + 0..7
+//   W4p : [dir][t][quarter(4)][u = 2G + st (10)][hi|lo][64 lanes] half8 — row l % 16 <-> L4 output 32 quarter + 16 st + l % 16
+//   bp  : pack_lstm_dir's fp32 bias layout (pack_lstm_dir: [dir][tile][r = 8q + 4hh + m] <-> gate m of unit 8 tile + 4 hh + q)
+// Row of pack_lstm_dir's bias tile (r = 8q' + 4hh + m <-> gate m of unit 8 tile + 4hh + q') that holds the bias of k_lstm2_w16's accumulator
+// row 4q + m of subtile st (gate m of unit 8 tile + 2q + st)
+__host__ __device__ constexpr int w16_bias_row(int st, int q, int m) { return 8 * ((2 * q + st) & 3) + 4 * ((2 * q + st) >> 2) + m; }
 template <int ABL = 0, bool RTS = false>
-__global__ __launch_bounds__(512, 2) void k_lstm2_w8(const _Float16 *__restrict__ xin, const half8 *__restrict__ Wp,
-                                                      const float *__restrict__ bp, int n, const half8 *__restrict__ W4p,
-                                                      float *__restrict__ a4part, int nstride, float wsc_arg = WSCALE, float wun_arg = WUNSCALE, float wun4_arg = WUNSCALE,
-                                                      int *tmo = nullptr /* the context's time-out word (lds_wait) */) {
+__global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict__ xin, const half8 *__restrict__ Wp,
+                                                       const float *__restrict__ bp, int n, const half8 *__restrict__ W4p,
+                                                       float *__restrict__ a4part, int nstride, float wsc_arg = WSCALE, float wun_arg = WUNSCALE, float wun4_arg = WUNSCALE,
+                                                       int *tmo = nullptr /* the context's time-out word (lds_wait) */) {
     const float wsc = RTS ? wsc_arg : WSCALE, wun = RTS ? wun_arg : WUNSCALE, wun4 = RTS ? wun4_arg : WUNSCALE;
-    constexpr int INP = 2 * NET_H1, H = NET_H2, NGX = INP / 16, NGH = H / 16, NG = NGX + NGH, HP = H + 8, NBLK = 4 * H / 32, NTQ = NBLK / 4;
-    constexpr int SB = 2, WG_SITES = 32 * SB, KC = INP / 8, PD = C3R_W8_PD;
-    static_assert(NTQ == 5 && NG == 26, "3 + 2 tile split of a quarter, 26 k-groups");
+    constexpr int INP = 2 * NET_H1, H = NET_H2, NGX = INP / 32, NGH = H / 32, NG = NGX + NGH, NU = 2 * NG, HP = H + 8, NBLK = 4 * H / 32, NTQ = NBLK / 4;
+    constexpr int SB = 4, WG_SITES = 16 * SB, KC = INP / 8, PD = C3R_W8_PD;
+    static_assert(NTQ == 5 && NU == 26 && PD == 1, "3 + 2 tile split of a quarter, 26 (k-group, subtile) units, one unit of prefetch");
     __shared__ __attribute__((aligned(16))) _Float16 hb_hi[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) _Float16 hb_lo[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) _Float16 xs[2][KC][WG_SITES][8];      // [plane][k/8][site][8]
-    __shared__ int s_ctr[4];        // C3R_W8_ASYNC: [0] wavefronts done reading x_t, [1] x DMAs landed, [2] wavefronts done writing h_t
+    __shared__ __attribute__((aligned(16))) float s_bias[NBLK][2][16];          // 2^s b: [tile][st][4q + m]
+    __shared__ int s_ctr[4];        // C3R_W8_ASYNC: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, hh = lane >> 5;
-    const int sq = C3R_W8_MAP ? (wave >> 1) : (wave & 3);      // quarter of the gate rows (the layouts' quarter index)
-    const bool heavy3 = C3R_W8_MAP ? !(wave & 1) : (wave < 4); // the 3-tile wavefront of its SIMD pair
+    const int c16 = lane & 15, q4 = lane >> 4;
+    const int sq = C3R_W8_MAP ? (wave >> 1) : (wave & 3);
+    const bool heavy3 = C3R_W8_MAP ? !(wave & 1) : (wave < 4);
     const int dir = C3R_DIR_ILV ? blockIdx.x : blockIdx.y;
     const int site0 = (C3R_DIR_ILV ? blockIdx.y : blockIdx.x) * WG_SITES;
     const int ns = nstride ? nstride : n;
     const size_t plane_in = (size_t)ns * NET_T * INP;
 
     for (int i = tid; i < WG_SITES * HP; i += 512) { (&hb_hi[0][0][0])[i] = (_Float16)0.f; (&hb_lo[0][0][0])[i] = (_Float16)0.f; }
+    for (int i = tid; i < NBLK * 32; i += 512) {
+        const int T = i >> 5, st = (i >> 4) & 1, q = (i >> 2) & 3, m = i & 3;
+        s_bias[T][st][4 * q + m] = wsc * bp[((size_t)dir * NBLK + T) * 32 + w16_bias_row(st, q, m)];
+    }
     if (tid < 4) s_ctr[tid] = 0;
 
     int xsite = site0 + lane;
     if (xsite >= n) xsite = n - 1;
-    // LDS-DMA of x_t: 2*KC = 64 rows of 1 KiB (one (plane, k/8) row of the 64 sites each), eight per wavefront
     auto dma_x = [&](int tt_) {
         typedef const _Float16 __attribute__((address_space(1))) *gp_t;
         typedef _Float16 __attribute__((address_space(3))) *lp_t;
@@ -404,13 +429,12 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w8(const _Float16 *__restrict_
             __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, 0);
         }
     };
-    auto dma_x16 = [&](int tt_) {          // C3R_W8_ASYNC: all 64 rows from the four 3-tile wavefronts (they finish their K loop first)
+    auto dma_x16 = [&](int tt_) {
         typedef const _Float16 __attribute__((address_space(1))) *gp_t;
         typedef _Float16 __attribute__((address_space(3))) *lp_t;
 #pragma unroll
         for (int r = 0; r < 2 * KC / 4; ++r) {
             const int row = (wave & 3) * (2 * KC / 4) + r, pl = row / KC, kc = row % KC;
-            if (C3R_PROBE_Y1 && pl == 1 && (kc & 1)) continue;      // timing probe (results wrong): a quarter of the y1 read traffic gone
             const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
             __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, 0);
         }
@@ -419,39 +443,23 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w8(const _Float16 *__restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    // The whole recurrence of one wavefront: NT gate tiles starting at tile TOFF of its quarter; L4T: also the L4 rows.
     auto body = [&](auto ntc, auto toffc, auto l4c) {
         constexpr int NT = decltype(ntc)::value, TOFF = decltype(toffc)::value;
         constexpr bool L4T = decltype(l4c)::value;
-        constexpr int NTH = NT + (L4T ? 1 : 0);          // tiles in the recurrent part
-        const half8 *wl = Wp + ((size_t)(dir * 4 + sq) * NG) * NTQ * 2 * 64 + (size_t)TOFF * 2 * 64 + lane;
-        // bias: one f16 MFMA per (tile, site block) and step — A = {hi, lo, 0...} of 2^12 b on the k-slots 0 and 1 (lane half 0),
-        // B = {1, 1, 0...}: 32 cycles instead of the 64 of an f32 MFMA; hi + lo carries 22 bits like every
-        // other operand of this path
-        typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-        unsigned bias_hl[NT];
-#pragma unroll
-        for (int tt = 0; tt < NT; ++tt) {
-            const float bv = wsc * bp[((size_t)dir * NBLK + sq * NTQ + TOFF + tt) * 32 + j];
-            half2v hl;
-            hl[0] = (_Float16)bv;
-            hl[1] = (_Float16)(bv - (float)hl[0]);
-            bias_hl[tt] = hh == 0 ? __builtin_bit_cast(unsigned, hl) : 0u;
-        }
-        const half2v one2 = {(_Float16)1.f, (_Float16)1.f};
-        const unsigned ones_b = hh == 0 ? __builtin_bit_cast(unsigned, one2) : 0u;
-        float cst[NT][SB][4];
+        constexpr int NTH = NT + (L4T ? 1 : 0);
+        const half8 *wl = Wp + ((size_t)(dir * 4 + sq) * NU) * NTQ * 2 * 64 + (size_t)TOFF * 2 * 64 + lane;
+        float cst[NT][2 * SB];          // [tile][4 st + sb]
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-            for (int sb = 0; sb < SB; ++sb)
+            for (int u = 0; u < 2 * SB; ++u) cst[tt][u] = 0.f;
+        floatx4 facc[L4T ? 2 : 1][L4T ? SB : 1];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) cst[tt][sb][q] = 0.f;
-        floatx16 facc[L4T ? SB : 1];
+        for (int st = 0; st < (L4T ? 2 : 1); ++st)
 #pragma unroll
-        for (int sb = 0; sb < (L4T ? SB : 1); ++sb)
+            for (int sb = 0; sb < (L4T ? SB : 1); ++sb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) facc[sb][r] = 0.f;
+                for (int r = 0; r < 4; ++r) facc[st][sb][r] = 0.f;
 
         typedef const half8 __attribute__((address_space(1))) *gptr_t;
         for (int step = 0; step < NET_T; ++step) {
@@ -462,204 +470,198 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w8(const _Float16 *__restrict_
             auto ldx = [&](int g, half8 (&bh)[SB], half8 (&bl)[SB]) {
 #pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
-                    if ((ABL & 32) && g > 0) continue;          // probe: no B-operand reads from LDS after the first k-group
-                    bh[sb] = *(const half8 *)&xs[0][2 * g + hh][32 * sb + j][0];
-                    bl[sb] = *(const half8 *)&xs[1][2 * g + hh][32 * sb + j][0];
+                    if ((ABL & 32) && g > 0) continue;
+                    bh[sb] = *(const half8 *)&xs[0][4 * g + q4][16 * sb + c16][0];
+                    bl[sb] = *(const half8 *)&xs[1][4 * g + q4][16 * sb + c16][0];
                 }
             };
             auto ldh = [&](int g, half8 (&bh)[SB], half8 (&bl)[SB]) {
 #pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
                     if (ABL & 32) continue;
-                    bh[sb] = *(const half8 *)&hb_hi[cur][32 * sb + j][16 * g + 8 * hh];
-                    bl[sb] = *(const half8 *)&hb_lo[cur][32 * sb + j][16 * g + 8 * hh];
+                    bh[sb] = *(const half8 *)&hb_hi[cur][16 * sb + c16][32 * g + 8 * q4];
+                    bl[sb] = *(const half8 *)&hb_lo[cur][16 * sb + c16][32 * g + 8 * q4];
                 }
             };
-            auto ldw = [&](int g, half8 (&ah)[NTH], half8 (&al)[NTH]) {
+            auto ldw = [&](int u, half8 (&ah)[NTH], half8 (&al)[NTH]) {
                 uintptr_t wbase = (uintptr_t)wl;                 // address laundering, address_space(1): see "Operand layouts", ldw
                 asm volatile("" : "+v"(wbase));
-                const gptr_t wg = (gptr_t)wbase + (size_t)((ABL & 1) ? 0 : g) * NTQ * 2 * 64;      // probe bit 1: one L1-hot k-group
+                const gptr_t wg = (gptr_t)wbase + (size_t)((ABL & 1) ? 0 : u) * NTQ * 2 * 64;
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt) {
-                    if ((ABL & 16) && g > 0) continue;
+                    if ((ABL & 16) && u > 0) continue;
                     ah[tt] = wg[(tt * 2 + 0) * 64]; al[tt] = wg[(tt * 2 + 1) * 64];
                 }
                 if constexpr (L4T) {
-                    if (g >= NGX && !((ABL & 16) && g > NGX)) {
-                        uintptr_t w4base = (uintptr_t)(W4p + (((size_t)(dir * NET_T + tprev) * 4 + sq) * NGH) * 2 * 64 + lane);
+                    if (u >= 2 * NGX && !((ABL & 16) && u > 2 * NGX)) {
+                        uintptr_t w4base = (uintptr_t)(W4p + (((size_t)(dir * NET_T + tprev) * 4 + sq) * 2 * NGH) * 2 * 64 + lane);
                         asm volatile("" : "+v"(w4base));
-                        const gptr_t w4 = (gptr_t)w4base + (size_t)(g - NGX) * 2 * 64;
+                        const gptr_t w4 = (gptr_t)w4base + (size_t)(u - 2 * NGX) * 2 * 64;
                         ah[NT] = w4[0]; al[NT] = w4[64];
                     }
                 }
             };
 
             if (C3R_W8_ASYNC && step > 0) lds_wait(&s_ctr[1], 4 * step, tmo);      // x_t has landed (four DMA wavefronts per step)
-            floatx16 acc[NT][SB];
-            {
-                floatx16 z;
+            floatx4 acc[NT][2][SB];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) z[r] = 0.f;
-                typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-                const uint4v bb = {ones_b, 0u, 0u, 0u};
+            for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-                for (int tt = 0; tt < NT; ++tt) {
-                    const uint4v ba = {bias_hl[tt], 0u, 0u, 0u};
+                for (int st = 0; st < 2; ++st) {
+                    const floatx4 b4 = *(const floatx4 *)&s_bias[sq * NTQ + TOFF + tt][st][4 * q4];
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb)
-                        acc[tt][sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, ba), __builtin_bit_cast(half8, bb), z, 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) acc[tt][st][sb] = b4;
                 }
-            }
-            auto mma = [&](const half8 (&ah)[NTH], const half8 (&al)[NTH], const half8 (&bh)[SB], const half8 (&bl)[SB], bool hpart, bool odd) {
+            // one (k-group, subtile) unit: hi x hi, hi x lo, lo x hi
+            auto mma = [&](const half8 (&ah)[NTH], const half8 (&al)[NTH], const half8 (&bh)[SB], const half8 (&bl)[SB], auto stc, bool hpart) {
+                constexpr int st = decltype(stc)::value;
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb) acc[tt][sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[tt], bh[sb], acc[tt][sb], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) acc[tt][st][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[tt], bh[sb], acc[tt][st][sb], 0, 0, 0);
                 if (L4T && hpart) {
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb) facc[L4T ? sb : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[L4T ? NT : 0], bh[sb], facc[L4T ? sb : 0], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) facc[L4T ? st : 0][L4T ? sb : 0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[L4T ? NT : 0], bh[sb], facc[L4T ? st : 0][L4T ? sb : 0], 0, 0, 0);
                 }
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb) acc[tt][sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[tt], bh[sb], acc[tt][sb], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) acc[tt][st][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[tt], bl[sb], acc[tt][st][sb], 0, 0, 0);
                 if (L4T && hpart) {
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb) facc[L4T ? sb : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[L4T ? NT : 0], bh[sb], facc[L4T ? sb : 0], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) facc[L4T ? st : 0][L4T ? sb : 0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[L4T ? NT : 0], bl[sb], facc[L4T ? st : 0][L4T ? sb : 0], 0, 0, 0);
                 }
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb) acc[tt][sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[tt], bl[sb], acc[tt][sb], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) acc[tt][st][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[tt], bh[sb], acc[tt][st][sb], 0, 0, 0);
                 if (L4T && hpart) {
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb) facc[L4T ? sb : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[L4T ? NT : 0], bl[sb], facc[L4T ? sb : 0], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) facc[L4T ? st : 0][L4T ? sb : 0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[L4T ? NT : 0], bh[sb], facc[L4T ? st : 0][L4T ? sb : 0], 0, 0, 0);
                 }
             };
-            half8 ah[PD + 1][NTH], al[PD + 1][NTH], bh[PD + 1][SB], bl[PD + 1][SB];
+            half8 ah[2][NTH], al[2][NTH], bh[2][SB], bl[2][SB];
 #define C3R_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define C3R_LOAD(G) do { ldw((G), ah[(G) % (PD + 1)], al[(G) % (PD + 1)]); \
-                         if ((G) < NGX) ldx((G), bh[(G) % (PD + 1)], bl[(G) % (PD + 1)]); \
-                         else ldh((G) - NGX, bh[(G) % (PD + 1)], bl[(G) % (PD + 1)]); } while (0)
-#define C3R_PRE(D) if constexpr ((D) < PD && (D) < NG) { C3R_LOAD(D); }
-#define C3R_STEP(G)                                                                                              \
-    if constexpr ((G) < NG) {                                                                                     \
+            // unit U = 2G + st: A of unit U in slot U % 2; B of k-group G in slot G % 2, read with the A of unit 2G (one unit ahead)
+#define C3R_LOAD(U) do { ldw((U), ah[(U) % 2], al[(U) % 2]);                                                       \
+                         if constexpr (((U) & 1) == 0) {                                                          \
+                             if constexpr ((U) / 2 < NGX) ldx((U) / 2, bh[((U) / 2) % 2], bl[((U) / 2) % 2]);      \
+                             else ldh((U) / 2 - NGX, bh[((U) / 2) % 2], bl[((U) / 2) % 2]); } } while (0)
+#define C3R_STEP(U)                                                                                              \
+    if constexpr ((U) < NU) {                                                                                     \
         C3R_FENCE();                                                                                              \
-        if constexpr (C3R_W8_ASYNC && (G) + PD == NGX) { lds_wait(&s_ctr[2], 8 * step, tmo); C3R_FENCE(); }   /* h_{t-1} is complete */ \
-        if constexpr ((G) + PD < NG) { C3R_LOAD((G) + PD); }                                                      \
-        mma(ah[(G) % (PD + 1)], al[(G) % (PD + 1)], bh[(G) % (PD + 1)], bl[(G) % (PD + 1)], (G) >= NGX, ((G) & 1) != 0);  \
-        if constexpr ((G) + PD < NG) {                                                                            \
-            constexpr int NMM = ((G) >= NGX ? NTH : NT) * SB * 3;         \
-            sched_interleave<NMM, ((G) + PD >= NGX ? NTH : NT) * 2, SB * 2>();                                    \
+        if constexpr (C3R_W8_ASYNC && (U) + 1 == 2 * NGX) { lds_wait(&s_ctr[2], 8 * step, tmo); C3R_FENCE(); }   /* h_{t-1} is complete */ \
+        if constexpr ((U) + 1 < NU) { C3R_LOAD((U) + 1); }                                                        \
+        mma(ah[(U) % 2], al[(U) % 2], bh[((U) / 2) % 2], bl[((U) / 2) % 2], std::integral_constant<int, (U) & 1>{}, (U) >= 2 * NGX); \
+        if constexpr ((U) + 1 < NU) {                                                                             \
+            constexpr int NMM = ((U) >= 2 * NGX ? NTH : NT) * SB * 3;                                             \
+            sched_interleave<NMM, ((U) + 1 >= 2 * NGX ? NTH : NT) * 2, (((U) & 1) ? SB * 2 : 0)>();                \
         }                                                                                                         \
-        if constexpr ((G) == NGX - 1) {                                                                           \
-            /* after this barrier every wavefront is done with x_t (the 2-tile wavefronts wait here for the     */ \
-            /* 3-tile ones, which then have the matrix pipe to themselves: no pipe time is lost)                */ \
+        if constexpr ((U) == 2 * NGX - 1) {                                                                       \
             C3R_FENCE();                                                                                          \
             if constexpr (C3R_W8_ASYNC) lds_arrive(&s_ctr[0]); else __syncthreads();                              \
         }                                                                                                         \
     }
-            C3R_PRE(0) C3R_PRE(1) C3R_PRE(2)
+            C3R_LOAD(0);
             C3R_STEP(0) C3R_STEP(1) C3R_STEP(2) C3R_STEP(3) C3R_STEP(4) C3R_STEP(5) C3R_STEP(6) C3R_STEP(7) C3R_STEP(8) C3R_STEP(9)
             C3R_STEP(10) C3R_STEP(11) C3R_STEP(12) C3R_STEP(13) C3R_STEP(14) C3R_STEP(15) C3R_STEP(16) C3R_STEP(17) C3R_STEP(18)
             C3R_STEP(19) C3R_STEP(20) C3R_STEP(21) C3R_STEP(22) C3R_STEP(23) C3R_STEP(24) C3R_STEP(25)
             C3R_FENCE();
-#undef C3R_PRE
 #undef C3R_STEP
 #undef C3R_LOAD
 #undef C3R_FENCE
-            // x_{t+1} by LDS-DMA now, so that no weight load queues behind it (vmcnt retires in order): it lands during the
-            // cell update
             if constexpr (C3R_W8_ASYNC) {
-                if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }      // (everyone is done with x_t)
+                if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }
             } else if (step + 1 < NET_T && !(ABL & 64)) dma_x(dir ? NET_T - 2 - step : step + 1);
-            // ---- lane-local cell update, one tile at a time; cell state in registers
+            // ---- lane-local cell update, one tile at a time: cell u = 4 st + sb is unit 8T + 2 q4 + st at site 16 sb + c16
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt) {
                 __builtin_amdgcn_sched_barrier(0);
-                constexpr int NU = 4 * SB;
+                constexpr int NC = 2 * SB;
                 const float K1 = -1.4426950408889634f * wun, K2 = -2.8853900817779268f * wun;
-                float cq[NU], ei[NU], ef[NU], eg[NU], eo[NU], hval[NU];
+                float cq[NC], ei[NC], ef[NC], eg[NC], eo[NC], hval[NC];
 #pragma unroll
-                for (int u = 0; u < NU; ++u) cq[u] = cst[tt][u >> 2][u & 3];
+                for (int u = 0; u < NC; ++u) cq[u] = cst[tt][u];
                 if (ABL & 2) {
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) hval[u] = acc[tt][u >> 2][4 * (u & 3)] + acc[tt][u >> 2][4 * (u & 3) + 1] + acc[tt][u >> 2][4 * (u & 3) + 2] + acc[tt][u >> 2][4 * (u & 3) + 3];
+                    for (int u = 0; u < NC; ++u) hval[u] = acc[tt][u / SB][u % SB][0] + acc[tt][u / SB][u % SB][1] + acc[tt][u / SB][u % SB][2] + acc[tt][u / SB][u % SB][3];
                 } else {
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 0]), 1e18f);
+                    for (int u = 0; u < NC; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][0]), 1e18f);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) ef[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 1]);
+                    for (int u = 0; u < NC; ++u) ef[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][1]);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[tt][u >> 2][4 * (u & 3) + 2]), 1e18f);
+                    for (int u = 0; u < NC; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[tt][u / SB][u % SB][2]), 1e18f);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) eo[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 3]), 1e18f);
+                    for (int u = 0; u < NC; ++u) eo[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][3]), 1e18f);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) ei[u] = gate_frac(ei[u], eg[u]);
+                    for (int u = 0; u < NC; ++u) ei[u] = gate_frac(ei[u], eg[u]);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
+                    for (int u = 0; u < NC; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) cq[u] = fmaf(ef[u], cq[u], ei[u]);
+                    for (int u = 0; u < NC; ++u) cq[u] = fmaf(ef[u], cq[u], ei[u]);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
+                    for (int u = 0; u < NC; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
 #pragma unroll
-                    for (int u = 0; u < NU; ++u) hval[u] = gate_frac(eo[u], eg[u]);
+                    for (int u = 0; u < NC; ++u) hval[u] = gate_frac(eo[u], eg[u]);
                 }
 #pragma unroll
+                for (int u = 0; u < NC; ++u) cst[tt][u] = cq[u];
+#pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
+                    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+                    half2v vh, vl;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) cst[tt][sb][q] = cq[4 * sb + q];
-                    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-                    half4 vh, vl;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        vh[q] = (_Float16)hval[4 * sb + q];
-                        float d = hval[4 * sb + q] - (float)vh[q];
+                    for (int st = 0; st < 2; ++st) {
+                        vh[st] = (_Float16)hval[SB * st + sb];
+                        float d = hval[SB * st + sb] - (float)vh[st];
                         asm volatile("" : "+v"(d));            // subtract, then convert (never v_fma_mixlo_f16: it rounds differently)
-                        vl[q] = (_Float16)d;
+                        vl[st] = (_Float16)d;
                     }
-                    *(half4 *)&hb_hi[nxt][32 * sb + j][8 * (sq * NTQ + TOFF + tt) + 4 * hh] = vh;
-                    *(half4 *)&hb_lo[nxt][32 * sb + j][8 * (sq * NTQ + TOFF + tt) + 4 * hh] = vl;
+                    *(half2v *)&hb_hi[nxt][16 * sb + c16][8 * (sq * NTQ + TOFF + tt) + 2 * q4] = vh;
+                    *(half2v *)&hb_lo[nxt][16 * sb + c16][8 * (sq * NTQ + TOFF + tt) + 2 * q4] = vl;
                 }
             }
             if constexpr (C3R_W8_ASYNC) {
-                lds_arrive(&s_ctr[2]);                                                  // my share of h_t is in LDS
-                if (!L4T && step + 1 < NET_T) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lds_arrive(&s_ctr[1]); }      // my share of x_{t+1} has landed
+                lds_arrive(&s_ctr[2]);
+                if (!L4T && step + 1 < NET_T) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lds_arrive(&s_ctr[1]); }
             } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // x_{t+1} has landed (LDS-DMA is tracked by vmcnt)
-            __syncthreads();                                       // h_t complete; everyone is done with h_{t-1}
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
             }
         }
         if constexpr (L4T) {
             if constexpr (C3R_W8_ASYNC) lds_wait(&s_ctr[2], 8 * NET_T, tmo);
             // ---- the last step's h (buffer NET_T & 1) still owes its L4 contribution
             const int tl = dir ? 0 : NET_T - 1, hbuf = NET_T & 1;
-            const half8 *w4 = W4p + (((size_t)(dir * NET_T + tl) * 4 + sq) * NGH) * 2 * 64 + lane;
-#pragma unroll 2
+            const half8 *w4 = W4p + (((size_t)(dir * NET_T + tl) * 4 + sq) * 2 * NGH) * 2 * 64 + lane;
+#pragma unroll 1
             for (int g = 0; g < NGH; ++g) {
-                const half8 a_h = w4[(size_t)(g * 2 + 0) * 64], a_l = w4[(size_t)(g * 2 + 1) * 64];
                 half8 b_h[SB], b_l[SB];
 #pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
-                    b_h[sb] = *(const half8 *)&hb_hi[hbuf][32 * sb + j][16 * g + 8 * hh];
-                    b_l[sb] = *(const half8 *)&hb_lo[hbuf][32 * sb + j][16 * g + 8 * hh];
+                    b_h[sb] = *(const half8 *)&hb_hi[hbuf][16 * sb + c16][32 * g + 8 * q4];
+                    b_l[sb] = *(const half8 *)&hb_lo[hbuf][16 * sb + c16][32 * g + 8 * q4];
                 }
 #pragma unroll
-                for (int sb = 0; sb < SB; ++sb) facc[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h, b_h[sb], facc[sb], 0, 0, 0);
+                for (int st = 0; st < 2; ++st) {
+                    const half8 a_h = w4[(size_t)((2 * g + st) * 2 + 0) * 64], a_l = w4[(size_t)((2 * g + st) * 2 + 1) * 64];
 #pragma unroll
-                for (int sb = 0; sb < SB; ++sb) facc[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l, b_h[sb], facc[sb], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) facc[st][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h, b_h[sb], facc[st][sb], 0, 0, 0);
 #pragma unroll
-                for (int sb = 0; sb < SB; ++sb) facc[sb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h, b_l[sb], facc[sb], 0, 0, 0);
+                    for (int sb = 0; sb < SB; ++sb) facc[st][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h, b_l[sb], facc[st][sb], 0, 0, 0);
+#pragma unroll
+                    for (int sb = 0; sb < SB; ++sb) facc[st][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_l, b_h[sb], facc[st][sb], 0, 0, 0);
+                }
             }
 #pragma unroll
             for (int sb = 0; sb < SB; ++sb) {
-                const int sidx = site0 + 32 * sb + j;
+                const int sidx = site0 + 16 * sb + c16;
                 if (sidx < n) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        float4 v = make_float4(facc[sb][4 * q] * wun4, facc[sb][4 * q + 1] * wun4, facc[sb][4 * q + 2] * wun4,
-                                               facc[sb][4 * q + 3] * wun4);
-                        *(float4 *)(a4part + ((size_t)sidx * 2 + dir) * NET_L4 + 32 * sq + 8 * q + 4 * hh) = v;
+                    for (int st = 0; st < 2; ++st) {
+                        const float4 v = make_float4(facc[st][sb][0] * wun4, facc[st][sb][1] * wun4, facc[st][sb][2] * wun4, facc[st][sb][3] * wun4);
+                        *(float4 *)(a4part + ((size_t)sidx * 2 + dir) * NET_L4 + 32 * sq + 16 * st + 4 * q4) = v;
                     }
                 }
             }
@@ -673,7 +675,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w8(const _Float16 *__restrict_
 
 // ------------------------------------------------------------------------------------------------
 // Precision 2: layer 2 (+ fused L4) with both correction terms on the block-scaled fp8 pipe — k_lstm2_mx.
-// k_lstm2_w8's decomposition (512 threads, 64 sites x one direction, tiles dealt 3 + 2 (+ L4) to the two wavefronts of a SIMD, x_t by
+// the split-f16 layer 2's decomposition (512 threads, 64 sites x one direction, tiles dealt 3 + 2 (+ L4) to the two wavefronts of a SIMD, x_t by
 // LDS-DMA, h double-buffered).  Per block of 32 k's the three f16 products of the split-f16 path,
 //        w_hi x_hi + w_hi x_lo + w_lo x_hi        (6 MFMAs of 32 cycles per tile and site block),
 // become two f16 MFMAs for w_hi x_hi and ONE v_mfma_scale_f32_32x32x64_f8f6f4 (64 cycles) whose K = 64 is the concatenation
@@ -687,7 +689,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w8(const _Float16 *__restrict_
 // "auto") before this path is used.
 //   xin: plane 0 = f16(x) [t][k/8][site][8 halves]; plane 1, same geometry, rows (kb, term, part) = kb * 4 + term * 2 + part of 16 bytes
 //        per site: fp8 of k = 32 kb + 16 part + 0..15, term 0 = (x - f16(x)) 2^18, term 1 = x 2^6   (written by k_lstm1_rs<.., YQ>)
-//   Wp / W4p: k_lstm2_w8's f16 fragments (only the hi halves are read); Wq / Wsc, W4q / W4sc: pack_mx
+//   Wp / W4p: the 32x32x16 split-f16 fragments of pack_lstm_dir_h / net_load's w4f (only the hi halves are read); Wq / Wsc, W4q / W4sc: pack_mx
 __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict__ xin, const half8 *__restrict__ Wp, const uint32_t *__restrict__ Wq,
                                                       const uint32_t *__restrict__ Wsc, const float *__restrict__ bp, int n,
                                                       const half8 *__restrict__ W4p, const uint32_t *__restrict__ W4q,
@@ -707,7 +709,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
     __shared__ __attribute__((aligned(16))) _Float16 hb_hi[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) intx4 hq[2][NKBH][2][2][WG_SITES];     // fp8 of h: [buffer][kb][term][part][site] 16 bytes
     __shared__ __attribute__((aligned(16))) _Float16 xs[2][KC][WG_SITES][8];      // [plane][row][site][16 bytes]
-    __shared__ int s_ctr[4];        // C3R_W8_ASYNC (see k_lstm2_w8): [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
+    __shared__ int s_ctr[4];        // C3R_W8_ASYNC: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, hh = lane >> 5;
@@ -724,7 +726,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 
     int xsite = site0 + lane;
     if (xsite >= n) xsite = n - 1;
-    auto dma_x = [&](int tt_) {          // 64 rows of 1 KiB, eight per wavefront (see k_lstm2_w8)
+    auto dma_x = [&](int tt_) {          // 64 rows of 1 KiB, eight per wavefront (see k_lstm2_w16)
         typedef const _Float16 __attribute__((address_space(1))) *gp_t;
         typedef _Float16 __attribute__((address_space(3))) *lp_t;
 #pragma unroll
@@ -861,7 +863,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
             };
 
             floatx16 acc[NT][SB];
-            {   // bias (see k_lstm2_w8)
+            {   // bias: one f16 MFMA per (tile, site block), A = {hi, lo} of 2^12 b on k-slots 0 and 1, B = {1, 1}
                 floatx16 z;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) z[r] = 0.f;
@@ -927,7 +929,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
             if constexpr (C3R_W8_ASYNC) {
                 if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }
             } else if (step + 1 < NET_T) dma_x(dir ? NET_T - 2 - step : step + 1);      // lands during the cell update
-            // ---- lane-local cell update (k_lstm2_w8's), h_t to LDS as f16 plus the two fp8 bytes per unit
+            // ---- lane-local cell update (k_lstm2_w16's), h_t to LDS as f16 plus the two fp8 bytes per unit
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -1046,7 +1048,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 template <int CIN, bool YQ = false, bool RTS = false>
 __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_v, const half8 *__restrict__ Wp, _Float16 *__restrict__ y, int n, int nstride,
                                                    const int32_t *__restrict__ row_idx /* row of site i in xin (the tensor build writes windows as they arrive); null: i */,
-                                                   float wun_arg = WUNSCALE /* RTS: 2^-s of the layer's weight scale (k_lstm2_w8) */,
+                                                   float wun_arg = WUNSCALE /* RTS: 2^-s of the layer's weight scale (k_lstm2_w16) */,
                                                    int x16 = 0 /* the rows are int16 (the tensor build's windows), not int32 (a caller's batch) */) {
     const int32_t *__restrict__ xin = (const int32_t *)xin_v;
     const int16_t *__restrict__ xin16 = (const int16_t *)xin_v;
@@ -1353,6 +1355,7 @@ struct NetState {
     float4 *d_w4 = nullptr; float *d_b4 = nullptr;     // packed L4
     float *d_w5 = nullptr, *d_b5 = nullptr, *d_wo = nullptr, *d_bo = nullptr;
     float4 *d_w5p = nullptr, *d_wcp = nullptr;          // heads in MFMA fragment order (k_heads_mfma)
+    half8 *d_w2w = nullptr, *d_w4w = nullptr;      // k_lstm2_w16's layer-2 and fused-L4 fragments (pack_lstm2_w16, pack_l4_w16)
     half8 *d_w1h = nullptr, *d_w2h = nullptr, *d_w4h = nullptr, *d_w4f = nullptr;   // d_w4f: L4 packed per (dir, t) for the fused path   // split-f16 packed weights (hi/lo, x 2^12)
     // precision 2 (MX corrections): fp8 (e4m3) fragments of w (lanes 0-31) and w - f16(w) (lanes 32-63) per block of 32 k, 32 bytes per
     // lane, and their E8M0 block scales, four blocks per dword: layer 1 (recurrent part only), layer 2, fused L4
@@ -1429,7 +1432,7 @@ inline size_t big_trim() {
 
 inline void net_free(NetState &s) {
     void *ptrs[] = {s.d_w1, s.d_b1, s.d_w2, s.d_b2, s.d_w4, s.d_b4, s.d_w5, s.d_b5, s.d_wo, s.d_bo, s.d_y2, s.d_a4, s.d_probs,
-                    s.d_w1h, s.d_w2h, s.d_w4h, s.d_w4f, s.d_w5p, s.d_wcp, s.d_w1q, s.d_w1s, s.d_w2q, s.d_w2s, s.d_w4q, s.d_w4s, s.d_tmo};
+                    s.d_w1h, s.d_w2h, s.d_w4h, s.d_w4f, s.d_w2w, s.d_w4w, s.d_w5p, s.d_wcp, s.d_w1q, s.d_w1s, s.d_w2q, s.d_w2s, s.d_w4q, s.d_w4s, s.d_tmo};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     big_give(s.d_y1, (size_t)s.cap_sites * NET_T * 2 * NET_H1 * sizeof(float));
     s = NetState();
@@ -1493,6 +1496,54 @@ inline void pack_lstm_dir_h(const float *Kin, int cin, int inp, const float *R, 
                         wp[((base + 1 * 64 + lane) * 8) + e] = lo;
                     }
         }
+}
+
+// k_lstm2_w16's layer-2 fragments of one direction: [quarter(4)][u = 2G + st (26)][tile(5)][hi|lo][64 lanes][8 halves], weights x 2^s.
+// Lane l of unit (G, st) of tile T holds row l % 16 of subtile st = gate m of unit 8T + 2q + st (l % 16 = 4q + m), k = 32G + 8 (l / 16) + 0..7
+// (v_mfma_f32_16x16x32_f16: A[row l % 16][k = 8 (l / 16) + i]; its accumulator gives lane l rows 4 (l / 16) + 0..3).
+inline void w16_gate_row(int T, int st, int r16, int H, int &unit, int &col) {
+    const int q = r16 >> 2, m = r16 & 3;
+    unit = 8 * T + 2 * q + st;
+    col = m * H + unit;
+}
+inline void pack_lstm2_w16(const float *Kin, int inp, const float *R, int H, std::vector<uint16_t> &wp, float wscale) {
+    const int K = inp + H, NG = K / 32, NU = 2 * NG, NBLK = 4 * H / 32, NT = NBLK / 4;
+    wp.assign((size_t)NBLK * NU * 2 * 64 * 8, 0);
+    for (int T = 0; T < NBLK; ++T)
+        for (int st = 0; st < 2; ++st)
+            for (int l = 0; l < 64; ++l) {
+                int unit, col;
+                w16_gate_row(T, st, l & 15, H, unit, col);
+                for (int g = 0; g < NG; ++g)
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = 32 * g + 8 * (l >> 4) + e;
+                        const float w = k < inp ? Kin[(size_t)k * 4 * H + col] : R[(size_t)(k - inp) * 4 * H + col];
+                        uint16_t hi, lo;
+                        split_h(wscale * w, hi, lo);
+                        const size_t base = ((((size_t)(T / NT) * NU + 2 * g + st) * NT + (T % NT)) * 2) * 64;
+                        wp[(base + l) * 8 + e] = hi;
+                        wp[(base + 64 + l) * 8 + e] = lo;
+                    }
+            }
+}
+// k_lstm2_w16's fused L4 fragments: [dir][t][quarter(4)][u = 2G + st (H / 16)][hi|lo][64 lanes][8]; lane l: L4 output 32 quarter + 16 st + l % 16,
+// h index k = 32G + 8 (l / 16) + 0..7 of direction d at time t (flatten row t * 2H + d * H + k)
+inline void pack_l4_w16(const float *W4, float wscale, std::vector<uint16_t> &w4p) {
+    const int NU4 = NET_H2 / 16;
+    w4p.assign((size_t)2 * NET_T * 4 * NU4 * 2 * 64 * 8, 0);
+    for (int d = 0; d < 2; ++d)
+        for (int t = 0; t < NET_T; ++t)
+            for (int sq = 0; sq < 4; ++sq)
+                for (int u = 0; u < NU4; ++u)
+                    for (int l = 0; l < 64; ++l)
+                        for (int e = 0; e < 8; ++e) {
+                            const int o = 32 * sq + 16 * (u & 1) + (l & 15), k = 32 * (u >> 1) + 8 * (l >> 4) + e;
+                            uint16_t hi, lo;
+                            split_h(wscale * W4[((size_t)t * 2 * NET_H2 + (size_t)d * NET_H2 + k) * NET_L4 + o], hi, lo);
+                            const size_t base = ((((size_t)(d * NET_T + t) * 4 + sq) * NU4 + u) * 2) * 64;
+                            w4p[(base + l) * 8 + e] = hi;
+                            w4p[(base + 64 + l) * 8 + e] = lo;
+                        }
 }
 
 // ---- precision 2: the two correction terms on the block-scaled fp8 pipe (v_mfma_scale_f32_32x32x64_f8f6f4, K = 64 = two terms x 32 k).
@@ -1609,7 +1660,7 @@ inline int net_load(NetState &s, const float *blob, int C, hipStream_t st, std::
     const float *q = blob;
     const int inp1 = 32;   // padded to an even number of 8-wide k-groups
     std::vector<float> w1, b1, w2, b2, tw, tb;
-    std::vector<uint16_t> w1h, w2h, th;
+    std::vector<uint16_t> w1h, w2h, w2w, th;
     std::vector<uint32_t> w1q, w1s, w2q, w2s, tq, ts;
     // gate row r of tile blk <-> Keras column (pack_lstm_dir_h): r = 8 q + 4 hh + m -> unit 8 blk + 4 hh + q, gate m
     auto gate_col = [](int blk, int r, int H) { const int qq = r >> 3, hh = (r >> 2) & 1, m = r & 3; return m * H + 8 * blk + 4 * hh + qq; };
@@ -1650,6 +1701,8 @@ inline int net_load(NetState &s, const float *blob, int C, hipStream_t st, std::
         w2.insert(w2.end(), tw.begin(), tw.end()); b2.insert(b2.end(), tb.begin(), tb.end());
         pack_lstm_dir_h(Kin, 2 * NET_H1, 2 * NET_H1, R, NET_H2, th, nullptr, wsc2);
         w2h.insert(w2h.end(), th.begin(), th.end());
+        pack_lstm2_w16(Kin, 2 * NET_H1, R, NET_H2, th, wsc2);
+        w2w.insert(w2w.end(), th.begin(), th.end());
         pack_mx([&](int k, int blk, int r) {
                     const int col = gate_col(blk, r, NET_H2);
                     return k < 2 * NET_H1 ? Kin[(size_t)k * 4 * NET_H2 + col] : R[(size_t)(k - 2 * NET_H1) * 4 * NET_H2 + col];
@@ -1703,6 +1756,8 @@ inline int net_load(NetState &s, const float *blob, int C, hipStream_t st, std::
                             w4f[(base + lane) * 8 + e] = hi;
                             w4f[(base + 64 + lane) * 8 + e] = lo;
                         }
+    std::vector<uint16_t> w4w;
+    pack_l4_w16(W4, wsc4, w4w);
     // fused L4 on the MX pipe: per (dir, t) one fragment set [quarter(4)][kb(5)][lane][32 B] (one tile per quarter)
     std::vector<uint32_t> w4q, w4s;
     for (int d = 0; d < 2; ++d)
@@ -1746,6 +1801,7 @@ inline int net_load(NetState &s, const float *blob, int C, hipStream_t st, std::
         (rc = net_upload(s.d_w5, w5, st, err)) || (rc = net_upload(s.d_b5, b5, st, err)) || (rc = net_upload(s.d_wo, wo, st, err)) ||
         (rc = net_upload(s.d_bo, bo, st, err)) || (rc = net_upload_h(s.d_w1h, w1h, st, err)) || (rc = net_upload_h(s.d_w2h, w2h, st, err)) ||
         (rc = net_upload_h(s.d_w4h, w4h, st, err)) || (rc = net_upload_h(s.d_w4f, w4f, st, err)) ||
+        (rc = net_upload_h(s.d_w2w, w2w, st, err)) || (rc = net_upload_h(s.d_w4w, w4w, st, err)) ||
         (rc = net_upload_u(s.d_w1q, w1q, st, err)) || (rc = net_upload_u(s.d_w1s, w1s, st, err)) || (rc = net_upload_u(s.d_w2q, w2q, st, err)) ||
         (rc = net_upload_u(s.d_w2s, w2s, st, err)) || (rc = net_upload_u(s.d_w4q, w4q, st, err)) || (rc = net_upload_u(s.d_w4s, w4s, st, err)))
         return rc;
@@ -1846,14 +1902,14 @@ inline int net_forward_slice(NetState &s, const void *d_x, const int32_t *row_id
         prof("k_lstm1", 1);
         prof("k_lstm2", 0);
         if (rts)
-            hipLaunchKernelGGL((k_lstm2_w8<0, true>), g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2h, (const float *)s.d_b2, (int)n,
-                               (const half8 *)s.d_w4f, s.d_a4, ns, wsc2, wun2, wun4, s.d_tmo);
+            hipLaunchKernelGGL((k_lstm2_w16<0, true>), g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2w, (const float *)s.d_b2, (int)n,
+                               (const half8 *)s.d_w4w, s.d_a4, ns, wsc2, wun2, wun4, s.d_tmo);
         else if (mx)
             hipLaunchKernelGGL(k_lstm2_mx, g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2h, (const uint32_t *)s.d_w2q, (const uint32_t *)s.d_w2s,
                                (const float *)s.d_b2, (int)n, (const half8 *)s.d_w4f, (const uint32_t *)s.d_w4q, (const uint32_t *)s.d_w4s, s.d_a4, ns, s.d_tmo);
         else
-            hipLaunchKernelGGL((k_lstm2_w8<0, false>), g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2h, (const float *)s.d_b2, (int)n,
-                               (const half8 *)s.d_w4f, s.d_a4, ns, WSCALE, WUNSCALE, WUNSCALE, s.d_tmo);
+            hipLaunchKernelGGL((k_lstm2_w16<0, false>), g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2w, (const float *)s.d_b2, (int)n,
+                               (const half8 *)s.d_w4w, s.d_a4, ns, WSCALE, WUNSCALE, WUNSCALE, s.d_tmo);
         prof("k_lstm2", 1);
         heads_parts = 2;
     } else {

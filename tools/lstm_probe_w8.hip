@@ -1,4 +1,4 @@
-// lstm_probe_w8.hip — timing-only ablation of k_lstm2_w8 (layer 2 + fused L4, two wavefronts per SIMD) on random operands.
+// lstm_probe_w8.hip — timing-only ablation of k_lstm2_w16 (layer 2 + fused L4, two wavefronts per SIMD) on random operands.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/lstm_probe_w8.hip -o tools/lstm_probe_w8
 //   ABL bits: 1 = every weight load hits one L1-hot k-group (L1 -> register traffic kept, L2 -> L1 traffic gone), 2 = no gate math (cell update replaced by 3 adds), 16 = weights loaded for the first k-group only
 //   (register-stationary afterwards: no L2 -> L1 weight stream), 64 = no x DMA after the first step
@@ -15,12 +15,12 @@ template <int ABL>
 static float run(const _Float16 *x, const half8 *w, const float *b, int n, int reps) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
-    dim3 grid = C3R_DIR_ILV ? dim3(2, (n + 63) / 64) : dim3((n + 63) / 64, 2);      // (k_lstm2_w8 reads the direction from blockIdx.x then)
+    dim3 grid = C3R_DIR_ILV ? dim3(2, (n + 63) / 64) : dim3((n + 63) / 64, 2);      // (k_lstm2_w16 reads the direction from blockIdx.x then)
     const int ns = (n + 127) / 128 * 128;
-    hipLaunchKernelGGL((k_lstm2_w8<ABL>), grid, dim3(512), 0, 0, x, w, b, n, g_w4, g_a4, ns);
+    hipLaunchKernelGGL((k_lstm2_w16<ABL>), grid, dim3(512), 0, 0, x, w, b, n, g_w4, g_a4, ns);
     hipDeviceSynchronize();
     hipEventRecord(e0);
-    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL((k_lstm2_w8<ABL>), grid, dim3(512), 0, 0, x, w, b, n, g_w4, g_a4, ns);
+    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL((k_lstm2_w16<ABL>), grid, dim3(512), 0, 0, x, w, b, n, g_w4, g_a4, ns);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0; hipEventElapsedTime(&ms, e0, e1);
@@ -63,5 +63,6 @@ int main(int argc, char **argv) {
     };
     for (auto &e : r) printf("%-26s %8.3f ms  %7.1f algorithmic TFLOP/s (x3 executed = %6.1f = %4.1f %% of 2500)\n", e.name, e.ms, flop / e.ms / 1e9,
                              3 * flop / e.ms / 1e9, 3 * flop / e.ms / 1e9 / 2500 * 100);
+
     return 0;
 }

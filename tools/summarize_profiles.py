@@ -25,13 +25,13 @@ def short(name):
         return "rocprim_radix_sort"
     if "k_prep<" in name or "k_prepIL" in name:
         return "k_prep_write" if ("k_prep<true>" in name or "k_prepILb1" in name) else "k_prep_count"
-    m = re.search(r"k_lstm2_mx|k_lstm2_w8|k_lstm1_rs|k_lstm|k_[a-z0-9_]+", name)
+    m = re.search(r"k_lstm2_mx|k_lstm2_w16|k_lstm2_w8|k_lstm1_rs|k_lstm|k_[a-z0-9_]+", name)
     if not m:
         return name[:40]
     k = m.group(0)
     if k == "k_lstm1_rs":
         return "k_lstm1"
-    if k in ("k_lstm2_w8", "k_lstm2_mx"):
+    if k in ("k_lstm2_w16", "k_lstm2_w8", "k_lstm2_mx"):
         return "k_lstm2"
     if k == "k_lstm":
         return "k_lstm2" if ("ILi256E" in name or "Li160E" in name or re.search(r"k_lstm<256,", name)) else "k_lstm1"
