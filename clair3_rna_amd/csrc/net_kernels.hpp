@@ -309,7 +309,7 @@ __device__ __forceinline__ void sched_interleave() {
 
 // Operand layouts of the split-f16 kernels (32-row gate blocks permuted for a lane-local cell update, see k_lstm):
 //   Wp  : [dir][quarter(4)][g][tile][hi|lo][64 lanes] half8  (k-groups of 16; lane half hh owns k = 16g + 8hh + 0..7; x 2^12)
-//   xin : layer 1: int32 [n][33][CIN] (exact in f16, lo = 0); layer 2: hi plane then lo plane, each f16 [33][CIN/8][nstride][8]
+//   xin : layer 1: int32 [n][33][CIN] (staged as up to four f16 integers that sum to the count exactly, k_lstm1_rs); layer 2: hi plane then lo plane, each f16 [33][CIN/8][nstride][8]
 //   y   : hi plane then lo plane, each f16 [33][2H/8][nstride][8]
 //   W4p : the flatten + Dense(128) layer L4, fused into layer 2: [dir][t][blk(4)][g(H/16)][hi|lo][64 lanes] half8, x 2^12; after every
 //         step the fresh h_t is multiplied by the [160 x 128] slice of W4 that belongs to (t, direction) and accumulated in
@@ -1045,6 +1045,14 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 // was "load, wait an L2 round trip, use": 13-16 k of a step's 21.7 k clocks.  The price: the workgroup's two 32-site blocks go through one
 // accumulator one after the other (no registers for two), and every B fragment is read from LDS by sixteen wavefronts.
 // Wp: [dir][quarter][g][tile(4)][hi|lo][lane] (tile blk = 4 quarter + tile); the bias rides on input slot CIN (x = 1 there).
+// The counts: f16 holds integers exactly only up to 2048 and ends at 65504, and a window's flank is not bounded by the A5 rescale (it
+// divides by the depth of the centre position alone).  Every int32 count is therefore staged as FOUR f16 integers,
+//   x = 65536 T + r,  T = round(x / 65536) = th + tl,  r = rh + rl      (|T|, |r| <= 32768: an f16 and a remainder of at most 8 each),
+// exactly.  rh is what the K loop always multiplies (for |x| <= 2048 it is x itself and the other three are zero); the others are
+// multiplied only from the first step on at which one of them is non-zero at one of the workgroup's 64 sites — s_xlvl[step], set while
+// the counts are staged: 1 = some rl, 2 = some T (never with int16 windows): the workgroup leaves the ordinary time loop for one that
+// multiplies them before the K loop, the (wh + wl)(th + tl) sum scaled by 65536 in the accumulator.  A site's result does not depend
+// on whether its neighbours raised the level: the extra products of its own zeros are zeros.
 template <int CIN, bool YQ = false, bool RTS = false>
 __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_v, const half8 *__restrict__ Wp, _Float16 *__restrict__ y, int n, int nstride,
                                                    const int32_t *__restrict__ row_idx /* row of site i in xin (the tensor build writes windows as they arrive); null: i */,
@@ -1059,8 +1067,9 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
     typedef _Float16 half4 __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) _Float16 hb_hi[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) _Float16 hb_lo[2][WG_SITES][HP];
-    __shared__ __attribute__((aligned(16))) _Float16 xs[2][WG_SITES][XP];
-    // the cell state lives in LDS (one float4 per lane, block and wavefront: 32 KB of the 80 KB this workgroup leaves free): its 8 registers
+    __shared__ __attribute__((aligned(16))) _Float16 xs[4][2][WG_SITES][XP];      // the counts' parts rh, rl, th, tl (one array: one address, four offsets)
+    __shared__ int s_xlvl[NET_T];              // per step: 0 = the 64 sites' counts are rh alone, 1 = some rl, 2 = some T
+    // the cell state lives in LDS (one float4 per lane, block and wavefront: 32 KB; with the counts' four parts the workgroup holds 140 of the CU's 160 KB): its 8 registers
     // pay for the second B-operand buffer below
     __shared__ __attribute__((aligned(16))) float4 s_c[16][2][64];
     const int tid = threadIdx.x, lane = tid & 63, blk = tid >> 6;      // blk: the wavefront's tile of the direction (units 8 blk .. 8 blk + 7)
@@ -1070,7 +1079,11 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
     const size_t plane_out = (size_t)nstride * NET_T * 2 * H;
 
     for (int i = tid; i < WG_SITES * HP; i += 1024) { (&hb_hi[0][0][0])[i] = (_Float16)0.f; (&hb_lo[0][0][0])[i] = (_Float16)0.f; }
-    for (int i = tid; i < 2 * WG_SITES * XP; i += 1024) (&xs[0][0][0])[i] = ((i % XP) == CIN) ? (_Float16)1.f : (_Float16)0.f;
+    for (int i = tid; i < 2 * WG_SITES * XP; i += 1024) {
+        (&xs[0][0][0][0])[i] = ((i % XP) == CIN) ? (_Float16)1.f : (_Float16)0.f;
+        (&xs[1][0][0][0])[i] = (_Float16)0.f; (&xs[2][0][0][0])[i] = (_Float16)0.f; (&xs[3][0][0][0])[i] = (_Float16)0.f;
+    }
+    if (tid < NET_T) s_xlvl[tid] = 0;
 
     half8 wh[NG], wl[NG];
     {
@@ -1098,17 +1111,36 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
             else xr = *(const int2v *)(xin + (size_t)(xrow + (uint32_t)(tt_ * CIN)));
         }
     };
-    auto x_store = [&](int buf) {
+    auto x_store = [&](int buf, int step_) {
         if (xmine) {
             typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-            half2v v;
-            v[0] = (_Float16)(float)xr[0]; v[1] = (_Float16)(float)xr[1];
-            *(half2v *)&xs[buf][tid / NPC][2 * (tid % NPC)] = v;
+            half2v vrh, vrl;
+            int r[2] = {xr[0], xr[1]}, any_t = 0;
+            const int site = tid / NPC, slot = 2 * (tid % NPC);
+            if (!x16) {                                                                       // (int16 rows: T = 0, as initialised)
+                half2v vth, vtl;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int T = (r[e] >> 16) + ((r[e] >> 15) & 1);                          // round(x / 65536), |T| <= 32768
+                    r[e] = (int)((uint32_t)r[e] - ((uint32_t)T << 16));                       // -32768 .. 32767 (for |x| <= 32767: x itself)
+                    vth[e] = (_Float16)(float)T;
+                    vtl[e] = (_Float16)(float)(T - (int)(float)vth[e]);
+                    any_t |= T;
+                }
+                *(half2v *)&xs[2][buf][site][slot] = vth; *(half2v *)&xs[3][buf][site][slot] = vtl;
+            }
+            vrh[0] = (_Float16)(float)r[0]; vrh[1] = (_Float16)(float)r[1];
+            const int rl0 = r[0] - (int)(float)vrh[0], rl1 = r[1] - (int)(float)vrh[1];
+            vrl[0] = (_Float16)(float)rl0; vrl[1] = (_Float16)(float)rl1;
+            const int any_rl = rl0 | rl1;
+            *(half2v *)&xs[0][buf][site][slot] = vrh;
+            *(half2v *)&xs[1][buf][site][slot] = vrl;
+            if (any_rl | any_t) atomicMax(&s_xlvl[step_], any_t ? 2 : 1);
         }
     };
     __syncthreads();
     x_fetch(dir ? NET_T - 1 : 0);
-    x_store(0);
+    x_store(0, 0);
     __syncthreads();
 #ifndef C3R_L1_K8
 #define C3R_L1_K8 1          // k_lstm1_rs, 18 channels: the 3 used slots of the second input group as a K = 8 product
@@ -1118,27 +1150,55 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
 #endif
     if (C3R_L1_RS_PRIO > 0 && blk >= C3R_L1_RS_PRIO) __builtin_amdgcn_s_setprio(1);
 
-    for (int step = 0; step < NET_T; ++step) {
+    // One time step.  DEEP = false is the loop every ordinary window runs; DEEP = true multiplies the counts' other parts as well and
+    // loads its B fragments in place (no second buffer: its registers go to those parts, and the path is rare)
+    auto one_step = [&](const int step, auto deep_c) {
+        constexpr bool DEEP = decltype(deep_c)::value;
         const int t = dir ? NET_T - 1 - step : step;
         const int cur = step & 1, nxt = cur ^ 1;
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) {
+            const _Float16 *xb = &xs[0][cur][32 * sb + j][8 * hh];      // the lane's B fragment of group 0, part rh: the others at constant offsets
+            constexpr int XPART = 2 * WG_SITES * XP;
             // x_{t+1}: requested when the second block starts — it lands under that block's K loop, and its two registers are not alive under the first
             if (sb == 1 && step + 1 < NET_T) x_fetch(dir ? NET_T - 2 - step : step + 1);
             floatx16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            // counts beyond one f16 somewhere in the workgroup (see the header): their other parts first.  Full K = 16 products also for the
+            // second group (its unused slots are zeros on both sides); the level is uniform over the workgroup
+            if constexpr (DEEP) {
+                if (__builtin_amdgcn_readfirstlane(s_xlvl[step]) == 2) {
+#pragma unroll
+                    for (int g = 0; g < NGX; ++g) {
+                        const half8 th = *(const half8 *)(xb + 2 * XPART + 16 * g), tl = *(const half8 *)(xb + 3 * XPART + 16 * g);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[g], th, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[g], th, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[g], tl, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[g], tl, acc, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] *= 65536.f;
+                }
+#pragma unroll
+                for (int g = 0; g < NGX; ++g) {
+                    const half8 rl = *(const half8 *)(xb + XPART + 16 * g);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[g], rl, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[g], rl, acc, 0, 0, 0);
+                }
+            }
             // B operands double-buffered: group g + 1's fragments are requested before group g's MFMAs are issued
             half8 bh[2], bl[2];
             auto ldb = [&](auto gc, half8 &h, half8 &l) {
                 constexpr int G = decltype(gc)::value;
-                if constexpr (G < NGX) h = *(const half8 *)&xs[cur][32 * sb + j][16 * G + 8 * hh];
+                if constexpr (G < NGX) h = *(const half8 *)(xb + 16 * G);
                 else { h = *(const half8 *)&hb_hi[cur][32 * sb + j][16 * (G - NGX) + 8 * hh]; l = *(const half8 *)&hb_lo[cur][32 * sb + j][16 * (G - NGX) + 8 * hh]; }
             };
-            ldb(std::integral_constant<int, 0>{}, bh[0], bl[0]);
+            if constexpr (!DEEP) ldb(std::integral_constant<int, 0>{}, bh[0], bl[0]);
             static_for<0, NG>([&](auto gc) {
                 constexpr int G = decltype(gc)::value;
-                if constexpr (G + 1 < NG) ldb(std::integral_constant<int, G + 1>{}, bh[(G + 1) & 1], bl[(G + 1) & 1]);
+                if constexpr (DEEP) ldb(std::integral_constant<int, G>{}, bh[G & 1], bl[G & 1]);
+                else if constexpr (G + 1 < NG) ldb(std::integral_constant<int, G + 1>{}, bh[(G + 1) & 1], bl[(G + 1) & 1]);
                 if constexpr (C3R_L1_K8 && G == NGX - 1 && CIN + 1 <= 16 + 4) {
                     // the second input group holds channels 16 .. CIN - 1 and the bias slot CIN, zeros after them: a K = 8 product covers it
                     // (lane half hh takes k = 4 hh .. 4 hh + 3 of the group: for hh = 0 the first half of the lane's K = 16 fragment, for
@@ -1150,7 +1210,7 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                 } else {
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bh[G & 1], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[G], bh[G & 1], acc, 0, 0, 0);
-                if constexpr (G >= NGX) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bl[G & 1], acc, 0, 0, 0);      // (the int32 input has no lo half)
+                if constexpr (G >= NGX) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bl[G & 1], acc, 0, 0, 0);      // (the counts' other parts: before the loop)
                 }
             });
             // ---- lane-local cell update of the block (four units per lane)
@@ -1206,10 +1266,17 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                 *(int *)(qp + (size_t)2 * nstride * 8) = w_hi;
             }
         }
-        if (step + 1 < NET_T) x_store(nxt);
+        if (step + 1 < NET_T) x_store(nxt, step + 1);
         __syncthreads();                                       // h_t and x_{t+1} complete; everyone is done with h_{t-1} and x_t (LDS counters
                                                                // instead of this barrier, as in layer 2, measured slower: 6.3 against 5.8 ms)
+    };
+    // the ordinary loop runs until a step's counts need more than one f16 each; the workgroup does the rest of its steps in the other one
+    int step = 0;
+    for (; step < NET_T; ++step) {
+        if (__builtin_amdgcn_readfirstlane(s_xlvl[step])) break;
+        one_step(step, std::false_type{});
     }
+    for (; step < NET_T; ++step) one_step(step, std::true_type{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1689,7 +1756,7 @@ inline int net_load(NetState &s, const float *blob, int C, hipStream_t st, std::
         w1.insert(w1.end(), tw.begin(), tw.end()); b1.insert(b1.end(), tb.begin(), tb.end());
         pack_lstm_dir_h(Kin, C, inp1, R, NET_H1, th, b, wsc1);
         w1h.insert(w1h.end(), th.begin(), th.end());
-        // (layer 1: the recurrent part only — the integer pileup counts are exact in f16 but not in fp8)
+        // (layer 1: the recurrent part only — the integer pileup counts go through the f16 pipe, split exactly (k_lstm1_rs), never through fp8)
         pack_mx([&](int k, int blk, int r) { return R[(size_t)k * 4 * NET_H1 + gate_col(blk, r, NET_H1)]; }, 4 * NET_H1 / 32, NET_H1 / 32, 0, NET_H1 / 32, tq, ts);
         w1q.insert(w1q.end(), tq.begin(), tq.end()); w1s.insert(w1s.end(), ts.begin(), ts.end());
     }

@@ -148,7 +148,10 @@ int c3r_load_weights(c3r_ctx *ctx, const float *blob, int64_t n_floats, int chan
 int64_t c3r_weight_count(int channels);
 /* Arithmetic of the network GEMMs: 0 = fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32); 1 (default) = split-f16:
  * every fp32 operand carried as hi + lo halves, products hi*hi + hi*lo + lo*hi accumulated in fp32 on the f16 matrix
- * pipe (fp32-equivalent: both modes meet the 1e-4 probability tolerance against the fp32 oracle);
+ * pipe (fp32-equivalent: both modes meet the 1e-4 probability tolerance against the fp32 oracle).  The input counts are no exception in
+ * modes 1, 2 and 3: layer 1 carries every int32 count as up to four f16 integers that sum to it exactly (one f16 holds integers only up to
+ * 2048 and ends at 65504, and a window's flank is not bounded by the depth > 216 rescale, which divides by the centre position's depth),
+ * so any count a caller or the tensor build delivers is taken as it is — nothing is rounded, nothing refused, no mode steps down;
  * 2 = f16 main term + both correction terms on the block-scaled fp8 pipe (v_mfma_scale_f32_32x32x64_f8f6f4): ~1.15x the
  * throughput of mode 1, max |dP| 2-3e-5 on N(0, 0.05) weights but NOT robust to weights of 2-3x that norm — opt-in;
  * 3 = auto: mode 2 if it agrees with mode 1 to 4e-5 on 2048 calibration windows run through the loaded weights (measured at

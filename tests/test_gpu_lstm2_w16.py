@@ -3,6 +3,8 @@ need a run-time scale, on ragged batches, and bit for bit wherever a site sits i
 import numpy as np
 import pytest
 
+from tests import helpers as H
+
 pytestmark = pytest.mark.gpu
 
 
@@ -25,13 +27,6 @@ def _windows(n, C, seed):
     return X
 
 
-def _blob_offsets(C):
-    H1, H2 = 128, 160
-    n1 = C * 4 * H1 + H1 * 4 * H1 + 4 * H1
-    n2 = 2 * H1 * 4 * H2 + H2 * 4 * H2 + 4 * H2
-    return dict(l2=2 * n1, l2_bias0=2 * n1 + 2 * H1 * 4 * H2 + H2 * 4 * H2, l4=2 * n1 + 2 * n2)
-
-
 @pytest.mark.parametrize("C", [18, 30])
 def test_w16_matches_oracle(eng, C):
     from clair3_rna_amd import synth
@@ -49,7 +44,7 @@ def test_w16_run_time_scale_matches_oracle(eng):
     from clair3_rna_amd import synth
     from oracle import oracle as orc
     C = 18
-    o = _blob_offsets(C)
+    o = H.blob_offsets(C)
     w = synth.random_weights(C, seed=1234)
     w[o["l2_bias0"] + 3] = 30.0
     w[o["l2"] + 11] = 9.0

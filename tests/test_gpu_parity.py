@@ -244,14 +244,6 @@ def test_precision_f16_f8_opt_in_and_auto_guard(eng):
         eng.set_precision("f16x3")
 
 
-def _blob_offsets(C):
-    """start of (LSTM1 dir0 K, R, b | dir1 ... | LSTM2 ... | L4 W, b | heads) in the weight blob (include/c3r.h, c3r_load_weights)."""
-    H1, H2 = 128, 160
-    n1 = C * 4 * H1 + H1 * 4 * H1 + 4 * H1
-    n2 = 2 * H1 * 4 * H2 + H2 * 4 * H2 + 4 * H2
-    return dict(l1=0, l1_bias0=C * 4 * H1 + H1 * 4 * H1, l2=2 * n1, l2_bias0=2 * n1 + 2 * H1 * 4 * H2 + H2 * 4 * H2, l4=2 * n1 + 2 * n2, l4_bias=2 * n1 + 2 * n2 + 33 * 320 * 128)
-
-
 def test_split_f16_guard_against_weights_f16_cannot_hold(eng):
     """Nothing in clair3_rna/model.py:126-172 bounds the weights, and the split-f16 operands are f16 numbers (65504 at most) times a scale:
     c3r_load_weights picks a per-layer power-of-two scale from max |w| (2^12 for ordinary weights), refuses non-finite values, measures
@@ -263,7 +255,7 @@ def test_split_f16_guard_against_weights_f16_cannot_hold(eng):
     from oracle import oracle as orc
     rng = np.random.RandomState(21)
     C = 18
-    o = _blob_offsets(C)
+    o = H.blob_offsets(C)
     X = np.concatenate([_pileup_like(200, C, 31), rng.randint(-40, 41, size=(40, 33, C)).astype(np.int32)])
     base = synth.random_weights(C, seed=1234)
     try:
