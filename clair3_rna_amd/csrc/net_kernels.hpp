@@ -67,12 +67,42 @@ __device__ __forceinline__ float fast_sigmoid(float x) {
 __device__ __forceinline__ float fast_tanh(float x) {
     return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.8853900817779268f * x)), -1.0f);
 }
-// (1 - b) / ((1 + a)(1 + b)) with a, b = clamped exp2 values: sigmoid(i) * tanh(g) and sigmoid(o) * tanh(c) of the cell update.
+// (1 - b) / ((1 + a)(1 + b)) with a, b = exp2 values: sigmoid(i) * tanh(g) and sigmoid(o) * tanh(c) of the cell update.
 // Written with explicit FMAs — t = 1 + a, d = t * b + t, r = 1 / d, r - b * r — 3 VALU operations + 1 rcp instead of 5 + 1.
+// b is always clamped (fminf(.., 1e18f) at the call sites): b = inf would give r - inf * 0 = NaN.  a = inf gives d = inf, r = 0 and
+// the result 0 — the limit of sigmoid — but only while b > 0: with b = 0, t * b + t is inf * 0 + inf = NaN.  So a keeps its clamp in
+// i * g, where g's exp2 underflows to 0 from a pre-activation of +52 on, and goes without it in o * tanh(c), where |c| <= 33 (it grows
+// by at most one a step) keeps b above 2^-96.
 __device__ __forceinline__ float gate_frac(float a, float b) {
     const float t = 1.0f + a;
     const float r = __builtin_amdgcn_rcpf(fmaf(t, b, t));
     return fmaf(-b, r, r);
+}
+// Value barrier of the cell updates: the value passes through one VGPR as it is.  Put on the results of the two FMA groups of a cell
+// update (i*g, f*c + i*g) it keeps the SLP vectoriser from pairing neighbouring cells into v_pk_fma_f32, which is slower than the two
+// v_fma_f32 it replaces beside MFMAs (measured in both layers: profiles/lstm_issue_stream_ab.txt); no instruction is emitted for it.
+__device__ __forceinline__ float cell_fence(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+// The split of two cells' h into f16 pairs, hi = f16(h) and lo = f16(h - hi) (both round-to-nearest-even), in four instructions:
+// v_cvt_pk_f16_f32 of the two h, one v_fma_mix_f32 per cell that reads its f16 half of the packed register directly (-hi * 1 + h,
+// exact in fp32), v_cvt_pk_f16_f32 of the two differences.  h enters through a value barrier, so it is evaluated once, in fp32
+// (without it the compiler forms it three times: v_fma_f32, v_fma_mixlo_f16 and v_fma_mixhi_f16 of the same operands).
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+typedef float float2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split_h2(float h0, float h1, half2v &hi, half2v &lo, float &d0, float &d1) {
+    asm("" : "+v"(h0));
+    asm("" : "+v"(h1));
+    const float2v h = {h0, h1};
+    hi = __builtin_convertvector(h, half2v);
+    // (the compiler has no pattern that reaches v_fma_mix_f32 from h - (float)hi: it converts first, then subtracts)
+    // -hi * 1.0 + h: the f16 half negated by its source modifier; the inline constant 1.0 in an f16-selected source reads as f16 1.0
+    // (outputs bit-identical to the constant in an SGPR and to the plain conversions on a fenced h: profiles/lstm_issue_stream_ab.txt)
+    asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,1,0]" : "=v"(d0) : "v"(hi), "v"(h0));
+    asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "=v"(d1) : "v"(hi), "v"(h1));
+    const float2v d = {d0, d1};
+    lo = __builtin_convertvector(d, half2v);
 }
 __device__ __forceinline__ float selu(float x) {
     const float scale = 1.0507009873554805f, alpha = 1.6732632423543772f;
@@ -401,7 +431,8 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
     __shared__ __attribute__((aligned(16))) float s_bias[NBLK][2][16];          // 2^s b: [tile][st][4q + m]
     __shared__ int s_ctr[4];        // C3R_W8_ASYNC: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // in an SGPR: the weight addresses below are scalar arithmetic plus one lane offset
     const int c16 = lane & 15, q4 = lane >> 4;
     const int sq = C3R_W8_MAP ? (wave >> 1) : (wave & 3);
     const bool heavy3 = C3R_W8_MAP ? !(wave & 1) : (wave < 4);
@@ -447,7 +478,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
         constexpr int NT = decltype(ntc)::value, TOFF = decltype(toffc)::value;
         constexpr bool L4T = decltype(l4c)::value;
         constexpr int NTH = NT + (L4T ? 1 : 0);
-        const half8 *wl = Wp + ((size_t)(dir * 4 + sq) * NU) * NTQ * 2 * 64 + (size_t)TOFF * 2 * 64 + lane;
+        const half8 *wl = Wp + ((size_t)(dir * 4 + sq) * NU) * NTQ * 2 * 64 + (size_t)TOFF * 2 * 64;      // uniform; the lane's fragment: + lane
         float cst[NT][2 * SB];          // [tile][4 st + sb]
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt)
@@ -462,6 +493,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                 for (int r = 0; r < 4; ++r) facc[st][sb][r] = 0.f;
 
         typedef const half8 __attribute__((address_space(1))) *gptr_t;
+        const uint32_t wlane = (uint32_t)lane;
         for (int step = 0; step < NET_T; ++step) {
             const int t = dir ? NET_T - 1 - step : step;
             const int tprev = step ? (dir ? t + 1 : t - 1) : t;      // step 0: h_{-1} = 0, any valid slice contributes nothing
@@ -484,20 +516,20 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                 }
             };
             auto ldw = [&](int u, half8 (&ah)[NTH], half8 (&al)[NTH]) {
-                uintptr_t wbase = (uintptr_t)wl;                 // address laundering, address_space(1): see "Operand layouts", ldw
-                asm volatile("" : "+v"(wbase));
-                const gptr_t wg = (gptr_t)wbase + (size_t)((ABL & 1) ? 0 : u) * NTQ * 2 * 64;
+                // address laundering, address_space(1): see "Operand layouts", ldw.  The unit's base is uniform: it is advanced by scalar
+                // adds and laundered in an SGPR pair; the loads take it as their scalar base with the lane offset in one VGPR
+                gptr_t wg = (gptr_t)wl + (size_t)((ABL & 1) ? 0 : u) * NTQ * 2 * 64;
+                asm volatile("" : "+s"(wg));
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt) {
                     if ((ABL & 16) && u > 0) continue;
-                    ah[tt] = wg[(tt * 2 + 0) * 64]; al[tt] = wg[(tt * 2 + 1) * 64];
+                    ah[tt] = wg[(tt * 2 + 0) * 64 + wlane]; al[tt] = wg[(tt * 2 + 1) * 64 + wlane];
                 }
                 if constexpr (L4T) {
                     if (u >= 2 * NGX && !((ABL & 16) && u > 2 * NGX)) {
-                        uintptr_t w4base = (uintptr_t)(W4p + (((size_t)(dir * NET_T + tprev) * 4 + sq) * 2 * NGH) * 2 * 64 + lane);
-                        asm volatile("" : "+v"(w4base));
-                        const gptr_t w4 = (gptr_t)w4base + (size_t)(u - 2 * NGX) * 2 * 64;
-                        ah[NT] = w4[0]; al[NT] = w4[64];
+                        gptr_t w4 = (gptr_t)(W4p + (((size_t)(dir * NET_T + tprev) * 4 + sq) * 2 * NGH) * 2 * 64) + (size_t)(u - 2 * NGX) * 2 * 64;
+                        asm volatile("" : "+s"(w4));
+                        ah[NT] = w4[wlane]; al[NT] = w4[64 + wlane];
                     }
                 }
             };
@@ -593,13 +625,13 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
 #pragma unroll
                     for (int u = 0; u < NC; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[tt][u / SB][u % SB][2]), 1e18f);
 #pragma unroll
-                    for (int u = 0; u < NC; ++u) eo[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][3]), 1e18f);
+                    for (int u = 0; u < NC; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][3]);
 #pragma unroll
-                    for (int u = 0; u < NC; ++u) ei[u] = gate_frac(ei[u], eg[u]);
+                    for (int u = 0; u < NC; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));
 #pragma unroll
                     for (int u = 0; u < NC; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
 #pragma unroll
-                    for (int u = 0; u < NC; ++u) cq[u] = fmaf(ef[u], cq[u], ei[u]);
+                    for (int u = 0; u < NC; ++u) cq[u] = cell_fence(fmaf(ef[u], cq[u], ei[u]));
 #pragma unroll
                     for (int u = 0; u < NC; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
 #pragma unroll
@@ -609,15 +641,9 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                 for (int u = 0; u < NC; ++u) cst[tt][u] = cq[u];
 #pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
-                    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
                     half2v vh, vl;
-#pragma unroll
-                    for (int st = 0; st < 2; ++st) {
-                        vh[st] = (_Float16)hval[SB * st + sb];
-                        float d = hval[SB * st + sb] - (float)vh[st];
-                        asm volatile("" : "+v"(d));            // subtract, then convert (never v_fma_mixlo_f16: it rounds differently)
-                        vl[st] = (_Float16)d;
-                    }
+                    float d0, d1;
+                    split_h2(hval[sb], hval[SB + sb], vh, vl, d0, d1);
                     *(half2v *)&hb_hi[nxt][16 * sb + c16][8 * (sq * NTQ + TOFF + tt) + 2 * q4] = vh;
                     *(half2v *)&hb_lo[nxt][16 * sb + c16][8 * (sq * NTQ + TOFF + tt) + 2 * q4] = vl;
                 }
@@ -945,13 +971,13 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 #pragma unroll
                 for (int u = 0; u < NU; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[tt][u >> 2][4 * (u & 3) + 2]), 1e18f);
 #pragma unroll
-                for (int u = 0; u < NU; ++u) eo[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 3]), 1e18f);
+                for (int u = 0; u < NU; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 3]);
 #pragma unroll
-                for (int u = 0; u < NU; ++u) ei[u] = gate_frac(ei[u], eg[u]);
+                for (int u = 0; u < NU; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));
 #pragma unroll
                 for (int u = 0; u < NU; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
 #pragma unroll
-                for (int u = 0; u < NU; ++u) cq[u] = fmaf(ef[u], cq[u], ei[u]);
+                for (int u = 0; u < NU; ++u) cq[u] = cell_fence(fmaf(ef[u], cq[u], ei[u]));
 #pragma unroll
                 for (int u = 0; u < NU; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
 #pragma unroll
@@ -962,15 +988,13 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 #pragma unroll
                     for (int q = 0; q < 4; ++q) cst[tt][sb][q] = cq[4 * sb + q];
                     typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-                    half4 vh;
+                    half2v vh01, vh23, vl01, vl23;
                     float lo[4];
+                    split_h2(hval[4 * sb + 0], hval[4 * sb + 1], vh01, vl01, lo[0], lo[1]);
+                    split_h2(hval[4 * sb + 2], hval[4 * sb + 3], vh23, vl23, lo[2], lo[3]);
+                    const half4 vh = __builtin_shufflevector(vh01, vh23, 0, 1, 2, 3);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        vh[q] = (_Float16)hval[4 * sb + q];
-                        float d = hval[4 * sb + q] - (float)vh[q];
-                        asm volatile("" : "+v"(d));            // subtract, then convert (never v_fma_mixlo_f16: it rounds differently)
-                        lo[q] = d * 262144.f;
-                    }
+                    for (int q = 0; q < 4; ++q) lo[q] *= 262144.f;
                     *(half4 *)&hb_hi[nxt][32 * sb + j][8 * T + 4 * hh] = vh;
                     int w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], 0, false);
                     w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], w_lo, true);
@@ -1058,27 +1082,25 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                                                    const int32_t *__restrict__ row_idx /* row of site i in xin (the tensor build writes windows as they arrive); null: i */,
                                                    float wun_arg = WUNSCALE /* RTS: 2^-s of the layer's weight scale (k_lstm2_w16) */,
                                                    int x16 = 0 /* the rows are int16 (the tensor build's windows), not int32 (a caller's batch) */) {
-    const int32_t *__restrict__ xin = (const int32_t *)xin_v;
-    const int16_t *__restrict__ xin16 = (const int16_t *)xin_v;
     const float wun = RTS ? wun_arg : WUNSCALE;
     constexpr int H = NET_H1, NGX = 2, NGH = H / 16, NG = NGX + NGH, HP = H + 8, NTQ = 4, WG_SITES = 64, HV = H / 8, XP = 40;
     constexpr int NPC = (CIN + 1) / 2;
     static_assert(CIN % 2 == 0 && CIN < 32 && WG_SITES * NPC <= 1024, "even channel count, one free slot for the bias, one x piece per thread");
     typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) _Float16 hb_hi[2][WG_SITES][HP];
-    __shared__ __attribute__((aligned(16))) _Float16 hb_lo[2][WG_SITES][HP];
+    __shared__ __attribute__((aligned(16))) _Float16 hb[2][2][WG_SITES][HP];      // h_t: [step parity][hi | lo] — a lane's hi and lo fragments of a block: one address, constant offsets
     __shared__ __attribute__((aligned(16))) _Float16 xs[4][2][WG_SITES][XP];      // the counts' parts rh, rl, th, tl (one array: one address, four offsets)
     __shared__ int s_xlvl[NET_T];              // per step: 0 = the 64 sites' counts are rh alone, 1 = some rl, 2 = some T
     // the cell state lives in LDS (one float4 per lane, block and wavefront: 32 KB; with the counts' four parts the workgroup holds 140 of the CU's 160 KB): its 8 registers
     // pay for the second B-operand buffer below
     __shared__ __attribute__((aligned(16))) float4 s_c[16][2][64];
-    const int tid = threadIdx.x, lane = tid & 63, blk = tid >> 6;      // blk: the wavefront's tile of the direction (units 8 blk .. 8 blk + 7)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int blk = __builtin_amdgcn_readfirstlane(tid >> 6);          // the wavefront's tile of the direction (units 8 blk .. 8 blk + 7); in an SGPR: what depends on it and the step alone is scalar arithmetic
     const int j = lane & 31, hh = lane >> 5;
     const int dir = C3R_DIR_ILV ? blockIdx.x : blockIdx.y;
     const int site0 = (C3R_DIR_ILV ? blockIdx.y : blockIdx.x) * WG_SITES;
     const size_t plane_out = (size_t)nstride * NET_T * 2 * H;
 
-    for (int i = tid; i < WG_SITES * HP; i += 1024) { (&hb_hi[0][0][0])[i] = (_Float16)0.f; (&hb_lo[0][0][0])[i] = (_Float16)0.f; }
+    for (int i = tid; i < 2 * WG_SITES * HP; i += 1024) (&hb[0][0][0][0])[i] = (_Float16)0.f;
     for (int i = tid; i < 2 * WG_SITES * XP; i += 1024) {
         (&xs[0][0][0][0])[i] = ((i % XP) == CIN) ? (_Float16)1.f : (_Float16)0.f;
         (&xs[1][0][0][0])[i] = (_Float16)0.f; (&xs[2][0][0][0])[i] = (_Float16)0.f; (&xs[3][0][0][0])[i] = (_Float16)0.f;
@@ -1105,10 +1127,14 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
         if (row_idx) sj = row_idx[sj];
         xrow = (uint32_t)sj * (uint32_t)(NET_T * CIN) + 2u * (uint32_t)(tid % NPC);
     }
+    // (the address: uniform base + 32-bit index x element size, the size a run-time scalar — one v_mad_u64_u32 and no 64-bit index held in registers)
+    uint32_t xesz = x16 ? 2u : 4u;
+    asm volatile("" : "+s"(xesz));       // (opaque: a known power of two becomes a 64-bit vector shift and a zero register kept for it)
     auto x_fetch = [&](int tt_) {
         if (xmine) {
-            if (x16) { const int pr = *(const int *)(xin16 + (size_t)(xrow + (uint32_t)(tt_ * CIN))); xr[0] = (int)(int16_t)(pr & 0xffff); xr[1] = pr >> 16; }
-            else xr = *(const int2v *)(xin + (size_t)(xrow + (uint32_t)(tt_ * CIN)));
+            const char *xa = (const char *)xin_v + (uint64_t)(xrow + (uint32_t)(tt_ * CIN)) * xesz;
+            if (x16) { const int pr = *(const int *)xa; xr[0] = (int)(int16_t)(pr & 0xffff); xr[1] = pr >> 16; }
+            else xr = *(const int2v *)xa;
         }
     };
     auto x_store = [&](int buf, int step_) {
@@ -1149,6 +1175,18 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
 #define C3R_L1_RS_PRIO 0     // k_lstm1_rs: raise the priority of the wavefronts that arrive last on their SIMD (blk >= this value; 0: off)
 #endif
     if (C3R_L1_RS_PRIO > 0 && blk >= C3R_L1_RS_PRIO) __builtin_amdgcn_s_setprio(1);
+    // The lane's LDS addresses: four registers for the whole loop.  Each is the address of the lane's first access of its kind, the
+    // step's parity included (moved by one buffer at the end of every step); blocks, groups, the hi | lo planes and the counts' parts
+    // are constant offsets of the instructions.  (Left to the compiler: ten registers of addresses that differ by constants.)
+    typedef const char __attribute__((address_space(3))) *lds_t;
+    typedef char __attribute__((address_space(3))) *ldsw_t;
+    typedef const half8 __attribute__((address_space(3))) *lds_h8;
+    constexpr int XBUF = WG_SITES * XP * 2, HBUF = 2 * WG_SITES * HP * 2, HLO = WG_SITES * HP * 2, XPARTB = 2 * XBUF;      // bytes
+    lds_t xrd = (lds_t)&xs[0][0][j][8 * hh];                  // B fragments of x_t, parity 0 first
+    lds_t hrd = (lds_t)&hb[0][0][j][8 * hh];                  // B fragments of h_{t-1}
+    ldsw_t hwr = (ldsw_t)&hb[1][0][j][8 * blk + 4 * hh];      // the lane's four units of h_t
+    const ldsw_t scp = (ldsw_t)&s_c[blk][0][lane];
+    asm volatile("" : "+v"(xrd), "+v"(hrd), "+v"(hwr));
 
     // One time step.  DEEP = false is the loop every ordinary window runs; DEEP = true multiplies the counts' other parts as well and
     // loads its B fragments in place (no second buffer: its registers go to those parts, and the path is rare)
@@ -1156,10 +1194,16 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
         constexpr bool DEEP = decltype(deep_c)::value;
         const int t = dir ? NET_T - 1 - step : step;
         const int cur = step & 1, nxt = cur ^ 1;
+        // y1 rows of the step: a uniform base (SGPRs) and one 32-bit lane offset
+        typedef _Float16 __attribute__((address_space(1))) *gh_t;
+        typedef half4 __attribute__((address_space(1))) *gh4_t;
+        gh_t yrow = (gh_t)(y + ((size_t)t * (2 * HV) + dir * HV + blk) * nstride * 8 + (size_t)site0 * 8);
+        asm volatile("" : "+s"(yrow));       // (stays a scalar base: otherwise the lane offset is folded into a 64-bit vector pointer outside the loop)
+        const uint32_t ylane = (uint32_t)(j * 8 + 4 * hh);
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) {
-            const _Float16 *xb = &xs[0][cur][32 * sb + j][8 * hh];      // the lane's B fragment of group 0, part rh: the others at constant offsets
-            constexpr int XPART = 2 * WG_SITES * XP;
+            const lds_t xb = xrd + 32 * sb * XP * 2;      // the lane's B fragment of group 0, part rh: the others at constant offsets
+            const lds_t hb_r = hrd + 32 * sb * HP * 2;
             // x_{t+1}: requested when the second block starts — it lands under that block's K loop, and its two registers are not alive under the first
             if (sb == 1 && step + 1 < NET_T) x_fetch(dir ? NET_T - 2 - step : step + 1);
             floatx16 acc;
@@ -1171,7 +1215,7 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                 if (__builtin_amdgcn_readfirstlane(s_xlvl[step]) == 2) {
 #pragma unroll
                     for (int g = 0; g < NGX; ++g) {
-                        const half8 th = *(const half8 *)(xb + 2 * XPART + 16 * g), tl = *(const half8 *)(xb + 3 * XPART + 16 * g);
+                        const half8 th = *(lds_h8)(xb + 2 * XPARTB + 32 * g), tl = *(lds_h8)(xb + 3 * XPARTB + 32 * g);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[g], th, acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[g], th, acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[g], tl, acc, 0, 0, 0);
@@ -1182,23 +1226,29 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                 }
 #pragma unroll
                 for (int g = 0; g < NGX; ++g) {
-                    const half8 rl = *(const half8 *)(xb + XPART + 16 * g);
+                    const half8 rl = *(lds_h8)(xb + XPARTB + 32 * g);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[g], rl, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[g], rl, acc, 0, 0, 0);
                 }
             }
-            // B operands double-buffered: group g + 1's fragments are requested before group g's MFMAs are issued
+            // B operands double-buffered: group g + 1's fragments (hi and lo together) are requested before group g's MFMAs are issued.
+            // The fences hold the compiler to it: left alone it sinks every read to its first use, one register quad, a full
+            // lgkmcnt(0) round trip in front of each MFMA pair
             half8 bh[2], bl[2];
             auto ldb = [&](auto gc, half8 &h, half8 &l) {
                 constexpr int G = decltype(gc)::value;
-                if constexpr (G < NGX) h = *(const half8 *)(xb + 16 * G);
-                else { h = *(const half8 *)&hb_hi[cur][32 * sb + j][16 * (G - NGX) + 8 * hh]; l = *(const half8 *)&hb_lo[cur][32 * sb + j][16 * (G - NGX) + 8 * hh]; }
+                if constexpr (G < NGX) h = *(lds_h8)(xb + 32 * G);
+                else { h = *(lds_h8)(hb_r + 32 * (G - NGX)); l = *(lds_h8)(hb_r + HLO + 32 * (G - NGX)); }
             };
             if constexpr (!DEEP) ldb(std::integral_constant<int, 0>{}, bh[0], bl[0]);
             static_for<0, NG>([&](auto gc) {
                 constexpr int G = decltype(gc)::value;
                 if constexpr (DEEP) ldb(std::integral_constant<int, G>{}, bh[G & 1], bl[G & 1]);
-                else if constexpr (G + 1 < NG) ldb(std::integral_constant<int, G + 1>{}, bh[(G + 1) & 1], bl[(G + 1) & 1]);
+                else {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (G + 1 < NG) ldb(std::integral_constant<int, G + 1>{}, bh[(G + 1) & 1], bl[(G + 1) & 1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 if constexpr (C3R_L1_K8 && G == NGX - 1 && CIN + 1 <= 16 + 4) {
                     // the second input group holds channels 16 .. CIN - 1 and the bias slot CIN, zeros after them: a K = 8 product covers it
                     // (lane half hh takes k = 4 hh .. 4 hh + 3 of the group: for hh = 0 the first half of the lane's K = 16 fragment, for
@@ -1217,8 +1267,8 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
             const float K1 = -1.4426950408889634f * wun, K2 = -2.8853900817779268f * wun;
             float ei[4], ef[4], eg[4], eo[4], cq[4], hval[4];
             {
-                const float4 c4 = s_c[blk][sb][lane];
-                cq[0] = c4.x; cq[1] = c4.y; cq[2] = c4.z; cq[3] = c4.w;
+                const floatx4 c4 = *(floatx4 __attribute__((address_space(3))) *)(scp + sb * 64 * 16);
+                cq[0] = c4[0]; cq[1] = c4[1]; cq[2] = c4[2]; cq[3] = c4[3];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[4 * u + 0]), 1e18f);
@@ -1227,46 +1277,51 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
 #pragma unroll
             for (int u = 0; u < 4; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[4 * u + 2]), 1e18f);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) eo[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[4 * u + 3]), 1e18f);
+            for (int u = 0; u < 4; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * acc[4 * u + 3]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) ei[u] = gate_frac(ei[u], eg[u]);
+            for (int u = 0; u < 4; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));
 #pragma unroll
             for (int u = 0; u < 4; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) cq[u] = fmaf(ef[u], cq[u], ei[u]);
+            for (int u = 0; u < 4; ++u) cq[u] = cell_fence(fmaf(ef[u], cq[u], ei[u]));
 #pragma unroll
             for (int u = 0; u < 4; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
 #pragma unroll
             for (int u = 0; u < 4; ++u) hval[u] = gate_frac(eo[u], eg[u]);
-            s_c[blk][sb][lane] = make_float4(cq[0], cq[1], cq[2], cq[3]);
-            half4 vh, vl;
+            *(floatx4 __attribute__((address_space(3))) *)(scp + sb * 64 * 16) = floatx4{cq[0], cq[1], cq[2], cq[3]};
+            half2v vh01, vh23, vl01, vl23;
             float lo[4];
+            split_h2(hval[0], hval[1], vh01, vl01, lo[0], lo[1]);
+            split_h2(hval[2], hval[3], vh23, vl23, lo[2], lo[3]);
+            const half4 vh = __builtin_shufflevector(vh01, vh23, 0, 1, 2, 3), vl = __builtin_shufflevector(vl01, vl23, 0, 1, 2, 3);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                vh[q] = (_Float16)hval[q];
-                float d = hval[q] - (float)vh[q];
-                asm volatile("" : "+v"(d));            // subtract, then convert (never v_fma_mixlo_f16: it rounds differently)
-                vl[q] = (_Float16)d;
-                lo[q] = d * 262144.f;
-            }
-            *(half4 *)&hb_hi[nxt][32 * sb + j][8 * blk + 4 * hh] = vh;
-            *(half4 *)&hb_lo[nxt][32 * sb + j][8 * blk + 4 * hh] = vl;
-            _Float16 *yp = y + ((size_t)t * (2 * HV) + dir * HV + blk) * nstride * 8 + (uint32_t)(site0 + 32 * sb + j) * 8 + 4 * hh;
-            *(half4 *)yp = vh;
+            for (int q = 0; q < 4; ++q) lo[q] *= 262144.f;
+            *(half4 __attribute__((address_space(3))) *)(hwr + 32 * sb * HP * 2) = vh;
+            *(half4 __attribute__((address_space(3))) *)(hwr + 32 * sb * HP * 2 + HLO) = vl;
+            const gh_t yp = yrow + (size_t)(ylane + 32 * sb * 8);
+            *(gh4_t)yp = vh;
             if constexpr (!YQ) {
-                if (!(C3R_PROBE_Y1 && (blk & 1))) *(half4 *)(yp + plane_out) = vl;
+                if (!(C3R_PROBE_Y1 && (blk & 1))) *(gh4_t)(yrow + plane_out + (size_t)(ylane + 32 * sb * 8)) = vl;
             } else {                                     // the fp8 plane precision 2's layer 2 reads (k_lstm2_mx's x layout)
                 int w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], 0, false);
                 w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], w_lo, true);
                 int w_hi = __builtin_amdgcn_cvt_pk_fp8_f32(hval[0] * 64.f, hval[1] * 64.f, 0, false);
                 w_hi = __builtin_amdgcn_cvt_pk_fp8_f32(hval[2] * 64.f, hval[3] * 64.f, w_hi, true);
                 const int row0 = (dir * 4 + (blk >> 2)) * 4 + ((blk & 3) >> 1);
-                _Float16 *qp = y + plane_out + ((size_t)t * (2 * HV) + row0) * nstride * 8 + (uint32_t)(site0 + 32 * sb + j) * 8 + 4 * (blk & 1) + 2 * hh;
-                *(int *)qp = w_lo;
-                *(int *)(qp + (size_t)2 * nstride * 8) = w_hi;
+                gh_t qrow = (gh_t)(y + plane_out + ((size_t)t * (2 * HV) + row0) * nstride * 8 + (size_t)site0 * 8 + 4 * (blk & 1));
+                asm volatile("" : "+s"(qrow));
+                typedef int __attribute__((address_space(1))) *gi_t;
+                const uint32_t qlane = (uint32_t)(j * 8 + 2 * hh + 32 * sb * 8);
+                *(gi_t)(qrow + (size_t)qlane) = w_lo;
+                *(gi_t)(qrow + (size_t)2 * nstride * 8 + (size_t)qlane) = w_hi;
             }
         }
         if (step + 1 < NET_T) x_store(nxt, step + 1);
+        {                                                      // the other parity for the next step
+            const int sg = cur ? -1 : 1;
+            xrd += sg * XBUF; hrd += sg * HBUF; hwr -= sg * HBUF;
+            asm volatile("" : "+v"(xrd), "+v"(hrd), "+v"(hwr));
+        }
         __syncthreads();                                       // h_t and x_{t+1} complete; everyone is done with h_{t-1} and x_t (LDS counters
                                                                // instead of this barrier, as in layer 2, measured slower: 6.3 against 5.8 ms)
     };
