@@ -37,7 +37,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_default_params", "c3r_set_params", "c3r_load_reads", "c3r_host_alloc", "c3r_host_free", "c3r_set_reference", "c3r_set_reference_view", "c3r_set_bed", "c3r_set_sites",
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
-           "c3r_get_kernel_stats"]
+           "c3r_get_kernel_stats", "c3r_get_scan_counts"]
 
 _lib = None
 
@@ -107,6 +107,7 @@ def load_library():
     L.c3r_set_profiling.argtypes = [vp, i32]
     L.c3r_reset_kernel_stats.argtypes = [vp]
     L.c3r_get_kernel_stats.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(i64), i32, C.POINTER(i32)]
+    L.c3r_get_scan_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -257,6 +258,13 @@ class Engine(object):
         self._chk(self.L.c3r_batch_count(self.h, C.byref(tot), None))
         self.n_candidates = tot.value
         return n.value
+
+    def scan_counts(self):
+        """dict(listed, deep, giant, slices): the spans of the last scan and the kernels that built them (c3r_get_scan_counts) — listed spans,
+        those left to k_fused_deep, the giant ones among them and the slices listed for k_deep_walk.  Zeros after a column-store scan."""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._chk(self.L.c3r_get_scan_counts(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("listed", "deep", "giant", "slices"), (x.value for x in v)))
 
     def begin_batch(self):
         """Scans append to the device-resident batch until end_batch(); infer() then covers all of them."""

@@ -130,6 +130,7 @@ struct c3r_ctx {
     DevBuf d_rawidx, d_export;             // c3r_get_tensors: index of a raw re-run, windows gathered into position order
     DevBuf d_tokexp, d_tokoff;             // c3r_get_tokens: tokens gathered into site order, their offsets there
     int32_t *h_scan = nullptr;             // pinned: what a fused scan reads back (totals, overflow flags)
+    int32_t scan_counts[4] = {0, 0, 0, 0}; // the last scan's spans: listed, deep, giant, slices listed for k_deep_walk (c3r_get_scan_counts)
     bool last_fused = false;
     std::vector<int64_t> last_starts, last_ends;
     // page-locked buffers for the upper-cased reference slice (upload source, decoder's view).  Three of them: a row snapshot
@@ -1154,6 +1155,7 @@ int c3r_pileup_scan_regions(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_
     { const int rc_af = af_table(ctx); if (rc_af) return rc_af; }
     ctx->last_starts.assign(ctg_starts, ctg_starts + n_regions); ctx->last_ends.assign(ctg_ends, ctg_ends + n_regions);
     ctx->last_scan_pruned = false;
+    memset(ctx->scan_counts, 0, sizeof ctx->scan_counts);          // (a fused scan that succeeds fills them in)
     // The plain mode runs in one fused tile kernel (k_fused_tiles).  Head/tail calling (the end-of-stream rule needs the last row of the
     // whole region), splice padding (in-place column edits, candidate after candidate) and genotyping mode (candidates in intron-only
     // spans) keep the column store and its selection / compaction / gather kernels.
@@ -1575,7 +1577,7 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
                                (unsigned long long *)(lb + lb_head + (size_t)nblk * 8), (int32_t *)ctx->d_spanbase.p, (int32_t *)(lb + 8));
             hipLaunchKernelGGL(k_finalize_sites, dim3((unsigned)std::min<int64_t>((rows + 15) / 16 + 1, 8192)), dim3(256), 0, ctx->stream, z);
         }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scan, lb + 8, 48, hipMemcpyDeviceToHost, ctx->stream));          // (.. [9]: deep spans listed)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scan, lb + 8, 52, hipMemcpyDeviceToHost, ctx->stream));          // (.. [9]: deep spans listed, [11]: giant spans met, [12]: their slices)
         HIPCHK(ctx, hipMemcpyAsync(ctx->h_scan + 16, lb + lb_alloc, (size_t)ALLOC_SHARDS * ALLOC_STRIDE * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipGetLastError());
@@ -1644,6 +1646,7 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
         want_t = std::max<int64_t>(want_t, need_t + need_t / 4 + 1024);
     }
     ctx->last_cand = n_cand; ctx->last_shards = nsh; ctx->last_shard_rows = (int32_t)want_c;
+    ctx->scan_counts[0] = ctx->h_scan[3]; ctx->scan_counts[1] = ctx->h_scan[9]; ctx->scan_counts[2] = ctx->h_scan[11]; ctx->scan_counts[3] = ctx->h_scan[12];
     if (n_candidates) *n_candidates = n_cand;
     ctx->tokens_ready = true;
     ctx->n_cand = base_cand + n_cand;
@@ -1664,6 +1667,15 @@ int c3r_batch_begin(c3r_ctx *ctx) {
 int c3r_batch_end(c3r_ctx *ctx) {
     if (!ctx) return C3R_EINVAL;
     ctx->batching = false;
+    return C3R_OK;
+}
+
+int c3r_get_scan_counts(c3r_ctx *ctx, int32_t *listed, int32_t *deep, int32_t *giant, int32_t *slices) {
+    if (!ctx) return C3R_EINVAL;
+    if (listed) *listed = ctx->scan_counts[0];
+    if (deep) *deep = ctx->scan_counts[1];
+    if (giant) *giant = ctx->scan_counts[2];
+    if (slices) *slices = ctx->scan_counts[3];
     return C3R_OK;
 }
 

@@ -216,6 +216,13 @@ int c3r_reset_kernel_stats(c3r_ctx *ctx);
 /* Writes up to cap entries; returns the number of distinct kernels via *n.  names[i] points into
  * storage owned by the context. */
 int c3r_get_kernel_stats(c3r_ctx *ctx, const char **names, double *total_ms, int64_t *launches, int cap, int *n);
+/* Which kernels built the spans of the last c3r_pileup_scan / c3r_pileup_scan_regions (read-only; tests and tuning).  listed: the spans
+ * that met enough records to be built at all; deep: those of 2048 records or more in range, left to k_fused_deep (the others are
+ * k_fused_tiles'); giant: those of 8192 records or more; slices: the record slices listed for k_deep_walk — 0 while the context has no
+ * giant-span pool yet (it is allocated after the first scan that met a giant span), and only the first 256 giant spans of a scan are
+ * sliced.  All zero after a scan that took the column store (head/tail calling, splice padding, genotyping mode) or found nothing to
+ * scan.  Any pointer may be NULL. */
+int c3r_get_scan_counts(c3r_ctx *ctx, int32_t *listed, int32_t *deep, int32_t *giant, int32_t *slices);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ int main(int argc, char **argv) {
     if (!b) { fprintf(stderr, "dlopen %s: %s\n", argv[2], dlerror()); return 3; }
     NEED(a, c3r_version); NEED(a, c3r_create); NEED(a, c3r_destroy); NEED(a, c3r_trim); NEED(a, c3r_last_error); NEED(a, c3r_default_params);
     NEED(a, c3r_set_params); NEED(a, c3r_load_reads); NEED(a, c3r_set_reference); NEED(a, c3r_pileup_scan); NEED(a, c3r_infer);
-    NEED(a, c3r_get_tensors); NEED(a, c3r_get_sites); NEED(a, c3r_get_tokens); NEED(a, c3r_load_weights); NEED(a, c3r_call_rows); NEED(a, c3r_set_precision); NEED(a, c3r_get_precision);
+    NEED(a, c3r_get_tensors); NEED(a, c3r_get_sites); NEED(a, c3r_get_tokens); NEED(a, c3r_load_weights); NEED(a, c3r_call_rows); NEED(a, c3r_set_precision); NEED(a, c3r_get_precision); NEED(a, c3r_get_scan_counts);
     NEED(b, c3r_bam_open); NEED(b, c3r_bam_fetch); NEED(b, c3r_bam_copy); NEED(b, c3r_bam_close); NEED(b, c3r_bam_index_build); NEED(b, c3r_vcf_merge); NEED(b, c3r_vcf_compress);
 
     const char *(*version)(void) = (const char *(*)(void))dlsym(a, "c3r_version");
@@ -33,6 +33,11 @@ int main(int argc, char **argv) {
     }
     if (wcount && wcount(18) != 2072216) { fprintf(stderr, "weight count %lld\n", (long long)wcount(18)); return 5; }
     if (sizeof(c3r_read_t) != 32 || sizeof(c3r_token_t) != 16 || sizeof(c3r_site_t) != 52) { fprintf(stderr, "struct layout\n"); return 6; }
+
+    /* a read-only accessor refuses a missing context instead of touching it */
+    int (*counts)(c3r_ctx *, int32_t *, int32_t *, int32_t *, int32_t *) = (int (*)(c3r_ctx *, int32_t *, int32_t *, int32_t *, int32_t *))dlsym(a, "c3r_get_scan_counts");
+    int32_t sc[4] = {7, 7, 7, 7};
+    if (counts(0, &sc[0], &sc[1], &sc[2], &sc[3]) != C3R_EINVAL || sc[0] != 7) { fprintf(stderr, "c3r_get_scan_counts(NULL)\n"); return 8; }
 
     int (*bopen)(const char *, int, c3r_bam **) = (int (*)(const char *, int, c3r_bam **))dlsym(b, "c3r_bam_open");
     void (*bclose)(c3r_bam *) = (void (*)(c3r_bam *))dlsym(b, "c3r_bam_close");

@@ -8,6 +8,22 @@
 #include <vector>
 #include "../../clair3_rna_amd/csrc/reads_kernels.hpp"
 
+// The thresholds that tests/test_gpu_deep_routes.py sizes its cases by: which kernel builds a span, and how its indel alleles are counted
+#define ROUTE_CONST(expr, what) static_assert(expr, what " changed: update tests/test_gpu_deep_routes.py (its brackets and case sizes)")
+ROUTE_CONST(c3r::DEEP_MIN_RECORDS == 2048, "DEEP_MIN_RECORDS, the records from which a span is k_fused_deep's,");
+ROUTE_CONST(c3r::SPLIT_MIN_RECORDS == 8192, "SPLIT_MIN_RECORDS, the records from which a span is giant,");
+ROUTE_CONST(c3r::DEEP_EV_LDS == 3072, "DEEP_EV_LDS, the events of k_fused_deep's LDS store,");
+ROUTE_CONST(c3r::DEEP_EV_LDS * sizeof(c3r::EvRec) / 8 == 9216, "LEAD_CAP (tile_columns: sizeof(M.ev) / 8), the events counted by first-of-allele slots in global buckets,");
+ROUTE_CONST(sizeof(c3r::TileMem<C3R_CH, c3r::DEEP_EV_LDS>::ev) / 8 == 9216, "LEAD_CAP (tile_columns: sizeof(M.ev) / 8)");
+ROUTE_CONST(c3r::EV_HASH_MIN == 1024, "EV_HASH_MIN, the events from which k_fused_tiles hashes,");
+ROUTE_CONST(c3r::DEEP_EVG_CAP == 49152, "DEEP_EVG_CAP, the events of a workgroup's arrival-order buffer,");
+ROUTE_CONST(c3r::TileMem<C3R_CH>::EV_LDS == 192 && c3r::TileMem<C3R_CH_PHASED>::EV_LDS == 0, "TileMem::EV_LDS, the events of k_fused_tiles' LDS store,");
+ROUTE_CONST(c3r::GIANT_SLICE == 4096, "GIANT_SLICE, the records of a slice at the natural thresholds (the tests force 64),");
+ROUTE_CONST(c3r::GIANT_MAX_HELP == 32, "GIANT_MAX_HELP, the slices of one span,");
+ROUTE_CONST(c3r::GIANT_SLOTS == 256, "GIANT_SLOTS, the giant spans of a scan that are sliced,");
+ROUTE_CONST(c3r::FUSE_IN == 224 && c3r::TILE == 256 && C3R_FLANK == 16, "FUSE_IN / TILE / C3R_FLANK, the positions of a span,");
+ROUTE_CONST(c3r::OP_CHOP == 30, "OP_CHOP, the positions of one record,");
+
 int main() {
     const uint32_t N = 8 * 1024;
     std::vector<int> seen(N, 0);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Differential run (build container only, nothing stored): random read sets (tests/test_gpu_fuzz.py's generator) ->
+"""Differential run (build container only, nothing stored): random read sets (the generator of tests/helpers.py that tests/test_gpu_fuzz.py uses) ->
 oracle A1 mpileup rows -> BOTH the reference's CreateTensorPileup driver and the oracle's create_tensor; the emitted lines
 must be identical.  Pins the oracle's A2/A3 on inputs far outside the committed goldens (odd CIGARs, dense indels, IUPAC,
 head/tail, splice padding, phased).  Cases on which the reference itself raises are skipped (and counted).
@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 import refharness as rh  # noqa: E402
 from clair3_rna_amd.reads import ReadSet  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
-from tests.test_gpu_fuzz import _case  # noqa: E402
+from tests.helpers import _case  # noqa: E402
 
 OPTS = [
     ([], dict(), False),

@@ -80,6 +80,521 @@ def fake_samtools(path, version):
     return path
 
 
+# ---- random-CIGAR read sets and the parity checks run on them (tests/test_gpu_fuzz.py with one engine and the natural thresholds,
+# tests/test_gpu_deep_routes.py with every span forced through the deep-span kernels) --------------------------------------------
+def _seeds(n):
+    """CI runs seeds 0..n-1; a soak run sets C3R_FUZZ_BASE / C3R_FUZZ_SCALE to walk further seeds (tests/evidence/README.md)."""
+    import os
+    base, scale = int(os.environ.get("C3R_FUZZ_BASE", "0")), int(os.environ.get("C3R_FUZZ_SCALE", "1"))
+    return range(base, base + n * scale)
+
+
+def _rand_cigar(rng, want_q, pads=True):
+    """Random op sequence: M/=/X/I/D/N/S/H/P incl. zero-length ops, leading/trailing I or D, runs of D D, I I, N next to
+    I or D, pads between insertions (pads = False: a short M in their place).  Returns (cigar string, query length)."""
+    ops = []
+    if rng.random() < 0.15:
+        ops.append((rng.randint(1, 5), "H"))
+    if rng.random() < 0.25:
+        ops.append((rng.randint(1, 6), "S"))
+    n_core = rng.randint(1, 9)
+    for k in range(n_core):
+        r = rng.random()
+        if r < 0.45:
+            ops.append((rng.randint(1, 25), rng.choice("MMMM=X")))
+        elif r < 0.58:
+            ops.append((rng.randint(1, 4) if rng.random() < 0.9 else rng.randint(17, 22), "I"))
+        elif r < 0.72:
+            ops.append((rng.randint(1, 5), "D"))
+        elif r < 0.84:
+            ops.append((rng.randint(1, 40), "N"))
+        elif r < 0.90:
+            ops.append((rng.randint(1, 3), "P" if pads else "M"))
+        elif r < 0.95:
+            ops.append((0, rng.choice("MID")))              # zero-length op
+        else:
+            ops.append((rng.randint(1, 3), "D")); ops.append((rng.randint(1, 3), "D"))   # split deletion
+    if rng.random() < 0.25:
+        ops.append((rng.randint(1, 6), "S"))
+    if rng.random() < 0.1:
+        ops.append((rng.randint(1, 5), "H"))
+    if not any(o in "M=X" and l > 0 for l, o in ops):
+        ops.insert(len(ops) // 2, (rng.randint(2, 12), "M"))
+    qlen = sum(l for l, o in ops if o in "MIS=X")
+    return "".join("%d%s" % lo for lo in ops), qlen
+
+
+def _case(seed, phased, pads=True):
+    import random
+    import re
+    rng = random.Random(seed)
+    L = rng.choice([300, 420, 777])
+    ref = "".join(rng.choice("ACGT") for _ in range(L))
+    if rng.random() < 0.3:          # some IUPAC / N / lower-case reference letters
+        ref = list(ref)
+        for _ in range(6):
+            ref[rng.randrange(L)] = rng.choice("NRYacgtn")
+        ref = "".join(ref)
+    recs = []
+    n_reads = rng.randint(25, 90)
+    hot = rng.randint(30, L - 120)
+    for _ in range(n_reads):
+        pos = max(1, int(rng.gauss(hot, 40)))
+        cg, qlen = _rand_cigar(rng, 0, pads)
+        if rng.random() < 0.1:
+            qlen = max(1, qlen - rng.randint(1, 3))          # query shorter than the CIGAR claims
+        seq = "".join(rng.choice("ACGTACGTACGTACGTN=RY") for _ in range(qlen))
+        flag = (16 if rng.random() < 0.5 else 0) | rng.choice([0] * 14 + [256, 2048, 4, 1024, 512, 8, 1, 3, 65, 131])
+        mapq = rng.choice([60] * 8 + [0, 3, 5, 4, 20, 255])
+        hp = rng.choice([0, 1, 2, 1, 2]) if phased else 0
+        recs.append(dict(pos=pos, cigar=cg, seq=seq, flag=flag, mapq=mapq, hp=hp))
+    recs.sort(key=lambda r: r["pos"])
+    # alignments must lie inside the contig (the reference indexes the reference string with every covered position)
+    end = max(r["pos"] + sum(int(n) for n, o in re.findall(r"(\d+)([MIDNSHP=X])", r["cigar"]) if o in "MDN=X") for r in recs)
+    if end + 40 > len(ref):
+        ref = ref + "".join(rng.choice("ACGT") for _ in range(end + 40 - len(ref)))
+    return ref, recs
+
+
+def _scanned(on_scan, eng, exp):
+    """on_scan(eng, exp): a caller's look at the engine after a scan (Engine.scan_counts(): which kernels built the spans; it stands until the
+    next scan, the raw re-run behind tensors(rescaled=False) and columns() leave it alone); exp is the oracle's result for that scan, or a list
+    of them for a scan of several regions."""
+    if on_scan is not None:
+        on_scan(eng, exp)
+
+
+def fuzz_match_oracle(eng, seeds, kw, case_base, on_scan=None):
+    """The random read sets case_base + seed through the engine with the parameters kw: every line equals the oracle's, and (18 channels,
+    no splice padding) every column of the scan equals generate_tensor on the oracle's mpileup row.  Returns (cases, lines) seen."""
+    from clair3_rna_amd import capi
+    from clair3_rna_amd.reads import ReadSet
+    channels = kw.get("channels", 18)
+    okw = dict(kw)
+    okw.pop("channels", None)
+    for k in ("head_tail", "splice_padding"):
+        if k in okw:
+            okw[k] = bool(okw[k])
+    if "snp_min_af" in okw:
+        okw["snp_af"] = okw.pop("snp_min_af")
+    n_cases, n_lines = 0, 0
+    for seed in seeds:
+        ref, recs = _case(case_base + seed, phased=(channels == 30))
+        rs = ReadSet.from_records(recs)
+        eng.params = capi.default_params()
+        eng.set_bed(0, None); eng.set_bed(1, None)
+        eng.set_params(min_coverage=kw.get("min_coverage", 2), **{k: v for k, v in kw.items() if k != "min_coverage"})
+        exp = oracle_chunk(rs, ref, 1, 1, len(ref), channels=channels, min_coverage=kw.get("min_coverage", 2),
+                           **{k: v for k, v in okw.items() if k != "min_coverage"})
+        got = engine_chunk(eng, rs, ref, 1, 1, len(ref))
+        _scanned(on_scan, eng, exp)
+        assert got["lines"] == exp["lines"], (seed, recs, first_diff(got["lines"], exp["lines"]))
+        if channels == 18 and not kw.get("splice_padding"):
+            col = eng.columns()
+            rows = exp["rows"]
+            assert len(rows) == int((col["flags"] & 1).sum()), (seed, recs)
+            for row in rows:
+                f = row.split("\t")
+                pos = int(f[1])
+                o = orc.generate_tensor(f[4], ref[pos - 1].upper(), pos, ref.upper(), 1, snp_af=okw.get("snp_af", 0.08))
+                i = pos - col["region_start"]
+                assert col["cols"][i].tolist() == o["tensor"], (seed, pos, f[4], recs)
+                assert col["depth"][i] == o["depth"], (seed, pos)
+        n_cases += 1
+        n_lines += len(exp["lines"])
+    eng.params = capi.default_params()
+    eng.set_params()
+    return n_cases, n_lines
+
+
+def fuzz_samtools_1_11(eng, seeds, kw, case_base, on_scan=None):
+    """The same with c3r_params_t.mpileup_compat = 1 (pads inside insertions, a deletion right behind an insertion).  Returns
+    (lines, columns that show an insertion with a deletion behind it, padded alleles, cases the pad table refused)."""
+    import re
+    from clair3_rna_amd import capi
+    from clair3_rna_amd.reads import ReadSet
+    channels = kw.get("channels", 18)
+    okw = {k: bool(v) for k, v in kw.items() if k != "channels"}
+    n_lines, n_both, n_padded, n_refused = 0, 0, 0, 0
+    eng.load_reads(ReadSet.from_records([]))
+    for seed in seeds:
+        ref, recs = _case(case_base + seed, phased=(channels == 30), pads=True)
+        rs = ReadSet.from_records(recs)
+        eng.params = capi.default_params()
+        eng.set_bed(0, None); eng.set_bed(1, None)
+        eng.set_params(min_coverage=2, mpileup_compat=1, **kw)
+        exp = oracle_chunk(rs, ref, 1, 1, len(ref), channels=channels, min_coverage=2, mpileup_compat=1, **okw)
+        try:
+            got = engine_chunk(eng, rs, ref, 1, 1, len(ref))
+            _scanned(on_scan, eng, exp)
+        except capi.C3RError as e:
+            # the documented limit of the pad table (c3r_padins_t: a 64-bit mask per run of I and P ops); the generator reaches it on a few seeds
+            assert "more than 64 characters" in str(e), (seed, e)
+            n_refused += 1
+            continue
+        assert got["lines"] == exp["lines"], (seed, recs, first_diff(got["lines"], exp["lines"]))
+        n_lines += len(exp["lines"])
+        n_both += sum(1 for r in exp["rows"] if re.search(r"[+][0-9]+[ACGTNacgtn=RYry*#]+-[0-9]+[Nn]", r.split("\t")[4]))
+        n_padded += sum(1 for l in exp["lines"] if re.search(r" I[ACGT][A-Z=]*[*#]", l.split("\t")[4]))
+        if seed % 20 == 0:                      # the same reads with the <= 1.10 text: the records are rebuilt when the parameter changes
+            eng.set_params(min_coverage=2, mpileup_compat=0, **kw)
+            n0 = eng.scan(1, len(ref))
+            old = oracle_chunk(rs, ref, 1, 1, len(ref), channels=channels, min_coverage=2, **okw)
+            _scanned(on_scan, eng, old)
+            assert n0 == len(old["lines"])
+    eng.params = capi.default_params()
+    eng.set_params()
+    return n_lines, n_both, n_padded, n_refused
+
+
+def fuzz_filters_and_regions(eng, seeds, mode, case_base, rng_base, head_tail=None, on_scan=None):
+    """The random read sets through the -l BED, the confident BED, a genotyping site list, a sub-region with a shifted reference slice,
+    and at depths that cross the 216 rescale threshold.  head_tail: None = on for the odd seeds, else that value for every case.
+    Returns the lines seen."""
+    import random
+    from clair3_rna_amd import capi
+    from clair3_rna_amd.reads import ReadSet
+    n_lines = 0
+    for seed in seeds:
+        rng = random.Random(rng_base + seed)
+        ref, recs = _case(case_base + seed, phased=False)
+        if mode == "deep":              # replicate the reads: depth 150-400 with identical alleles (I1/D1 multiplicities, rescale)
+            rep = rng.randint(6, 9)
+            recs = [dict(r) for r in recs for _ in range(rep)]
+            recs.sort(key=lambda r: r["pos"])
+        rs = ReadSet.from_records(recs)
+        L = len(ref)
+
+        def intervals(k):
+            out = []
+            for _ in range(k):
+                a = rng.randint(0, L - 2)
+                out.append((a, min(L, a + rng.choice([1, 2, 5, 17, 33, 60, 150]))))
+            return out
+        lbed = intervals(rng.randint(1, 6)) if mode in ("lbed", "both_beds") else None
+        cbed = intervals(rng.randint(1, 6)) if mode in ("cbed", "both_beds") else None
+        sites = sorted(set(rng.randint(1, L) for _ in range(rng.randint(1, 25)))) if mode == "sites" else None
+        ref_start, a, b = 1, 1, L
+        if mode == "subregion":
+            a = rng.randint(2, L // 2); b = rng.randint(a, L)
+            ref_start = rng.randint(1, max(1, a - 49))   # the slice starts before the region's halo and its windows (the
+                                                         # reference fetches ctg_start - 1000: every row and flank is covered)
+        if mode == "sites":
+            a, b = min(sites), max(sites)
+        ht = seed % 2 if head_tail is None else int(head_tail)
+        eng.params = capi.default_params()
+        eng.set_bed(0, lbed); eng.set_bed(1, cbed)
+        if sites is not None:
+            eng.set_sites(sites)
+        eng.set_params(min_coverage=2, genotyping_mode=int(sites is not None), head_tail=ht)
+        refslice = ref[ref_start - 1:]
+        exp = oracle_chunk(rs, refslice, ref_start, a, b, lbed=lbed, bed=cbed, sites=sites, min_coverage=2, head_tail=bool(ht))
+        got = engine_chunk(eng, rs, refslice, ref_start, a, b)
+        _scanned(on_scan, eng, exp)
+        assert got["lines"] == exp["lines"], (mode, seed, lbed, cbed, sites, (ref_start, a, b), first_diff(got["lines"], exp["lines"]))
+        assert np.array_equal(got["X"], exp["X"]), (mode, seed)
+        n_lines += len(exp["lines"])
+    eng.params = capi.default_params()
+    eng.set_bed(0, None); eng.set_bed(1, None)
+    eng.set_params()
+    return n_lines
+
+
+def fuzz_decode_rows_and_regions(eng, seeds, compat, case_base, rng_base, on_scan=None):
+    """On the random read sets: (1) c3r_call_rows (C++: tokens -> ordered alt_info -> decode -> row text) equals the Python path fed with the
+    ORACLE's alt_info strings; (2) a multi-region scan over random chunk boundaries equals successive scans.  Returns (rows, genotypes seen)."""
+    import random
+    from clair3_rna_amd import capi, decode, synth
+    from clair3_rna_amd.reads import ReadSet
+    w = synth.random_weights(18, seed=4242)
+    w[-24 * 129:] *= 6.0                       # sharper output layers: not everything decodes to RefCall
+    eng.load_weights(w, 18)
+    eng.set_precision("f16x3")
+    n_rows, kinds = 0, set()
+    seeds = list(seeds)
+    for seed in seeds:
+        rng = random.Random(rng_base + seed)
+        ref, recs = _case(case_base + seed, phased=False, pads=True)
+        rs = ReadSet.from_records(recs)
+        L = len(ref)
+        eng.params = capi.default_params()
+        eng.set_bed(0, None); eng.set_bed(1, None)
+        if seed == seeds[0]:
+            eng.load_reads(ReadSet.from_records([]))
+        eng.set_params(min_coverage=2, mpileup_compat=compat)
+        exp = oracle_chunk(rs, ref, 1, 1, L, min_coverage=2, mpileup_compat=compat)
+        got = engine_chunk(eng, rs, ref, 1, 1, L)
+        _scanned(on_scan, eng, exp)
+        assert got["lines"] == exp["lines"]
+        if exp["lines"]:
+            probs = eng.infer()
+            po = orc.forward(w, exp["X"])
+            assert np.abs(probs - po).max() < 1e-4
+            f = [l.split("\t") for l in exp["lines"]]
+            py = decode.vcf_rows("chr20", [int(x[1]) for x in f], [x[2] for x in f], [x[4] for x in f], probs)
+            cpp = eng.call_rows("chr20")
+            assert cpp == py, (seed, [a for a, b in zip(cpp, py) if a != b][:2], [b for a, b in zip(cpp, py) if a != b][:2])
+            n_rows += len(py)
+            kinds.update(r.split("\t")[9].split(":")[0] for r in py)
+        # random chunking of the same contig
+        cuts = sorted(set([1, L] + [rng.randint(2, L - 1) for _ in range(rng.randint(1, 5))]))
+        chunks = [(cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
+        eng.begin_batch()
+        for a, b in chunks:
+            eng.scan(a, b)
+            _scanned(on_scan, eng, None)
+        eng.end_batch()
+        X1, S1, T1 = eng.tensors(), eng.sites(), eng.tokens()
+        eng.begin_batch(); eng.scan_regions(chunks); eng.end_batch()
+        _scanned(on_scan, eng, None)
+        assert np.array_equal(X1, eng.tensors()) and S1.tobytes() == eng.sites().tobytes() and T1.tobytes() == eng.tokens().tobytes(), (seed, chunks)
+    eng.params = capi.default_params()
+    eng.set_params()
+    return n_rows, kinds
+
+
+def fuzz_depth_cap(eng, seeds, channels, case_base, rng_base, splice_padding=None, head_tail=None, on_scan=None):
+    """samtools mpileup -d on replicated random read sets, small caps: the engine equals the oracle for the region and for its two halves
+    (a two-region scan equals two successive scans equals the per-region oracle).  splice_padding / head_tail: None = by the seed's
+    low bits, else that value for every case.  Returns the cases in which the cap changed the output."""
+    import random
+    from clair3_rna_amd import capi
+    from clair3_rna_amd.reads import ReadSet
+    n_dropped_cases = 0
+    for seed in seeds:
+        rng = random.Random(rng_base + seed)
+        ref, recs = _case(case_base + seed, phased=(channels == 30))
+        rep = rng.randint(3, 7)
+        recs = [dict(r) for r in recs for _ in range(rep)]
+        recs.sort(key=lambda r: r["pos"])
+        rs = ReadSet.from_records(recs)
+        L = len(ref)
+        cap = rng.choice([8, 20, 60, 150])
+        sp = seed % 2 if splice_padding is None else int(splice_padding)
+        ht = (seed // 2) % 2 if head_tail is None else int(head_tail)
+        kw = dict(min_coverage=2, max_depth=cap, splice_padding=sp, head_tail=ht)
+        okw = dict(channels=channels, min_coverage=2, splice_padding=bool(sp), head_tail=bool(ht))
+        eng.params = capi.default_params()
+        eng.set_bed(0, None); eng.set_bed(1, None)
+        eng.set_params(channels=channels, **kw)
+        a = rng.randint(1, L // 3); b = rng.randint(2 * L // 3, L)
+        exp = oracle_chunk(rs, ref, 1, a, b, max_depth=cap, **okw)
+        got = engine_chunk(eng, rs, ref, 1, a, b)
+        _scanned(on_scan, eng, exp)
+        nocap = oracle_chunk(rs, ref, 1, a, b, max_depth=0, **okw)
+        n_dropped_cases += int(exp["lines"] != nocap["lines"])
+        assert got["lines"] == exp["lines"], (seed, cap, first_diff(got["lines"], exp["lines"]))
+        assert np.array_equal(got["X"], exp["X"])
+        # the same through a two-region scan (masks are per region)
+        mid = (a + b) // 2
+        e1 = oracle_chunk(rs, ref, 1, a, mid, max_depth=cap, **okw)
+        e2 = oracle_chunk(rs, ref, 1, mid, b, max_depth=cap, **okw)
+        eng.begin_batch()
+        eng.scan(a, mid); _scanned(on_scan, eng, e1)
+        eng.scan(mid, b); _scanned(on_scan, eng, e2)
+        eng.end_batch()
+        X1, S1 = eng.tensors(), eng.sites()
+        eng.begin_batch(); eng.scan_regions([(a, mid), (mid, b)]); eng.end_batch()
+        _scanned(on_scan, eng, [e1, e2])
+        assert np.array_equal(X1, eng.tensors()) and S1.tobytes() == eng.sites().tobytes()
+        assert [int(l.split("\t")[1]) for l in e1["lines"] + e2["lines"]] == S1["pos"].tolist()
+        assert np.array_equal(X1, np.concatenate([e1["X"], e2["X"]])) if len(S1) else True
+    eng.params = capi.default_params()
+    eng.set_params()
+    return n_dropped_cases
+
+
+# ---- read sets sized for the thresholds of the deep-span kernels (tests/test_gpu_deep_routes.py) ------------------------------------------
+def _zoo_alleles(rng, n, compat):
+    """n indel alleles as (cigar ops, inserted bases, reference length): insertions of 1-22 bases (the event key holds 16: pairs that agree in
+    their first 16 bases and differ behind them), '='-only insertions (no strand), deletions of 1-5 bases whole, split `D D` and with a
+    zero-length op inside; compat = 1 adds `I P I` runs and an I with a D right behind it (what samtools >= 1.11 prints differently).
+    The three most frequent alleles are such a pair and a third sibling: a comparison that stops at the key would merge them into a count
+    that no true allele of the column has (long_insertions_tell)."""
+    b = "".join(rng.choice("ACGT") for _ in range(20))
+    out = [("20I", b, 0), ("20I", b[:16] + ("A" if b[16] != "A" else "C") + b[17:], 0), ("20I", b[:-1] + ("G" if b[-1] != "G" else "T"), 0)]
+    while len(out) < n:
+        r = rng.random()
+        if r < 0.40:
+            k = rng.randint(1, 4)
+            out.append(("%dI" % k, "".join(rng.choice("ACGT") for _ in range(k)), 0))
+        elif r < 0.55:                                            # longer than the key: siblings that differ in base 17 and in the last base
+            k = rng.randint(17, 22)
+            b = "".join(rng.choice("ACGT") for _ in range(k))
+            out.append(("%dI" % k, b, 0))
+            out.append(("%dI" % k, b[:16] + ("A" if b[16] != "A" else "C") + b[17:], 0))
+            out.append(("%dI" % k, b[:-1] + ("G" if b[-1] != "G" else "T"), 0))
+            out.append(("%dI" % (k - 1), b[:-1], 0))              # (and its prefix: same key, another length)
+        elif r < 0.62:
+            k = rng.choice([1, 2, 3, 16, 17, 18])
+            out.append(("%dI" % k, "=" * k, 0))
+            if k > 16:
+                out.append(("%dI" % k, "=" * (k - 1) + "A", 0))    # '=' in the key, a base behind it: that one has a strand
+        elif r < 0.85:
+            k = rng.randint(1, 5)
+            out.append(("%dD" % k, "", k))
+            if k > 1:
+                j = rng.randint(1, k - 1)
+                out.append(("%dD%dD" % (j, k - j), "", k))
+                out.append(("%dD0%s%dD" % (j, rng.choice("MI"), k - j), "", k))
+        elif compat:
+            if rng.random() < 0.5:
+                j, k, q = rng.randint(1, 3), rng.randint(1, 3), rng.randint(1, 2)
+                out.append(("%dI%dP%dI" % (j, q, k), "".join(rng.choice("ACGT") for _ in range(j + k)), 0))
+            else:
+                k, d = rng.randint(1, 3), rng.randint(1, 3)
+                out.append(("%dI%dD" % (k, d), "".join(rng.choice("ACGT") for _ in range(k)), d))
+    return out[:n]
+
+
+def _ip_run_chars(cigar):
+    """The longest printed run of I and P ops of a CIGAR (the pad table of mpileup_compat = 1 takes 64 characters)."""
+    import re
+    best = cur = 0
+    for n, o in re.findall(r"(\d+)([MIDNSHP=X])", cigar):
+        if o in "IP":
+            cur += int(n)
+            best = max(best, cur)
+        elif int(n) > 0:
+            cur = 0
+    return best
+
+
+def allele_zoo(n_reads, seed, compat=0, events_per_read=1, random_share=0.1, n_alleles=300, anchors=(300, 303, 306), offset=0, ref=None):
+    """(ref, records): short reads around two or three anchor columns (0-based, + offset), every read with an insertion or a deletion on its
+    anchor drawn from a skewed (1 / rank) distribution over n_alleles alleles (_zoo_alleles), both strands, three haplotype tags, 5 % mismatches.
+    events_per_read = 1: `aM <indel> bM`, a and b in 2 .. 5.  events_per_read = k > 1: `1M (<indel> 1M) * k` with the indels that take at most one
+    reference base, all starting within three positions — more than 0.375 events per record, all of them inside 17 positions.  random_share of
+    the reads take a CIGAR, flags and a mapping quality from the random generator instead (runs of I and P ops within the pad table's 64 characters)."""
+    import random
+    rng = random.Random(seed)
+    alleles = _zoo_alleles(rng, n_alleles, compat)
+    if events_per_read > 1:
+        alleles = [a for a in alleles if a[2] <= 1]
+    weights = [1.0 / (k + 1) for k in range(len(alleles))]
+    L = 900 + offset
+    if ref is None:
+        ref = "".join(rng.choice("ACGT") for _ in range(L))
+
+    def aligned(p, n):
+        return "".join(c if rng.random() >= 0.05 else rng.choice("ACGT") for c in ref[p:p + n])
+    recs = []
+    n_random = int(round(n_reads * random_share))
+    picks = rng.choices(range(len(alleles)), weights=weights, k=(n_reads - n_random) * events_per_read)
+    for r in range(n_reads - n_random):
+        if events_per_read == 1:
+            ops, ins, dl = alleles[picks[r]]
+            a, b = rng.randint(2, 5), rng.randint(2, 5)
+            p0 = offset + rng.choice(anchors) - a
+            cigar, seq = "%dM%s%dM" % (a, ops, b), aligned(p0, a) + ins + aligned(p0 + a + dl, b)
+        else:
+            p0 = offset + anchors[0] + rng.randint(0, 2)
+            cigar, seq, p = "1M", aligned(p0, 1), p0 + 1
+            for e in range(events_per_read):
+                ops, ins, dl = alleles[picks[r * events_per_read + e]]
+                cigar += ops + "1M"
+                seq += ins + aligned(p + dl, 1)
+                p += dl + 1
+        recs.append(dict(pos=p0, cigar=cigar, seq=seq, flag=16 if rng.random() < 0.5 else 0, mapq=60, hp=rng.choice([0, 1, 2])))
+    for _ in range(n_random):
+        while True:
+            cg, qlen = _rand_cigar(rng, 0, pads=True)
+            if _ip_run_chars(cg) <= 64:
+                break
+        if rng.random() < 0.1:
+            qlen = max(1, qlen - rng.randint(1, 3))
+        recs.append(dict(pos=max(1, offset + int(rng.gauss(anchors[0], 40))), cigar=cg, seq="".join(rng.choice("ACGTACGTACGTACGTN=RY") for _ in range(qlen)),
+                         flag=(16 if rng.random() < 0.5 else 0) | rng.choice([0] * 14 + [256, 2048, 4, 1024, 512, 8, 1, 3, 65, 131]),
+                         mapq=rng.choice([60] * 8 + [0, 3, 5, 4, 20, 255]), hp=rng.choice([0, 1, 2])))
+    recs.sort(key=lambda r: r["pos"])
+    end = max(r["pos"] + cigar_ref_len(r["cigar"]) for r in recs)
+    if end + 40 > len(ref):
+        ref = ref + "".join(rng.choice("ACGT") for _ in range(end + 40 - len(ref)))
+    return ref, recs
+
+
+def long_insertions_tell(recs, min_mq=5, excl_flags=2316):
+    """True if a comparison of insertions that looked at the 16 bases of the event key only would change I1 or i1 somewhere: on some column and
+    strand the plain insertions (`aM kI ...`, no pads) that share length and first 16 bases outnumber the most frequent insertion allele."""
+    import re
+    full, trunc = {}, {}
+    for r in recs:
+        if r.get("mapq", 60) < min_mq or (r.get("flag", 0) & excl_flags):
+            continue
+        ops = re.findall(r"(\d+)([MIDNSHP=X])", r["cigar"])
+        p, q = r["pos"], 0
+        for k, (ln, o) in enumerate(ops):
+            ln = int(ln)
+            if o == "I":
+                where = (p, r.get("flag", 0) & 16)
+                alone = (k == 0 or ops[k - 1][1] in "M=X") and (k + 1 == len(ops) or ops[k + 1][1] in "M=X")
+                bases = r["seq"][q:q + ln] if alone else "%d:%s" % (k, r["cigar"])          # (runs of ops: every CIGAR an allele of its own)
+                full.setdefault(where, {}).setdefault((ln, bases), 0)
+                full[where][(ln, bases)] += 1
+                trunc.setdefault(where, {}).setdefault((ln, bases[:16] if alone else bases), 0)
+                trunc[where][(ln, bases[:16] if alone else bases)] += 1
+            if o in "M=XDN":
+                p += ln
+            if o in "MIS=X":
+                q += ln
+    return any(max(trunc[w].values()) > max(full[w].values()) for w in full)
+
+
+def cigar_ref_len(cigar):
+    import re
+    return sum(int(n) for n, o in re.findall(r"(\d+)([MIDNSHP=X])", cigar) if o in "MDN=X")
+
+
+def span_bounds(recs, rows, ref, ref_start=1, min_mq=5, excl_flags=2316):
+    """What the largest span of a scan must and may hold, from the CIGARs (records) and the oracle's columns (indel events; rows: its mpileup
+    rows for the scan).  A span builds the columns of up to 256 positions — its own 224 and 16 on either side — from every record that touches
+    them, so:
+      * at least: whatever lies within 16 consecutive positions (the span that holds the first of them reaches 16 further), hence also what
+        lies on one position, and total / (ceil(extent / 224) + 1) when everything lies within `extent` positions;
+      * at most: the total.
+    Records: one per M / = / X / D piece of at most 30 positions plus one per insertion, counted at their first position (the insertion: at the
+    base before it); the lower bound takes the reads that pass the filters and no insertion, the upper one every read and every op.
+    Events: the I + i + D + d counts of the oracle's column.  Returns dict(rec_lo, rec_hi, ev_lo, ev_hi, max_depth)."""
+    import re
+    n = max(r["pos"] + cigar_ref_len(r["cigar"]) for r in recs) + 64
+    starts = np.zeros(n + 32, np.int64)
+    rec_hi = 0
+    for r in recs:
+        ok = r.get("mapq", 60) >= min_mq and not (r.get("flag", 0) & excl_flags)
+        p = r["pos"]
+        for ln, o in re.findall(r"(\d+)([MIDNSHP=X])", r["cigar"]):
+            ln = int(ln)
+            if o in "M=XD":
+                for q in range(0, ln, 30):
+                    rec_hi += 1
+                    if ok:
+                        starts[p + q] += 1
+                p += ln
+            elif o == "N":
+                p += ln
+            elif o == "I":
+                rec_hi += 1
+    ev = np.zeros(n + 32, np.int64)
+    depth = 0
+    up = ref.upper()
+    for row in rows:
+        f = row.split("\t")
+        pos = int(f[1])
+        o = orc.generate_tensor(f[4], up[pos - ref_start], pos, up, ref_start)
+        t = o["tensor"]
+        ev[pos - 1] = t[4] + t[6] + t[13] + t[15]                 # I, D, i, d
+        depth = max(depth, o["depth"])
+
+    def lower(v):
+        nz = np.nonzero(v)[0]
+        if len(nz) == 0:
+            return 0
+        c = np.concatenate([[0], np.cumsum(v)])
+        extent = int(nz[-1] - nz[0] + 1)
+        return int(max((c[16:] - c[:-16]).max(), -(-int(v.sum()) // (-(-extent // 224) + 1))))
+    return dict(rec_lo=max(lower(starts), depth), rec_hi=rec_hi, ev_lo=lower(ev), ev_hi=int(ev.sum()), max_depth=depth)
+
+
 # ---- network inputs and weights shared by the network tests ---------------------------------------------------------------------
 def blob_offsets(C):
     """start of (LSTM1 dir0 K, R, b | dir1 ... | LSTM2 ... | L4 W, b | heads) in the weight blob (include/c3r.h, c3r_load_weights)."""
