@@ -56,6 +56,23 @@ constexpr int LSTM_SITES = NET_SITES * LSTM_SB;
 #ifndef C3R_DIR_ILV
 #define C3R_DIR_ILV 1        // k_lstm1_rs / layer 2: grid (2, groups) — the two directions of a site group are dispatched back to back
 #endif
+// y1 (6.8 GB per chr20 pass) and a4part are written once and read once, and layer 2's hot set — a direction's weights and its W4p time
+// slices, 3.8 MB — is nearly the whole of an XCD's 4 MB L2: the single-use streams carry the non-temporal policy, the weights do not.
+#ifndef C3R_Y1_NT_LOAD
+#define C3R_Y1_NT_LOAD 1     // layer 2: the LDS-DMA of y1 (dma_x, dma_x16) with the nt bit
+#endif
+#ifndef C3R_Y1_NT_STORE
+#define C3R_Y1_NT_STORE 1    // k_lstm1_rs's y1 stores and layer 2's a4part stores with the nt bit
+#endif
+#ifndef C3R_L2_SKIP0
+#define C3R_L2_SKIP0 1       // k_lstm2_w16: step 0 has no recurrent part (h_{-1} = 0: ten of its 26 units and the L4 tile are exact zeros)
+#endif
+#define C3R_Y1_AUX (C3R_Y1_NT_LOAD ? 2 : 0)      // __builtin_amdgcn_global_load_lds's cache policy: bit 1 = nt
+template <class V, class P>
+__device__ __forceinline__ void y1_store(V v, P p) {
+    if constexpr (C3R_Y1_NT_STORE) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
 constexpr int NET_FLAT = NET_T * 2 * NET_H2;   // 10560
 constexpr int NET_L4 = 128;
 
@@ -409,7 +426,8 @@ __device__ __forceinline__ void lds_wait(int *c, int target, int *tmo) {
 //   * the pipeline runs over (k-group G, subtile st) units — 26 of them, A operands of the same size as the 16-k groups of the
 //     32x32x16 layout, so the same two-slot ring; the B operands (four site blocks, hi and lo) are read once per k-group, one unit ahead, and serve both subtiles;
 //   * the accumulators start from the fp32 bias x 2^s (exact; kept in LDS) instead of a bias MFMA;
-//   * the fused L4's 32 rows of a quarter are two subtiles as well: a lane's 4 rows are 4 consecutive L4 outputs (float4 stores).
+//   * the fused L4's 32 rows of a quarter are two subtiles as well: a lane's 4 rows are 4 consecutive L4 outputs (float4 stores);
+//   * step 0 is the x part alone (C3R_L2_SKIP0); y1 comes in and a4part goes out with the non-temporal policy (C3R_Y1_NT_LOAD / _STORE).
 //   Wp  : [dir][quarter(4)][u = 2G + st (26)][tile(5)][hi|lo][64 lanes] half8 — lane l: row l % 16 of subtile st, k = 32G + 8 (l / 16) + 0..7
 //   W4p : [dir][t][quarter(4)][u = 2G + st (10)][hi|lo][64 lanes] half8 — row l % 16 <-> L4 output 32 quarter + 16 st + l % 16
 //   bp  : pack_lstm_dir's fp32 bias layout (pack_lstm_dir: [dir][tile][r = 8q + 4hh + m] <-> gate m of unit 8 tile + 4 hh + q)
@@ -457,7 +475,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
         for (int r = 0; r < 2 * KC / 8; ++r) {
             const int row = wave * (2 * KC / 8) + r, pl = row / KC, kc = row % KC;
             const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
         }
     };
     auto dma_x16 = [&](int tt_) {
@@ -467,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
         for (int r = 0; r < 2 * KC / 4; ++r) {
             const int row = (wave & 3) * (2 * KC / 4) + r, pl = row / KC, kc = row % KC;
             const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
         }
     };
     dma_x(dir ? NET_T - 1 : 0);
@@ -488,15 +506,23 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
 #pragma unroll
         for (int st = 0; st < (L4T ? 2 : 1); ++st)
 #pragma unroll
-            for (int sb = 0; sb < (L4T ? SB : 1); ++sb)
+            for (int sb = 0; sb < (L4T ? SB : 1); ++sb) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) facc[st][sb][r] = 0.f;
+                for (int r = 0; r < 4; ++r) {
+                    // (every zero a value of its own: facc now enters the loop past the step-0 branch, and zeros the compiler knows to be
+                    // one value are set up before the loop as 16 v_mov_b64 copies of a register pair — harmless, but tests/test_lstm_isa.py
+                    // takes any v_mov_b64 in this kernel for a weight address rebuilt in vector registers)
+                    float z = 0.f;
+                    if constexpr (C3R_L2_SKIP0 && L4T) asm volatile("" : "+v"(z));
+                    facc[st][sb][r] = z;
+                }
+            }
 
         typedef const half8 __attribute__((address_space(1))) *gptr_t;
         const uint32_t wlane = (uint32_t)lane;
         for (int step = 0; step < NET_T; ++step) {
             const int t = dir ? NET_T - 1 - step : step;
-            const int tprev = step ? (dir ? t + 1 : t - 1) : t;      // step 0: h_{-1} = 0, any valid slice contributes nothing
+            const int tprev = step ? (dir ? t + 1 : t - 1) : t;      // step 0: any valid slice (C3R_L2_SKIP0: unit 2 NGX's is still requested, never multiplied)
             const int cur = step & 1, nxt = cur ^ 1;
 
             auto ldx = [&](int g, half8 (&bh)[SB], half8 (&bl)[SB]) {
@@ -594,10 +620,19 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
             if constexpr (C3R_W8_ASYNC) lds_arrive(&s_ctr[0]); else __syncthreads();                              \
         }                                                                                                         \
     }
+            // Step 0 ends with the x part: h_{-1} = 0, so the recurrent units U >= 2 NGX (their weight stream, their reads of a zeroed hb,
+            // their MFMAs, the fused L4 tile) add exact zeros.  One uniform branch, no second copy of the body; the counters see the
+            // same arrivals (s_ctr[0] after unit 2 NGX - 1, s_ctr[2] and s_ctr[1] after the cell update).  The operands of unit 2 NGX are
+            // still requested at step 0, under the MFMAs of the unit before it as at every step: with that request inside the branch
+            // too, its loads no longer share registers with the operands that die under those MFMAs, and 12 registers spill.
+            static_assert(2 * NGX == 16, "the unit lists below: the x part ends with unit 15");
             C3R_LOAD(0);
             C3R_STEP(0) C3R_STEP(1) C3R_STEP(2) C3R_STEP(3) C3R_STEP(4) C3R_STEP(5) C3R_STEP(6) C3R_STEP(7) C3R_STEP(8) C3R_STEP(9)
-            C3R_STEP(10) C3R_STEP(11) C3R_STEP(12) C3R_STEP(13) C3R_STEP(14) C3R_STEP(15) C3R_STEP(16) C3R_STEP(17) C3R_STEP(18)
+            C3R_STEP(10) C3R_STEP(11) C3R_STEP(12) C3R_STEP(13) C3R_STEP(14) C3R_STEP(15)
+            if (!C3R_L2_SKIP0 || step) {
+            C3R_STEP(16) C3R_STEP(17) C3R_STEP(18)
             C3R_STEP(19) C3R_STEP(20) C3R_STEP(21) C3R_STEP(22) C3R_STEP(23) C3R_STEP(24) C3R_STEP(25)
+            }
             C3R_FENCE();
 #undef C3R_STEP
 #undef C3R_LOAD
@@ -686,8 +721,8 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                 if (sidx < n) {
 #pragma unroll
                     for (int st = 0; st < 2; ++st) {
-                        const float4 v = make_float4(facc[st][sb][0] * wun4, facc[st][sb][1] * wun4, facc[st][sb][2] * wun4, facc[st][sb][3] * wun4);
-                        *(float4 *)(a4part + ((size_t)sidx * 2 + dir) * NET_L4 + 32 * sq + 16 * st + 4 * q4) = v;
+                        const floatx4 v = {facc[st][sb][0] * wun4, facc[st][sb][1] * wun4, facc[st][sb][2] * wun4, facc[st][sb][3] * wun4};
+                        y1_store(v, (floatx4 *)(a4part + ((size_t)sidx * 2 + dir) * NET_L4 + 32 * sq + 16 * st + 4 * q4));
                     }
                 }
             }
@@ -759,7 +794,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
         for (int r = 0; r < 2 * KC / 8; ++r) {
             const int row = wave * (2 * KC / 8) + r, pl = row / KC, kc = row % KC;
             const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
         }
     };
     auto dma_x16 = [&](int tt_) {          // C3R_W8_ASYNC: all 64 rows from the four 3-tile wavefronts
@@ -769,7 +804,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
         for (int r = 0; r < 2 * KC / 4; ++r) {
             const int row = (wave & 3) * (2 * KC / 4) + r, pl = row / KC, kc = row % KC;
             const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
         }
     };
     dma_x(dir ? NET_T - 1 : 0);
@@ -1044,9 +1079,9 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
                 if (sidx < n) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        float4 v = make_float4(facc[sb][4 * q] * WUNSCALE, facc[sb][4 * q + 1] * WUNSCALE, facc[sb][4 * q + 2] * WUNSCALE,
-                                               facc[sb][4 * q + 3] * WUNSCALE);
-                        *(float4 *)(a4part + ((size_t)sidx * 2 + dir) * NET_L4 + 32 * sq + 8 * q + 4 * hh) = v;
+                        const floatx4 v = {facc[sb][4 * q] * WUNSCALE, facc[sb][4 * q + 1] * WUNSCALE, facc[sb][4 * q + 2] * WUNSCALE,
+                                           facc[sb][4 * q + 3] * WUNSCALE};
+                        y1_store(v, (floatx4 *)(a4part + ((size_t)sidx * 2 + dir) * NET_L4 + 32 * sq + 8 * q + 4 * hh));
                     }
                 }
             }
@@ -1299,9 +1334,9 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
             *(half4 __attribute__((address_space(3))) *)(hwr + 32 * sb * HP * 2) = vh;
             *(half4 __attribute__((address_space(3))) *)(hwr + 32 * sb * HP * 2 + HLO) = vl;
             const gh_t yp = yrow + (size_t)(ylane + 32 * sb * 8);
-            *(gh4_t)yp = vh;
+            y1_store(vh, (gh4_t)yp);
             if constexpr (!YQ) {
-                if (!(C3R_PROBE_Y1 && (blk & 1))) *(gh4_t)(yrow + plane_out + (size_t)(ylane + 32 * sb * 8)) = vl;
+                if (!(C3R_PROBE_Y1 && (blk & 1))) y1_store(vl, (gh4_t)(yrow + plane_out + (size_t)(ylane + 32 * sb * 8)));
             } else {                                     // the fp8 plane precision 2's layer 2 reads (k_lstm2_mx's x layout)
                 int w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], 0, false);
                 w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], w_lo, true);
@@ -1312,8 +1347,8 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                 asm volatile("" : "+s"(qrow));
                 typedef int __attribute__((address_space(1))) *gi_t;
                 const uint32_t qlane = (uint32_t)(j * 8 + 2 * hh + 32 * sb * 8);
-                *(gi_t)(qrow + (size_t)qlane) = w_lo;
-                *(gi_t)(qrow + (size_t)2 * nstride * 8 + (size_t)qlane) = w_hi;
+                y1_store(w_lo, (gi_t)(qrow + (size_t)qlane));
+                y1_store(w_hi, (gi_t)(qrow + (size_t)2 * nstride * 8 + (size_t)qlane));
             }
         }
         if (step + 1 < NET_T) x_store(nxt, step + 1);
