@@ -20,11 +20,15 @@ The host stages overlap on threads (the GIL is released inside libc3r / libc3r_i
              for its kernels the others prepare or decode
     merge    per-record rules + order, in calling order as the contigs come out (libc3r_io.so)
 
-Not covered (use the reference's own orchestration around call_var_bam for these): whatshap/longphase phasing between the
-two passes (external tools), gVCF.  `--enable_phasing_model` here expects an already haplotagged BAM (HP tags) and runs the
-30-channel pass only — the second half of run_clair3_rna:729-852.
+Not covered (use the reference's own orchestration around call_var_bam for these): whatshap/longphase PHASING between the
+two passes (external tools), gVCF.  `--enable_phasing_model` runs the 30-channel pass only — the second half of
+run_clair3_rna:729-852 — either on an already haplotagged BAM (HP tags), or, with `--phased_vcf_fn`, on the ORIGINAL BAM plus
+the phased VCF(s) the phasing step wrote: the reads are then haplotagged on the GPU while they are prepared (c3r_set_phase_sites),
+and the reference's "Haplotag the BAM" commands (run_clair3_rna:769-801: whatshap / longphase haplotag, samtools index) are not needed.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
+    python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
+        --enable_phasing_model --phased_vcf_fn out/tmp/phased_output/phased_vcf --output_dir out
 """
 import argparse
 import os
@@ -131,7 +135,11 @@ def build_parser():
     a("-p", "--platform", type=str, default="ont")
     a("--pileup_model_path", type=str, required=True, help="checkpoint prefix (…/variables), as passed to call_var_bam --chkpnt_fn")
     a("--phased_pileup_model_path", type=str, default=None)
-    a("--enable_phasing_model", action="store_true", help="30-channel pass on an already haplotagged BAM")
+    a("--enable_phasing_model", action="store_true", help="30-channel pass on an already haplotagged BAM, or on an untagged one with --phased_vcf_fn")
+    a("--phased_vcf_fn", type=str, default=None,
+      help="with --enable_phasing_model: one phased VCF for all contigs (plain or gzipped), or a directory that holds phased_<ctg>.vcf.gz "
+           "(what `whatshap phase` / `longphase phase` write per contig); the reads are haplotagged on the GPU from its phased heterozygous "
+           "SNVs and HP tags of the BAM are ignored.  A contig without phased sites runs with all reads untagged")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
     a("--genotyping_mode_vcf_fn", type=str, default=None)
@@ -315,6 +323,11 @@ def Run(args, log=None):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
     bed_fn, vcf_fn = existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn)
+    phased_vcf_fn = getattr(args, "phased_vcf_fn", None)
+    if phased_vcf_fn and not args.enable_phasing_model:
+        sys.exit("[ERROR] --phased_vcf_fn needs --enable_phasing_model (haplotags only enter the 30-channel tensors)")
+    if phased_vcf_fn and not os.path.exists(phased_vcf_fn):
+        sys.exit("[ERROR] file %s not found" % phased_vcf_fn)
     channels = 30 if args.enable_phasing_model else 18
     model = args.phased_pileup_model_path if args.enable_phasing_model else args.pileup_model_path
     if model is None:
@@ -448,8 +461,9 @@ def Run(args, log=None):
     # compression pass is left after the last contig)
     merger = sort_vcf.SampleMerger(out_fn, header, qual_merge, args.print_ref_calls, table, out_nt_fn, stream_gz=not args.no_compress) if rank == 0 else None
 
-    def device_stage(eng, ctg, rs, ref):
-        """-> number of candidates left resident in `eng` (rows are produced by decode_stage)."""
+    def device_stage(eng, ctg, rs, ref, phase=None):
+        """-> number of candidates left resident in `eng` (rows are produced by decode_stage).  phase: the contig's phase sites
+        (--phased_vcf_fn; None without the flag)."""
         extend_bed = existing(os.path.join(split_dir, ctg)) if bed_fn else None
         regions, site_sets, ext_iv = [], [], []
         for k in range(1, chunk_nums[ctg] + 1):
@@ -467,6 +481,11 @@ def Run(args, log=None):
                        indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
                        splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(vcf_fn is not None),
                        mpileup_compat=compat)
+        if phase is not None:                        # (--phased_vcf_fn; without it a context never holds a table)
+            eng.load_reads(_empty_reads())           # (the previous contig's reads are done with: a new table would tag them again first)
+            eng.set_phase_sites(phase)               # before the reads: they are tagged while they are prepared
+            if not len(phase):
+                rs.reads["hp"] = 0                   # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
         t = [time()]
         eng.load_reads(rs); t.append(time())
         eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str))); t.append(time())      # (the fetcher's array: upper-cased, used in place)
@@ -531,6 +550,19 @@ def Run(args, log=None):
             part_counts[k] = (m.n_read, m.n_kept, m.n_tagged)
 
     fetcher = _Fetcher(bam_fn, args.ref_fn)
+    phase_all, phase_lock = [], threading.Lock()
+
+    def phase_sites_of(ctg):
+        """--phased_vcf_fn: the contig's site table, read on a fetch thread.  One VCF for the whole sample is parsed once, by the
+        first thread that asks; a directory is read file by file."""
+        from . import phasedvcf
+        if os.path.isdir(phased_vcf_fn):
+            return phasedvcf.contig_sites(phased_vcf_fn, ctg)
+        with phase_lock:
+            if not phase_all:
+                phase_all.append(phasedvcf.read_all_phase_sites(phased_vcf_fn))
+        hit = phase_all[0].get(ctg)
+        return hit[0] if hit else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
     t_setup = time() - t_all
     # contigs fetched (or being fetched) but not yet through their context: every context busy + every fetch thread running ahead.
     # (n_ctx + 2 starved the contexts: a fetch takes ~100 ms, a context needs a new contig every ~35 ms)
@@ -551,7 +583,7 @@ def Run(args, log=None):
         t0 = time()
         ranges = fetcher.plan(fai[ctg], max(1, args.fetch_threads))
         out = Future()
-        state = dict(left=len(ranges) + 1, parts=[None] * len(ranges), ref=b"", err=None)
+        state = dict(left=len(ranges) + 1 + int(bool(phased_vcf_fn)), parts=[None] * len(ranges), ref=b"", err=None, phase=None)
         lk = threading.Lock()
 
         def done_one():
@@ -567,6 +599,7 @@ def Run(args, log=None):
                 mark(ctg, "fetch", t0)
                 if timeline:
                     log("[timeline-fetch %s] %d range(s): %d reads, %d CIGAR ops, %.0f MB of bases, %.0f Mb of reference" % (ctg, len(ranges), len(rs.reads), len(rs.cigar), len(rs.seq) / 1e6, len(state["ref"]) / 1e6))
+                rs.phase_sites = state["phase"]
                 out.set_result((rs, state["ref"] if len(rs.reads) else b"", time() - t0))
             except BaseException as e:
                 out.set_exception(e)
@@ -585,9 +618,18 @@ def Run(args, log=None):
                 state["err"] = e
             done_one()
 
+        def phase_task():
+            try:
+                state["phase"] = phase_sites_of(ctg)
+            except BaseException as e:
+                state["err"] = e
+            done_one()
+
         for k, (beg, end) in enumerate(ranges):
             pool.submit(part_task, k, beg, end)
         pool.submit(ref_task)
+        if phased_vcf_fn:
+            pool.submit(phase_task)
         return out
 
     def context_task(eng, ctg, fut):
@@ -602,7 +644,7 @@ def Run(args, log=None):
             # because a multi-GB hipMalloc under another context's kernels took 0.3-0.5 s; with the network's buffers reserved
             # ahead (c3r_reserve) what is left is cheaper than the wait: 1.38-1.47 s against 1.58-1.60 s on 22 half-length contigs.)
             t0 = time()
-            todo = device_stage(eng, ctg, rs, ref)
+            todo = device_stage(eng, ctg, rs, ref, getattr(rs, "phase_sites", None))
             t1 = time()
             mark(ctg, "device", t0)
             with lock:

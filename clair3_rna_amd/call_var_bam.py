@@ -111,6 +111,10 @@ def build_parser():
     a('--pypy', type=str, default="pypy3")
     a('--python', type=str, default="python3")
     a('--enable_phasing_model', type=str2bool, default=False)
+    a('--phased_vcf_fn', type=str, default=None,
+      help="with --enable_phasing_model True: a phased VCF (`whatshap phase` / `longphase phase`, plain or gzipped), or a directory that holds "
+           "phased_<ctg>.vcf.gz; the reads of --bam_fn are haplotagged on the GPU from its phased heterozygous SNVs (HP tags of the BAM are "
+           "ignored), so the BAM needs no `whatshap haplotag` pass")
     a('--minCoverage', type=int, default=4)
     a('--minMQ', type=int, default=5)
     a('--minBQ', type=int, default=0)
@@ -156,6 +160,9 @@ def Run(args, engine=None):
             sys.exit("[ERROR] --%s is not supported by the MI355X pileup path" % flag)
     if not args.pileup:
         sys.exit("[ERROR] only --pileup calling is implemented by the MI355X path")
+    phased_vcf_fn = getattr(args, "phased_vcf_fn", None)
+    if phased_vcf_fn and not args.enable_phasing_model:
+        sys.exit("[ERROR] --phased_vcf_fn needs --enable_phasing_model True (haplotags only enter the 30-channel tensors)")
     for need in (args.bam_fn, args.ref_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
@@ -186,11 +193,22 @@ def Run(args, engine=None):
     eng.set_bed(1, cbed)
     if sites is not None:
         eng.set_sites(sites)
+    # the phase sites of the WHOLE contig, before the reads: a read's tag must not depend on the chunk it is loaded for
+    phase_sites = None
+    if phased_vcf_fn:
+        from . import phasedvcf
+        phase_sites = phasedvcf.contig_sites(phased_vcf_fn, ctg)
+        if engine is not None:
+            from .reads import ReadSet
+            engine.load_reads(ReadSet.from_records([]))      # (a caller's engine may still hold a chunk's reads: a new table would tag them again first)
+    eng.set_phase_sites(phase_sites)
     eng.set_params(channels=channels, min_mq=args.minMQ, min_coverage=args.minCoverage, snp_min_af=args.snp_min_af,
                    indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
                    splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(sites is not None),
                    mpileup_compat=compat)
     rs = io.load_reads(args.bam_fn, ctg, extend_start - 1, extend_end)      # mpileup -r ctg:extend_start-extend_end
+    if phased_vcf_fn and not len(phase_sites):
+        rs.reads["hp"] = 0                  # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
     eng.load_reads(rs)
     eng.set_reference(ref_start, ref_seq)
     eng.load_weights(io.load_weights(args.chkpnt_fn, channels), channels)

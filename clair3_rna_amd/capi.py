@@ -15,7 +15,9 @@ SITE_DTYPE = np.dtype([("pos", "<i4"), ("depth", "<i4"), ("ref33", "S36"), ("n_t
 TOKEN_DTYPE = np.dtype([("read_idx", "<u4"), ("indel", "<i4"), ("qpos", "<u4"), ("base", "u1"), ("rev", "u1"), ("del_after", "<u2")],
                        align=True)
 PADINS_DTYPE = np.dtype([("read_idx", "<u4"), ("qpos", "<u4"), ("n_bases", "<u4"), ("total", "<u4"), ("pad_mask", "<u8")], align=True)
-assert SITE_DTYPE.itemsize == 52 and TOKEN_DTYPE.itemsize == 16 and PADINS_DTYPE.itemsize == 24
+# c3r_phase_site_t: one phased heterozygous SNV (phasedvcf.read_phase_sites); ref / alt are BAM 4-bit base codes (A 1, C 2, G 4, T 8)
+PHASE_SITE_DTYPE = np.dtype([("pos", "<i4"), ("ps", "<i4"), ("ref", "u1"), ("alt", "u1"), ("h1", "u1"), ("reserved", "u1")], align=True)
+assert SITE_DTYPE.itemsize == 52 and TOKEN_DTYPE.itemsize == 16 and PADINS_DTYPE.itemsize == 24 and PHASE_SITE_DTYPE.itemsize == 12
 
 C3R_ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EUNSUPPORTED", -6: "EOVERFLOW"}
 
@@ -25,6 +27,10 @@ class Params(C.Structure):
                 ("snp_min_af", C.c_double), ("indel_min_af", C.c_double), ("head_tail", C.c_int32),
                 ("splice_padding", C.c_int32), ("genotyping_mode", C.c_int32), ("max_depth_rescale", C.c_int32),
                 ("max_depth", C.c_int32), ("mpileup_compat", C.c_int32)]
+
+
+class HaplotagStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_reads", "n_hp1", "n_hp2", "n_no_vote", "n_tie", "n_votes")]
 
 
 class C3RError(RuntimeError):
@@ -37,7 +43,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_default_params", "c3r_set_params", "c3r_load_reads", "c3r_host_alloc", "c3r_host_free", "c3r_set_reference", "c3r_set_reference_view", "c3r_set_bed", "c3r_set_sites",
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
-           "c3r_get_kernel_stats", "c3r_get_scan_counts"]
+           "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags"]
 
 _lib = None
 
@@ -75,6 +81,8 @@ def load_library():
     L.c3r_set_reference_view.argtypes = [vp, i64, vp, i64]
     L.c3r_set_bed.argtypes = [vp, i32, vp, i64]
     L.c3r_set_sites.argtypes = [vp, vp, i64]
+    L.c3r_set_phase_sites.argtypes = [vp, vp, i64]
+    L.c3r_get_haplotags.argtypes = [vp, vp, i64, C.POINTER(HaplotagStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.c3r_batch_begin.argtypes = [vp]
@@ -236,6 +244,25 @@ class Engine(object):
     def set_sites(self, sites):
         a = np.ascontiguousarray(np.asarray(sites, dtype=np.int32))
         self._chk(self.L.c3r_set_sites(self.h, _ptr(a), len(a)))
+
+    def set_phase_sites(self, sites):
+        """The contig's phased heterozygous SNVs (a PHASE_SITE_DTYPE array sorted by pos, phasedvcf.read_phase_sites): from now on
+        load_reads haplotags every read on the device and the 30-channel build uses those tags instead of the records' own hp.  None or
+        an empty array clears the table.  Reads that are already loaded are tagged at once."""
+        a = np.zeros(0, PHASE_SITE_DTYPE) if sites is None else np.asarray(sites)
+        if a.dtype != PHASE_SITE_DTYPE:
+            raise TypeError("phase sites must be a capi.PHASE_SITE_DTYPE array, got %r" % (a.dtype,))
+        a = np.ascontiguousarray(a)
+        self._chk(self.L.c3r_set_phase_sites(self.h, _ptr(a), len(a)))
+
+    def haplotags(self):
+        """(uint8[n] tags of the loaded reads in load order, dict(n_reads, n_hp1, n_hp2, n_no_vote, n_tie, n_votes)); an error while no
+        phase sites are set."""
+        st = HaplotagStats()
+        self._chk(self.L.c3r_get_haplotags(self.h, None, 0, C.byref(st)))
+        hp = np.zeros(st.n_reads, dtype=np.uint8)
+        self._chk(self.L.c3r_get_haplotags(self.h, _ptr(hp), len(hp), C.byref(st)))
+        return hp, {k: int(getattr(st, k)) for k, _ in HaplotagStats._fields_}
 
     # ---- tensor build
     def scan(self, ctg_start, ctg_end):

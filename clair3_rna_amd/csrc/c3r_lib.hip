@@ -24,6 +24,7 @@
 #include "net_kernels.hpp"
 #include "pileup_kernels.hpp"
 #include "reads_kernels.hpp"
+#include "haplotag_kernels.hpp"
 #include <sched.h>
 
 using namespace c3r;
@@ -150,6 +151,10 @@ struct c3r_ctx {
     bool has_bed[2] = {false, false};
     std::vector<int32_t> h_sites;
     DevBuf d_sites;
+    // haplotagging (c3r_set_phase_sites): the contig's phased SNVs and, once reads have been loaded under them, the reads' tags
+    // (tag | votes << 2 per read, k_haplotag).  Nothing is allocated or launched while the table is empty.
+    int64_t n_phase = 0;
+    DevBuf d_phase, d_hptag;
 
     // ---- scan state
     int32_t reg_beg0 = 0, reg_end0 = 0;   // first region of the most recent scan (c3r_get_columns)
@@ -554,6 +559,18 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     ctx->padins.reset();
     if (hs.n_padreads > 0 && (rc = build_padins(ctx, n))) return rc;          // (hand-made CIGARs only: off the measured path)
     const auto t_sync = std::chrono::steady_clock::now();
+    // ---- haplotags from the phase sites, if the caller has set any: the records have passed the range checks above, and the second pass
+    // takes every read's hp from the header this kernel writes it to (nothing here waits for the device)
+    if (ctx->n_phase > 0) {
+        if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16))) return rc;
+        HapArgs h;
+        memset(&h, 0, sizeof h);
+        h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
+        h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_phase_site_t *)ctx->d_phase.p; h.n_sites = (int32_t)ctx->n_phase;
+        h.tags = (uint32_t *)ctx->d_hptag.p;
+        Launch L(ctx, "k_haplotag");
+        hipLaunchKernelGGL(k_haplotag, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
+    }
     // ---- second pass (nothing below waits for the device): every record into its bin
     if ((rc = ensure(ctx, ctx->d_recs, (size_t)hs.n_rec * sizeof(PileRec) + 64))) return rc;
     {
@@ -706,7 +723,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -907,6 +924,57 @@ int c3r_set_sites(c3r_ctx *ctx, const int32_t *sites, int64_t n) {
     int rc = upload(ctx, ctx->d_sites, ctx->h_sites.data(), ctx->h_sites.size());
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return C3R_OK;
+}
+
+int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n) {
+    if (!ctx || n < 0 || (n && !sites)) return C3R_EINVAL;
+    if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many phase sites");
+    for (int64_t i = 0; i < n; ++i) {
+        const c3r_phase_site_t &e = sites[i];
+        auto base = [](uint8_t c) { return c == 1 || c == 2 || c == 4 || c == 8; };
+        if (e.pos < 1) return fail(ctx, C3R_EINVAL, "phase site %lld: pos %d is not a 1-based position", (long long)i, e.pos);
+        if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "phase site %lld: positions must be strictly increasing (%d after %d)", (long long)i, e.pos, sites[i - 1].pos);
+        if (!base(e.ref) || !base(e.alt)) return fail(ctx, C3R_EINVAL, "phase site %lld: ref / alt must be base codes 1, 2, 4 or 8 (got %d / %d)", (long long)i, e.ref, e.alt);
+        if (e.ref == e.alt) return fail(ctx, C3R_EINVAL, "phase site %lld: ref and alt are the same base", (long long)i);
+        if (e.h1 > 1) return fail(ctx, C3R_EINVAL, "phase site %lld: h1 must be 0 (GT 0|1) or 1 (GT 1|0)", (long long)i);
+        if (e.ps < 0) return fail(ctx, C3R_EINVAL, "phase site %lld: phase set %d is negative", (long long)i, e.ps);
+    }
+    if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->last_scan_pruned = false;
+    if (n) {
+        int rc = upload(ctx, ctx->d_phase, sites, (size_t)n);
+        if (rc) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's array may go once this returns)
+    }
+    ctx->n_phase = n;
+    // reads already loaded: their tables again, from the records the device holds (what c3r_set_params does for new filters)
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
+int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats_t *stats) {
+    if (!ctx) return C3R_EINVAL;
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads carry their records' own hp");
+    const int64_t n = ctx->n_reads;
+    if (hp && cap < n) return fail(ctx, C3R_EOVERFLOW, "haplotags of %lld reads do not fit %lld slots", (long long)n, (long long)cap);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> t((size_t)n);
+    if (n) {
+        HIPCHK(ctx, hipMemcpyAsync(t.data(), ctx->d_hptag.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    c3r_haplotag_stats_t st;
+    memset(&st, 0, sizeof st);
+    st.n_reads = n;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t tag = t[(size_t)i] & 3u, votes = t[(size_t)i] >> 2;
+        if (hp) hp[i] = (uint8_t)tag;
+        st.n_votes += votes;
+        if (tag == 1) st.n_hp1 += 1; else if (tag == 2) st.n_hp2 += 1; else if (votes == 0) st.n_no_vote += 1; else st.n_tie += 1;
+    }
+    if (stats) *stats = st;
     return C3R_OK;
 }
 

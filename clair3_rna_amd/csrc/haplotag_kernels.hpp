@@ -1,0 +1,147 @@
+// haplotag_kernels.hpp — k_haplotag: every loaded read's haplotype from the contig's phased heterozygous SNVs (c3r_set_phase_sites), on the
+// device, as part of read preparation.  Included by c3r_lib.hip only.
+//
+// What it replaces: the "Haplotag the BAM" step of the reference flow (run_clair3_rna:769-801: `whatshap haplotag` / `longphase haplotag` per
+// contig, then `samtools index`), which rewrites the whole BAM to add one byte per read.  The rule is stated in include/c3r.h and restated,
+// independently of this file, by tests/hapref.py.
+//
+// Where it runs: between the host wait of c3r_load_reads and k_prep<true>, so the records have passed k_prep<false>'s range checks (a load
+// that fails them never gets here) and DevRead / `serial` are there.  It overwrites DevRead::hp — the one field all three consumers of a
+// read's haplotype take it from (k_prep<true>: PileRec::w; the ordered recompute; k_legacy_write: DevSeg::hp) — and leaves the caller's
+// records (d_rawreads) alone: without a table k_prep<false> copies their hp as before.
+//
+// 16 lanes per read, like k_prep, and the same two walks (walk_plain_ops / walk_serial_ops).  Per read:
+//   1. two searches of the table for the read's span [pos, end), by the 16 lanes together (hap_lower_group): no site there (most reads of a
+//      sample whose phased SNVs are a kilobase apart) and the CIGAR is never touched;
+//   2. the walk: every M op searches its own stretch of the read's sites once and reads one nibble per site;
+//   3. the lanes' votes meet by shuffles.  When all votes of the read lie in one phase set (the common case) that is all.  Otherwise the
+//      phase sets are taken one at a time in the order of their numbers: each further walk counts the votes of one set and finds the next
+//      number above it, so any number of sets — interleaved as they may be — is exact in P + 1 walks with no storage.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "reads_kernels.hpp"
+
+namespace c3r {
+
+struct HapArgs {
+    DevRead *reads; int32_t n_reads;          // headers of k_prep<false>; hp is overwritten
+    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
+    const uint32_t *cigars;
+    const uint8_t *seq;                       // 4-bit packed bases
+    const c3r_phase_site_t *sites; int32_t n_sites;
+    uint32_t *tags;                           // [n_reads] tag | votes of the read on all phase sets << 2
+};
+
+// first site of [lo, hi) with pos >= p (hi: none)
+__device__ __forceinline__ int hap_lower(const c3r_phase_site_t *sites, int lo, int hi, long long p) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)sites[mid].pos < p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The same search by the 16 lanes of a read together: sixteen probes a round and a seventeenth of the candidates left after it (64 k sites:
+// four dependent loads where hap_lower takes sixteen).  All lanes of the group call it, with the same arguments, and all return the index.
+__device__ __forceinline__ int hap_lower_group(const c3r_phase_site_t *sites, int lo, int hi, long long p, int gl) {
+    const int shift = (int)(threadIdx.x & 63u) & ~(PREP_GRP - 1);              // where the group's lanes lie in the wavefront's ballot
+    while (lo < hi) {
+        const long long span = hi - lo;                                         // pivot g = lo + (g + 1) * span / 17: in [lo, hi), never decreasing with g
+        const bool below = (long long)sites[lo + (int)(((long long)gl + 1) * span / (PREP_GRP + 1))].pos < p;
+        const int c = __popc((uint32_t)(__ballot(below) >> shift) & ((1u << PREP_GRP) - 1u));          // pivots 0 .. c - 1 lie below p
+        const int nlo = c > 0 ? lo + (int)((long long)c * span / (PREP_GRP + 1)) + 1 : lo;
+        const int nhi = c < PREP_GRP ? lo + (int)(((long long)c + 1) * span / (PREP_GRP + 1)) : hi;
+        lo = nlo; hi = nhi;
+    }
+    return lo;
+}
+
+constexpr uint32_t HAP_NONE = 0xffffffffu;    // no phase set (ps is an int32 >= 0)
+
+// What one walk over a read gathers in one lane, and in all lanes of the group after reduce().
+struct HapTally {
+    uint32_t c1, c2;          // votes for haplotype 1 / 2 in the phase set `cur` (HAP_NONE: in all sets)
+    uint32_t first;           // table index of the first voting site of those (HAP_NONE: none)
+    uint32_t ps_min, ps_max;  // smallest / largest phase set above `cur` that holds a vote (ps_min HAP_NONE: none)
+    __device__ __forceinline__ void clear() { c1 = 0; c2 = 0; first = HAP_NONE; ps_min = HAP_NONE; ps_max = 0; }
+    __device__ __forceinline__ void reduce() {
+#pragma unroll
+        for (int off = PREP_GRP / 2; off > 0; off >>= 1) {
+            c1 += __shfl_xor(c1, off, PREP_GRP);
+            c2 += __shfl_xor(c2, off, PREP_GRP);
+            first = min(first, (uint32_t)__shfl_xor(first, off, PREP_GRP));
+            ps_min = min(ps_min, (uint32_t)__shfl_xor(ps_min, off, PREP_GRP));
+            ps_max = max(ps_max, (uint32_t)__shfl_xor(ps_max, off, PREP_GRP));
+        }
+    }
+};
+
+// One walk: the votes of the sites [lo, hi) that the read's M ops cover.  cur = HAP_NONE: every vote counts and ps_min / ps_max span all
+// sets; else only the votes of set `cur` count and ps_min is the next set above it.  All lanes of the group come here together.
+__device__ __forceinline__ HapTally hap_walk(const ReadInfo &R, int gl, bool serial, const HapArgs &a, int lo, int hi, uint32_t cur) {
+    HapTally t;
+    t.clear();
+    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &) __attribute__((always_inline)) {
+        if (op != C3R_CIG_M) return;
+        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
+            const c3r_phase_site_t e = a.sites[s];
+            const long long d = (long long)e.pos - 1 - x;
+            if (d >= (long long)len) break;
+            const unsigned long long q = (unsigned long long)y + (unsigned long long)d;
+            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
+            const uint32_t byte = a.seq[R.seq_off + (q >> 1)], b = (q & 1) ? (byte & 15u) : (byte >> 4);
+            if (b != e.ref && b != e.alt) continue;
+            const uint32_t ps = (uint32_t)e.ps;
+            if (cur == HAP_NONE) { t.ps_min = min(t.ps_min, ps); t.ps_max = max(t.ps_max, ps); }
+            else {
+                if (ps > cur) t.ps_min = min(t.ps_min, ps);
+                if (ps != cur) continue;
+            }
+            const uint32_t allele = b == e.alt ? 1u : 0u;
+            if (allele == e.h1) t.c1 += 1; else t.c2 += 1;
+            t.first = min(t.first, (uint32_t)s);
+        }
+    };
+    if (!serial) walk_plain_ops(R, gl, on_op);
+    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+    t.reduce();
+    return t;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
+    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
+    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
+    if (i >= a.n_reads) return;                                        // (whole groups leave: the shuffles below stay inside a group)
+    const DevRead d = a.reads[i];
+    // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
+    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
+    uint32_t tag = 0, votes = 0;
+    if (lo < hi) {
+        ReadInfo R;
+        R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
+        R.compat = 0; R.padbit = 0;
+        const bool serial = a.serial[i] != 0;
+        HapTally t = hap_walk(R, gl, serial, a, lo, hi, HAP_NONE);
+        votes = t.c1 + t.c2;
+        if (votes && t.ps_min != t.ps_max) {
+            // several phase sets: one walk each, in the order of their numbers; the set with the most votes wins, the earlier first site among equals
+            uint32_t best_n = 0, best_first = HAP_NONE, b1 = 0, b2 = 0;
+            for (uint32_t cur = t.ps_min; cur != HAP_NONE;) {
+                const HapTally u = hap_walk(R, gl, serial, a, lo, hi, cur);
+                const uint32_t n = u.c1 + u.c2;
+                if (n > best_n || (n == best_n && u.first < best_first)) { best_n = n; best_first = u.first; b1 = u.c1; b2 = u.c2; }
+                cur = u.ps_min;
+            }
+            t.c1 = b1; t.c2 = b2;
+        }
+        tag = t.c1 > t.c2 ? 1u : t.c2 > t.c1 ? 2u : 0u;
+    }
+    if (gl == 0) {
+        a.reads[i].hp = (uint8_t)tag;
+        a.tags[i] = tag | (votes << 2);
+    }
+}
+
+}  // namespace c3r

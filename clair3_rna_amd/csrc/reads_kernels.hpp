@@ -11,6 +11,7 @@
 //   k_prefmax_bins    inclusive prefix maximum of the passing reads' ends (one pass, decoupled look-back) + its histogram over the bins
 //   k_bin_scan        exclusive prefix sums over the bins (one pass, decoupled look-back): first record / reads started before /
 //                     reads whose prefix-max end lies before / reads ended before each bin; upper bound of the deepest coverage
+//   (k_haplotag       haplotag_kernels.hpp, only while phase sites are set: every read's hp from the phased SNVs, through the same two walks)
 //   k_prep<true>      the same walk again: every record takes its slot in its bin (the bin counters count down to zero)
 // Round 3 prepared per-read normalised CIGARs, aligned segments, two rocPRIM radix sorts, prefix maxima, a bucket index and an op
 // table in ~45 launches and 0.85 ms per chr20; those tables survive only as the LEGACY tables below, built on demand for the one
@@ -219,8 +220,9 @@ __device__ __forceinline__ bool cigar_is_plain(const ReadInfo &R, int gl, long l
 }
 
 // The parallel walk: lane gl of the group takes ops gl, gl + 16, ...; reference / query offsets by 16-lane prefix sums.
-template <class Emit>
-__device__ __forceinline__ void walk_plain(const ReadInfo &R, int gl, Emit &&emit) {
+// on_op(op, len, x, y, neighbours) receives every op of the read (folded: = and X are M), by the lane that holds it.
+template <class OnOp>
+__device__ __forceinline__ void walk_plain_ops(const ReadInfo &R, int gl, OnOp &&on_op) {
     uint32_t x = (uint32_t)R.pos, y = 0;                       // (less than 2^28 reference positions: 32 bits do)
     for (uint32_t k0 = 0; k0 < R.n_cig; k0 += PREP_GRP) {
         const uint32_t k = k0 + (uint32_t)gl;
@@ -241,10 +243,15 @@ __device__ __forceinline__ void walk_plain(const ReadInfo &R, int gl, Emit &&emi
             const uint32_t tr = __shfl_up(ri, off, PREP_GRP), tq = __shfl_up(qi, off, PREP_GRP);
             if (gl >= off) { ri += tr; qi += tq; }
         }
-        if (in) op_records(R, op, len, (long long)(int32_t)(x + ri - rl), y + qi - ql, cx, emit);
+        if (in) on_op(op, len, (long long)(int32_t)(x + ri - rl), y + qi - ql, cx);
         x += __shfl(ri, PREP_GRP - 1, PREP_GRP);
         y += __shfl(qi, PREP_GRP - 1, PREP_GRP);
     }
+}
+// ... with the pile records of every op: emit(rstart, w, naddr, q, nxt, aux), see op_records
+template <class Emit>
+__device__ __forceinline__ void walk_plain(const ReadInfo &R, int gl, Emit &&emit) {
+    walk_plain_ops(R, gl, [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) __attribute__((always_inline)) { op_records(R, op, len, x, y, cx, emit); });
 }
 
 // The serial walk (one lane): walk_norm's stream, two ops of look-ahead (the indel attached to an op's last column, and with
@@ -254,8 +261,9 @@ __device__ __forceinline__ void walk_plain(const ReadInfo &R, int gl, Emit &&emi
 // does not change (pads consume nothing; the record of the merged I op carries the bases); a read that has such a run is flagged
 // (*pads = true: its I records carry PR_INS_PADS) and the host builds the table of those runs (c3r_padins_t) that ev_equal and the
 // decoder look up.  A run of more than 64 characters is refused (LD_PAD_INS): the table describes the pads by a 64-bit mask.
-template <class Emit>
-__device__ __forceinline__ int walk_serial(const ReadInfo &R, Emit &&emit, bool *pads = nullptr) {
+// on_op(op, len, x, y, neighbours) receives every op of the NORMALISED form (walk_serial_ops); walk_serial turns them into pile records.
+template <class OnOp>
+__device__ __forceinline__ int walk_serial_ops(const ReadInfo &R, OnOp &&on_op, bool *pads = nullptr) {
     if (R.compat) {
         uint32_t run_i = 0, run_p = 0;
         bool any = false;
@@ -282,7 +290,7 @@ __device__ __forceinline__ int walk_serial(const ReadInfo &R, Emit &&emit, bool 
     auto flush = [&](const NOp &o, uint32_t nop, uint32_t nlen, uint32_t n2op, uint32_t n2len) {
         OpCtx cx;
         cx.prev = o.prev; cx.prev2 = o.prev2; cx.nop = nop; cx.nlen = nlen; cx.n2op = n2op; cx.n2len = n2len;
-        op_records(R, o.op, o.len, o.x, o.y, cx, emit);
+        on_op(o.op, o.len, o.x, o.y, cx);
     };
     const int err = walk_norm(R.cig, R.n_cig, [&](uint32_t op, uint32_t len) {
         NOp c;
@@ -300,6 +308,10 @@ __device__ __forceinline__ int walk_serial(const ReadInfo &R, Emit &&emit, bool 
     else if (nq == 1) flush(q0, 15u, 0u, 15u, 0u);
     w.close(seg);
     return w.bad;
+}
+template <class Emit>
+__device__ __forceinline__ int walk_serial(const ReadInfo &R, Emit &&emit, bool *pads = nullptr) {
+    return walk_serial_ops(R, [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) __attribute__((always_inline)) { op_records(R, op, len, x, y, cx, emit); }, pads);
 }
 
 struct PrepArgs {

@@ -97,6 +97,24 @@ int c3r_set_reference_view(c3r_ctx *ctx, int64_t ref_start, const char *ref_uppe
 int c3r_set_bed(c3r_ctx *ctx, int which, const int32_t *start_end_pairs, int64_t n);
 /* Genotyping mode site list (--vcf_fn; src/create_tensor_pileup.py:399-407,555-556), 1-based. */
 int c3r_set_sites(c3r_ctx *ctx, const int32_t *sites, int64_t n);
+/* Haplotagging on the device: the phased heterozygous SNVs of the contig (what `whatshap phase` / `longphase phase` wrote,
+ * run_clair3_rna:729-767), sorted by strictly increasing pos.  While a table is set, every c3r_load_reads computes each read's haplotype from
+ * it as part of read preparation (k_haplotag, csrc/haplotag_kernels.hpp) and the 30-channel tensor build uses that tag INSTEAD of the
+ * record's own hp — the "Haplotag the BAM" step of the reference flow (run_clair3_rna:769-801: whatshap / longphase haplotag, samtools
+ * index) is not needed.  The rule, per read, whatever excl_flags / min_mq say: walk the CIGAR (M, = and X consume reference and query, D and
+ * N the reference, I and S the query, H, P and empty ops nothing); a site under an M / = / X op at a query offset below l_seq votes when
+ * the read's base there is the site's ref (allele 0) or alt (allele 1) — for haplotype 1 when allele == h1, else for haplotype 2; votes
+ * are counted per phase set as (c1, c2); the read's phase set is the one with the most votes (equal: the one whose first voting site on
+ * the read comes first); hp = 1 if c1 > c2, 2 if c2 > c1, else 0.  This is whatshap's per-phase-set majority with unit weights and the
+ * allele read off the CIGAR position: no realignment, and no base-quality weights (the records carry no qualities).
+ * n = 0 clears the table: nothing is launched then and the records' own hp count again.  C3R_EINVAL, naming the first bad index, for an
+ * unsorted or repeated position, pos < 1, a base code other than 1, 2, 4, 8, ref == alt, h1 > 1 or ps < 0.  Valid before or after c3r_load_reads
+ * with the same result: when reads are loaded their tables are rebuilt from the records the device holds (as c3r_set_params does for new
+ * filters).  The table stays for later c3r_load_reads calls until it is replaced. */
+int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n);
+/* The tags of the loaded reads, in load order (hp: [cap], cap >= the number of loaded reads; may be NULL), and their statistics (may be
+ * NULL).  C3R_EINVAL when no phase sites are set. */
+int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats_t *stats);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped

@@ -114,6 +114,30 @@ typedef struct c3r_padins {
     uint64_t pad_mask;    /* bit j: character j of the printed insertion is a pad                    */
 } c3r_padins_t;
 
+/* One phased heterozygous biallelic SNV of the loaded contig (c3r_set_phase_sites): what `whatshap phase` / `longphase phase` wrote
+ * (run_clair3_rna:729-767) as far as haplotagging needs it.  The table is sorted by strictly increasing pos. */
+typedef struct c3r_phase_site {
+    int32_t pos;          /* 1-based position                                                        */
+    int32_t ps;           /* phase set (the PS FORMAT field), >= 0                                   */
+    uint8_t ref, alt;     /* BAM 4-bit base codes, each one of 1, 2, 4, 8 (A, C, G, T); ref != alt   */
+    uint8_t h1;           /* 0: GT 0|1 (REF on haplotype 1); 1: GT 1|0 (ALT on haplotype 1)          */
+    uint8_t reserved;     /* must be 0                                                               */
+} c3r_phase_site_t;
+#ifdef __cplusplus
+static_assert(sizeof(c3r_phase_site_t) == 12, "c3r_phase_site_t must be 12 bytes");
+#else
+_Static_assert(sizeof(c3r_phase_site_t) == 12, "c3r_phase_site_t must be 12 bytes");
+#endif
+
+/* What the haplotagging of the loaded reads came to (c3r_get_haplotags).  n_reads = n_hp1 + n_hp2 + n_no_vote + n_tie. */
+typedef struct c3r_haplotag_stats {
+    int64_t n_reads;      /* loaded reads (all of them vote, whatever the filters say)               */
+    int64_t n_hp1, n_hp2; /* reads tagged 1 / 2                                                      */
+    int64_t n_no_vote;    /* reads that show REF or ALT on no phase site: untagged                   */
+    int64_t n_tie;        /* reads whose phase set came to c1 == c2: untagged                        */
+    int64_t n_votes;      /* votes of all reads on all phase sets                                    */
+} c3r_haplotag_stats_t;
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Pin the two "parity unpinned" halves against the third-party tools themselves, the day they exist beside this repository
-(neither samtools nor TensorFlow is in the build image).
+"""Pin the "parity unpinned" halves against the third-party tools themselves, the day they exist beside this repository
+(neither samtools nor TensorFlow nor whatshap is in the build image).
 
   python tools/pin_third_party.py --samtools /path/to/samtools            # A1: reads -> mpileup text
   python tools/pin_third_party.py --tf --reference_repo /path/to/Clair3-RNA   # F5: a TensorFlow-written checkpoint through tfckpt.py
+  python tools/pin_third_party.py --whatshap /path/to/whatshap            # K0: haplotags against `whatshap haplotag`  (NEVER RUN: no whatshap on any machine so far)
 
 A1.  Every known-answer case of tests/test_oracle_mpileup.py (harvested by running those tests with a recording `pile`), plus the depth-cap
      case (8000 / 8001 reads starting on one position, `-d 8000`), is written as SAM + FASTA, turned into an indexed BAM by the given
@@ -14,6 +15,12 @@ A1.  Every known-answer case of tests/test_oracle_mpileup.py (harvested by runni
 F5.  Builds the reference's Keras model (clair3_rna/model.py) for 18 and 30 channels, save_weights() into a temporary directory, reads the
      bundle with clair3_rna_amd/tfckpt.py and compares every tensor with model.get_weights() bit for bit
      (clair3_rna/call_variants.py:1472 is where the reference loads such a bundle).
+K0.  NEVER RUN.  The random two-haplotype read sets of tests/hapref.py (gen_case, seeds 0-2) are written as an indexed BAM (bam.write_bam,
+     reads named r1, r2, ... in load order) with a FASTA and a phased VCF, `whatshap haplotag --output-haplotag-list` tags them, and the list is
+     compared with our tags (the GPU's when a device is there, else tests/hapref.py, which the GPU tests hold equal to it).  The two rules
+     are NOT the same — whatshap realigns reads around each variant and weights votes by base quality; ours reads the allele off the CIGAR
+     position with unit weights (include/c3r.h) — so this leg REPORTS agreement (reads tagged alike / differently / by one side only) and
+     fails only when fewer than 95 % of the reads both sides tag carry the same haplotype.  That figure is a guess until the leg has run.
 Exit status 0: everything agreed."""
 import argparse
 import os
@@ -146,10 +153,54 @@ def pin_tf(reference_repo):
     return ok
 
 
+def pin_whatshap(whatshap):
+    """K0 (never run): our haplotags against `whatshap haplotag --output-haplotag-list` on tests/hapref.py's generated cases."""
+    import gzip
+    import numpy as np
+    from clair3_rna_amd import bam, bamio, io
+    from clair3_rna_amd.reads import NT16
+    from tests import hapref
+    ok = True
+    for seed in (0, 1, 2):
+        ref, rs, sites, _ = hapref.gen_case(seed)
+        try:
+            from clair3_rna_amd import capi
+            eng = capi.Engine(0)
+            eng.set_phase_sites(sites)
+            eng.load_reads(rs)
+            ours, who = eng.haplotags()[0], "k_haplotag"
+            eng.close()
+        except Exception:          # noqa: BLE001 (no device here: the restatement of the rule)
+            ours, who = hapref.haplotag(rs, sites)[0], "tests/hapref.py"
+        with tempfile.TemporaryDirectory() as tmp:
+            fa, bm, vcf, lst = (os.path.join(tmp, n) for n in ("ref.fa", "in.bam", "phased.vcf.gz", "tags.tsv"))
+            io.write_fasta(fa, [("c", ref)])
+            bam.write_bam(bm, [("c", len(ref))], {"c": rs})
+            bamio.index_build(bm)
+            with gzip.open(vcf, "wt") as f:          # (whatshap wants bgzip + tabix: `bgzip` / `tabix -p vcf` beside it do that; plain gzip is tried first)
+                f.write("##fileformat=VCFv4.2\n##contig=<ID=c,length=%d>\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"\">\n"
+                        "##FORMAT=<ID=PS,Number=1,Type=Integer,Description=\"\">\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE\n" % len(ref))
+                for s_ in sites:
+                    f.write("c\t%d\t.\t%s\t%s\t30\tPASS\t.\tGT:PS\t%s:%d\n" % (s_["pos"], NT16[s_["ref"]], NT16[s_["alt"]], "1|0" if s_["h1"] else "0|1", s_["ps"]))
+            subprocess.check_call([whatshap, "haplotag", "--reference", fa, "--ignore-read-groups", "--output-haplotag-list", lst, "-o", os.path.join(tmp, "out.bam"), vcf, bm])
+            theirs = np.zeros(len(rs), np.uint8)
+            for row in open(lst):
+                f_ = row.split("\t")
+                if row[0] != "#" and f_[0][0] == "r" and f_[1] in ("H1", "H2"):
+                    theirs[int(f_[0][1:]) - 1] = 1 if f_[1] == "H1" else 2
+        both = (ours > 0) & (theirs > 0)
+        same = int((ours[both] == theirs[both]).sum())
+        print("K0 seed %d (%s): %d reads, both tag %d (same %d, different %d), only ours %d, only whatshap %d" %
+              (seed, who, len(rs), int(both.sum()), same, int(both.sum()) - same, int(((ours > 0) & (theirs == 0)).sum()), int(((ours == 0) & (theirs > 0)).sum())))
+        ok = ok and both.sum() > 0 and same >= 0.95 * both.sum()
+    return ok
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samtools")
     ap.add_argument("--tf", action="store_true")
+    ap.add_argument("--whatshap", help="K0 (never run): compare our haplotags with `whatshap haplotag --output-haplotag-list`")
     ap.add_argument("--reference_repo", default="/root/reference")
     ap.add_argument("--list", action="store_true", help="only count the harvested cases (needs neither tool)")
     a = ap.parse_args()
@@ -161,6 +212,8 @@ def main():
         ok = pin_samtools(a.samtools) and ok
     if a.tf:
         ok = pin_tf(a.reference_repo) and ok
+    if a.whatshap:
+        ok = pin_whatshap(a.whatshap) and ok
     sys.exit(0 if ok else 1)
 
 
