@@ -20,15 +20,21 @@ The host stages overlap on threads (the GIL is released inside libc3r / libc3r_i
              for its kernels the others prepare or decode
     merge    per-record rules + order, in calling order as the contigs come out (libc3r_io.so)
 
-Not covered (use the reference's own orchestration around call_var_bam for these): whatshap/longphase PHASING between the
-two passes (external tools), gVCF.  `--enable_phasing_model` runs the 30-channel pass only — the second half of
+Not covered (use the reference's own orchestration around call_var_bam for these): gVCF.  `--enable_phasing_model` runs the 30-channel pass only — the second half of
 run_clair3_rna:729-852 — either on an already haplotagged BAM (HP tags), or, with `--phased_vcf_fn`, on the ORIGINAL BAM plus
 the phased VCF(s) the phasing step wrote: the reads are then haplotagged on the GPU while they are prepared (c3r_set_phase_sites),
 and the reference's "Haplotag the BAM" commands (run_clair3_rna:769-801: whatshap / longphase haplotag, samtools index) are not needed.
+`--enable_phasing_model --phasing builtin` (both model paths, no --phased_vcf_fn) is the whole phased flow in this process, with no external
+tool between the passes: the unphased run (<prefix>.vcf.gz), phase_vcf on that file — the built-in phasing of its heterozygous SNVs from read
+linkage on the GPU, a greedy linkage chain, not whatshap's wMEC (include/c3r.h: c3r_phase_links / c3r_phase_resolve) — into
+<output_dir>/tmp/phased_output/phased_vcf, then the run with --phased_vcf_fn on that directory (<prefix>_enable_phasing.vcf.gz).  One process
+only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line — run the three steps as three commands there.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
         --enable_phasing_model --phased_vcf_fn out/tmp/phased_output/phased_vcf --output_dir out
+    python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
+        --enable_phasing_model --phasing builtin --output_dir out
 """
 import argparse
 import os
@@ -140,6 +146,11 @@ def build_parser():
       help="with --enable_phasing_model: one phased VCF for all contigs (plain or gzipped), or a directory that holds phased_<ctg>.vcf.gz "
            "(what `whatshap phase` / `longphase phase` write per contig); the reads are haplotagged on the GPU from its phased heterozygous "
            "SNVs and HP tags of the BAM are ignored.  A contig without phased sites runs with all reads untagged")
+    a("--phasing", type=str, default=None, choices=["builtin"],
+      help="with --enable_phasing_model and without --phased_vcf_fn: run the whole flow in this process — the unphased pass (<prefix>.vcf.gz), "
+           "the built-in phasing of its heterozygous SNVs from read linkage on the GPU (phase_vcf: a greedy linkage chain, not whatshap's wMEC) "
+           "into <output_dir>/tmp/phased_output/phased_vcf, then the 30-channel pass on those files.  Needs both model paths; one process only "
+           "(not under torch.distributed.run)")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
     a("--genotyping_mode_vcf_fn", type=str, default=None)
@@ -288,6 +299,57 @@ def _empty_reads():
 
 
 def Run(args, log=None):
+    """One pass (_run_pass), or with `--phasing builtin` the three steps of the phased flow one after the other: the unphased pass, phase_vcf
+    on the file it wrote, the 30-channel pass with --phased_vcf_fn on phase_vcf's directory — nothing inside a pass changes."""
+    if getattr(args, "phasing", None) is None:
+        return _run_pass(args, log)
+    import copy
+    from . import phase_vcf
+    log = log or (lambda m: print(m, file=sys.stderr))
+    if not args.enable_phasing_model:
+        sys.exit("[ERROR] --phasing builtin needs --enable_phasing_model (it prepares the 30-channel pass)")
+    if getattr(args, "phased_vcf_fn", None):
+        sys.exit("[ERROR] --phasing builtin and --phased_vcf_fn exclude each other: the built-in phasing writes the phased VCFs itself")
+    if not args.phased_pileup_model_path:
+        sys.exit("[ERROR] --phased_pileup_model_path is required with --enable_phasing_model")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("[ERROR] --phasing builtin runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the unphased pass, "
+                 "`python -m clair3_rna_amd.phase_vcf`, and the pass with --phased_vcf_fn as three commands")
+    first = copy.copy(args)
+    first.phasing, first.enable_phasing_model = None, False
+    rc = _run_pass(first, log)
+    if rc:
+        return rc
+    vcf_fn = os.path.join(args.output_dir, args.output_prefix + (".vcf" if args.no_compress else ".vcf.gz"))
+    phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
+    # the BAM the passes read: this run's, or — when IT has no index — the link with an index beside it that the first pass left in tmp/
+    # (asked of the BAM again, not guessed from the link: an earlier run in this directory may have left one to another file)
+    bam_fn = args.bam_fn
+    if bam_fn.endswith(".bam"):
+        from . import bamio
+        with bamio.BamFile(bam_fn) as probe:
+            indexed = probe.has_index
+        link = os.path.join(args.output_dir, "tmp", "input.bam")
+        if not indexed and os.path.exists(link + ".bai") and os.path.realpath(link) == os.path.realpath(bam_fn):
+            bam_fn = link
+    # phased_<ctg>.vcf.gz of an earlier run in this directory: a contig without a row in this run's VCF would keep its file, and the second
+    # pass would haplotag from it
+    if os.path.isdir(phased_dir):
+        for name in os.listdir(phased_dir):
+            if name.startswith("phased_") and name.endswith(".vcf.gz"):
+                os.remove(os.path.join(phased_dir, name))
+    if os.path.isfile(vcf_fn):                                # (no contig found: the first pass wrote nothing, and neither will the second)
+        phase_vcf.Run(phase_vcf.build_parser().parse_args(
+            ["--bam_fn", bam_fn, "--vcf_fn", vcf_fn, "--output_dir", phased_dir, "--min_mq", str(args.min_mq)]
+            + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
+    else:
+        os.makedirs(phased_dir, exist_ok=True)
+    second = copy.copy(args)
+    second.phasing, second.phased_vcf_fn = None, phased_dir
+    return _run_pass(second, log)
+
+
+def _run_pass(args, log=None):
     from . import capi
     log = log or (lambda m: print(m, file=sys.stderr))
     t_all = time()

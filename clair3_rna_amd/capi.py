@@ -33,6 +33,17 @@ class HaplotagStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_reads", "n_hp1", "n_hp2", "n_no_vote", "n_tie", "n_votes")]
 
 
+PHASE_LINKS = 8                                              # C3R_PHASE_LINKS (include/c3r_types.h): predecessors every site is linked to
+
+
+class PhaseParams(C.Structure):
+    _fields_ = [("min_reads", C.c_int32), ("min_agree_pct", C.c_int32)]
+
+
+class PhaseStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_sites", "n_phased", "n_blocks", "max_block")]
+
+
 class C3RError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, "libc3r: %s (%s)" % (msg, C3R_ERRORS.get(code, code)))
@@ -43,7 +54,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_default_params", "c3r_set_params", "c3r_load_reads", "c3r_host_alloc", "c3r_host_free", "c3r_set_reference", "c3r_set_reference_view", "c3r_set_bed", "c3r_set_sites",
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
-           "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags"]
+           "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve"]
 
 _lib = None
 
@@ -83,6 +94,8 @@ def load_library():
     L.c3r_set_sites.argtypes = [vp, vp, i64]
     L.c3r_set_phase_sites.argtypes = [vp, vp, i64]
     L.c3r_get_haplotags.argtypes = [vp, vp, i64, C.POINTER(HaplotagStats)]
+    L.c3r_phase_links.argtypes = [vp, vp, i64, vp]
+    L.c3r_phase_resolve.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(PhaseStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.c3r_batch_begin.argtypes = [vp]
@@ -264,6 +277,21 @@ class Engine(object):
         self._chk(self.L.c3r_get_haplotags(self.h, _ptr(hp), len(hp), C.byref(st)))
         return hp, {k: int(getattr(st, k)) for k, _ in HaplotagStats._fields_}
 
+    def phase_links(self, sites):
+        """uint32 (n, PHASE_LINKS, 2) cis / trans counts between every candidate site (a PHASE_SITE_DTYPE array sorted by pos; ps and h1 are
+        ignored) and the PHASE_LINKS sites before it in the table, from the loaded reads that pass the current filters
+        (c3r_phase_links).  Leaves the reads' haplotags, the table of set_phase_sites and every scan as they are."""
+        a = _phase_site_array(sites)
+        links = np.zeros((len(a), PHASE_LINKS, 2), dtype=np.uint32)
+        self._chk(self.L.c3r_phase_links(self.h, _ptr(a), len(a), _ptr(links)))
+        return links
+
+    def phase_sites(self, sites, min_reads=2, min_agree_pct=75):
+        """phase_links, then the greedy chain of phase_resolve: (PHASE_SITE_DTYPE array with ps / h1 filled in — ps = -1: the site stays
+        unphased, drop it before set_phase_sites —, dict(n_sites, n_phased, n_blocks, max_block))."""
+        a = _phase_site_array(sites)
+        return phase_resolve(a, self.phase_links(a), min_reads, min_agree_pct)
+
     # ---- tensor build
     def scan(self, ctg_start, ctg_end):
         n = C.c_int64(0)
@@ -443,6 +471,29 @@ class Engine(object):
         n = C.c_int(0)
         self._chk(self.L.c3r_get_kernel_stats(self.h, names, ms, cnt, cap, C.byref(n)))
         return {names[i].decode(): dict(total_ms=ms[i], launches=cnt[i]) for i in range(min(n.value, cap))}
+
+
+def _phase_site_array(sites):
+    a = np.zeros(0, PHASE_SITE_DTYPE) if sites is None else np.asarray(sites)
+    if a.dtype != PHASE_SITE_DTYPE:
+        raise TypeError("sites must be a capi.PHASE_SITE_DTYPE array, got %r" % (a.dtype,))
+    return np.ascontiguousarray(a)
+
+
+def phase_resolve(sites, links, min_reads=2, min_agree_pct=75):
+    """The resolution rule of include/c3r.h on the host (c3r_phase_resolve; no GPU, no engine): candidate sites and their (n, PHASE_LINKS, 2)
+    link table -> (sites with ps / h1 filled in, ps = -1 for a site alone in its block; dict(n_sites, n_phased, n_blocks, max_block))."""
+    L = load_library()
+    a = _phase_site_array(sites)
+    lk = np.ascontiguousarray(links, dtype=np.uint32)
+    if lk.shape != (len(a), PHASE_LINKS, 2):
+        raise ValueError("links must have shape (%d, %d, 2), got %r" % (len(a), PHASE_LINKS, lk.shape))
+    out = np.zeros(len(a), dtype=PHASE_SITE_DTYPE)
+    p, st = PhaseParams(int(min_reads), int(min_agree_pct)), PhaseStats()
+    rc = L.c3r_phase_resolve(_ptr(a), len(a), _ptr(lk), C.byref(p), _ptr(out), C.byref(st))
+    if rc != 0:
+        raise C3RError(rc, "c3r_phase_resolve: sites must be sorted by strictly increasing pos, min_reads >= 0, 0 <= min_agree_pct <= 100")
+    return out, {k: int(getattr(st, k)) for k, _ in PhaseStats._fields_}
 
 
 class RowSnapshot(object):

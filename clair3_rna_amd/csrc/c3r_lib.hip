@@ -25,6 +25,7 @@
 #include "pileup_kernels.hpp"
 #include "reads_kernels.hpp"
 #include "haplotag_kernels.hpp"
+#include "phase_kernels.hpp"
 #include <sched.h>
 
 using namespace c3r;
@@ -155,6 +156,8 @@ struct c3r_ctx {
     // (tag | votes << 2 per read, k_haplotag).  Nothing is allocated or launched while the table is empty.
     int64_t n_phase = 0;
     DevBuf d_phase, d_hptag;
+    // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
+    DevBuf d_plsites, d_links;
 
     // ---- scan state
     int32_t reg_beg0 = 0, reg_end0 = 0;   // first region of the most recent scan (c3r_get_columns)
@@ -723,7 +726,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_plsites, &ctx->d_links, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -927,19 +930,25 @@ int c3r_set_sites(c3r_ctx *ctx, const int32_t *sites, int64_t n) {
     return C3R_OK;
 }
 
-int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n) {
-    if (!ctx || n < 0 || (n && !sites)) return C3R_EINVAL;
-    if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many phase sites");
+// The checks of a site table: `phased` = c3r_set_phase_sites (h1 and ps count), else c3r_phase_links (they are ignored).
+static int check_phase_sites(c3r_ctx *ctx, const char *what, const c3r_phase_site_t *sites, int64_t n, bool phased) {
+    if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many %ss", what);
     for (int64_t i = 0; i < n; ++i) {
         const c3r_phase_site_t &e = sites[i];
         auto base = [](uint8_t c) { return c == 1 || c == 2 || c == 4 || c == 8; };
-        if (e.pos < 1) return fail(ctx, C3R_EINVAL, "phase site %lld: pos %d is not a 1-based position", (long long)i, e.pos);
-        if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "phase site %lld: positions must be strictly increasing (%d after %d)", (long long)i, e.pos, sites[i - 1].pos);
-        if (!base(e.ref) || !base(e.alt)) return fail(ctx, C3R_EINVAL, "phase site %lld: ref / alt must be base codes 1, 2, 4 or 8 (got %d / %d)", (long long)i, e.ref, e.alt);
-        if (e.ref == e.alt) return fail(ctx, C3R_EINVAL, "phase site %lld: ref and alt are the same base", (long long)i);
-        if (e.h1 > 1) return fail(ctx, C3R_EINVAL, "phase site %lld: h1 must be 0 (GT 0|1) or 1 (GT 1|0)", (long long)i);
-        if (e.ps < 0) return fail(ctx, C3R_EINVAL, "phase site %lld: phase set %d is negative", (long long)i, e.ps);
+        if (e.pos < 1) return fail(ctx, C3R_EINVAL, "%s %lld: pos %d is not a 1-based position", what, (long long)i, e.pos);
+        if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "%s %lld: positions must be strictly increasing (%d after %d)", what, (long long)i, e.pos, sites[i - 1].pos);
+        if (!base(e.ref) || !base(e.alt)) return fail(ctx, C3R_EINVAL, "%s %lld: ref / alt must be base codes 1, 2, 4 or 8 (got %d / %d)", what, (long long)i, e.ref, e.alt);
+        if (e.ref == e.alt) return fail(ctx, C3R_EINVAL, "%s %lld: ref and alt are the same base", what, (long long)i);
+        if (phased && e.h1 > 1) return fail(ctx, C3R_EINVAL, "%s %lld: h1 must be 0 (GT 0|1) or 1 (GT 1|0)", what, (long long)i);
+        if (phased && e.ps < 0) return fail(ctx, C3R_EINVAL, "%s %lld: phase set %d is negative", what, (long long)i, e.ps);
     }
+    return C3R_OK;
+}
+
+int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n) {
+    if (!ctx || n < 0 || (n && !sites)) return C3R_EINVAL;
+    if (int rc = check_phase_sites(ctx, "phase site", sites, n, true)) return rc;
     if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->last_scan_pruned = false;
@@ -952,6 +961,83 @@ int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n) 
     // reads already loaded: their tables again, from the records the device holds (what c3r_set_params does for new filters)
     ctx->host_cache.reset();
     return ::refilter(ctx);
+}
+
+int c3r_phase_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *links) {
+    if (!ctx || n < 0 || (n && (!sites || !links))) return C3R_EINVAL;
+    if (int rc = check_phase_sites(ctx, "candidate site", sites, n, false)) return rc;
+    if (n == 0) return C3R_OK;
+    const size_t words = (size_t)n * C3R_PHASE_LINKS * 2;
+    if (ctx->n_reads == 0) { memset(links, 0, words * 4); return C3R_OK; }               // (no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->d_plsites, sites, (size_t)n)) || (rc = ensure(ctx, ctx->d_links, words * 4))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_links.p, 0, words * 4, ctx->stream));
+    LinkArgs a;
+    memset(&a, 0, sizeof a);
+    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
+    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_phase_site_t *)ctx->d_plsites.p; a.n_sites = (int32_t)n;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.links = (uint32_t *)ctx->d_links.p;
+    {
+        Launch L(ctx, "k_phase_links");
+        hipLaunchKernelGGL(k_phase_links, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(links, ctx->d_links.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's site array may go once this returns, and the table is there)
+    return C3R_OK;
+}
+
+int c3r_phase_resolve(const c3r_phase_site_t *in, int64_t n, const uint32_t *links, const c3r_phase_params_t *p, c3r_phase_site_t *out, c3r_phase_stats_t *stats) {
+    if (n < 0 || (n && (!in || !links || !out))) return C3R_EINVAL;
+    const int64_t min_reads = p ? p->min_reads : 2, pct = p ? p->min_agree_pct : 75;
+    if (min_reads < 0 || pct < 0 || pct > 100) return C3R_EINVAL;
+    for (int64_t j = 1; j < n; ++j) if (in[j].pos <= in[j - 1].pos) return C3R_EINVAL;
+    constexpr int K = C3R_PHASE_LINKS;
+    std::vector<int64_t> block((size_t)n), first, size;              // block of every site; per block: its first site, its sites
+    std::vector<uint8_t> h1((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+        // the blocks of the K predecessors, in the order of their nearest member (k ascending)
+        int nb = 0;
+        int64_t bid[K];
+        uint64_t v0[K], v1[K];
+        for (int k = 1; k <= K && k <= j; ++k) {
+            const int64_t i = j - k;
+            const uint64_t cis = links[((size_t)j * K + (size_t)(k - 1)) * 2], trans = links[((size_t)j * K + (size_t)(k - 1)) * 2 + 1];
+            int b = 0;
+            while (b < nb && bid[b] != block[(size_t)i]) ++b;
+            if (b == nb) { bid[nb] = block[(size_t)i]; v0[nb] = 0; v1[nb] = 0; ++nb; }
+            v1[b] += h1[(size_t)i] ? cis : trans;
+            v0[b] += h1[(size_t)i] ? trans : cis;
+        }
+        int best = -1;
+        uint64_t best_diff = 0;
+        for (int b = 0; b < nb; ++b) {
+            const uint64_t w = v0[b] + v1[b], hi = std::max(v0[b], v1[b]), diff = hi - std::min(v0[b], v1[b]);
+            if (w < (uint64_t)min_reads || diff == 0 || 100 * hi < (uint64_t)pct * w) continue;
+            if (best < 0 || diff > best_diff) { best = b; best_diff = diff; }          // (equal: the earlier entry holds the nearer predecessor)
+        }
+        if (best >= 0) { block[(size_t)j] = bid[best]; h1[(size_t)j] = v1[best] > v0[best] ? 1 : 0; size[(size_t)bid[best]] += 1; }
+        else { block[(size_t)j] = (int64_t)first.size(); h1[(size_t)j] = 0; first.push_back(j); size.push_back(1); }
+    }
+    c3r_phase_stats_t st;
+    memset(&st, 0, sizeof st);
+    st.n_sites = n;
+    for (size_t b = 0; b < size.size(); ++b) {
+        if (size[b] >= 2) { st.n_blocks += 1; st.n_phased += size[b]; }
+        st.max_block = std::max(st.max_block, size[b]);
+    }
+    for (int64_t j = 0; j < n; ++j) {
+        const size_t b = (size_t)block[(size_t)j];
+        c3r_phase_site_t e = in[j];
+        const bool phased = size[b] >= 2;
+        e.ps = phased ? in[first[b]].pos : -1;                       // (out == in: pos is written back unchanged)
+        e.h1 = phased ? h1[(size_t)j] : 0;
+        e.reserved = 0;
+        out[j] = e;
+    }
+    if (stats) *stats = st;
+    return C3R_OK;
 }
 
 int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats_t *stats) {

@@ -287,8 +287,12 @@ __device__ __forceinline__ bool read_dropped(const uint32_t *drop, int words, in
 __host__ __device__ __forceinline__ bool flag_fails(unsigned flag, int excl) {
     return (flag & (unsigned)excl) || (flag & 4u) || ((flag & 1u) && !(flag & 2u));
 }
+// ... of read preparation: the reads whose records enter the pile table (k_prep) and that vote in k_phase_links
+__host__ __device__ __forceinline__ bool read_kept(unsigned flag, int mapq, int min_mq, int excl) {
+    return !(flag_fails(flag, excl) || mapq < min_mq);
+}
 __device__ __forceinline__ bool read_passes(const DevRead &r, int min_mq, int excl) {
-    return !flag_fails(r.flag, excl) && r.mapq >= min_mq && r.end > r.pos;
+    return read_kept(r.flag, r.mapq, min_mq, excl) && r.end > r.pos;
 }
 // The reads [lo, hi) and the records [rlo, rhi) that can touch the positions [e0, e1): supersets by less than a bin on either side.
 //   reads: everything up to the last read whose prefix-max end is <= e0 ends before e0; reads from the first one with pos >= e1 on

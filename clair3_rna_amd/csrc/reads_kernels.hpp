@@ -420,7 +420,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep(const PrepArgs a) {
             R.cig = a.cigars + r.cigar_off; R.pos = r.pos; R.n_cig = err ? 0u : r.n_cigar; R.l_seq = r.l_seq; R.seq_off = r.seq_off;
             R.wbits = ((r.flag & 16u) ? 64u : 0u) | ((r.hp == 1 ? 1u : r.hp == 2 ? 2u : 0u) << 7);
             plain = cigar_is_plain(R, gl, ref_len, n_indel);
-            pass = !err && !flag_fails(r.flag, a.excl_flags) && r.mapq >= a.min_mq;
+            pass = !err && read_kept(r.flag, r.mapq, a.min_mq, a.excl_flags);
             if (!err) {
                 if (plain) { if (pass) walk_plain(R, gl, tally); }
                 else if (gl == 0) {                                        // (also for a read the filters drop: its CIGAR is validated all the same)
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep(const PrepArgs a) {
         bool pass = false, serial = false;
         if (valid) {
             const DevRead d = a.out[i];
-            pass = !(flag_fails(d.flag, a.excl_flags) || d.mapq < a.min_mq);
+            pass = read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags);
             serial = a.serial[i] != 0;
             R.padbit = a.serial[i] == 3 ? PR_INS_PADS : 0u;
             R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.seq_off = d.seq_off;

@@ -115,6 +115,40 @@ int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n);
 /* The tags of the loaded reads, in load order (hp: [cap], cap >= the number of loaded reads; may be NULL), and their statistics (may be
  * NULL).  C3R_EINVAL when no phase sites are set. */
 int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats_t *stats);
+/* Phasing on the device from read linkage: what stands where `whatshap phase` / `longphase phase` stand in the reference flow
+ * (run_clair3_rna:729-767), in two steps.  It is a GREEDY LINKAGE CHAIN, not whatshap's wMEC: every heterozygous SNV gets a block and an
+ * orientation from the reads that cover it together with one of the K = C3R_PHASE_LINKS sites before it, once, in table order.
+ *
+ * Input: the contig's candidate sites, sorted by strictly increasing pos; ref and alt are valid, ps and h1 are ignored; validated as in
+ * c3r_set_phase_sites (except ps and h1).
+ * Voters: the loaded reads that the tensor build keeps under the current c3r_params — the excl_flags / min_mq test of read preparation
+ * (one function, csrc/pileup_kernels.hpp: read_kept) — without the depth cap.  This DIFFERS from c3r_set_phase_sites, where every loaded
+ * read is tagged whatever the filters say: a phase inferred from MAPQ-0 reads is worse than none.
+ * Observation: exactly as in c3r_set_phase_sites — a site under an M / = / X op at a query offset below l_seq shows allele 0 when the read's
+ * base there is the site's ref, allele 1 when it is alt, otherwise nothing.
+ * Links (c3r_phase_links): links[j][k - 1][0] = the voting reads that observe both site j and site j - k with the SAME allele index (cis),
+ * links[j][k - 1][1] = those with different indices (trans), k = 1 .. K.  The predecessors are the K sites before j in the table, not "on
+ * the read".  Entries with j - k < 0 are 0.  All sums are integers: neither read order nor arrival order shows.
+ * Resolution (c3r_phase_resolve), sequential over j = 0 .. n - 1, every processed site holding (block_j, h1_j): group the predecessors
+ * i = j - k by block; per block b, v1_b = sum over its i of (h1_i ? cis : trans), v0_b = sum of (h1_i ? trans : cis), w_b = v0_b + v1_b.
+ * b is accepted iff w_b >= min_reads, v0_b != v1_b and 100 max(v0_b, v1_b) >= min_agree_pct w_b.  Among the accepted blocks the one with
+ * the largest |v1_b - v0_b| is taken (equal: the block that holds the nearest predecessor); block_j = b, h1_j = (v1_b > v0_b).  No accepted
+ * block: j opens a new block with h1_j = 0.  Blocks are NEVER MERGED afterwards (a site that links two blocks joins one of them).  The
+ * agreement test keeps sites that are not haplotype-linked (an A>G RNA-editing site called 0/1: cis and trans near equal) out of a block
+ * instead of letting them flip one.
+ * Output: a site in a block of two or more gets ps = the pos of the block's first site (whatshap's convention) and its h1; a site alone in
+ * its block gets ps = -1 and h1 = 0 — the caller drops it before c3r_set_phase_sites.
+ *
+ * c3r_phase_links needs c3r_load_reads before it (no reads loaded: every count is 0); it uploads the sites, clears a device table, runs
+ * k_phase_links (csrc/phase_kernels.hpp) on the context's stream and reads the table back (links: [n][K][2], 64 n bytes).  It changes
+ * neither the reads' haplotags, nor the table of c3r_set_phase_sites, nor anything a scan reads.  n = 0 succeeds and launches nothing.
+ * Its device buffers are allocated at the first call and kept.
+ * c3r_phase_resolve is host code: no context, no device (it works on a machine without a GPU).  The resolution is a dependency chain of
+ * n steps of K terms — tens of thousands of sites per contig: under a millisecond on one core, tens of milliseconds on one wavefront —
+ * and the table it reads is 64 n bytes, so it is not a kernel.  p = NULL: the defaults (2, 75).  stats may be NULL.  out may be `in`. */
+int c3r_phase_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *links);
+int c3r_phase_resolve(const c3r_phase_site_t *in, int64_t n, const uint32_t *links, const c3r_phase_params_t *p, c3r_phase_site_t *out,
+                      c3r_phase_stats_t *stats);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped

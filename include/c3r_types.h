@@ -138,6 +138,24 @@ typedef struct c3r_haplotag_stats {
     int64_t n_votes;      /* votes of all reads on all phase sets                                    */
 } c3r_haplotag_stats_t;
 
+/* Phasing from read linkage (c3r_phase_links / c3r_phase_resolve, include/c3r.h).  C3R_PHASE_LINKS = K: every site is linked to the K
+ * sites before it IN THE TABLE; the link table is uint32 [n][K][2], [j][k - 1][0] = cis, [1] = trans counts of the pair (j, j - k). */
+#define C3R_PHASE_LINKS 8
+
+/* Parameters of the resolution rule — parameters of the rule, not measured thresholds. */
+typedef struct c3r_phase_params {
+    int32_t min_reads;      /* fewest linking observations that let a site join a block, default 2                    */
+    int32_t min_agree_pct;  /* fewest per cent of them that agree on the orientation, default 75 (0 .. 100)           */
+} c3r_phase_params_t;
+
+/* What c3r_phase_resolve came to. */
+typedef struct c3r_phase_stats {
+    int64_t n_sites;        /* sites in the table                                                                      */
+    int64_t n_phased;       /* sites in a block of two or more (ps >= 0 on output)                                     */
+    int64_t n_blocks;       /* blocks of two or more sites                                                             */
+    int64_t max_block;      /* sites of the largest block (0: no site; 1: singletons only)                             */
+} c3r_phase_stats_t;
+
 #ifdef __cplusplus
 }
 #endif

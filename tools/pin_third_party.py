@@ -21,6 +21,10 @@ K0.  NEVER RUN.  The random two-haplotype read sets of tests/hapref.py (gen_case
      are NOT the same — whatshap realigns reads around each variant and weights votes by base quality; ours reads the allele off the CIGAR
      position with unit weights (include/c3r.h) — so this leg REPORTS agreement (reads tagged alike / differently / by one side only) and
      fails only when fewer than 95 % of the reads both sides tag carry the same haplotype.  That figure is a guess until the leg has run.
+     A second leg, also NEVER RUN: the built-in phasing (c3r_phase_links / c3r_phase_resolve — a greedy linkage chain, not whatshap's wMEC)
+     against `whatshap phase` on tests/phaseref.py's generated cases with ONT-like errors (seeds 1, 3, 5): both phase the same unphased VCF
+     from the same BAM, and `whatshap compare` prints switch errors, flips and block statistics between the two phased VCFs.  This leg
+     only REPORTS (whatshap's table goes to stdout): what agreement to ask for is unknown until it has run.
 Exit status 0: everything agreed."""
 import argparse
 import os
@@ -196,11 +200,49 @@ def pin_whatshap(whatshap):
     return ok
 
 
+def compare_phasing(whatshap):
+    """K0, second leg (never run): `whatshap compare` between our phased VCF and `whatshap phase`'s, tests/phaseref.py's cases with errors."""
+    import gzip
+    from clair3_rna_amd import bam, bamio, io, phasing
+    from clair3_rna_amd.reads import NT16
+    from tests import phaseref
+    for seed in (1, 3, 5):
+        ref, rs, sites, _, _ = phaseref.gen_case(seed, errors=True)
+        from clair3_rna_amd import capi
+        try:
+            eng = capi.Engine(0)
+        except (ImportError, capi.C3RError) as ex:           # no library or no device here: the restatement of the rule, and the line says so
+            print("K0 phasing: no engine (%s)" % ex)
+            eng = None
+        if eng is None:
+            ours, who = phaseref.phase(rs, sites)[0], "tests/phaseref.py"
+        else:                                                # (an error of the library from here on is an error of this leg)
+            eng.set_params()
+            eng.load_reads(rs)
+            ours, who = eng.phase_sites(sites)[0], "k_phase_links + c3r_phase_resolve"
+            eng.close()
+        with tempfile.TemporaryDirectory() as tmp:
+            fa, bm, vcf, mine, theirs = (os.path.join(tmp, n) for n in ("ref.fa", "in.bam", "unphased.vcf", "phased_c.vcf.gz", "whatshap.vcf"))
+            io.write_fasta(fa, [("c", ref)])
+            bam.write_bam(bm, [("c", len(ref))], {"c": rs})
+            bamio.index_build(bm)
+            with open(vcf, "w") as f:
+                f.write("##fileformat=VCFv4.2\n##contig=<ID=c,length=%d>\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"\">\n"
+                        "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE\n" % len(ref))
+                for s_ in sites:
+                    f.write("c\t%d\t.\t%s\t%s\t30\tPASS\t.\tGT\t0/1\n" % (s_["pos"], NT16[s_["ref"]], NT16[s_["alt"]]))
+            phasing.write_phased_vcf(vcf, "c", ours, mine)
+            subprocess.check_call([whatshap, "phase", "--reference", fa, "--ignore-read-groups", "--distrust-genotypes", "-o", theirs, vcf, bm])
+            print("K0 phasing, seed %d (%s): %d of %d sites phased by us; whatshap compare (ours, whatshap):" % (seed, who, int((ours["ps"] >= 0).sum()), len(sites)), flush=True)
+            subprocess.check_call([whatshap, "compare", "--names", "builtin,whatshap", mine, theirs])
+    return True
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samtools")
     ap.add_argument("--tf", action="store_true")
-    ap.add_argument("--whatshap", help="K0 (never run): compare our haplotags with `whatshap haplotag --output-haplotag-list`")
+    ap.add_argument("--whatshap", help="K0 (never run): compare our haplotags with `whatshap haplotag --output-haplotag-list`, and our phased VCF with `whatshap phase`'s through `whatshap compare`")
     ap.add_argument("--reference_repo", default="/root/reference")
     ap.add_argument("--list", action="store_true", help="only count the harvested cases (needs neither tool)")
     a = ap.parse_args()
@@ -214,6 +256,7 @@ def main():
         ok = pin_tf(a.reference_repo) and ok
     if a.whatshap:
         ok = pin_whatshap(a.whatshap) and ok
+        ok = compare_phasing(a.whatshap) and ok
     sys.exit(0 if ok else 1)
 
 
