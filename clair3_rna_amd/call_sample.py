@@ -27,7 +27,8 @@ and the reference's "Haplotag the BAM" commands (run_clair3_rna:769-801: whatsha
 `--enable_phasing_model --phasing builtin` (both model paths, no --phased_vcf_fn) is the whole phased flow in this process, with no external
 tool between the passes: the unphased run (<prefix>.vcf.gz), phase_vcf on that file — the built-in phasing of its heterozygous SNVs from read
 linkage on the GPU, a greedy linkage chain, not whatshap's wMEC (include/c3r.h: c3r_phase_links / c3r_phase_resolve) — into
-<output_dir>/tmp/phased_output/phased_vcf, then the run with --phased_vcf_fn on that directory (<prefix>_enable_phasing.vcf.gz).  One process
+<output_dir>/tmp/phased_output/phased_vcf, then the run with --phased_vcf_fn on that directory (<prefix>_enable_phasing.vcf.gz).
+`--phase_merge_levels N` (default 0: off) is handed to phase_vcf as --merge_levels: up to N levels of the block-merge stage after the chain.  One process
 only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line — run the three steps as three commands there.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
@@ -151,6 +152,9 @@ def build_parser():
            "the built-in phasing of its heterozygous SNVs from read linkage on the GPU (phase_vcf: a greedy linkage chain, not whatshap's wMEC) "
            "into <output_dir>/tmp/phased_output/phased_vcf, then the 30-channel pass on those files.  Needs both model paths; one process only "
            "(not under torch.distributed.run)")
+    a("--phase_merge_levels", type=int, default=0,
+      help="with --phasing builtin: handed to phase_vcf as --merge_levels — up to that many levels of the block-merge stage after the chain, "
+           "which joins the blocks that reads bridge across a run of unlinked sites (0: off)")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
     a("--genotyping_mode_vcf_fn", type=str, default=None)
@@ -302,12 +306,17 @@ def Run(args, log=None):
     """One pass (_run_pass), or with `--phasing builtin` the three steps of the phased flow one after the other: the unphased pass, phase_vcf
     on the file it wrote, the 30-channel pass with --phased_vcf_fn on phase_vcf's directory — nothing inside a pass changes."""
     if getattr(args, "phasing", None) is None:
+        if getattr(args, "phase_merge_levels", 0):
+            sys.exit("[ERROR] --phase_merge_levels belongs to the built-in phasing: it needs --phasing builtin")
         return _run_pass(args, log)
     import copy
     from . import phase_vcf
     log = log or (lambda m: print(m, file=sys.stderr))
     if not args.enable_phasing_model:
         sys.exit("[ERROR] --phasing builtin needs --enable_phasing_model (it prepares the 30-channel pass)")
+    merge_levels = getattr(args, "phase_merge_levels", 0)
+    if merge_levels < 0:
+        sys.exit("[ERROR] --phase_merge_levels must be >= 0")
     if getattr(args, "phased_vcf_fn", None):
         sys.exit("[ERROR] --phasing builtin and --phased_vcf_fn exclude each other: the built-in phasing writes the phased VCFs itself")
     if not args.phased_pileup_model_path:
@@ -340,7 +349,7 @@ def Run(args, log=None):
                 os.remove(os.path.join(phased_dir, name))
     if os.path.isfile(vcf_fn):                                # (no contig found: the first pass wrote nothing, and neither will the second)
         phase_vcf.Run(phase_vcf.build_parser().parse_args(
-            ["--bam_fn", bam_fn, "--vcf_fn", vcf_fn, "--output_dir", phased_dir, "--min_mq", str(args.min_mq)]
+            ["--bam_fn", bam_fn, "--vcf_fn", vcf_fn, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(merge_levels)]
             + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
     else:
         os.makedirs(phased_dir, exist_ok=True)

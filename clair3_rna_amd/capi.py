@@ -54,7 +54,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_default_params", "c3r_set_params", "c3r_load_reads", "c3r_host_alloc", "c3r_host_free", "c3r_set_reference", "c3r_set_reference_view", "c3r_set_bed", "c3r_set_sites",
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
-           "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve"]
+           "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
+           "c3r_phase_unit_links", "c3r_phase_merge"]
 
 _lib = None
 
@@ -96,6 +97,8 @@ def load_library():
     L.c3r_get_haplotags.argtypes = [vp, vp, i64, C.POINTER(HaplotagStats)]
     L.c3r_phase_links.argtypes = [vp, vp, i64, vp]
     L.c3r_phase_resolve.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(PhaseStats)]
+    L.c3r_phase_unit_links.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64)]
+    L.c3r_phase_merge.argtypes = [vp, i64, vp, i64, C.POINTER(PhaseParams), vp, C.POINTER(PhaseStats), C.POINTER(i64)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.c3r_batch_begin.argtypes = [vp]
@@ -286,11 +289,37 @@ class Engine(object):
         self._chk(self.L.c3r_phase_links(self.h, _ptr(a), len(a), _ptr(links)))
         return links
 
-    def phase_sites(self, sites, min_reads=2, min_agree_pct=75):
-        """phase_links, then the greedy chain of phase_resolve: (PHASE_SITE_DTYPE array with ps / h1 filled in — ps = -1: the site stays
-        unphased, drop it before set_phase_sites —, dict(n_sites, n_phased, n_blocks, max_block))."""
+    def phase_unit_links(self, sites):
+        """uint32 (U, PHASE_LINKS, 2) same / different haplotype counts between every unit of a chain's table (a PHASE_SITE_DTYPE array as
+        phase_resolve leaves it: ps = -1 or >= 1, h1; the units are its distinct ps >= 0 in increasing order) and the PHASE_LINKS units
+        before it, from the loaded reads that pass the current filters (c3r_phase_unit_links, the block-merge stage of include/c3r.h).
+        Leaves the reads' haplotags, the table of set_phase_sites and every scan as they are."""
         a = _phase_site_array(sites)
-        return phase_resolve(a, self.phase_links(a), min_reads, min_agree_pct)
+        ulinks = np.zeros((len(a), PHASE_LINKS, 2), dtype=np.uint32)          # (U <= n)
+        u = C.c_int64(0)
+        self._chk(self.L.c3r_phase_unit_links(self.h, _ptr(a), len(a), _ptr(ulinks), len(a), C.byref(u)))
+        return np.ascontiguousarray(ulinks[:u.value])
+
+    def phase_sites(self, sites, min_reads=2, min_agree_pct=75, merge_levels=0):
+        """phase_links, then the greedy chain of phase_resolve: (PHASE_SITE_DTYPE array with ps / h1 filled in — ps = -1: the site stays
+        unphased, drop it before set_phase_sites —, dict(n_sites, n_phased, n_blocks, max_block)).  merge_levels > 0: then up to that many
+        levels of the block-merge stage (phase_unit_links + phase_merge), ending early at a level that joins nothing; the dict then also
+        holds merge_levels_run and merge_units_joined.  merge_levels = 0 calls nothing of it."""
+        if int(merge_levels) < 0:
+            raise ValueError("merge_levels must be >= 0, got %r" % (merge_levels,))
+        a = _phase_site_array(sites)
+        out, st = phase_resolve(a, self.phase_links(a), min_reads, min_agree_pct)
+        if int(merge_levels) == 0:
+            return out, st
+        levels = joined = 0
+        while levels < int(merge_levels):
+            out, st, n = phase_merge(out, self.phase_unit_links(out), min_reads, min_agree_pct)
+            levels += 1
+            joined += n
+            if n == 0:
+                break
+        st["merge_levels_run"], st["merge_units_joined"] = levels, joined
+        return out, st
 
     # ---- tensor build
     def scan(self, ctg_start, ctg_end):
@@ -555,3 +584,21 @@ def decode_text(ctg, positions, ref33_list, alt_info_list, probs, qual=2, show_r
         raise C3RError(rc, "c3r_decode_text failed")
     text = buf.value.decode()
     return text.split("\n")[:-1] if text else []
+
+
+def phase_merge(sites, ulinks, min_reads=2, min_agree_pct=75):
+    """One level of the block-merge stage of include/c3r.h on the host (c3r_phase_merge; no GPU, no engine): a chain's table and the
+    (U, PHASE_LINKS, 2) link table of its units -> (table with the joined units' ps / h1 rewritten, dict(n_sites, n_phased, n_blocks,
+    max_block) of that table, number of units that joined)."""
+    L = load_library()
+    a = _phase_site_array(sites)
+    lk = np.ascontiguousarray(ulinks, dtype=np.uint32)
+    if lk.ndim != 3 or lk.shape[1:] != (PHASE_LINKS, 2):
+        raise ValueError("ulinks must have shape (units, %d, 2), got %r" % (PHASE_LINKS, lk.shape))
+    out = np.zeros(len(a), dtype=PHASE_SITE_DTYPE)
+    p, st, joined = PhaseParams(int(min_reads), int(min_agree_pct)), PhaseStats(), C.c_int64(0)
+    rc = L.c3r_phase_merge(_ptr(a), len(a), _ptr(lk), lk.shape[0], C.byref(p), _ptr(out), C.byref(st), C.byref(joined))
+    if rc != 0:
+        raise C3RError(rc, "c3r_phase_merge: sites must be sorted by strictly increasing pos with ps = -1 or >= 1 and h1 0 or 1, ulinks must "
+                           "hold one row per distinct ps >= 0, min_reads >= 0, 0 <= min_agree_pct <= 100")
+    return out, {k: int(getattr(st, k)) for k, _ in PhaseStats._fields_}, int(joined.value)

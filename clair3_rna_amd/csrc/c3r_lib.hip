@@ -157,7 +157,7 @@ struct c3r_ctx {
     int64_t n_phase = 0;
     DevBuf d_phase, d_hptag;
     // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
-    DevBuf d_plsites, d_links;
+    DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
 
     // ---- scan state
     int32_t reg_beg0 = 0, reg_end0 = 0;   // first region of the most recent scan (c3r_get_columns)
@@ -726,7 +726,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_plsites, &ctx->d_links, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1037,6 +1037,92 @@ int c3r_phase_resolve(const c3r_phase_site_t *in, int64_t n, const uint32_t *lin
         out[j] = e;
     }
     if (stats) *stats = st;
+    return C3R_OK;
+}
+
+// The units of the block-merge stage: the distinct ps >= 0 of a chain's table in increasing order (unit_ps), and every site's unit
+// (unit_of, -1 for a singleton).  The table has been checked: ps is -1 or >= 1.
+static void phase_units(const c3r_phase_site_t *sites, int64_t n, std::vector<int32_t> &unit_ps, std::vector<int32_t> &unit_of) {
+    unit_ps.clear();
+    for (int64_t j = 0; j < n; ++j) if (sites[j].ps >= 0) unit_ps.push_back(sites[j].ps);
+    std::sort(unit_ps.begin(), unit_ps.end());
+    unit_ps.erase(std::unique(unit_ps.begin(), unit_ps.end()), unit_ps.end());
+    unit_of.assign((size_t)n, -1);
+    for (int64_t j = 0; j < n; ++j)
+        if (sites[j].ps >= 0) unit_of[(size_t)j] = (int32_t)(std::lower_bound(unit_ps.begin(), unit_ps.end(), sites[j].ps) - unit_ps.begin());
+}
+
+int c3r_phase_unit_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *ulinks, int64_t cap_units, int64_t *n_units) {
+    if (!ctx || n < 0 || cap_units < 0 || (n && !sites)) return C3R_EINVAL;
+    if (int rc = check_phase_sites(ctx, "unit site", sites, n, false)) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        if (sites[i].ps != -1 && sites[i].ps < 1) return fail(ctx, C3R_EINVAL, "unit site %lld: ps %d is neither -1 (no block) nor a 1-based position", (long long)i, sites[i].ps);
+        if (sites[i].h1 > 1) return fail(ctx, C3R_EINVAL, "unit site %lld: h1 must be 0 (GT 0|1) or 1 (GT 1|0)", (long long)i);
+    }
+    std::vector<int32_t> unit_ps, unit_of;
+    phase_units(sites, n, unit_ps, unit_of);
+    const int64_t U = (int64_t)unit_ps.size();
+    if (n_units) *n_units = U;
+    if (!ulinks) return C3R_OK;                                     // (the caller asks for the count)
+    if (cap_units < U) return fail(ctx, C3R_EOVERFLOW, "the links of %lld units do not fit %lld slots", (long long)U, (long long)cap_units);
+    const size_t words = (size_t)U * C3R_PHASE_LINKS * 2;
+    if (U < 2 || ctx->n_reads == 0) { if (words) memset(ulinks, 0, words * 4); return C3R_OK; }      // (nothing to link, or no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->d_plsites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_unitof, unit_of.data(), (size_t)n)) || (rc = ensure(ctx, ctx->d_links, words * 4))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_links.p, 0, words * 4, ctx->stream));
+    UnitLinkArgs a;
+    memset(&a, 0, sizeof a);
+    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
+    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_phase_site_t *)ctx->d_plsites.p; a.n_sites = (int32_t)n;
+    a.unit_of = (const int32_t *)ctx->d_unitof.p; a.n_units = (int32_t)U;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.ulinks = (uint32_t *)ctx->d_links.p;
+    {
+        Launch L(ctx, "k_phase_unit_links");
+        hipLaunchKernelGGL(k_phase_unit_links, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ulinks, ctx->d_links.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (unit_of and the caller's site array may go once this returns, and the table is there)
+    return C3R_OK;
+}
+
+int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulinks, int64_t n_units, const c3r_phase_params_t *p, c3r_phase_site_t *out,
+                    c3r_phase_stats_t *stats, int64_t *n_joined) {
+    if (n < 0 || n >= INT32_MAX || n_units < 0 || (n && (!in || !out)) || (n_units && !ulinks)) return C3R_EINVAL;
+    for (int64_t j = 0; j < n; ++j)
+        if ((j > 0 && in[j].pos <= in[j - 1].pos) || (in[j].ps != -1 && in[j].ps < 1) || in[j].h1 > 1) return C3R_EINVAL;
+    std::vector<int32_t> unit_ps, unit_of;
+    phase_units(in, n, unit_ps, unit_of);
+    const size_t U = unit_ps.size();
+    if ((int64_t)U != n_units) return C3R_EINVAL;
+    // the chain's rule on the pseudo-table of units (pos = the unit's ps): one copy of the rule, c3r_phase_resolve
+    std::vector<c3r_phase_site_t> unit(U);
+    for (size_t u = 0; u < U; ++u) { memset(&unit[u], 0, sizeof unit[u]); unit[u].pos = unit_ps[u]; unit[u].ref = 1; unit[u].alt = 2; }
+    if (int rc = c3r_phase_resolve(unit.data(), (int64_t)U, ulinks, p, unit.data(), nullptr)) return rc;
+    int64_t joined = 0;
+    for (size_t u = 0; u < U; ++u) if (unit[u].ps >= 0 && unit[u].ps != unit_ps[u]) joined += 1;
+    for (int64_t j = 0; j < n; ++j) {
+        c3r_phase_site_t e = in[j];
+        const int32_t u = unit_of[(size_t)j];
+        if (u >= 0 && unit[(size_t)u].ps >= 0) { e.ps = unit[(size_t)u].ps; e.h1 ^= unit[(size_t)u].h1; }
+        e.reserved = 0;
+        out[j] = e;
+    }
+    if (stats) {
+        // from the final table: a block is a ps >= 0, whatever its size; max_block counts a site without one as a block of its own
+        c3r_phase_stats_t st;
+        memset(&st, 0, sizeof st);
+        st.n_sites = n;
+        std::vector<int32_t> ps;
+        for (int64_t j = 0; j < n; ++j) { if (out[j].ps >= 0) ps.push_back(out[j].ps); else st.max_block = 1; }
+        std::sort(ps.begin(), ps.end());
+        st.n_phased = (int64_t)ps.size();
+        for (size_t k = 0, k0 = 0; k <= ps.size(); ++k)
+            if (k == ps.size() || ps[k] != ps[k0]) { if (k > k0) { st.n_blocks += 1; st.max_block = std::max(st.max_block, (int64_t)(k - k0)); } k0 = k; }
+        *stats = st;
+    }
+    if (n_joined) *n_joined = joined;
     return C3R_OK;
 }
 

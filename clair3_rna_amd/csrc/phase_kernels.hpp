@@ -1,5 +1,6 @@
 // phase_kernels.hpp — k_phase_links: pairwise linkage counts between the contig's heterozygous SNVs from the loaded reads (c3r_phase_links),
-// the device half of the project's own phasing.  Included by c3r_lib.hip only.
+// the device half of the project's own phasing; and k_phase_unit_links, the same between the blocks the chain left (c3r_phase_unit_links,
+// the block-merge stage; at the end of the file).  Included by c3r_lib.hip only.
 //
 // What it replaces: the read pass of `whatshap phase` / `longphase phase` between the two passes of the reference flow
 // (run_clair3_rna:729-767).  The rule — a greedy linkage chain, not wMEC — is stated in include/c3r.h and restated, independently of this
@@ -101,6 +102,109 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) 
             }
         }
         __syncthreads();                                                       // (the next window clears the slab)
+    }
+}
+
+// ---- k_phase_unit_links: the link table of the block-merge stage (c3r_phase_unit_links; the rule is in include/c3r.h, restated by
+// tests/phasemergeref.py).  The units are the blocks the chain left (unit_of[s]: the unit of table site s, -1 for a singleton), and a read
+// observes a unit with the majority of its sites' votes there: haplotype 1 / 2, nothing on a tie.
+//
+// The shape of k_haplotag: 16 lanes per read, no LDS, no workgroup barrier, whole groups leave early, and every loop count is a reduced
+// value, the same in all lanes of a group.  A first walk finds the lowest and the highest unit the read observes; one unit (the common
+// case after the chain) or none and the read is done without a global write.  Otherwise one walk per unit in increasing unit number,
+// each of which counts that unit's votes and finds the next unit above it (the P + 1 walks of k_haplotag).  What the read has seen of
+// the K units before the current one is two bit masks in registers — bit k: unit u - k was observed (not tied) / with haplotype 2 —
+// shifted by the distance to the next unit, so a tied unit or one the read does not touch leaves a hole and no link spans more than K
+// unit numbers.  Lane k - 1 of the group adds the link to unit u - k (relaxed, agent scope: integer sums, arrival order never shows).
+struct UnitLinkArgs {
+    const DevRead *reads; int32_t n_reads;    // headers of k_prep<false>; read only
+    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
+    const uint32_t *cigars;
+    const uint8_t *seq;                       // 4-bit packed bases
+    const c3r_phase_site_t *sites; int32_t n_sites;       // the chain's table: ref, alt and h1 are read, ps never (it holds -1)
+    const int32_t *unit_of;                   // [n_sites] unit of every site, -1: singleton
+    int32_t n_units;
+    int32_t min_mq, excl_flags;               // the voters: read_kept
+    uint32_t *ulinks;                         // [n_units][PHASE_K][2] same / different haplotype, zero on entry
+};
+static_assert(PHASE_K <= PREP_GRP && PHASE_K < 31, "one lane per predecessor unit, one mask bit per unit");
+
+constexpr int32_t UNIT_NONE = 0x7fffffff;     // no unit (a unit number is below n_units <= n_sites < 2^31 - 1)
+
+struct UnitTally {
+    uint32_t c1, c2;          // votes for haplotype 1 / 2 in unit `cur` (cur < 0: not counted)
+    int32_t u_min, u_max;     // smallest / largest observed unit above `cur` (u_min UNIT_NONE: none)
+    __device__ __forceinline__ void reduce() {
+#pragma unroll
+        for (int off = PREP_GRP / 2; off > 0; off >>= 1) {
+            c1 += __shfl_xor(c1, off, PREP_GRP);
+            c2 += __shfl_xor(c2, off, PREP_GRP);
+            u_min = min(u_min, (int32_t)__shfl_xor(u_min, off, PREP_GRP));
+            u_max = max(u_max, (int32_t)__shfl_xor(u_max, off, PREP_GRP));
+        }
+    }
+};
+
+// One walk over the sites [lo, hi) that the read's M ops cover; singleton sites are skipped before anything else.  All lanes of the group
+// come here together.
+__device__ __forceinline__ UnitTally unit_walk(const ReadInfo &R, int gl, bool serial, const UnitLinkArgs &a, int lo, int hi, int32_t cur) {
+    UnitTally t;
+    t.c1 = 0; t.c2 = 0; t.u_min = UNIT_NONE; t.u_max = -1;
+    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &) __attribute__((always_inline)) {
+        if (op != C3R_CIG_M) return;
+        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
+            const c3r_phase_site_t e = a.sites[s];
+            const long long d = (long long)e.pos - 1 - x;
+            if (d >= (long long)len) break;
+            const unsigned long long q = (unsigned long long)y + (unsigned long long)d;
+            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
+            const int32_t u = a.unit_of[s];
+            if (u < 0 || u < cur) continue;
+            const uint32_t byte = a.seq[R.seq_off + (q >> 1)], b = (q & 1) ? (byte & 15u) : (byte >> 4);
+            if (b != e.ref && b != e.alt) continue;
+            if (u > cur) { t.u_min = min(t.u_min, u); t.u_max = max(t.u_max, u); continue; }
+            const uint32_t allele = b == e.alt ? 1u : 0u;              // (u == cur)
+            if (allele == e.h1) t.c1 += 1; else t.c2 += 1;
+        }
+    };
+    if (!serial) walk_plain_ops(R, gl, on_op);
+    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+    t.reduce();
+    return t;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLinkArgs a) {
+    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
+    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
+    if (i >= a.n_reads) return;                                        // (whole groups leave: the shuffles below stay inside a group)
+    const DevRead d = a.reads[i];
+    if (!read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) return;
+    // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
+    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
+    if (hi - lo < 2) return;                                           // (two units take two sites)
+    ReadInfo R;
+    R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
+    R.compat = 0; R.padbit = 0;
+    const bool serial = a.serial[i] != 0;
+    const UnitTally all = unit_walk(R, gl, serial, a, lo, hi, -1);
+    if (all.u_min >= all.u_max) return;                                // no unit observed (UNIT_NONE, -1) or one
+    uint32_t seen = 0, hap2 = 0;                                       // bit k: unit `last` - k was observed / with haplotype 2
+    int32_t last = all.u_min;
+    for (int32_t u = all.u_min; u != UNIT_NONE;) {
+        const UnitTally t = unit_walk(R, gl, serial, a, lo, hi, u);
+        const int32_t dist = u - last;
+        seen = dist < 32 ? seen << dist : 0u;                          // now bit k: unit u - k
+        hap2 = dist < 32 ? hap2 << dist : 0u;
+        last = u;
+        if (t.c1 != t.c2) {                                            // (a tie is no observation: it links nothing and is not kept)
+            const uint32_t h = t.c2 > t.c1 ? 1u : 0u;
+            const int k = gl + 1;
+            if (k <= PHASE_K && ((seen >> k) & 1u) && u < a.n_units)
+                __hip_atomic_fetch_add(&a.ulinks[((size_t)u * PHASE_K + (size_t)(k - 1)) * 2 + ((((hap2 >> k) & 1u) != h) ? 1 : 0)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            seen |= 1u;
+            hap2 |= h;
+        }
+        u = t.u_min;
     }
 }
 

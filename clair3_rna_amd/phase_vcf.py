@@ -5,6 +5,10 @@ Per contig: the alignments (io.load_reads) -> Engine.load_reads -> Engine.phase_
 PASS, biallelic SNV, GT 0/1) -> <output_dir>/phased_<ctg>.vcf.gz, the names `--phased_vcf_fn <output_dir>` of call_sample and call_var_bam
 consume (phasedvcf.contig_file).  A contig without candidates writes no file.  One [INFO] line per contig.
 
+--merge_levels N (default 0: off) runs up to N levels of the block-merge stage after the chain (include/c3r.h: c3r_phase_unit_links /
+c3r_phase_merge): blocks that reads bridge across a run of unlinked sites — RNA-editing sites called 0/1 — become one.  The [INFO] line
+then also says how many units joined in how many levels.
+
 The rule (include/c3r.h: c3r_phase_links / c3r_phase_resolve) is a greedy linkage chain, not whatshap's wMEC: agreement with whatshap has
 not been measured.
 
@@ -27,6 +31,8 @@ def build_parser():
     a("--min_mq", type=int, default=5, help="reads below it do not vote (the tensor build's filter)")
     a("--min_reads", type=int, default=2, help="fewest linking observations that let a site join a block")
     a("--min_agree_pct", type=int, default=75, help="fewest per cent of them that agree on the orientation")
+    a("--merge_levels", type=int, default=0,
+      help="levels of the block-merge stage after the chain: joins the blocks that reads bridge across a run of unlinked sites (0: off)")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 
@@ -39,6 +45,9 @@ def Run(args, log=None):
             sys.exit("[ERROR] file %s not found" % need)
     if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
         sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
+    merge_levels = getattr(args, "merge_levels", 0)
+    if merge_levels < 0:
+        sys.exit("[ERROR] --merge_levels must be >= 0")
     per = phasing.candidates_from_vcf(args.vcf_fn, None)
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -59,13 +68,14 @@ def Run(args, log=None):
                 eng.set_params(min_mq=args.min_mq)
             rs = io.load_reads(args.bam_fn, ctg)
             eng.load_reads(rs)
-            out, st = eng.phase_sites(sites, args.min_reads, args.min_agree_pct)
+            out, st = eng.phase_sites(sites, args.min_reads, args.min_agree_pct, merge_levels)
             fn = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
             phasing.write_phased_vcf(args.vcf_fn, ctg, out, fn)
             written.append(fn)
-            log("[INFO] %s: %d reads, %d candidate sites (%s), %d phased in %d blocks, largest block %d sites -> %s"
+            merged = ", block merge: %d units joined in %d levels" % (st["merge_units_joined"], st["merge_levels_run"]) if merge_levels else ""
+            log("[INFO] %s: %d reads, %d candidate sites (%s), %d phased in %d blocks, largest block %d sites%s -> %s"
                 % (ctg, len(rs), st["n_sites"], ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
-                   st["n_phased"], st["n_blocks"], st["max_block"], fn))
+                   st["n_phased"], st["n_blocks"], st["max_block"], merged, fn))
     finally:
         if eng is not None:
             eng.close()

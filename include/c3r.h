@@ -149,6 +149,41 @@ int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats
 int c3r_phase_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *links);
 int c3r_phase_resolve(const c3r_phase_site_t *in, int64_t n, const uint32_t *links, const c3r_phase_params_t *p, c3r_phase_site_t *out,
                       c3r_phase_stats_t *stats);
+/* The block-merge stage: an optional step after the chain that joins the blocks which reads bridge.  The chain gives a site its block from
+ * the K table sites before it and from nothing else, so a run of K + 1 or more sites that belong to no haplotype (RNA-editing sites called
+ * 0/1, a hyper-edited Alu stretch: they fail the agreement test, stay alone and still fill the predecessor slots) cuts a block in two
+ * however many reads span the run.  The stage applies the chain's own rule once more, one level up: to whole blocks instead of sites.
+ *
+ * Input: a table as c3r_phase_resolve leaves it — ps = -1 (a site without a block) or ps >= 1, and h1 (0 or 1).
+ * One LEVEL:
+ *  1. Units: the distinct ps >= 0 of the table, numbered 0 .. U - 1 by increasing ps.  A site with ps = -1 is no unit and takes no part.  The
+ *     sites of a unit need not be contiguous in the table (blocks interleave).
+ *  2. Voters: as for c3r_phase_links — the loaded reads that the tensor build keeps under the current c3r_params, without the depth cap.
+ *  3. A read's observation of unit u: over the unit's sites that the read observes (the observation rule of c3r_phase_links), c1 = those
+ *     whose allele index equals the site's h1, c2 = the others.  The read shows haplotype 1 when c1 > c2, haplotype 2 when c2 > c1 and
+ *     NOTHING when c1 == c2 (a tied unit is not observed, and neither is one with no observed site).
+ *  4. Unit links (c3r_phase_unit_links): ulinks[u][k - 1][0] = the voting reads that observe both unit u and unit u - k with the same
+ *     haplotype, [1] = with different ones, k = 1 .. K = C3R_PHASE_LINKS: the K unit NUMBERS before u, observed by the read or not.
+ *     uint32 [U][K][2], the shape of the site link table; entries with u - k < 0 are 0.
+ *  5. Resolution (c3r_phase_merge): c3r_phase_resolve's rule, unchanged and with the same parameters, on the pseudo-table of the units
+ *     (pos = the unit's ps, links = ulinks).  A unit that comes out with ps' >= 0 has joined a super-block: every one of its sites gets
+ *     ps = ps' and h1 ^= h1'.  The other units and the sites with ps = -1 stay as they are.  n_joined = the units whose ps changed (the
+ *     first unit of a super-block keeps its own).  The statistics are counted from the table that results: n_phased = sites with
+ *     ps >= 0, n_blocks = distinct ps >= 0, max_block = the most sites on one ps (a site without a block counts as a block of one, as in c3r_phase_resolve).
+ * A caller repeats levels until n_joined == 0 or as often as it likes: a later level links the super-blocks, which a level made
+ * neighbours in the numbering.  Sites are never re-oriented inside their block and a site without a block never gets one.
+ *
+ * c3r_phase_unit_links validates the table like c3r_phase_links and in addition refuses, naming the index, a ps that is neither -1 nor
+ * >= 1 and an h1 above 1.  *n_units (may be NULL) receives U.  ulinks = NULL: only that.  Otherwise cap_units >= U (C3R_EOVERFLOW if
+ * not); the call uploads the sites and every site's unit, clears a device table, runs k_phase_unit_links (csrc/phase_kernels.hpp) on the
+ * context's stream and reads U rows back.  U < 2, n = 0 or no reads loaded: nothing is launched and the U rows are 0.  Like
+ * c3r_phase_links it changes neither the reads' haplotags, nor the table of c3r_set_phase_sites, nor anything a scan reads.
+ * c3r_phase_merge is host code like c3r_phase_resolve (no context, no device) and calls it for step 5.  C3R_EINVAL for positions that do
+ * not increase, such a ps or h1, parameters out of range, or an n_units that is not the table's U.  stats and n_joined may be NULL; out
+ * may be `in`. */
+int c3r_phase_unit_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *ulinks, int64_t cap_units, int64_t *n_units);
+int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulinks, int64_t n_units, const c3r_phase_params_t *p,
+                    c3r_phase_site_t *out, c3r_phase_stats_t *stats, int64_t *n_joined);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped
