@@ -21,7 +21,7 @@
 
 #include "../../include/c3r.h"
 #include "decode.hpp"
-#include "net_kernels.hpp"
+#include "net_host.hpp"
 #include "pileup_kernels.hpp"
 #include "reads_kernels.hpp"
 #include "haplotag_kernels.hpp"

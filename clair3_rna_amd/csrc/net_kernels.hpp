@@ -1,4 +1,5 @@
-// net_kernels.hpp — gfx950 kernels for the Clair3-RNA pileup network (K2-K5) and their host driver.
+// net_kernels.hpp — gfx950 kernels for the Clair3-RNA pileup network (K2-K5).  Their operands are packed on the host by net_pack.hpp
+// (which also defines the network's dimensions and the split-f16 scale); net_host.hpp uploads them and launches the kernels.
 //
 // What it replaces: clair3_rna/model.py:126-216 (Clair3_P: BiLSTM(128) -> BiLSTM(160) -> flatten ->
 // Dense128 selu -> {Dense128 selu -> Dense21 selu -> softmax ; Dense128 selu -> Dense3 selu -> softmax})
@@ -20,27 +21,17 @@
 //   * 4 wavefronts split the 4H/32 row blocks evenly (H=128: 4 each, H=160: 5 each).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <mutex>
-#include <chrono>
 #include <type_traits>
 #include <stdint.h>
 
-#include <cmath>
-#include <cstring>
-#include <functional>
-#include <string>
-#include <vector>
-
 #include "../../include/c3r.h"
+#include "net_pack.hpp"       // NET_H1, NET_H2, NET_T, NET_FLAT, NET_L4, WSCALE_LOG2, WSCALE, WUNSCALE
 
 namespace c3r {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-constexpr int NET_H1 = 128;
-constexpr int NET_H2 = 160;
-constexpr int NET_T = C3R_WINDOW;          // 33 time steps
 constexpr int NET_SITES = 32;              // sites per MFMA column block
 constexpr int LSTM_SB = 2;                 // column blocks per wavefront in k_lstm
 constexpr int LSTM_SITES = NET_SITES * LSTM_SB;
@@ -73,8 +64,6 @@ __device__ __forceinline__ void y1_store(V v, P p) {
     if constexpr (C3R_Y1_NT_STORE) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
-constexpr int NET_FLAT = NET_T * 2 * NET_H2;   // 10560
-constexpr int NET_L4 = 128;
 
 // sigmoid / tanh on the hardware transcendentals: v_exp_f32 + v_rcp_f32 (about 1 ulp each), no IEEE division
 // sequence.  exp2 overflow -> inf -> rcp 0; underflow -> 0 -> rcp(1) = 1, so both saturate correctly.
@@ -318,9 +307,6 @@ __global__ __launch_bounds__(256, (SB == 1 ? 2 : 1)) void k_lstm(const void *__r
 // cycles replace 8 MFMAs of 64 cycles per 16 k's: 5.3x less matrix-pipe time at the same 1e-4 probability bar
 // (tests/test_gpu_parity.py compares both paths with the fp32 oracle).
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-constexpr float WSCALE_LOG2 = 12.0f;
-constexpr float WSCALE = 4096.0f;
-constexpr float WUNSCALE = 1.0f / 4096.0f;
 
 __device__ __forceinline__ float sigmoid_scaled(float acc) {   // sigmoid(acc * 2^-12)
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((-1.4426950408889634f * WUNSCALE) * acc));
@@ -1500,604 +1486,6 @@ __global__ __launch_bounds__(256) void k_heads_mfma(const float *__restrict__ a4
             for (int o = o0; o < o1; ++o) probs[(size_t)(site0 + sl) * C3R_NPROB + o] = __expf(lg[o - o0] - m) / sum;
         }
     }
-}
-
-// ================================================================================================ host
-struct NetState {
-    bool loaded = false;
-    int channels = 0;
-    int inp1 = 0;                 // padded layer-1 input width
-    float4 *d_w1 = nullptr; float *d_b1 = nullptr;     // packed LSTM1 (both dirs)
-    float4 *d_w2 = nullptr; float *d_b2 = nullptr;     // packed LSTM2
-    float4 *d_w4 = nullptr; float *d_b4 = nullptr;     // packed L4
-    float *d_w5 = nullptr, *d_b5 = nullptr, *d_wo = nullptr, *d_bo = nullptr;
-    float4 *d_w5p = nullptr, *d_wcp = nullptr;          // heads in MFMA fragment order (k_heads_mfma)
-    half8 *d_w2w = nullptr, *d_w4w = nullptr;      // k_lstm2_w16's layer-2 and fused-L4 fragments (pack_lstm2_w16, pack_l4_w16)
-    half8 *d_w1h = nullptr, *d_w2h = nullptr, *d_w4h = nullptr, *d_w4f = nullptr;   // d_w4f: L4 packed per (dir, t) for the fused path   // split-f16 packed weights (hi/lo, x 2^12)
-    // precision 2 (MX corrections): fp8 (e4m3) fragments of w (lanes 0-31) and w - f16(w) (lanes 32-63) per block of 32 k, 32 bytes per
-    // lane, and their E8M0 block scales, four blocks per dword: layer 1 (recurrent part only), layer 2, fused L4
-    uint32_t *d_w1q = nullptr, *d_w1s = nullptr, *d_w2q = nullptr, *d_w2s = nullptr, *d_w4q = nullptr, *d_w4s = nullptr;
-    // log2 of the power-of-two scale the split-f16 weights of layer 1 / layer 2 / L4 were packed with: 12 unless some |w| (or a bias that
-    // travels with the weights) would overflow f16 at 2^12 (net_load); below 12 the run-time-scale variants of the kernels run
-    int wlog2[3] = {12, 12, 12};
-    int precision = 1;            // 0 = fp32 MFMA, 1 = split-f16 (f16x3, fp32-equivalent), 2 = f16 main term + both corrections on the MX fp8 pipe
-    float *d_y1 = nullptr, *d_y2 = nullptr, *d_a4 = nullptr, *d_probs = nullptr;
-    int32_t *d_tmo = nullptr;        // the context's time-out word of the layer-2 rendezvous (lds_wait); allocated with the weights
-    int64_t cap_probs = 0;           // sites d_probs holds (the whole batch); cap_sites bounds one network slice
-    int64_t cap_sites = 0;
-};
-
-inline int64_t net_weight_count(int C) {
-    int64_t n = 0;
-    n += 2 * ((int64_t)C * 4 * NET_H1 + (int64_t)NET_H1 * 4 * NET_H1 + 4 * NET_H1);
-    n += 2 * ((int64_t)2 * NET_H1 * 4 * NET_H2 + (int64_t)NET_H2 * 4 * NET_H2 + 4 * NET_H2);
-    n += (int64_t)NET_FLAT * NET_L4 + NET_L4;
-    n += 2 * (128 * 128 + 128);
-    n += 128 * 21 + 21 + 128 * 3 + 3;
-    return n;
-}
-
-// The layer-1 output of a full slice is one 8.9-GB allocation.  A process that destroys a context and creates another (a second
-// sample, a test suite) would hand it back to the driver and ask for it again: the driver clears freed memory before it is
-// reused, and that hipMalloc then takes 0.8 s instead of 0.3 ms.  Up to two such blocks per process are kept for the next context
-// of the same device (C3R_NO_BLOCK_CACHE=1, or C3R_POISON — which wants fresh memory — turns this off).
-struct BigBlock { int dev; size_t bytes; void *p; };
-inline std::mutex &big_mu() { static std::mutex m; return m; }
-inline std::vector<BigBlock> &big_cache() { static std::vector<BigBlock> v; return v; }
-inline bool big_cache_on() {
-    static const bool on = [] { const char *a = getenv("C3R_NO_BLOCK_CACHE"), *b = getenv("C3R_POISON"); return !(a && *a == '1') && !(b && *b); }();
-    return on;
-}
-inline void *big_take(size_t bytes) {
-    if (!big_cache_on()) return nullptr;
-    int dev = 0; (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> g(big_mu());
-    auto &c = big_cache();
-    for (size_t k = 0; k < c.size(); ++k) if (c[k].dev == dev && c[k].bytes == bytes) { void *p = c[k].p; c.erase(c.begin() + (long)k); return p; }
-    return nullptr;
-}
-inline void big_give(void *p, size_t bytes) {
-    if (!p) return;
-    if (big_cache_on() && bytes >= ((size_t)1 << 30)) {
-        int dev = 0; (void)hipGetDevice(&dev);
-        void *evict = nullptr;
-        {
-            std::lock_guard<std::mutex> g(big_mu());
-            auto &c = big_cache();
-            if (c.size() >= 2) { evict = c.front().p; c.erase(c.begin()); }      // the older of the two goes: sizes nobody asks for again do not stay
-            c.push_back(BigBlock{dev, bytes, p});
-        }
-        if (evict) (void)hipFree(evict);
-        return;
-    }
-    (void)hipFree(p);
-}
-
-// every cached block back to the driver (c3r_trim): a host application that destroys its contexts to give HBM back gets all of it
-inline size_t big_trim() {
-    std::vector<BigBlock> all;
-    {
-        std::lock_guard<std::mutex> g(big_mu());
-        all.swap(big_cache());
-    }
-    size_t bytes = 0;
-    int cur = 0; (void)hipGetDevice(&cur);
-    for (auto &b : all) { (void)hipSetDevice(b.dev); (void)hipFree(b.p); bytes += b.bytes; }
-    (void)hipSetDevice(cur);
-    return bytes;
-}
-
-inline void net_free(NetState &s) {
-    void *ptrs[] = {s.d_w1, s.d_b1, s.d_w2, s.d_b2, s.d_w4, s.d_b4, s.d_w5, s.d_b5, s.d_wo, s.d_bo, s.d_y2, s.d_a4, s.d_probs,
-                    s.d_w1h, s.d_w2h, s.d_w4h, s.d_w4f, s.d_w2w, s.d_w4w, s.d_w5p, s.d_wcp, s.d_w1q, s.d_w1s, s.d_w2q, s.d_w2s, s.d_w4q, s.d_w4s, s.d_tmo};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    big_give(s.d_y1, (size_t)s.cap_sites * NET_T * 2 * NET_H1 * sizeof(float));
-    s = NetState();
-}
-
-// float -> IEEE binary16 (round to nearest even) and back, host side
-inline uint16_t f2h(float f) {
-    uint32_t x; memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    const int32_t e = (int32_t)((x >> 23) & 0xff) - 127 + 15;
-    uint32_t m = x & 0x7fffffu;
-    if (((x >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (m ? 0x200u : 0));
-    if (e >= 31) return (uint16_t)(sign | 0x7c00u);
-    if (e <= 0) {
-        if (e < -10) return (uint16_t)sign;
-        m |= 0x800000u;
-        const int shift = 14 - e;
-        uint32_t hm = m >> shift;
-        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-        if (rem > half || (rem == half && (hm & 1u))) ++hm;
-        return (uint16_t)(sign | hm);
-    }
-    uint32_t h = (uint32_t)(e << 10) | (m >> 13);
-    const uint32_t rem = m & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;
-    return (uint16_t)(sign | h);
-}
-inline float h2f(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ffu, x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else { int sh = 0; while (!(m & 0x400u)) { m <<= 1; ++sh; } m &= 0x3ffu; x = sign | ((uint32_t)(127 - 15 - sh + 1) << 23) | (m << 13); }
-    } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
-    else x = sign | ((e - 15 + 127) << 23) | (m << 13);
-    float f; memcpy(&f, &x, 4); return f;
-}
-inline void split_h(float v, uint16_t &hi, uint16_t &lo) { hi = f2h(v); lo = f2h(v - h2f(hi)); }
-
-// Split-f16 packing of one LSTM direction: [wave][g16][tile][hi|lo][lane][8 halves], weights x 2^12.
-// bias_slot != nullptr (layer 1): the bias rides on the first padded input slot (k = cin).
-inline void pack_lstm_dir_h(const float *Kin, int cin, int inp, const float *R, int H, std::vector<uint16_t> &wp, const float *bias_slot = nullptr, float wscale = WSCALE) {
-    const int K = inp + H, NG = K / 16, NBLK = 4 * H / 32, NT = NBLK / 4;
-    wp.assign((size_t)NBLK * NG * 2 * 64 * 8, 0);
-    auto wcat = [&](int k, int col) -> float {
-        if (k < inp) return k < cin ? Kin[(size_t)k * 4 * H + col] : (bias_slot && k == cin ? bias_slot[col] : 0.f);
-        return R[(size_t)(k - inp) * 4 * H + col];
-    };
-    for (int blk = 0; blk < NBLK; ++blk)
-        for (int r = 0; r < 32; ++r) {
-            const int q = r >> 3, hh = (r >> 2) & 1, m = r & 3;
-            const int unit = 8 * blk + 4 * hh + q, col = m * H + unit;
-            for (int g = 0; g < NG; ++g)
-                for (int kh = 0; kh < 2; ++kh)
-                    for (int e = 0; e < 8; ++e) {
-                        uint16_t hi, lo;
-                        split_h(wscale * wcat(16 * g + 8 * kh + e, col), hi, lo);
-                        const int lane = kh * 32 + r;
-                        const size_t base = ((((size_t)(blk / NT) * NG + g) * NT + (blk % NT)) * 2) * 64;
-                        wp[((base + 0 * 64 + lane) * 8) + e] = hi;
-                        wp[((base + 1 * 64 + lane) * 8) + e] = lo;
-                    }
-        }
-}
-
-// k_lstm2_w16's layer-2 fragments of one direction: [quarter(4)][u = 2G + st (26)][tile(5)][hi|lo][64 lanes][8 halves], weights x 2^s.
-// Lane l of unit (G, st) of tile T holds row l % 16 of subtile st = gate m of unit 8T + 2q + st (l % 16 = 4q + m), k = 32G + 8 (l / 16) + 0..7
-// (v_mfma_f32_16x16x32_f16: A[row l % 16][k = 8 (l / 16) + i]; its accumulator gives lane l rows 4 (l / 16) + 0..3).
-inline void w16_gate_row(int T, int st, int r16, int H, int &unit, int &col) {
-    const int q = r16 >> 2, m = r16 & 3;
-    unit = 8 * T + 2 * q + st;
-    col = m * H + unit;
-}
-inline void pack_lstm2_w16(const float *Kin, int inp, const float *R, int H, std::vector<uint16_t> &wp, float wscale) {
-    const int K = inp + H, NG = K / 32, NU = 2 * NG, NBLK = 4 * H / 32, NT = NBLK / 4;
-    wp.assign((size_t)NBLK * NU * 2 * 64 * 8, 0);
-    for (int T = 0; T < NBLK; ++T)
-        for (int st = 0; st < 2; ++st)
-            for (int l = 0; l < 64; ++l) {
-                int unit, col;
-                w16_gate_row(T, st, l & 15, H, unit, col);
-                for (int g = 0; g < NG; ++g)
-                    for (int e = 0; e < 8; ++e) {
-                        const int k = 32 * g + 8 * (l >> 4) + e;
-                        const float w = k < inp ? Kin[(size_t)k * 4 * H + col] : R[(size_t)(k - inp) * 4 * H + col];
-                        uint16_t hi, lo;
-                        split_h(wscale * w, hi, lo);
-                        const size_t base = ((((size_t)(T / NT) * NU + 2 * g + st) * NT + (T % NT)) * 2) * 64;
-                        wp[(base + l) * 8 + e] = hi;
-                        wp[(base + 64 + l) * 8 + e] = lo;
-                    }
-            }
-}
-// k_lstm2_w16's fused L4 fragments: [dir][t][quarter(4)][u = 2G + st (H / 16)][hi|lo][64 lanes][8]; lane l: L4 output 32 quarter + 16 st + l % 16,
-// h index k = 32G + 8 (l / 16) + 0..7 of direction d at time t (flatten row t * 2H + d * H + k)
-inline void pack_l4_w16(const float *W4, float wscale, std::vector<uint16_t> &w4p) {
-    const int NU4 = NET_H2 / 16;
-    w4p.assign((size_t)2 * NET_T * 4 * NU4 * 2 * 64 * 8, 0);
-    for (int d = 0; d < 2; ++d)
-        for (int t = 0; t < NET_T; ++t)
-            for (int sq = 0; sq < 4; ++sq)
-                for (int u = 0; u < NU4; ++u)
-                    for (int l = 0; l < 64; ++l)
-                        for (int e = 0; e < 8; ++e) {
-                            const int o = 32 * sq + 16 * (u & 1) + (l & 15), k = 32 * (u >> 1) + 8 * (l >> 4) + e;
-                            uint16_t hi, lo;
-                            split_h(wscale * W4[((size_t)t * 2 * NET_H2 + (size_t)d * NET_H2 + k) * NET_L4 + o], hi, lo);
-                            const size_t base = ((((size_t)(d * NET_T + t) * 4 + sq) * NU4 + u) * 2) * 64;
-                            w4p[(base + l) * 8 + e] = hi;
-                            w4p[(base + 64 + l) * 8 + e] = lo;
-                        }
-}
-
-// ---- precision 2: the two correction terms on the block-scaled fp8 pipe (v_mfma_scale_f32_32x32x64_f8f6f4, K = 64 = two terms x 32 k).
-// float -> OCP e4m3fn, round to nearest even, saturating (|v| < 256 by construction here)
-inline uint8_t f2e4m3(float v) {
-    const uint8_t sign = std::signbit(v) ? 0x80 : 0;
-    float a = std::fabs(v);
-    if (!(a == a)) return 0x7f;
-    if (a >= 464.f) return (uint8_t)(sign | 0x7e);
-    if (a < 0.015625f) {                                   // subnormal: multiples of 2^-9
-        const int q = (int)std::nearbyint(a * 512.f);
-        return (uint8_t)(sign | q);                        // q == 8 is the smallest normal (0x08)
-    }
-    int e;
-    const float fr = std::frexp(a, &e);                    // a = fr * 2^e, fr in [0.5, 1)
-    int q = (int)std::nearbyint((fr * 2.f - 1.f) * 8.f), ex = e - 1;
-    if (q == 8) { q = 0; ++ex; }
-    int code = ((ex + 7) << 3) | q;
-    if (code > 0x7e) code = 0x7e;
-    return (uint8_t)(sign | code);
-}
-// One fragment set: rows = NBLK tiles of 32 gate rows (row r of tile blk <-> column col(blk, r) of W), k = k0 .. k0 + 32 * nkb.
-// K order of the instruction (tools/mx_scale_probe.hip): a lane (r, g = lane / 32) holds k = 16 g + 0..15 of the FIRST scale block
-// in its bytes 0-15 and k = 32 + 16 g + 0..15, the second scale block, in its bytes 16-31; the scale byte of lane r covers the first
-// block of row r, that of lane 32 + r the second.  First block = term 0 (w), second = term 1 (w - f16(w)):
-//   q: [quarter][kb][tile][term][64 lanes][16 bytes]   lane = 32 g + r: k = k0 + 32 kb + 16 g + 0..15; a lane's operand = its term-0 bytes then its term-1 bytes
-//   sc: [quarter][kb / 4][tile][64 lanes] u32    lane = 32 term + r, byte kb % 4 = E8M0 scale: 2^(sc - 127) * byte = 2^12 * value
-template <class WF>
-inline void pack_mx(WF &&w /* (k, blk, r) -> weight */, int NBLK, int NT, int k0, int nkb, std::vector<uint32_t> &q, std::vector<uint32_t> &sc) {
-    const int nk4 = (nkb + 3) / 4;
-    q.assign((size_t)NBLK * nkb * 64 * 8, 0u);
-    sc.assign((size_t)NBLK * nk4 * 64, 0x7f7f7f7fu);
-    uint8_t *qb = reinterpret_cast<uint8_t *>(q.data());
-    uint8_t *sb = reinterpret_cast<uint8_t *>(sc.data());
-    for (int blk = 0; blk < NBLK; ++blk)
-        for (int r = 0; r < 32; ++r)
-            for (int kb = 0; kb < nkb; ++kb)
-                for (int term = 0; term < 2; ++term) {
-                    float v[32], m = 0.f;
-                    for (int b = 0; b < 32; ++b) {
-                        const float x = w(k0 + 32 * kb + b, blk, r);
-                        v[b] = term ? x - h2f(f2h(WSCALE * x)) * WUNSCALE : x;       // (the f16 main term carries f16(2^12 w))
-                        m = std::max(m, std::fabs(v[b]));
-                    }
-                    int e = 0;                                                   // block scale 2^e: the block's maximum lands in [128, 256)
-                    if (m > 0.f) { int ex; (void)std::frexp(m, &ex); e = 8 - ex; }
-                    e = std::min(e, 139);                                        // (E8M0 byte = 139 - e >= 0)
-                    const size_t fo = (((size_t)(blk / NT) * nkb + kb) * NT + (blk % NT)) * 64;
-                    // (each 16-byte half of a lane's 32 bytes is stored as its own 1 KiB run of the 64 lanes: two fully coalesced loads)
-                    for (int b = 0; b < 32; ++b) qb[((fo * 2 + (size_t)term * 64) + 32 * (b / 16) + r) * 16 + (b % 16)] = f2e4m3(std::ldexp(v[b], e));
-                    const size_t so = ((((size_t)(blk / NT) * nk4 + kb / 4) * NT + (blk % NT)) * 64 + 32 * term + r) * 4 + (kb % 4);
-                    sb[so] = (uint8_t)std::max(0, 127 + (int)WSCALE_LOG2 - e);
-                }
-}
-
-// Pack one LSTM direction: Wcat = [K_in (padded to INP rows) ; R] of shape [INP+H][4H] (Keras: [in][4H],
-// gate-major columns i|f|c|o) into MFMA fragment order [blk][g][lane][s] and bias into [blk][hh][q][m].
-inline void pack_lstm_dir(const float *Kin, int cin, int inp, const float *R, const float *b, int H,
-                          std::vector<float> &wp, std::vector<float> &bpk) {
-    const int K = inp + H, NG = K / 8, NBLK = 4 * H / 32, NT = NBLK / 4;
-    wp.assign((size_t)NBLK * NG * 64 * 4, 0.f);
-    bpk.assign((size_t)NBLK * 32, 0.f);
-    auto wcat = [&](int k, int col) -> float {
-        if (k < inp) return k < cin ? Kin[(size_t)k * 4 * H + col] : 0.f;
-        return R[(size_t)(k - inp) * 4 * H + col];
-    };
-    for (int blk = 0; blk < NBLK; ++blk) {
-        for (int r = 0; r < 32; ++r) {
-            const int q = r >> 3, hh = (r >> 2) & 1, m = r & 3;     // r = 8q + 4hh + m
-            const int unit = 8 * blk + 4 * hh + q, col = m * H + unit;
-            bpk[(size_t)blk * 32 + r] = b[col];
-            for (int g = 0; g < NG; ++g)
-                for (int kh = 0; kh < 2; ++kh)
-                    for (int s = 0; s < 4; ++s) {
-                        const int lane = kh * 32 + r;
-                        wp[((((size_t)(blk / NT) * NG + g) * NT + (blk % NT)) * 64 + lane) * 4 + s] = wcat(8 * g + 4 * kh + s, col);
-                    }
-        }
-    }
-}
-
-#define NET_HIP(call)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return C3R_EHIP; } \
-    } while (0)
-
-template <typename T>
-inline int net_upload(T *&dst, const std::vector<float> &src, hipStream_t st, std::string &err) {
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    NET_HIP(hipMalloc((void **)&dst, src.size() * sizeof(float)));
-    NET_HIP(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    NET_HIP(hipStreamSynchronize(st));
-    return C3R_OK;
-}
-
-inline int net_upload_h(half8 *&dst, const std::vector<uint16_t> &src, hipStream_t st, std::string &err) {
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    NET_HIP(hipMalloc((void **)&dst, src.size() * 2));
-    NET_HIP(hipMemcpyAsync(dst, src.data(), src.size() * 2, hipMemcpyHostToDevice, st));
-    NET_HIP(hipStreamSynchronize(st));
-    return C3R_OK;
-}
-
-inline int net_upload_u(uint32_t *&dst, const std::vector<uint32_t> &src, hipStream_t st, std::string &err) {
-    if (dst) { (void)hipFree(dst); dst = nullptr; }
-    NET_HIP(hipMalloc((void **)&dst, src.size() * 4));
-    NET_HIP(hipMemcpyAsync(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice, st));
-    NET_HIP(hipStreamSynchronize(st));
-    return C3R_OK;
-}
-
-inline int net_load(NetState &s, const float *blob, int C, hipStream_t st, std::string &err) {
-    const float *q = blob;
-    const int inp1 = 32;   // padded to an even number of 8-wide k-groups
-    std::vector<float> w1, b1, w2, b2, tw, tb;
-    std::vector<uint16_t> w1h, w2h, w2w, th;
-    std::vector<uint32_t> w1q, w1s, w2q, w2s, tq, ts;
-    // gate row r of tile blk <-> Keras column (pack_lstm_dir_h): r = 8 q + 4 hh + m -> unit 8 blk + 4 hh + q, gate m
-    auto gate_col = [](int blk, int r, int H) { const int qq = r >> 3, hh = (r >> 2) & 1, m = r & 3; return m * H + 8 * blk + 4 * hh + qq; };
-    // ---- the split-f16 scale of each layer.  2^12 keeps the lo halves of ordinary weights normal f16 numbers, but f16 ends at 65504: a
-    // weight (or a bias: layer 1's rides on an input slot, layer 2's is multiplied by the same scale) of 16 or more would become inf and
-    // the probabilities NaN.  So the scale is the largest power of two <= 2^12 that keeps 2^s max|w| <= 2^15 (a factor two of headroom);
-    // nothing in clair3_rna/model.py:126-172 bounds the weights.  Non-finite values are refused.
-    {
-        const int64_t nw = net_weight_count(C);
-        for (int64_t i = 0; i < nw; ++i) if (!std::isfinite(blob[i])) { err = "weight blob holds a non-finite value (index " + std::to_string(i) + ")"; return C3R_EINVAL; }
-        auto amax = [](const float *p, size_t n) { float m = 0.f; for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(p[i])); return m; };
-        const size_t n1 = (size_t)C * 4 * NET_H1 + (size_t)NET_H1 * 4 * NET_H1 + 4 * NET_H1, n2 = (size_t)2 * NET_H1 * 4 * NET_H2 + (size_t)NET_H2 * 4 * NET_H2 + 4 * NET_H2;
-        const float m[3] = {amax(blob, 2 * n1), amax(blob + 2 * n1, 2 * n2), amax(blob + 2 * n1 + 2 * n2, (size_t)NET_FLAT * NET_L4)};
-        for (int l = 0; l < 3; ++l) {
-            int sl = 12;
-            while (sl > -24 && std::ldexp(m[l], sl) > 32768.f) --sl;
-            s.wlog2[l] = sl;
-        }
-    }
-    const float wsc1 = std::ldexp(1.f, s.wlog2[0]), wsc2 = std::ldexp(1.f, s.wlog2[1]), wsc4 = std::ldexp(1.f, s.wlog2[2]);
-    for (int d = 0; d < 2; ++d) {
-        const float *Kin = q; q += (size_t)C * 4 * NET_H1;
-        const float *R = q; q += (size_t)NET_H1 * 4 * NET_H1;
-        const float *b = q; q += 4 * NET_H1;
-        pack_lstm_dir(Kin, C, inp1, R, b, NET_H1, tw, tb);
-        w1.insert(w1.end(), tw.begin(), tw.end()); b1.insert(b1.end(), tb.begin(), tb.end());
-        pack_lstm_dir_h(Kin, C, inp1, R, NET_H1, th, b, wsc1);
-        w1h.insert(w1h.end(), th.begin(), th.end());
-        // (layer 1: the recurrent part only — the integer pileup counts go through the f16 pipe, split exactly (k_lstm1_rs), never through fp8)
-        pack_mx([&](int k, int blk, int r) { return R[(size_t)k * 4 * NET_H1 + gate_col(blk, r, NET_H1)]; }, 4 * NET_H1 / 32, NET_H1 / 32, 0, NET_H1 / 32, tq, ts);
-        w1q.insert(w1q.end(), tq.begin(), tq.end()); w1s.insert(w1s.end(), ts.begin(), ts.end());
-    }
-    for (int d = 0; d < 2; ++d) {
-        const float *Kin = q; q += (size_t)2 * NET_H1 * 4 * NET_H2;
-        const float *R = q; q += (size_t)NET_H2 * 4 * NET_H2;
-        const float *b = q; q += 4 * NET_H2;
-        pack_lstm_dir(Kin, 2 * NET_H1, 2 * NET_H1, R, b, NET_H2, tw, tb);
-        w2.insert(w2.end(), tw.begin(), tw.end()); b2.insert(b2.end(), tb.begin(), tb.end());
-        pack_lstm_dir_h(Kin, 2 * NET_H1, 2 * NET_H1, R, NET_H2, th, nullptr, wsc2);
-        w2h.insert(w2h.end(), th.begin(), th.end());
-        pack_lstm2_w16(Kin, 2 * NET_H1, R, NET_H2, th, wsc2);
-        w2w.insert(w2w.end(), th.begin(), th.end());
-        pack_mx([&](int k, int blk, int r) {
-                    const int col = gate_col(blk, r, NET_H2);
-                    return k < 2 * NET_H1 ? Kin[(size_t)k * 4 * NET_H2 + col] : R[(size_t)(k - 2 * NET_H1) * 4 * NET_H2 + col];
-                }, 4 * NET_H2 / 32, 4 * NET_H2 / 128, 0, (2 * NET_H1 + NET_H2) / 32, tq, ts);
-        w2q.insert(w2q.end(), tq.begin(), tq.end()); w2s.insert(w2s.end(), ts.begin(), ts.end());
-    }
-    const float *W4 = q; q += (size_t)NET_FLAT * NET_L4;
-    const float *b4 = q; q += NET_L4;
-    const float *W51 = q; q += 128 * 128; const float *b51 = q; q += 128;
-    const float *W52 = q; q += 128 * 128; const float *b52 = q; q += 128;
-    const float *Wg = q; q += 128 * 21; const float *bg = q; q += 21;
-    const float *Wz = q; q += 128 * 3; const float *bz = q; q += 3;
-    // L4 packed [blk(4)][g][lane][s]: row r of block blk <-> output unit 32*blk + r
-    const int NG4 = NET_FLAT / 8;
-    std::vector<float> w4((size_t)4 * NG4 * 64 * 4);
-    for (int blk = 0; blk < 4; ++blk)
-        for (int g = 0; g < NG4; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int sidx = 0; sidx < 4; ++sidx) {
-                    const int r = lane & 31, kh = lane >> 5;
-                    w4[(((size_t)blk * NG4 + g) * 64 + lane) * 4 + sidx] = W4[(size_t)(8 * g + 4 * kh + sidx) * NET_L4 + 32 * blk + r];
-                }
-    // L4 split-f16: [blk(4)][g16][hi|lo][lane][8]
-    const int NG4h = NET_FLAT / 16;
-    std::vector<uint16_t> w4h((size_t)4 * NG4h * 2 * 64 * 8);
-    for (int blk = 0; blk < 4; ++blk)
-        for (int g = 0; g < NG4h; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int r = lane & 31, kh = lane >> 5;
-                    uint16_t hi, lo;
-                    split_h(wsc4 * W4[(size_t)(16 * g + 8 * kh + e) * NET_L4 + 32 * blk + r], hi, lo);
-                    const size_t base = (((size_t)blk * NG4h + g) * 2) * 64;
-                    w4h[(base + lane) * 8 + e] = hi;
-                    w4h[(base + 64 + lane) * 8 + e] = lo;
-                }
-    // L4 for the fused LSTM2 epilogue: [dir][t][blk(4)][g(10)][hi|lo][lane][8]; flatten order is [t][fwd 160 | bwd 160]
-    const int NGF = NET_H2 / 16;
-    std::vector<uint16_t> w4f((size_t)2 * NET_T * 4 * NGF * 2 * 64 * 8);
-    for (int d = 0; d < 2; ++d)
-        for (int t = 0; t < NET_T; ++t)
-            for (int blk = 0; blk < 4; ++blk)
-                for (int g = 0; g < NGF; ++g)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int r = lane & 31, kh = lane >> 5;
-                            const size_t row = (size_t)t * 2 * NET_H2 + (size_t)d * NET_H2 + 16 * g + 8 * kh + e;
-                            uint16_t hi, lo;
-                            split_h(wsc4 * W4[row * NET_L4 + 32 * blk + r], hi, lo);
-                            const size_t base = ((((size_t)(d * NET_T + t) * 4 + blk) * NGF + g) * 2) * 64;
-                            w4f[(base + lane) * 8 + e] = hi;
-                            w4f[(base + 64 + lane) * 8 + e] = lo;
-                        }
-    std::vector<uint16_t> w4w;
-    pack_l4_w16(W4, wsc4, w4w);
-    // fused L4 on the MX pipe: per (dir, t) one fragment set [quarter(4)][kb(5)][lane][32 B] (one tile per quarter)
-    std::vector<uint32_t> w4q, w4s;
-    for (int d = 0; d < 2; ++d)
-        for (int t = 0; t < NET_T; ++t) {
-            pack_mx([&](int k, int blk, int r) { return W4[((size_t)t * 2 * NET_H2 + (size_t)d * NET_H2 + k) * NET_L4 + 32 * blk + r]; }, 4, 1, 0, NET_H2 / 32, tq, ts);
-            w4q.insert(w4q.end(), tq.begin(), tq.end()); w4s.insert(w4s.end(), ts.begin(), ts.end());
-        }
-    std::vector<float> vb4(b4, b4 + NET_L4);
-    std::vector<float> w5((size_t)128 * 256), b5(256), wo((size_t)128 * 24), bo(24);
-    for (int k = 0; k < 128; ++k)
-        for (int o = 0; o < 128; ++o) { w5[(size_t)k * 256 + o] = W51[k * 128 + o]; w5[(size_t)k * 256 + 128 + o] = W52[k * 128 + o]; }
-    for (int o = 0; o < 128; ++o) { b5[o] = b51[o]; b5[128 + o] = b52[o]; }
-    for (int k = 0; k < 128; ++k) {
-        for (int o = 0; o < 21; ++o) wo[(size_t)k * 24 + o] = Wg[k * 21 + o];
-        for (int o = 0; o < 3; ++o) wo[(size_t)k * 24 + 21 + o] = Wz[k * 3 + o];
-    }
-    for (int o = 0; o < 21; ++o) bo[o] = bg[o];
-    for (int o = 0; o < 3; ++o) bo[21 + o] = bz[o];
-    // heads for k_heads_mfma: W5 = [L5_1 | L5_2] as 8 row tiles; the 24 logits as one tile over K = 256 (block structure)
-    std::vector<float> w5p((size_t)8 * 16 * 64 * 4), wcp((size_t)32 * 64 * 4, 0.f);
-    for (int blk = 0; blk < 8; ++blk)
-        for (int g = 0; g < 16; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int sidx = 0; sidx < 4; ++sidx) {
-                    const int r = lane & 31, kh = lane >> 5;
-                    w5p[(((size_t)blk * 16 + g) * 64 + lane) * 4 + sidx] = w5[(size_t)(8 * g + 4 * kh + sidx) * 256 + 32 * blk + r];
-                }
-    for (int g = 0; g < 32; ++g)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int sidx = 0; sidx < 4; ++sidx) {
-                const int r = lane & 31, kh = lane >> 5, k = 8 * g + 4 * kh + sidx;       // k indexes a5 = [L5_1 | L5_2]
-                float v = 0.f;
-                if (r < 21 && k < 128) v = wo[(size_t)k * 24 + r];
-                else if (r >= 21 && r < 24 && k >= 128) v = wo[(size_t)(k - 128) * 24 + r];
-                wcp[((size_t)g * 64 + lane) * 4 + sidx] = v;
-            }
-    int rc;
-    if ((rc = net_upload(s.d_w5p, w5p, st, err)) || (rc = net_upload(s.d_wcp, wcp, st, err))) return rc;
-    if ((rc = net_upload(s.d_w1, w1, st, err)) || (rc = net_upload(s.d_b1, b1, st, err)) || (rc = net_upload(s.d_w2, w2, st, err)) ||
-        (rc = net_upload(s.d_b2, b2, st, err)) || (rc = net_upload(s.d_w4, w4, st, err)) || (rc = net_upload(s.d_b4, vb4, st, err)) ||
-        (rc = net_upload(s.d_w5, w5, st, err)) || (rc = net_upload(s.d_b5, b5, st, err)) || (rc = net_upload(s.d_wo, wo, st, err)) ||
-        (rc = net_upload(s.d_bo, bo, st, err)) || (rc = net_upload_h(s.d_w1h, w1h, st, err)) || (rc = net_upload_h(s.d_w2h, w2h, st, err)) ||
-        (rc = net_upload_h(s.d_w4h, w4h, st, err)) || (rc = net_upload_h(s.d_w4f, w4f, st, err)) ||
-        (rc = net_upload_h(s.d_w2w, w2w, st, err)) || (rc = net_upload_h(s.d_w4w, w4w, st, err)) ||
-        (rc = net_upload_u(s.d_w1q, w1q, st, err)) || (rc = net_upload_u(s.d_w1s, w1s, st, err)) || (rc = net_upload_u(s.d_w2q, w2q, st, err)) ||
-        (rc = net_upload_u(s.d_w2s, w2s, st, err)) || (rc = net_upload_u(s.d_w4q, w4q, st, err)) || (rc = net_upload_u(s.d_w4s, w4s, st, err)))
-        return rc;
-    if (!s.d_tmo) {
-        if (hipMalloc((void **)&s.d_tmo, 64) != hipSuccess) { err = "hipMalloc(64) failed"; return C3R_ENOMEM; }
-        if (hipMemsetAsync(s.d_tmo, 0, 64, st) != hipSuccess) { err = "hipMemsetAsync failed"; return C3R_EHIP; }
-    }
-    s.channels = C; s.inp1 = inp1; s.loaded = true;
-    return C3R_OK;
-}
-
-// The network runs over the batch in slices of at most NET_SLICE sites: the layer-1 output is 33.8 KB per site (a 0.8 M-site
-// contig would take 27 GB, and sizing that buffer cost 1.2 s), a slice of 2^18 sites is 1024 workgroup rounds of layer 2 —
-// far beyond what the launch needs to fill the chip — and BASELINE's chr20 batch (201,945 sites) is still one slice.
-constexpr int64_t NET_SLICE = 262144;
-
-inline int net_reserve(NetState &s, int64_t n_total, hipStream_t st, std::string &err) {
-    const int64_t n = std::min(n_total, NET_SLICE);
-    const int64_t need = (n + 127) / 128 * 128;    // the y1 planes are stored with the site stride rounded up to 128
-    const bool want_y2 = s.precision == 0;         // split-f16 fuses L4 into layer 2: y2 (42 KB per site) is never materialised
-    if (n_total > s.cap_probs) {
-        NET_HIP(hipStreamSynchronize(st));
-        if (s.d_probs) { (void)hipFree(s.d_probs); s.d_probs = nullptr; }
-        const int64_t cap = n_total + n_total / 4 + 256;
-        NET_HIP(hipMalloc((void **)&s.d_probs, (size_t)cap * C3R_NPROB * sizeof(float)));
-        if (const char *e = getenv("C3R_POISON")) if (*e) { NET_HIP(hipMemsetAsync(s.d_probs, atoi(e) & 0xff, (size_t)cap * C3R_NPROB * sizeof(float), st)); NET_HIP(hipStreamSynchronize(st)); }
-        s.cap_probs = cap;
-    }
-    if (need <= s.cap_sites && (!want_y2 || s.d_y2)) return C3R_OK;
-    const bool grow = need > s.cap_sites;
-    const int64_t cap = grow ? std::min((need + need / 4 + 256 + 127) / 128 * 128, NET_SLICE) : s.cap_sites;
-    const auto t0_ = std::chrono::steady_clock::now();
-    NET_HIP(hipStreamSynchronize(st));
-    float **bufs[] = {&s.d_y1, &s.d_y2, &s.d_a4};
-    const size_t sizes[] = {(size_t)cap * NET_T * 2 * NET_H1, (size_t)cap * NET_T * 2 * NET_H2, (size_t)cap * NET_L4 * 2};
-    for (int i = 0; i < 3; ++i) {
-        const bool is_y2 = i == 1;
-        if (!grow && !is_y2) continue;                                   // only y2 is missing (precision switched to fp32)
-        if (*bufs[i]) { if (i == 0) big_give(*bufs[i], (size_t)s.cap_sites * NET_T * 2 * NET_H1 * sizeof(float)); else (void)hipFree(*bufs[i]); *bufs[i] = nullptr; }
-        if (is_y2 && !want_y2) continue;
-        if (i == 0 && (*bufs[i] = (float *)big_take(sizes[i] * sizeof(float)))) continue;
-        NET_HIP(hipMalloc((void **)bufs[i], sizes[i] * sizeof(float)));
-        if (const char *e = getenv("C3R_POISON")) if (*e) { NET_HIP(hipMemsetAsync(*bufs[i], atoi(e) & 0xff, sizes[i] * sizeof(float), st)); NET_HIP(hipStreamSynchronize(st)); }
-    }
-    s.cap_sites = cap;
-    if (getenv("C3R_TIMING")) fprintf(stderr, "[net_reserve] %lld sites per slice: %.1f ms\n", (long long)cap, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count());
-    return C3R_OK;
-}
-
-// d_x: device int32 [n][33][C].  prof(name, 0|1) brackets each kernel for optional event timing.
-inline int net_forward_slice(NetState &s, const void *d_x, const int32_t *row_idx, int64_t n, float *d_probs, hipStream_t st,
-                             const std::function<void(const char *, int)> &prof, std::string &err, bool x16);
-
-// d_x: device int32 [rows][33][C]; site i of the batch reads row row_idx[i] (row_idx == nullptr: row i)
-// x16: the rows are int16 (the tensor build's windows) instead of int32 (a caller's batch, the calibration windows)
-inline int net_forward(NetState &s, const void *d_x, const int32_t *row_idx, int64_t n, hipStream_t st,
-                       const std::function<void(const char *, int)> &prof, std::string &err, bool x16 = false) {
-    int rc = net_reserve(s, n, st, err);
-    if (rc) return rc;
-    const int64_t step = std::min(n, NET_SLICE);
-    for (int64_t off = 0; off < n; off += step) {
-        const int64_t m = std::min(step, n - off);
-        const void *x = row_idx ? d_x : (const void *)((const char *)d_x + (size_t)off * NET_T * s.channels * (x16 ? 2 : 4));
-        if ((rc = net_forward_slice(s, x, row_idx ? row_idx + off : nullptr, m, s.d_probs + (size_t)off * C3R_NPROB, st, prof, err, x16))) return rc;
-    }
-    return C3R_OK;
-}
-
-inline int net_forward_slice(NetState &s, const void *d_x, const int32_t *row_idx, int64_t n, float *d_probs, hipStream_t st,
-                             const std::function<void(const char *, int)> &prof, std::string &err, bool x16) {
-    const int xi = x16 ? 1 : 0;
-    const int nb = (int)((n + NET_SITES - 1) / NET_SITES);
-    const dim3 grid((unsigned)((n + LSTM_SITES - 1) / LSTM_SITES), 2), block(256);
-    int heads_parts = 1;
-    if (s.precision == 1 || s.precision == 2) {
-        // split-f16 path: y1 holds a hi and a lo f16 plane (same bytes as one fp32 plane), stored with the site stride rounded up to 128
-        // so that layer 1 needs no bounds guard.  Precision 2 (f16 main term + both corrections on the block-scaled fp8 pipe,
-        // k_lstm2_mx): y1 = f16 plane + fp8 plane of the same geometry.  Layer 2 has the L4 dense layer fused in: y2 is never materialised.
-        static_assert(C3R_DIR_ILV == 1, "the split-f16 kernels are launched on the (2, groups) grid");
-        _Float16 *y1h = (_Float16 *)s.d_y1;
-        const int ns = (int)((n + 127) / 128 * 128);
-        const dim3 g2(2, grid.x);
-        const bool mx = s.precision == 2;
-        const bool rts = s.wlog2[0] != 12 || s.wlog2[1] != 12 || s.wlog2[2] != 12;      // (never with precision 2: c3r_lib refuses that pairing)
-        if (mx && rts) { err = "the fp8-corrected path (precision 2) needs weights that fit the 2^12 split-f16 scale"; return C3R_EINVAL; }
-        const float wun1 = std::ldexp(1.f, -s.wlog2[0]), wsc2 = std::ldexp(1.f, s.wlog2[1]), wun2 = std::ldexp(1.f, -s.wlog2[1]), wun4 = std::ldexp(1.f, -s.wlog2[2]);
-        prof("k_lstm1", 0);
-        if (rts) {
-            if (s.channels == C3R_CH) hipLaunchKernelGGL((k_lstm1_rs<C3R_CH, false, true>), g2, dim3(1024), 0, st, d_x, (const half8 *)s.d_w1h, y1h, (int)n, ns, row_idx, wun1, xi);
-            else hipLaunchKernelGGL((k_lstm1_rs<C3R_CH_PHASED, false, true>), g2, dim3(1024), 0, st, d_x, (const half8 *)s.d_w1h, y1h, (int)n, ns, row_idx, wun1, xi);
-        } else if (s.channels == C3R_CH) {
-            if (mx) hipLaunchKernelGGL((k_lstm1_rs<C3R_CH, true>), g2, dim3(1024), 0, st, d_x, (const half8 *)s.d_w1h, y1h, (int)n, ns, row_idx, WUNSCALE, xi);
-            else hipLaunchKernelGGL((k_lstm1_rs<C3R_CH, false>), g2, dim3(1024), 0, st, d_x, (const half8 *)s.d_w1h, y1h, (int)n, ns, row_idx, WUNSCALE, xi);
-        } else {
-            if (mx) hipLaunchKernelGGL((k_lstm1_rs<C3R_CH_PHASED, true>), g2, dim3(1024), 0, st, d_x, (const half8 *)s.d_w1h, y1h, (int)n, ns, row_idx, WUNSCALE, xi);
-            else hipLaunchKernelGGL((k_lstm1_rs<C3R_CH_PHASED, false>), g2, dim3(1024), 0, st, d_x, (const half8 *)s.d_w1h, y1h, (int)n, ns, row_idx, WUNSCALE, xi);
-        }
-        prof("k_lstm1", 1);
-        prof("k_lstm2", 0);
-        if (rts)
-            hipLaunchKernelGGL((k_lstm2_w16<0, true>), g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2w, (const float *)s.d_b2, (int)n,
-                               (const half8 *)s.d_w4w, s.d_a4, ns, wsc2, wun2, wun4, s.d_tmo);
-        else if (mx)
-            hipLaunchKernelGGL(k_lstm2_mx, g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2h, (const uint32_t *)s.d_w2q, (const uint32_t *)s.d_w2s,
-                               (const float *)s.d_b2, (int)n, (const half8 *)s.d_w4f, (const uint32_t *)s.d_w4q, (const uint32_t *)s.d_w4s, s.d_a4, ns, s.d_tmo);
-        else
-            hipLaunchKernelGGL((k_lstm2_w16<0, false>), g2, dim3(512), 0, st, (const _Float16 *)y1h, (const half8 *)s.d_w2w, (const float *)s.d_b2, (int)n,
-                               (const half8 *)s.d_w4w, s.d_a4, ns, WSCALE, WUNSCALE, WUNSCALE, s.d_tmo);
-        prof("k_lstm2", 1);
-        heads_parts = 2;
-    } else {
-    prof("k_lstm1", 0);
-    if (s.channels == C3R_CH) {
-        constexpr int INP = 32;
-        hipLaunchKernelGGL((k_lstm<INP, C3R_CH, NET_H1, true, LSTM_SB>), grid, block, 0, st, (const void *)d_x,
-                           (const float4 *)s.d_w1, (const float *)s.d_b1, s.d_y1, (int)n, row_idx, xi);
-    } else {
-        constexpr int INP = 32;
-        hipLaunchKernelGGL((k_lstm<INP, C3R_CH_PHASED, NET_H1, true, LSTM_SB>), grid, block, 0, st, (const void *)d_x,
-                           (const float4 *)s.d_w1, (const float *)s.d_b1, s.d_y1, (int)n, row_idx, xi);
-    }
-    prof("k_lstm1", 1);
-    prof("k_lstm2", 0);
-    {
-        constexpr int INP = 2 * NET_H1;
-        hipLaunchKernelGGL((k_lstm<INP, INP, NET_H2, false, LSTM_SB>), grid, block, 0, st, (const void *)s.d_y1,
-                           (const float4 *)s.d_w2, (const float *)s.d_b2, s.d_y2, (int)n);
-    }
-    prof("k_lstm2", 1);
-    prof("k_fc4", 0);
-    hipLaunchKernelGGL(k_fc4, dim3(nb), block, 0, st, (const float *)s.d_y2, (const float4 *)s.d_w4, (const float *)s.d_b4, s.d_a4, (int)n);
-    prof("k_fc4", 1);
-    }
-    prof("k_heads", 0);
-    hipLaunchKernelGGL(k_heads_mfma, dim3((unsigned)((n + 31) / 32)), block, 0, st, (const float *)s.d_a4, heads_parts, (const float *)s.d_b4,
-                       (const float4 *)s.d_w5p, (const float *)s.d_b5, (const float4 *)s.d_wcp, (const float *)s.d_bo, d_probs, (int)n);
-    prof("k_heads", 1);
-    NET_HIP(hipGetLastError());
-    return C3R_OK;
 }
 
 }  // namespace c3r

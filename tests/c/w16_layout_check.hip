@@ -1,4 +1,4 @@
-// Host-side check of k_lstm2_w16's operand packing (clair3_rna_amd/csrc/net_kernels.hpp: pack_lstm2_w16, pack_l4_w16, w16_bias_row):
+// Host-side check of k_lstm2_w16's operand packing (clair3_rna_amd/csrc/net_pack.hpp: pack_lstm2_w16, pack_l4_w16; net_kernels.hpp: w16_bias_row):
 // compiled by hipcc, runs without a GPU.  Every weight is packed with a value that names its Keras position, read back at the address the
 // kernel loads it from (ldw: unit u = 2G + st, tile, hi|lo, lane), and compared with what v_mfma_f32_16x16x32_f16 makes of it:
 //   A lane l, element e  = A[row l % 16][k = 8 (l / 16) + e] of k-group G   (the B operand of lane l holds the same k of column l % 16)
@@ -8,7 +8,8 @@
 #include <cstdio>
 #include <cstdint>
 #include <vector>
-#include "../../clair3_rna_amd/csrc/net_kernels.hpp"
+#include "../../clair3_rna_amd/csrc/net_kernels.hpp"   // w16_bias_row
+#include "../../clair3_rna_amd/csrc/net_pack.hpp"      // the packers
 using namespace c3r;
 
 static int check_layer2() {

@@ -1,4 +1,4 @@
-"""Every launch of net_forward_slice (csrc/net_kernels.hpp), once: arithmetic variant x channel count x kind of input.
+"""Every launch of net_forward_slice (csrc/net_host.hpp), once: arithmetic variant x channel count x kind of input.
 
     variant      layer 1                                    layer 2 (+ L4)               reached by
     f32          k_lstm<32, C, 128, true>                   k_lstm<256, 256, 160, false>, k_fc4     set_precision("f32")

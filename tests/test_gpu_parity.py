@@ -517,7 +517,7 @@ def test_network_result_does_not_depend_on_batch_position(eng):
 
 
 def test_network_slices_of_a_long_batch(eng):
-    """The network runs over a batch in slices of at most 2^18 sites (net_kernels.hpp, NET_SLICE).  A batch longer than one slice —
+    """The network runs over a batch in slices of at most 2^18 sites (net_host.hpp, NET_SLICE).  A batch longer than one slice —
     a short block of windows repeated — must give every copy the probabilities of the short batch, bit for bit, including
     across the slice seam and in the ragged last workgroup."""
     from clair3_rna_amd import synth
