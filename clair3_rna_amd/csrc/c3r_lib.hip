@@ -2134,7 +2134,7 @@ static int apply_precision(c3r_ctx *ctx) {
     const bool rts = ctx->net.wlog2[0] != 12 || ctx->net.wlog2[1] != 12 || ctx->net.wlog2[2] != 12;
     int rc;
     // ---- the guard of the split-f16 arithmetic: once per set of weights
-    // (C3R_NO_F16_GUARD=1: development aid for timing probes whose kernels compute garbage on purpose — tools/y1_probe.sh)
+    // (C3R_NO_F16_GUARD=1: development aid for timing probes whose kernels compute garbage on purpose, such as profiles/r5/y1_traffic_probe.txt's)
     static const bool no_guard = [] { const char *e = getenv("C3R_NO_F16_GUARD"); return e && *e == '1'; }();
     if (no_guard) ctx->f16_calib_err = 0.0;
     if (ctx->f16_calib_err < 0.0) {

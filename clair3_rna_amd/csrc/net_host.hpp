@@ -1,5 +1,6 @@
 // net_host.hpp — host driver of the pileup network: the per-context device state, the weight upload (net_pack.hpp packs, this file
-// copies), the activation buffers and the launches of the kernels of net_kernels.hpp.
+// copies), the activation buffers and the launches of the kernels of net_kernels.hpp.  The kernels have no build-time variants: what
+// this file launches is the one form of each (fp32: grid (groups, 2); split-f16 and fp8-corrected: grid (2, groups)).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -204,10 +205,9 @@ inline int net_forward_slice(NetState &s, const void *d_x, const int32_t *row_id
         // split-f16 path: y1 holds a hi and a lo f16 plane (same bytes as one fp32 plane), stored with the site stride rounded up to 128
         // so that layer 1 needs no bounds guard.  Precision 2 (f16 main term + both corrections on the block-scaled fp8 pipe,
         // k_lstm2_mx): y1 = f16 plane + fp8 plane of the same geometry.  Layer 2 has the L4 dense layer fused in: y2 is never materialised.
-        static_assert(C3R_DIR_ILV == 1, "the split-f16 kernels are launched on the (2, groups) grid");
         _Float16 *y1h = (_Float16 *)s.d_y1;
         const int ns = (int)((n + 127) / 128 * 128);
-        const dim3 g2(2, grid.x);
+        const dim3 g2(2, grid.x);          // the split-f16 kernels read the direction from blockIdx.x, the site group from blockIdx.y
         const bool mx = s.precision == 2;
         const bool rts = s.wlog2[0] != 12 || s.wlog2[1] != 12 || s.wlog2[2] != 12;      // (never with precision 2: c3r_lib refuses that pairing)
         if (mx && rts) { err = "the fp8-corrected path (precision 2) needs weights that fit the 2^12 split-f16 scale"; return C3R_EINVAL; }

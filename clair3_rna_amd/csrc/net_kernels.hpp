@@ -35,34 +35,15 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int NET_SITES = 32;              // sites per MFMA column block
 constexpr int LSTM_SB = 2;                 // column blocks per wavefront in k_lstm
 constexpr int LSTM_SITES = NET_SITES * LSTM_SB;
-#ifndef C3R_W8_PD
-#define C3R_W8_PD 1          // prefetch distance (k-groups / units) of the layer-2 kernels' operand ring
-#endif
-#ifndef C3R_W8_MAP
-#define C3R_W8_MAP 0         // layer 2: which wavefronts pair up on a SIMD — 0: w and w+4 (round-robin placement; measured 19.3 ms), 1: 2w and 2w+1 (20.5 ms)
-#endif
-#ifndef C3R_W8_PRIO
-#define C3R_W8_PRIO 0        // 1: s_setprio 1 for the 3-tile wavefronts, 2: for the 2-tile wavefronts
-#endif
-#ifndef C3R_DIR_ILV
-#define C3R_DIR_ILV 1        // k_lstm1_rs / layer 2: grid (2, groups) — the two directions of a site group are dispatched back to back
-#endif
+// The split-f16 kernels (k_lstm1_rs, k_lstm2_w16, k_lstm2_mx) run on the grid (2, groups): blockIdx.x is the direction, so the two
+// directions of a site group are dispatched back to back.  (The alternatives that were measured and closed: DESIGN.md §kernels.)
 // y1 (6.8 GB per chr20 pass) and a4part are written once and read once, and layer 2's hot set — a direction's weights and its W4p time
-// slices, 3.8 MB — is nearly the whole of an XCD's 4 MB L2: the single-use streams carry the non-temporal policy, the weights do not.
-#ifndef C3R_Y1_NT_LOAD
-#define C3R_Y1_NT_LOAD 1     // layer 2: the LDS-DMA of y1 (dma_x, dma_x16) with the nt bit
-#endif
-#ifndef C3R_Y1_NT_STORE
-#define C3R_Y1_NT_STORE 1    // k_lstm1_rs's y1 stores and layer 2's a4part stores with the nt bit
-#endif
-#ifndef C3R_L2_SKIP0
-#define C3R_L2_SKIP0 1       // k_lstm2_w16: step 0 has no recurrent part (h_{-1} = 0: ten of its 26 units and the L4 tile are exact zeros)
-#endif
-#define C3R_Y1_AUX (C3R_Y1_NT_LOAD ? 2 : 0)      // __builtin_amdgcn_global_load_lds's cache policy: bit 1 = nt
+// slices, 3.8 MB — is nearly the whole of an XCD's 4 MB L2: the single-use streams carry the non-temporal policy (layer 2's LDS-DMA of
+// y1, k_lstm1_rs's y1 stores, layer 2's a4part stores), the weights do not.
+constexpr int Y1_NT_AUX = 2;      // __builtin_amdgcn_global_load_lds's cache policy: bit 1 = nt
 template <class V, class P>
 __device__ __forceinline__ void y1_store(V v, P p) {
-    if constexpr (C3R_Y1_NT_STORE) __builtin_nontemporal_store(v, p);
-    else *p = v;
+    __builtin_nontemporal_store(v, p);
 }
 
 // sigmoid / tanh on the hardware transcendentals: v_exp_f32 + v_rcp_f32 (about 1 ulp each), no IEEE division
@@ -109,6 +90,33 @@ __device__ __forceinline__ void split_h2(float h0, float h1, half2v &hi, half2v 
     asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "=v"(d1) : "v"(hi), "v"(h1));
     const float2v d = {d0, d1};
     lo = __builtin_convertvector(d, half2v);
+}
+// The LSTM cell update of the split-f16 kernels (k_lstm1_rs, k_lstm2_w16, k_lstm2_mx) for a lane's N cells: zi, zf, zg, zo are the gate
+// pre-activations as they leave the accumulators (still times the weight scale), K1 = -log2(e) / scale for the sigmoids, K2 = 2 K1 for
+// tanh; c is updated in place, h receives o * tanh(c).  Nine stages, each over all N cells before the next begins: the transcendentals of
+// one stage are independent and fill each other's latency.  tests/test_lstm_isa.py guards the instruction stream this compiles to.
+template <int N>
+__device__ __forceinline__ void lstm_cell_update(const float (&zi)[N], const float (&zf)[N], const float (&zg)[N], const float (&zo)[N],
+                                                 float (&c)[N], float (&h)[N], const float K1, const float K2) {
+    float ei[N], ef[N], eg[N], eo[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * zi[u]), 1e18f);
+#pragma unroll
+    for (int u = 0; u < N; ++u) ef[u] = __builtin_amdgcn_exp2f(K1 * zf[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * zg[u]), 1e18f);
+#pragma unroll
+    for (int u = 0; u < N; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * zo[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));                                  // sigmoid(i) * tanh(g)
+#pragma unroll
+    for (int u = 0; u < N; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);                                  // sigmoid(f)
+#pragma unroll
+    for (int u = 0; u < N; ++u) c[u] = cell_fence(fmaf(ef[u], c[u], ei[u]));
+#pragma unroll
+    for (int u = 0; u < N; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * c[u]), 1e18f);
+#pragma unroll
+    for (int u = 0; u < N; ++u) h[u] = gate_frac(eo[u], eg[u]);                                               // sigmoid(o) * tanh(c)
 }
 __device__ __forceinline__ float selu(float x) {
     const float scale = 1.0507009873554805f, alpha = 1.6732632423543772f;
@@ -365,14 +373,11 @@ __device__ __forceinline__ void sched_interleave() {
 //   * the 2-tile wavefronts also own the fused L4 rows: W4[t-1, dir] x h_{t-1} rides in the recurrent part of step t as a
 //     third tile on the very same B fragments (h_{t-1} hi/lo) — no separate pass, its weights join the prefetch ring; in the
 //     recurrent part both wavefronts of a SIMD therefore carry three tiles each;
-//   * one barrier after the input part (x_t is dead from there on: each wavefront issues its share of the LDS-DMA of
-//     x_{t+1} after its recurrent part, and it lands under the cell update), one at the end of the step (h_t complete); h is
+//   * no workgroup barriers inside the time loop: the wavefronts meet through three LDS counters (x_t read by all / x_{t+1} landed /
+//     h_t written by all), so that one wavefront's cell update runs under its SIMD partner's MFMAs.  x_t is dead after the input
+//     part: the four 3-tile wavefronts issue the LDS-DMA of x_{t+1} after their recurrent part, and it lands under the cell update; h is
 //     double-buffered because a wavefront's cell update now runs while others still read h_{t-1}.  LDS: 2 x 42 KB (h hi/lo) + 64 KB (x tile) = 148 KB.
 //   Wp / W4p / bp / a4part: see "Operand layouts" above (the "quarter" sq = wave & 3 indexes them).
-#ifndef C3R_W8_ASYNC
-#define C3R_W8_ASYNC 1       // layer 2: 1 = no workgroup barriers inside the time loop — the wavefronts meet through three LDS counters (x_t read by
-                             // all / x_{t+1} landed / h_t written by all), so that one wavefront's cell update runs under its SIMD partner's MFMAs
-#endif
 // Counters in LDS that only grow: arrive = release + one increment per wavefront, wait = spin until the count is reached, then acquire.
 __device__ __forceinline__ void lds_arrive(int *c) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -390,15 +395,24 @@ __device__ __forceinline__ void lds_wait(int *c, int target, int *tmo) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// LDS-DMA of layer 2's input of time slice tt_ (both planes: 2 KC rows of 1 KiB — 64 sites x 16 bytes) into the x tile, the rows dealt
+// evenly to NW wavefronts of which the caller is number w; lane l fetches site xsite's 16 bytes of each of its wavefront's rows.
+// Non-temporal: y1 is read once.  The caller waits (vmcnt) before anyone reads the tile.
+template <int NW, int KC, int WG_SITES>
+__device__ __forceinline__ void dma_x_rows(_Float16 (&xs)[2][KC][WG_SITES][8], const _Float16 *xin, size_t plane_in, int ns, int xsite, int w, int tt_) {
+    typedef const _Float16 __attribute__((address_space(1))) *gp_t;
+    typedef _Float16 __attribute__((address_space(3))) *lp_t;
+#pragma unroll
+    for (int r = 0; r < 2 * KC / NW; ++r) {
+        const int row = w * (2 * KC / NW) + r, pl = row / KC, kc = row % KC;
+        const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
+        __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, Y1_NT_AUX);
+    }
+}
+
 // RTS ("run-time scale"): the weights were packed with a power-of-two scale below 2^12 because some |w| would not fit f16 at 2^12
 // (net_load, NetState::wlog2); the scale (layer 2: wsc = 2^s, wun = 2^-s; fused L4: wun4) then comes in as kernel arguments.  With RTS
 // = false — every set of weights seen so far — the constants fold exactly as before.
-// C3R_PROBE_Y1 (timing only, results wrong): what a y1 format with a lo plane of half the bytes — an 8-bit block-scaled residual instead of
-// f16 — could gain at most: layer 2 skips every other lo-plane row of its LDS-DMA (a quarter of its y1 reads), layer 1 stores only half
-// of its lo plane (a quarter of its y1 writes).  profiles/r5/y1_traffic_probe.txt.
-#ifndef C3R_PROBE_Y1
-#define C3R_PROBE_Y1 0
-#endif
 // ------------------------------------------------------------------------------------------------
 // Layer 2 (+ fused L4) on v_mfma_f32_16x16x32_f16: k_lstm2_w16.  The decomposition above (512 threads, 64 sites x one direction per
 // workgroup, tiles dealt 3 + 2 (+ L4) to the two wavefronts of a SIMD, x_t by LDS-DMA one step ahead, the three LDS counters, h
@@ -413,7 +427,10 @@ __device__ __forceinline__ void lds_wait(int *c, int target, int *tmo) {
 //     32x32x16 layout, so the same two-slot ring; the B operands (four site blocks, hi and lo) are read once per k-group, one unit ahead, and serve both subtiles;
 //   * the accumulators start from the fp32 bias x 2^s (exact; kept in LDS) instead of a bias MFMA;
 //   * the fused L4's 32 rows of a quarter are two subtiles as well: a lane's 4 rows are 4 consecutive L4 outputs (float4 stores);
-//   * step 0 is the x part alone (C3R_L2_SKIP0); y1 comes in and a4part goes out with the non-temporal policy (C3R_Y1_NT_LOAD / _STORE).
+//   * step 0 is the x part alone (h_{-1} = 0: ten of its 26 units and the L4 tile are exact zeros); y1 comes in and a4part goes out with
+//     the non-temporal policy.
+//   ABL : timing-only ablation bits for tools/lstm_probe_w8.hip (0 in the product): 1 weights from one L1-hot unit, 2 no gate math,
+//         16 weights loaded for unit 0 only, 32 B operands read for k-group 0 only.
 //   Wp  : [dir][quarter(4)][u = 2G + st (26)][tile(5)][hi|lo][64 lanes] half8 — lane l: row l % 16 of subtile st, k = 32G + 8 (l / 16) + 0..7
 //   W4p : [dir][t][quarter(4)][u = 2G + st (10)][hi|lo][64 lanes] half8 — row l % 16 <-> L4 output 32 quarter + 16 st + l % 16
 //   bp  : pack_lstm_dir's fp32 bias layout (pack_lstm_dir: [dir][tile][r = 8q + 4hh + m] <-> gate m of unit 8 tile + 4 hh + q)
@@ -427,21 +444,21 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                                                        int *tmo = nullptr /* the context's time-out word (lds_wait) */) {
     const float wsc = RTS ? wsc_arg : WSCALE, wun = RTS ? wun_arg : WUNSCALE, wun4 = RTS ? wun4_arg : WUNSCALE;
     constexpr int INP = 2 * NET_H1, H = NET_H2, NGX = INP / 32, NGH = H / 32, NG = NGX + NGH, NU = 2 * NG, HP = H + 8, NBLK = 4 * H / 32, NTQ = NBLK / 4;
-    constexpr int SB = 4, WG_SITES = 16 * SB, KC = INP / 8, PD = C3R_W8_PD;
-    static_assert(NTQ == 5 && NU == 26 && PD == 1, "3 + 2 tile split of a quarter, 26 (k-group, subtile) units, one unit of prefetch");
+    constexpr int SB = 4, WG_SITES = 16 * SB, KC = INP / 8;
+    static_assert(NTQ == 5 && NU == 26, "3 + 2 tile split of a quarter, 26 (k-group, subtile) units (the operand ring holds one unit of prefetch)");
     __shared__ __attribute__((aligned(16))) _Float16 hb_hi[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) _Float16 hb_lo[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) _Float16 xs[2][KC][WG_SITES][8];      // [plane][k/8][site][8]
     __shared__ __attribute__((aligned(16))) float s_bias[NBLK][2][16];          // 2^s b: [tile][st][4q + m]
-    __shared__ int s_ctr[4];        // C3R_W8_ASYNC: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
+    __shared__ int s_ctr[4];        // the LDS counters: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // in an SGPR: the weight addresses below are scalar arithmetic plus one lane offset
     const int c16 = lane & 15, q4 = lane >> 4;
-    const int sq = C3R_W8_MAP ? (wave >> 1) : (wave & 3);
-    const bool heavy3 = C3R_W8_MAP ? !(wave & 1) : (wave < 4);
-    const int dir = C3R_DIR_ILV ? blockIdx.x : blockIdx.y;
-    const int site0 = (C3R_DIR_ILV ? blockIdx.y : blockIdx.x) * WG_SITES;
+    const int sq = wave & 3;                     // quarter of the gate rows
+    const bool heavy3 = wave < 4;                // the 3-tile wavefront of its SIMD pair (waves w and w + 4 share a SIMD: round-robin placement)
+    const int dir = blockIdx.x;
+    const int site0 = blockIdx.y * WG_SITES;
     const int ns = nstride ? nstride : n;
     const size_t plane_in = (size_t)ns * NET_T * INP;
 
@@ -454,26 +471,8 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
 
     int xsite = site0 + lane;
     if (xsite >= n) xsite = n - 1;
-    auto dma_x = [&](int tt_) {
-        typedef const _Float16 __attribute__((address_space(1))) *gp_t;
-        typedef _Float16 __attribute__((address_space(3))) *lp_t;
-#pragma unroll
-        for (int r = 0; r < 2 * KC / 8; ++r) {
-            const int row = wave * (2 * KC / 8) + r, pl = row / KC, kc = row % KC;
-            const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
-        }
-    };
-    auto dma_x16 = [&](int tt_) {
-        typedef const _Float16 __attribute__((address_space(1))) *gp_t;
-        typedef _Float16 __attribute__((address_space(3))) *lp_t;
-#pragma unroll
-        for (int r = 0; r < 2 * KC / 4; ++r) {
-            const int row = (wave & 3) * (2 * KC / 4) + r, pl = row / KC, kc = row % KC;
-            const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
-        }
-    };
+    auto dma_x = [&](int tt_) { dma_x_rows<8>(xs, xin, plane_in, ns, xsite, wave, tt_); };            // before the time loop: eight rows per wavefront
+    auto dma_x16 = [&](int tt_) { dma_x_rows<4>(xs, xin, plane_in, ns, xsite, wave & 3, tt_); };      // inside it: all 64 rows from the four 3-tile wavefronts
     dma_x(dir ? NET_T - 1 : 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -499,7 +498,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                     // one value are set up before the loop as 16 v_mov_b64 copies of a register pair — harmless, but tests/test_lstm_isa.py
                     // takes any v_mov_b64 in this kernel for a weight address rebuilt in vector registers)
                     float z = 0.f;
-                    if constexpr (C3R_L2_SKIP0 && L4T) asm volatile("" : "+v"(z));
+                    if constexpr (L4T) asm volatile("" : "+v"(z));
                     facc[st][sb][r] = z;
                 }
             }
@@ -508,7 +507,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
         const uint32_t wlane = (uint32_t)lane;
         for (int step = 0; step < NET_T; ++step) {
             const int t = dir ? NET_T - 1 - step : step;
-            const int tprev = step ? (dir ? t + 1 : t - 1) : t;      // step 0: any valid slice (C3R_L2_SKIP0: unit 2 NGX's is still requested, never multiplied)
+            const int tprev = step ? (dir ? t + 1 : t - 1) : t;      // step 0: any valid slice (unit 2 NGX's is still requested, never multiplied)
             const int cur = step & 1, nxt = cur ^ 1;
 
             auto ldx = [&](int g, half8 (&bh)[SB], half8 (&bl)[SB]) {
@@ -546,7 +545,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                 }
             };
 
-            if (C3R_W8_ASYNC && step > 0) lds_wait(&s_ctr[1], 4 * step, tmo);      // x_t has landed (four DMA wavefronts per step)
+            if (step > 0) lds_wait(&s_ctr[1], 4 * step, tmo);      // x_t has landed (four DMA wavefronts per step)
             floatx4 acc[NT][2][SB];
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt)
@@ -594,7 +593,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
 #define C3R_STEP(U)                                                                                              \
     if constexpr ((U) < NU) {                                                                                     \
         C3R_FENCE();                                                                                              \
-        if constexpr (C3R_W8_ASYNC && (U) + 1 == 2 * NGX) { lds_wait(&s_ctr[2], 8 * step, tmo); C3R_FENCE(); }   /* h_{t-1} is complete */ \
+        if constexpr ((U) + 1 == 2 * NGX) { lds_wait(&s_ctr[2], 8 * step, tmo); C3R_FENCE(); }   /* h_{t-1} is complete */ \
         if constexpr ((U) + 1 < NU) { C3R_LOAD((U) + 1); }                                                        \
         mma(ah[(U) % 2], al[(U) % 2], bh[((U) / 2) % 2], bl[((U) / 2) % 2], std::integral_constant<int, (U) & 1>{}, (U) >= 2 * NGX); \
         if constexpr ((U) + 1 < NU) {                                                                             \
@@ -603,7 +602,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
         }                                                                                                         \
         if constexpr ((U) == 2 * NGX - 1) {                                                                       \
             C3R_FENCE();                                                                                          \
-            if constexpr (C3R_W8_ASYNC) lds_arrive(&s_ctr[0]); else __syncthreads();                              \
+            lds_arrive(&s_ctr[0]);                                                    /* done with x_t */           \
         }                                                                                                         \
     }
             // Step 0 ends with the x part: h_{-1} = 0, so the recurrent units U >= 2 NGX (their weight stream, their reads of a zeroed hb,
@@ -615,51 +614,29 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
             C3R_LOAD(0);
             C3R_STEP(0) C3R_STEP(1) C3R_STEP(2) C3R_STEP(3) C3R_STEP(4) C3R_STEP(5) C3R_STEP(6) C3R_STEP(7) C3R_STEP(8) C3R_STEP(9)
             C3R_STEP(10) C3R_STEP(11) C3R_STEP(12) C3R_STEP(13) C3R_STEP(14) C3R_STEP(15)
-            if (!C3R_L2_SKIP0 || step) {
-            C3R_STEP(16) C3R_STEP(17) C3R_STEP(18)
-            C3R_STEP(19) C3R_STEP(20) C3R_STEP(21) C3R_STEP(22) C3R_STEP(23) C3R_STEP(24) C3R_STEP(25)
+            if (step) {
+                C3R_STEP(16) C3R_STEP(17) C3R_STEP(18)
+                C3R_STEP(19) C3R_STEP(20) C3R_STEP(21) C3R_STEP(22) C3R_STEP(23) C3R_STEP(24) C3R_STEP(25)
             }
             C3R_FENCE();
 #undef C3R_STEP
 #undef C3R_LOAD
 #undef C3R_FENCE
-            if constexpr (C3R_W8_ASYNC) {
-                if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }
-            } else if (step + 1 < NET_T && !(ABL & 64)) dma_x(dir ? NET_T - 2 - step : step + 1);
+            // x_{t+1}: once all eight wavefronts are done with x_t, the four 3-tile wavefronts fetch it; it lands during the cell update
+            if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }
             // ---- lane-local cell update, one tile at a time: cell u = 4 st + sb is unit 8T + 2 q4 + st at site 16 sb + c16
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt) {
                 __builtin_amdgcn_sched_barrier(0);
                 constexpr int NC = 2 * SB;
                 const float K1 = -1.4426950408889634f * wun, K2 = -2.8853900817779268f * wun;
-                float cq[NC], ei[NC], ef[NC], eg[NC], eo[NC], hval[NC];
+                float zi[NC], zf[NC], zg[NC], zo[NC], hval[NC];
 #pragma unroll
-                for (int u = 0; u < NC; ++u) cq[u] = cst[tt][u];
+                for (int u = 0; u < NC; ++u) { zi[u] = acc[tt][u / SB][u % SB][0]; zf[u] = acc[tt][u / SB][u % SB][1]; zg[u] = acc[tt][u / SB][u % SB][2]; zo[u] = acc[tt][u / SB][u % SB][3]; }
                 if (ABL & 2) {
 #pragma unroll
-                    for (int u = 0; u < NC; ++u) hval[u] = acc[tt][u / SB][u % SB][0] + acc[tt][u / SB][u % SB][1] + acc[tt][u / SB][u % SB][2] + acc[tt][u / SB][u % SB][3];
-                } else {
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][0]), 1e18f);
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) ef[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][1]);
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[tt][u / SB][u % SB][2]), 1e18f);
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u / SB][u % SB][3]);
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) cq[u] = cell_fence(fmaf(ef[u], cq[u], ei[u]));
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
-#pragma unroll
-                    for (int u = 0; u < NC; ++u) hval[u] = gate_frac(eo[u], eg[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < NC; ++u) cst[tt][u] = cq[u];
+                    for (int u = 0; u < NC; ++u) hval[u] = zi[u] + zf[u] + zg[u] + zo[u];
+                } else lstm_cell_update(zi, zf, zg, zo, cst[tt], hval, K1, K2);
 #pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
                     half2v vh, vl;
@@ -669,16 +646,11 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
                     *(half2v *)&hb_lo[nxt][16 * sb + c16][8 * (sq * NTQ + TOFF + tt) + 2 * q4] = vl;
                 }
             }
-            if constexpr (C3R_W8_ASYNC) {
-                lds_arrive(&s_ctr[2]);
-                if (!L4T && step + 1 < NET_T) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lds_arrive(&s_ctr[1]); }
-            } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            }
+            lds_arrive(&s_ctr[2]);
+            if (!L4T && step + 1 < NET_T) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lds_arrive(&s_ctr[1]); }      // (LDS-DMA is tracked by vmcnt)
         }
         if constexpr (L4T) {
-            if constexpr (C3R_W8_ASYNC) lds_wait(&s_ctr[2], 8 * NET_T, tmo);
+            lds_wait(&s_ctr[2], 8 * NET_T, tmo);
             // ---- the last step's h (buffer NET_T & 1) still owes its L4 contribution
             const int tl = dir ? 0 : NET_T - 1, hbuf = NET_T & 1;
             const half8 *w4 = W4p + (((size_t)(dir * NET_T + tl) * 4 + sq) * 2 * NGH) * 2 * 64 + lane;
@@ -714,8 +686,6 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_w16(const _Float16 *__restrict
             }
         }
     };
-    if (C3R_W8_PRIO == 1 && heavy3) __builtin_amdgcn_s_setprio(1);
-    if (C3R_W8_PRIO == 2 && !heavy3) __builtin_amdgcn_s_setprio(1);
     if (heavy3) body(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, std::false_type{});
     else body(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}, std::true_type{});
 }
@@ -742,13 +712,7 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
                                                       const half8 *__restrict__ W4p, const uint32_t *__restrict__ W4q,
                                                       const uint32_t *__restrict__ W4sc, float *__restrict__ a4part, int nstride, int *tmo = nullptr) {
     constexpr int INP = 2 * NET_H1, H = NET_H2, NGX = INP / 16, NGH = H / 16, NG = NGX + NGH, HP = H + 8, NBLK = 4 * H / 32, NTQ = NBLK / 4;
-    #ifndef C3R_MX_PD
-#define C3R_MX_PD 1
-#endif
-#ifndef C3R_MX_EVEN_BURST
-#define C3R_MX_EVEN_BURST 0      // 1: the short even steps issue their loads (among them the next block's fp8 fragments) as one burst ahead of the MFMAs
-#endif
-    constexpr int SB = 2, WG_SITES = 32 * SB, KC = INP / 8, PD = C3R_MX_PD;
+    constexpr int SB = 2, WG_SITES = 32 * SB, KC = INP / 8;
     constexpr int NKB = NG / 2, NKBX = NGX / 2, NKBH = NGH / 2, NK4 = (NKB + 3) / 4, NK4L = (NKBH + 3) / 4;
     static_assert(NTQ == 5 && NG == 26 && NGX % 2 == 0 && NGH % 2 == 0, "3 + 2 tile split of a quarter, whole 32-k blocks");
     typedef int intx8 __attribute__((ext_vector_type(8)));
@@ -756,14 +720,14 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
     __shared__ __attribute__((aligned(16))) _Float16 hb_hi[2][WG_SITES][HP];
     __shared__ __attribute__((aligned(16))) intx4 hq[2][NKBH][2][2][WG_SITES];     // fp8 of h: [buffer][kb][term][part][site] 16 bytes
     __shared__ __attribute__((aligned(16))) _Float16 xs[2][KC][WG_SITES][8];      // [plane][row][site][16 bytes]
-    __shared__ int s_ctr[4];        // C3R_W8_ASYNC: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
+    __shared__ int s_ctr[4];        // the LDS counters: [0] done reading x_t, [1] x DMAs landed, [2] done writing h_t
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, hh = lane >> 5;
     const int sq = wave & 3;                     // quarter of the gate rows
     const bool heavy3 = wave < 4;                // the 3-tile wavefront of its SIMD pair (waves w and w + 4 share a SIMD)
-    const int dir = C3R_DIR_ILV ? blockIdx.x : blockIdx.y;
-    const int site0 = (C3R_DIR_ILV ? blockIdx.y : blockIdx.x) * WG_SITES;
+    const int dir = blockIdx.x;
+    const int site0 = blockIdx.y * WG_SITES;
     const int ns = nstride ? nstride : n;
     const size_t plane_in = (size_t)ns * NET_T * INP;
 
@@ -773,26 +737,8 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 
     int xsite = site0 + lane;
     if (xsite >= n) xsite = n - 1;
-    auto dma_x = [&](int tt_) {          // 64 rows of 1 KiB, eight per wavefront (see k_lstm2_w16)
-        typedef const _Float16 __attribute__((address_space(1))) *gp_t;
-        typedef _Float16 __attribute__((address_space(3))) *lp_t;
-#pragma unroll
-        for (int r = 0; r < 2 * KC / 8; ++r) {
-            const int row = wave * (2 * KC / 8) + r, pl = row / KC, kc = row % KC;
-            const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
-        }
-    };
-    auto dma_x16 = [&](int tt_) {          // C3R_W8_ASYNC: all 64 rows from the four 3-tile wavefronts
-        typedef const _Float16 __attribute__((address_space(1))) *gp_t;
-        typedef _Float16 __attribute__((address_space(3))) *lp_t;
-#pragma unroll
-        for (int r = 0; r < 2 * KC / 4; ++r) {
-            const int row = (wave & 3) * (2 * KC / 4) + r, pl = row / KC, kc = row % KC;
-            const _Float16 *src = xin + (size_t)pl * plane_in + (((size_t)tt_ * KC + kc) * ns + xsite) * 8;
-            __builtin_amdgcn_global_load_lds((gp_t)src, (lp_t)&xs[pl][kc][0][0], 16, 0, C3R_Y1_AUX);
-        }
-    };
+    auto dma_x = [&](int tt_) { dma_x_rows<8>(xs, xin, plane_in, ns, xsite, wave, tt_); };            // before the time loop: eight rows per wavefront
+    auto dma_x16 = [&](int tt_) { dma_x_rows<4>(xs, xin, plane_in, ns, xsite, wave & 3, tt_); };      // inside it: all 64 rows from the four 3-tile wavefronts
     dma_x(dir ? NET_T - 1 : 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -846,8 +792,8 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
             const int tprev = step ? (dir ? t + 1 : t - 1) : t;
             const int cur = step & 1, nxt = cur ^ 1;
 
-            if (C3R_W8_ASYNC && step > 0) lds_wait(&s_ctr[1], 4 * step, tmo);      // x_t has landed
-            half8 ah[PD + 1][NTH], bh[PD + 1][SB];
+            if (step > 0) lds_wait(&s_ctr[1], 4 * step, tmo);      // x_t has landed
+            half8 ah[2][NTH], bh[2][SB];          // two-slot ring: group G in slot G % 2, requested one group ahead
             intx8 a8[NTH], b8[SB];
             int sc[NTH];
             // operands of k-group G: the f16 hi fragments; with an odd G also the fp8 fragments (and every fourth block the scale words) of
@@ -953,56 +899,41 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
 #define C3R_STEP(G)                                                                                              \
     if constexpr ((G) < NG) {                                                                                     \
         C3R_FENCE();                                                                                              \
-        if constexpr (C3R_W8_ASYNC && (G) + PD == NGX) { lds_wait(&s_ctr[2], 8 * step, tmo); C3R_FENCE(); }   /* h_{t-1} is complete */ \
-        if constexpr (PD == 0 || (G) + PD < NG) { load(std::integral_constant<int, (G) + PD>{}, ah[((G) + PD) % (PD + 1)], bh[((G) + PD) % (PD + 1)]); } \
-        mma(std::integral_constant<int, (G)>{}, ah[(G) % (PD + 1)], bh[(G) % (PD + 1)]);                          \
-        if constexpr (PD > 0 && (G) + PD < NG && (((G) & 1) || !C3R_MX_EVEN_BURST)) {                              \
+        if constexpr ((G) + 1 == NGX) { lds_wait(&s_ctr[2], 8 * step, tmo); C3R_FENCE(); }   /* h_{t-1} is complete */ \
+        if constexpr ((G) + 1 < NG) { load(std::integral_constant<int, (G) + 1>{}, ah[((G) + 1) % 2], bh[((G) + 1) % 2]); } \
+        mma(std::integral_constant<int, (G)>{}, ah[(G) % 2], bh[(G) % 2]);                                        \
+        if constexpr ((G) + 1 < NG) {                                                                             \
             constexpr int NMM = ((G) >= NGX ? NTH : NT) * SB * (((G) & 1) ? 2 : 1);                               \
-            constexpr int NTL = ((G) + PD >= NGX ? NTH : NT);                                                     \
-            sched_interleave<NMM, NTL * ((((G) + PD) & 1) ? 3 : 1), SB * ((((G) + PD) & 1) ? 3 : 1)>();           \
+            constexpr int NTL = ((G) + 1 >= NGX ? NTH : NT);                                                      \
+            sched_interleave<NMM, NTL * ((((G) + 1) & 1) ? 3 : 1), SB * ((((G) + 1) & 1) ? 3 : 1)>();             \
         }                                                                                                         \
         if constexpr ((G) == NGX - 1) {                                                                           \
             C3R_FENCE();                                                                                          \
-            if constexpr (C3R_W8_ASYNC) lds_arrive(&s_ctr[0]); else __syncthreads();     /* done with x_t */        \
+            lds_arrive(&s_ctr[0]);                                                       /* done with x_t */        \
         }                                                                                                         \
     }
-            if constexpr (PD > 0) { load(std::integral_constant<int, 0>{}, ah[0], bh[0]); }
+            load(std::integral_constant<int, 0>{}, ah[0], bh[0]);
             C3R_STEP(0) C3R_STEP(1) C3R_STEP(2) C3R_STEP(3) C3R_STEP(4) C3R_STEP(5) C3R_STEP(6) C3R_STEP(7) C3R_STEP(8) C3R_STEP(9)
             C3R_STEP(10) C3R_STEP(11) C3R_STEP(12) C3R_STEP(13) C3R_STEP(14) C3R_STEP(15) C3R_STEP(16) C3R_STEP(17) C3R_STEP(18)
             C3R_STEP(19) C3R_STEP(20) C3R_STEP(21) C3R_STEP(22) C3R_STEP(23) C3R_STEP(24) C3R_STEP(25)
             C3R_FENCE();
 #undef C3R_STEP
 #undef C3R_FENCE
-            if constexpr (C3R_W8_ASYNC) {
-                if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }
-            } else if (step + 1 < NET_T) dma_x(dir ? NET_T - 2 - step : step + 1);      // lands during the cell update
+            if (!L4T && step + 1 < NET_T) { lds_wait(&s_ctr[0], 8 * (step + 1), tmo); dma_x16(dir ? NET_T - 2 - step : step + 1); }      // lands during the cell update
             // ---- lane-local cell update (k_lstm2_w16's), h_t to LDS as f16 plus the two fp8 bytes per unit
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt) {
                 __builtin_amdgcn_sched_barrier(0);
                 constexpr int NU = 4 * SB;
                 constexpr float K1 = -1.4426950408889634f * WUNSCALE, K2 = -2.8853900817779268f * WUNSCALE;
-                float cq[NU], ei[NU], ef[NU], eg[NU], eo[NU], hval[NU];
+                float zi[NU], zf[NU], zg[NU], zo[NU], cq[NU], hval[NU];
 #pragma unroll
-                for (int u = 0; u < NU; ++u) cq[u] = cst[tt][u >> 2][u & 3];
-#pragma unroll
-                for (int u = 0; u < NU; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 0]), 1e18f);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) ef[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 1]);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[tt][u >> 2][4 * (u & 3) + 2]), 1e18f);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * acc[tt][u >> 2][4 * (u & 3) + 3]);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));
-#pragma unroll
-                for (int u = 0; u < NU; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) cq[u] = cell_fence(fmaf(ef[u], cq[u], ei[u]));
-#pragma unroll
-                for (int u = 0; u < NU; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) hval[u] = gate_frac(eo[u], eg[u]);
+                for (int u = 0; u < NU; ++u) {
+                    cq[u] = cst[tt][u >> 2][u & 3];
+                    zi[u] = acc[tt][u >> 2][4 * (u & 3) + 0]; zf[u] = acc[tt][u >> 2][4 * (u & 3) + 1];
+                    zg[u] = acc[tt][u >> 2][4 * (u & 3) + 2]; zo[u] = acc[tt][u >> 2][4 * (u & 3) + 3];
+                }
+                lstm_cell_update(zi, zf, zg, zo, cq, hval, K1, K2);
                 const int T = sq * NTQ + TOFF + tt;          // tile of the direction: units 8 T + 4 hh + q
 #pragma unroll
                 for (int sb = 0; sb < SB; ++sb) {
@@ -1028,16 +959,11 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
                     }
                 }
             }
-            if constexpr (C3R_W8_ASYNC) {
-                lds_arrive(&s_ctr[2]);
-                if (!L4T && step + 1 < NET_T) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lds_arrive(&s_ctr[1]); }
-            } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // x_{t+1} has landed (LDS-DMA is tracked by vmcnt)
-            __syncthreads();                                       // h_t complete; everyone is done with h_{t-1}
-            }
+            lds_arrive(&s_ctr[2]);
+            if (!L4T && step + 1 < NET_T) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lds_arrive(&s_ctr[1]); }      // (LDS-DMA is tracked by vmcnt)
         }
         if constexpr (L4T) {
-            if constexpr (C3R_W8_ASYNC) lds_wait(&s_ctr[2], 8 * NET_T, tmo);
+            lds_wait(&s_ctr[2], 8 * NET_T, tmo);
             // ---- the last step's h (buffer NET_T & 1) still owes its L4 contribution
             const int tl = dir ? 0 : NET_T - 1, hbuf = NET_T & 1;
             const half8 *w4 = W4p + (((size_t)(dir * NET_T + tl) * 4 + sq) * NGH) * 2 * 64 + lane;
@@ -1073,11 +999,6 @@ __global__ __launch_bounds__(512, 2) void k_lstm2_mx(const _Float16 *__restrict_
             }
         }
     };
-#ifndef C3R_MX_PRIO
-#define C3R_MX_PRIO 0        // 1: s_setprio 1 for the 3-tile wavefronts, 2: for the 2-tile (+ L4) wavefronts
-#endif
-    if (C3R_MX_PRIO == 1 && heavy3) __builtin_amdgcn_s_setprio(1);
-    if (C3R_MX_PRIO == 2 && !heavy3) __builtin_amdgcn_s_setprio(1);
     if (heavy3) body(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, std::false_type{});
     else body(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}, std::true_type{});
 }
@@ -1117,8 +1038,8 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
     const int tid = threadIdx.x, lane = tid & 63;
     const int blk = __builtin_amdgcn_readfirstlane(tid >> 6);          // the wavefront's tile of the direction (units 8 blk .. 8 blk + 7); in an SGPR: what depends on it and the step alone is scalar arithmetic
     const int j = lane & 31, hh = lane >> 5;
-    const int dir = C3R_DIR_ILV ? blockIdx.x : blockIdx.y;
-    const int site0 = (C3R_DIR_ILV ? blockIdx.y : blockIdx.x) * WG_SITES;
+    const int dir = blockIdx.x;
+    const int site0 = blockIdx.y * WG_SITES;
     const size_t plane_out = (size_t)nstride * NET_T * 2 * H;
 
     for (int i = tid; i < 2 * WG_SITES * HP; i += 1024) (&hb[0][0][0][0])[i] = (_Float16)0.f;
@@ -1189,13 +1110,6 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
     x_fetch(dir ? NET_T - 1 : 0);
     x_store(0, 0);
     __syncthreads();
-#ifndef C3R_L1_K8
-#define C3R_L1_K8 1          // k_lstm1_rs, 18 channels: the 3 used slots of the second input group as a K = 8 product
-#endif
-#ifndef C3R_L1_RS_PRIO
-#define C3R_L1_RS_PRIO 0     // k_lstm1_rs: raise the priority of the wavefronts that arrive last on their SIMD (blk >= this value; 0: off)
-#endif
-    if (C3R_L1_RS_PRIO > 0 && blk >= C3R_L1_RS_PRIO) __builtin_amdgcn_s_setprio(1);
     // The lane's LDS addresses: four registers for the whole loop.  Each is the address of the lane's first access of its kind, the
     // step's parity included (moved by one buffer at the end of every step); blocks, groups, the hi | lo planes and the counts' parts
     // are constant offsets of the instructions.  (Left to the compiler: ten registers of addresses that differ by constants.)
@@ -1270,8 +1184,8 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                     if constexpr (G + 1 < NG) ldb(std::integral_constant<int, G + 1>{}, bh[(G + 1) & 1], bl[(G + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if constexpr (C3R_L1_K8 && G == NGX - 1 && CIN + 1 <= 16 + 4) {
-                    // the second input group holds channels 16 .. CIN - 1 and the bias slot CIN, zeros after them: a K = 8 product covers it
+                if constexpr (G == NGX - 1 && CIN + 1 <= 16 + 4) {
+                    // 18 channels: the second input group holds channels 16 .. CIN - 1 and the bias slot CIN, zeros after them: a K = 8 product covers it
                     // (lane half hh takes k = 4 hh .. 4 hh + 3 of the group: for hh = 0 the first half of the lane's K = 16 fragment, for
                     // hh = 1 zeros — as is the first half of ITS fragment, k = 8 .. 11 of the group)
                     const half4 a_h = __builtin_shufflevector(wh[G], wh[G], 0, 1, 2, 3), a_l = __builtin_shufflevector(wl[G], wl[G], 0, 1, 2, 3);
@@ -1279,36 +1193,21 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
                     acc = __builtin_amdgcn_mfma_f32_32x32x8f16(a_h, b_h, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x8f16(a_l, b_h, acc, 0, 0, 0);
                 } else {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bh[G & 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[G], bh[G & 1], acc, 0, 0, 0);
-                if constexpr (G >= NGX) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bl[G & 1], acc, 0, 0, 0);      // (the counts' other parts: before the loop)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bh[G & 1], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[G], bh[G & 1], acc, 0, 0, 0);
+                    if constexpr (G >= NGX) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[G], bl[G & 1], acc, 0, 0, 0);      // (the counts' other parts: before the loop)
                 }
             });
             // ---- lane-local cell update of the block (four units per lane)
             const float K1 = -1.4426950408889634f * wun, K2 = -2.8853900817779268f * wun;
-            float ei[4], ef[4], eg[4], eo[4], cq[4], hval[4];
+            float zi[4], zf[4], zg[4], zo[4], cq[4], hval[4];
             {
                 const floatx4 c4 = *(floatx4 __attribute__((address_space(3))) *)(scp + sb * 64 * 16);
                 cq[0] = c4[0]; cq[1] = c4[1]; cq[2] = c4[2]; cq[3] = c4[3];
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) ei[u] = fminf(__builtin_amdgcn_exp2f(K1 * acc[4 * u + 0]), 1e18f);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ef[u] = __builtin_amdgcn_exp2f(K1 * acc[4 * u + 1]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(K2 * acc[4 * u + 2]), 1e18f);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) eo[u] = __builtin_amdgcn_exp2f(K1 * acc[4 * u + 3]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ei[u] = cell_fence(gate_frac(ei[u], eg[u]));
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ef[u] = __builtin_amdgcn_rcpf(1.0f + ef[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) cq[u] = cell_fence(fmaf(ef[u], cq[u], ei[u]));
-#pragma unroll
-            for (int u = 0; u < 4; ++u) eg[u] = fminf(__builtin_amdgcn_exp2f(-2.8853900817779268f * cq[u]), 1e18f);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) hval[u] = gate_frac(eo[u], eg[u]);
+            for (int u = 0; u < 4; ++u) { zi[u] = acc[4 * u + 0]; zf[u] = acc[4 * u + 1]; zg[u] = acc[4 * u + 2]; zo[u] = acc[4 * u + 3]; }
+            lstm_cell_update(zi, zf, zg, zo, cq, hval, K1, K2);
             *(floatx4 __attribute__((address_space(3))) *)(scp + sb * 64 * 16) = floatx4{cq[0], cq[1], cq[2], cq[3]};
             half2v vh01, vh23, vl01, vl23;
             float lo[4];
@@ -1322,7 +1221,7 @@ __global__ __launch_bounds__(1024) void k_lstm1_rs(const void *__restrict__ xin_
             const gh_t yp = yrow + (size_t)(ylane + 32 * sb * 8);
             y1_store(vh, (gh4_t)yp);
             if constexpr (!YQ) {
-                if (!(C3R_PROBE_Y1 && (blk & 1))) y1_store(vl, (gh4_t)(yrow + plane_out + (size_t)(ylane + 32 * sb * 8)));
+                y1_store(vl, (gh4_t)(yrow + plane_out + (size_t)(ylane + 32 * sb * 8)));
             } else {                                     // the fp8 plane precision 2's layer 2 reads (k_lstm2_mx's x layout)
                 int w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], 0, false);
                 w_lo = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], w_lo, true);

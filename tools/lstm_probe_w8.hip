@@ -1,7 +1,7 @@
 // lstm_probe_w8.hip — timing-only ablation of k_lstm2_w16 (layer 2 + fused L4, two wavefronts per SIMD) on random operands.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/lstm_probe_w8.hip -o tools/lstm_probe_w8
 //   ABL bits: 1 = every weight load hits one L1-hot k-group (L1 -> register traffic kept, L2 -> L1 traffic gone), 2 = no gate math (cell update replaced by 3 adds), 16 = weights loaded for the first k-group only
-//   (register-stationary afterwards: no L2 -> L1 weight stream), 64 = no x DMA after the first step
+//   (register-stationary afterwards: no L2 -> L1 weight stream), 32 = B operands read from LDS for the first k-group only
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -15,7 +15,7 @@ template <int ABL>
 static float run(const _Float16 *x, const half8 *w, const float *b, int n, int reps) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
-    dim3 grid = C3R_DIR_ILV ? dim3(2, (n + 63) / 64) : dim3((n + 63) / 64, 2);      // (k_lstm2_w16 reads the direction from blockIdx.x then)
+    const dim3 grid(2, (n + 63) / 64);      // (k_lstm2_w16 reads the direction from blockIdx.x)
     const int ns = (n + 127) / 128 * 128;
     hipLaunchKernelGGL((k_lstm2_w16<ABL>), grid, dim3(512), 0, 0, x, w, b, n, g_w4, g_a4, ns);
     hipDeviceSynchronize();
@@ -57,7 +57,6 @@ int main(int argc, char **argv) {
         {"w8 no gate, no weights", run<18>(x, w, b, n, 3)},
         {"w8 weights L1-hot", run<1>(x, w, b, n, 3)},
         {"w8 no LDS operand reads", run<32>(x, w, b, n, 3)},
-        {"w8 no x DMA", run<64>(x, w, b, n, 3)},
         {"w8 full (again)", run<0>(x, w, b, n, 3)},
         {"w8 full (3rd)", run<0>(x, w, b, n, 3)},
     };
