@@ -30,6 +30,9 @@ linkage on the GPU, a greedy linkage chain, not whatshap's wMEC (include/c3r.h: 
 <output_dir>/tmp/phased_output/phased_vcf, then the run with --phased_vcf_fn on that directory (<prefix>_enable_phasing.vcf.gz).
 `--phase_merge_levels N` (default 0: off) is handed to phase_vcf as --merge_levels: up to N levels of the block-merge stage after the chain.  One process
 only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line — run the three steps as three commands there.
+`--phase_output` (with --enable_phasing_model and --phased_vcf_fn or --phasing builtin; one process only) adds a step behind the phased pass:
+hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU into
+<prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
@@ -155,6 +158,11 @@ def build_parser():
     a("--phase_merge_levels", type=int, default=0,
       help="with --phasing builtin: handed to phase_vcf as --merge_levels — up to that many levels of the block-merge stage after the chain, "
            "which joins the blocks that reads bridge across a run of unlinked sites (0: off)")
+    a("--phase_output", action="store_true",
+      help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: after the 30-channel pass, phase the heterozygous SNVs of "
+           "<prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU (hap_vcf: SNVs only, a majority rule over CIGAR-position "
+           "alleles) into <prefix>_enable_phasing_phased.vcf.gz and write the counts to <prefix>_enable_phasing_hap_counts.tsv.  One process only "
+           "(not under torch.distributed.run)")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
     a("--genotyping_mode_vcf_fn", type=str, default=None)
@@ -302,7 +310,50 @@ def _empty_reads():
     return out
 
 
+def _indexed_bam(args):
+    """The BAM the steps around the passes read: this run's, or — when IT has no index — the link with an index beside it that a pass left in
+    tmp/ (asked of the BAM again, not guessed from the link: an earlier run in this directory may have left one to another file)."""
+    bam_fn = args.bam_fn
+    if bam_fn.endswith(".bam"):
+        from . import bamio
+        with bamio.BamFile(bam_fn) as probe:
+            indexed = probe.has_index
+        link = os.path.join(args.output_dir, "tmp", "input.bam")
+        if not indexed and os.path.exists(link + ".bai") and os.path.realpath(link) == os.path.realpath(bam_fn):
+            bam_fn = link
+    return bam_fn
+
+
 def Run(args, log=None):
+    """The passes (_run_flow), and with `--phase_output` one further step behind them: hap_vcf on the phased pass's VCF — nothing inside a
+    pass changes."""
+    if not getattr(args, "phase_output", False):
+        return _run_flow(args, log)
+    from . import hap_vcf
+    builtin = getattr(args, "phasing", None) is not None
+    if not args.enable_phasing_model:
+        sys.exit("[ERROR] --phase_output needs --enable_phasing_model (it phases the 30-channel pass's VCF)")
+    if not builtin and not getattr(args, "phased_vcf_fn", None):
+        sys.exit("[ERROR] --phase_output needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("[ERROR] --phase_output runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the pass without it and then "
+                 "`python -m clair3_rna_amd.hap_vcf --bam_fn ... --vcf_fn <prefix>_enable_phasing.vcf.gz --phased_vcf_fn ... --output_fn ...`")
+    rc = _run_flow(args, log)
+    if rc:
+        return rc
+    ext = ".vcf" if args.no_compress else ".vcf.gz"
+    stem = os.path.join(args.output_dir, args.output_prefix + "_enable_phasing")
+    if not os.path.isfile(stem + ext):                        # (no contig found: the pass wrote nothing)
+        return rc
+    source = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf") if builtin else args.phased_vcf_fn
+    hap_vcf.Run(hap_vcf.build_parser().parse_args(
+        ["--bam_fn", _indexed_bam(args), "--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext,
+         "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)]
+        + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
+    return rc
+
+
+def _run_flow(args, log=None):
     """One pass (_run_pass), or with `--phasing builtin` the three steps of the phased flow one after the other: the unphased pass, phase_vcf
     on the file it wrote, the 30-channel pass with --phased_vcf_fn on phase_vcf's directory — nothing inside a pass changes."""
     if getattr(args, "phasing", None) is None:
@@ -331,16 +382,7 @@ def Run(args, log=None):
         return rc
     vcf_fn = os.path.join(args.output_dir, args.output_prefix + (".vcf" if args.no_compress else ".vcf.gz"))
     phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
-    # the BAM the passes read: this run's, or — when IT has no index — the link with an index beside it that the first pass left in tmp/
-    # (asked of the BAM again, not guessed from the link: an earlier run in this directory may have left one to another file)
-    bam_fn = args.bam_fn
-    if bam_fn.endswith(".bam"):
-        from . import bamio
-        with bamio.BamFile(bam_fn) as probe:
-            indexed = probe.has_index
-        link = os.path.join(args.output_dir, "tmp", "input.bam")
-        if not indexed and os.path.exists(link + ".bai") and os.path.realpath(link) == os.path.realpath(bam_fn):
-            bam_fn = link
+    bam_fn = _indexed_bam(args)
     # phased_<ctg>.vcf.gz of an earlier run in this directory: a contig without a row in this run's VCF would keep its file, and the second
     # pass would haplotag from it
     if os.path.isdir(phased_dir):

@@ -44,6 +44,10 @@ class PhaseStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_sites", "n_phased", "n_blocks", "max_block")]
 
 
+class HapAssignStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_sites", "n_phased", "n_few_reads", "n_disagree")]
+
+
 class C3RError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, "libc3r: %s (%s)" % (msg, C3R_ERRORS.get(code, code)))
@@ -55,7 +59,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
-           "c3r_phase_unit_links", "c3r_phase_merge"]
+           "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign"]
 
 _lib = None
 
@@ -99,6 +103,9 @@ def load_library():
     L.c3r_phase_resolve.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(PhaseStats)]
     L.c3r_phase_unit_links.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64)]
     L.c3r_phase_merge.argtypes = [vp, i64, vp, i64, C.POINTER(PhaseParams), vp, C.POINTER(PhaseStats), C.POINTER(i64)]
+    L.c3r_get_read_phase_sets.argtypes = [vp, vp, i64]
+    L.c3r_hap_counts.argtypes = [vp, vp, i64, vp]
+    L.c3r_hap_assign.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(HapAssignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.c3r_batch_begin.argtypes = [vp]
@@ -279,6 +286,25 @@ class Engine(object):
         hp = np.zeros(st.n_reads, dtype=np.uint8)
         self._chk(self.L.c3r_get_haplotags(self.h, _ptr(hp), len(hp), C.byref(st)))
         return hp, {k: int(getattr(st, k)) for k, _ in HaplotagStats._fields_}
+
+    def read_phase_sets(self):
+        """int32[n]: the phase set every loaded read's tag was decided in, in load order; -1 where the tag is 0 (c3r_get_read_phase_sets).  An
+        error while no phase sites are set."""
+        st = HaplotagStats()
+        self._chk(self.L.c3r_get_haplotags(self.h, None, 0, C.byref(st)))
+        ps = np.zeros(st.n_reads, dtype=np.int32)
+        self._chk(self.L.c3r_get_read_phase_sets(self.h, _ptr(ps), len(ps)))
+        return ps
+
+    def hap_counts(self, sites):
+        """uint32 (n, 3, 3): at every query site (a PHASE_SITE_DTYPE array sorted by pos; ps = the phase set to count against, h1 is ignored)
+        the loaded reads that pass the current filters, by row — 0: the read is untagged, tied or tagged in another set, 1 / 2: its haplotype —
+        and by column — REF, ALT, another base (c3r_hap_counts).  Needs a table (set_phase_sites).  Leaves the reads' haplotags, the table and
+        every scan as they are."""
+        a = _phase_site_array(sites)
+        counts = np.zeros((len(a), 3, 3), dtype=np.uint32)
+        self._chk(self.L.c3r_hap_counts(self.h, _ptr(a), len(a), _ptr(counts)))
+        return counts
 
     def phase_links(self, sites):
         """uint32 (n, PHASE_LINKS, 2) cis / trans counts between every candidate site (a PHASE_SITE_DTYPE array sorted by pos; ps and h1 are
@@ -523,6 +549,23 @@ def phase_resolve(sites, links, min_reads=2, min_agree_pct=75):
     if rc != 0:
         raise C3RError(rc, "c3r_phase_resolve: sites must be sorted by strictly increasing pos, min_reads >= 0, 0 <= min_agree_pct <= 100")
     return out, {k: int(getattr(st, k)) for k, _ in PhaseStats._fields_}
+
+
+def hap_assign(sites, counts, min_reads=2, min_agree_pct=75):
+    """The assignment rule of include/c3r.h on the host (c3r_hap_assign; no GPU, no engine): query sites and their (n, 3, 3) count table
+    (Engine.hap_counts) -> (sites with h1 filled in and ps kept where the haplotype-tagged reads agree, ps = -1 and h1 = 0 elsewhere;
+    dict(n_sites, n_phased, n_few_reads, n_disagree))."""
+    L = load_library()
+    a = _phase_site_array(sites)
+    ct = np.ascontiguousarray(counts, dtype=np.uint32)
+    if ct.shape != (len(a), 3, 3):
+        raise ValueError("counts must have shape (%d, 3, 3), got %r" % (len(a), ct.shape))
+    out = np.zeros(len(a), dtype=PHASE_SITE_DTYPE)
+    p, st = PhaseParams(int(min_reads), int(min_agree_pct)), HapAssignStats()
+    rc = L.c3r_hap_assign(_ptr(a), len(a), _ptr(ct), C.byref(p), _ptr(out), C.byref(st))
+    if rc != 0:
+        raise C3RError(rc, "c3r_hap_assign: min_reads >= 0, 0 <= min_agree_pct <= 100")
+    return out, {k: int(getattr(st, k)) for k, _ in HapAssignStats._fields_}
 
 
 class RowSnapshot(object):

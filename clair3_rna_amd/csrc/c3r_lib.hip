@@ -26,6 +26,7 @@
 #include "reads_kernels.hpp"
 #include "haplotag_kernels.hpp"
 #include "phase_kernels.hpp"
+#include "hapcount_kernels.hpp"
 #include <sched.h>
 
 using namespace c3r;
@@ -153,11 +154,14 @@ struct c3r_ctx {
     std::vector<int32_t> h_sites;
     DevBuf d_sites;
     // haplotagging (c3r_set_phase_sites): the contig's phased SNVs and, once reads have been loaded under them, the reads' tags
-    // (tag | votes << 2 per read, k_haplotag).  Nothing is allocated or launched while the table is empty.
+    // (tag | votes << 2 per read, k_haplotag) and the phase set each tag was decided in.  Nothing is allocated or launched while the table
+    // is empty.
     int64_t n_phase = 0;
-    DevBuf d_phase, d_hptag;
+    DevBuf d_phase, d_hptag, d_hpps;
     // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
     DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
+    // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
+    DevBuf d_hcsites, d_hcounts;
 
     // ---- scan state
     int32_t reg_beg0 = 0, reg_end0 = 0;   // first region of the most recent scan (c3r_get_columns)
@@ -565,12 +569,12 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     // ---- haplotags from the phase sites, if the caller has set any: the records have passed the range checks above, and the second pass
     // takes every read's hp from the header this kernel writes it to (nothing here waits for the device)
     if (ctx->n_phase > 0) {
-        if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16))) return rc;
+        if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16)) || (rc = ensure(ctx, ctx->d_hpps, (size_t)n * 4 + 16))) return rc;
         HapArgs h;
         memset(&h, 0, sizeof h);
         h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
         h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_phase_site_t *)ctx->d_phase.p; h.n_sites = (int32_t)ctx->n_phase;
-        h.tags = (uint32_t *)ctx->d_hptag.p;
+        h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p;
         Launch L(ctx, "k_haplotag");
         hipLaunchKernelGGL(k_haplotag, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
     }
@@ -726,7 +730,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1145,6 +1149,69 @@ int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats
         if (hp) hp[i] = (uint8_t)tag;
         st.n_votes += votes;
         if (tag == 1) st.n_hp1 += 1; else if (tag == 2) st.n_hp2 += 1; else if (votes == 0) st.n_no_vote += 1; else st.n_tie += 1;
+    }
+    if (stats) *stats = st;
+    return C3R_OK;
+}
+
+int c3r_get_read_phase_sets(c3r_ctx *ctx, int32_t *ps, int64_t cap) {
+    if (!ctx || cap < 0) return C3R_EINVAL;
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads have no phase set");
+    const int64_t n = ctx->n_reads;
+    if (n && (!ps || cap < n)) return fail(ctx, C3R_EOVERFLOW, "phase sets of %lld reads do not fit %lld slots", (long long)n, (long long)cap);
+    if (n == 0) return C3R_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(ps, ctx->d_hpps.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return C3R_OK;
+}
+
+int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *counts) {
+    if (!ctx || n < 0 || (n && (!sites || !counts))) return C3R_EINVAL;
+    if (int rc = check_phase_sites(ctx, "query site", sites, n, false)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (sites[i].ps < 0) return fail(ctx, C3R_EINVAL, "query site %lld: phase set %d is negative", (long long)i, sites[i].ps);
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads carry no tags to count by");
+    if (n == 0) return C3R_OK;
+    const size_t words = (size_t)n * 9;
+    if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->d_hcsites, sites, (size_t)n)) || (rc = ensure(ctx, ctx->d_hcounts, words * 4))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_hcounts.p, 0, words * 4, ctx->stream));
+    HapCountArgs a;
+    memset(&a, 0, sizeof a);
+    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
+    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_phase_site_t *)ctx->d_hcsites.p; a.n_sites = (int32_t)n;
+    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.counts = (uint32_t *)ctx->d_hcounts.p;
+    {
+        Launch L(ctx, "k_hap_counts");
+        hipLaunchKernelGGL(k_hap_counts, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_hcounts.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's site array may go once this returns, and the table is there)
+    return C3R_OK;
+}
+
+int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts, const c3r_phase_params_t *p, c3r_phase_site_t *out,
+                   c3r_hap_assign_stats_t *stats) {
+    if (n < 0 || (n && (!in || !counts || !out))) return C3R_EINVAL;
+    const int64_t min_reads = p ? p->min_reads : 2, pct = p ? p->min_agree_pct : 75;
+    if (min_reads < 0 || pct < 0 || pct > 100) return C3R_EINVAL;
+    c3r_hap_assign_stats_t st;
+    memset(&st, 0, sizeof st);
+    st.n_sites = n;
+    for (int64_t j = 0; j < n; ++j) {
+        const uint32_t *c = counts + (size_t)j * 9;                  // [row][allele]
+        const uint64_t v1 = (uint64_t)c[1 * 3 + 1] + c[2 * 3 + 0], v0 = (uint64_t)c[1 * 3 + 0] + c[2 * 3 + 1], w = v0 + v1, hi = std::max(v0, v1);
+        c3r_phase_site_t e = in[j];
+        if (w < (uint64_t)min_reads) { st.n_few_reads += 1; e.ps = -1; e.h1 = 0; }
+        else if (v0 == v1 || 100 * hi < (uint64_t)pct * w) { st.n_disagree += 1; e.ps = -1; e.h1 = 0; }
+        else { st.n_phased += 1; e.h1 = v1 > v0 ? 1 : 0; }
+        e.reserved = 0;
+        out[j] = e;
     }
     if (stats) *stats = st;
     return C3R_OK;

@@ -17,6 +17,8 @@
 //   3. the lanes' votes meet by shuffles.  When all votes of the read lie in one phase set (the common case) that is all.  Otherwise the
 //      phase sets are taken one at a time in the order of their numbers: each further walk counts the votes of one set and finds the next
 //      number above it, so any number of sets — interleaved as they may be — is exact in P + 1 walks with no storage.
+// The set the tag was decided in is kept beside the tag (read_ps): k_hap_counts (hapcount_kernels.hpp) counts a read on a haplotype only at
+// the sites of that set.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +34,7 @@ struct HapArgs {
     const uint8_t *seq;                       // 4-bit packed bases
     const c3r_phase_site_t *sites; int32_t n_sites;
     uint32_t *tags;                           // [n_reads] tag | votes of the read on all phase sets << 2
+    int32_t *read_ps;                         // [n_reads] the phase set the tag was decided in, -1 when the tag is 0
 };
 
 // first site of [lo, hi) with pos >= p (hi: none)
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
     const DevRead d = a.reads[i];
     // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
     const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
-    uint32_t tag = 0, votes = 0;
+    uint32_t tag = 0, votes = 0, set = HAP_NONE;
     if (lo < hi) {
         ReadInfo R;
         R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
@@ -125,13 +128,14 @@ __global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
         const bool serial = a.serial[i] != 0;
         HapTally t = hap_walk(R, gl, serial, a, lo, hi, HAP_NONE);
         votes = t.c1 + t.c2;
+        set = t.ps_min;                                                // (one set, or no vote: HAP_NONE)
         if (votes && t.ps_min != t.ps_max) {
             // several phase sets: one walk each, in the order of their numbers; the set with the most votes wins, the earlier first site among equals
             uint32_t best_n = 0, best_first = HAP_NONE, b1 = 0, b2 = 0;
             for (uint32_t cur = t.ps_min; cur != HAP_NONE;) {
                 const HapTally u = hap_walk(R, gl, serial, a, lo, hi, cur);
                 const uint32_t n = u.c1 + u.c2;
-                if (n > best_n || (n == best_n && u.first < best_first)) { best_n = n; best_first = u.first; b1 = u.c1; b2 = u.c2; }
+                if (n > best_n || (n == best_n && u.first < best_first)) { best_n = n; best_first = u.first; b1 = u.c1; b2 = u.c2; set = cur; }
                 cur = u.ps_min;
             }
             t.c1 = b1; t.c2 = b2;
@@ -141,6 +145,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
     if (gl == 0) {
         a.reads[i].hp = (uint8_t)tag;
         a.tags[i] = tag | (votes << 2);
+        a.read_ps[i] = tag ? (int32_t)set : -1;
     }
 }
 

@@ -1,0 +1,163 @@
+"""Phase the FINAL VCF of a phased run and report every call's haplotype support: per-haplotype allele counts on the GPU from the reads
+that the phased VCF haplotags (include/c3r.h: c3r_hap_counts / c3r_hap_assign), without an external tool.
+
+Per contig: the phase table through phasedvcf (exactly what the 30-channel pass reads) -> the candidates of the final VCF
+(phasing.candidates_from_vcf: PASS, biallelic SNV, GT 0/1, first row of a position), each counted against the phase set of the NEAREST
+table site by position (at equal distance the one before; a candidate that is itself a table site gets its own set) ->
+Engine.set_params(min_mq), set_phase_sites, load_reads, hap_counts, hap_assign.  A candidate on which the haplotype-tagged reads agree
+gets GT `0|1` / `1|0` and its set's PS (phasing.phased_row: the row rewrite of phase_vcf); every other row is written byte for byte.  All
+contigs go to one file; an --output_fn that ends in .gz is bgzipped and tabix-indexed.  A contig whose table is empty keeps its rows
+unchanged and has no line in the counts file.  One [INFO] line per contig.
+
+--hap_counts_fn: one tab-separated line per candidate, phased or not — COLUMNS below; PS is the set the reads were counted against, GT
+says whether the candidate was phased in it; HP1 / HP2 / NONE are the reads tagged 1, tagged 2 and the others (untagged, tied, or tagged in
+another set), REF / ALT / OTHER the allele the read shows.
+
+It covers SNVs only and is a majority rule over CIGAR-position alleles: no indels, no multi-allelic or homozygous rows, no realignment, no
+base qualities.  Agreement with `whatshap` has not been measured.
+
+    python -m clair3_rna_amd.hap_vcf --bam_fn x.bam --vcf_fn out/output_enable_phasing.vcf.gz \\
+        --phased_vcf_fn out/tmp/phased_output/phased_vcf --output_fn out/phased.vcf.gz --hap_counts_fn out/hap_counts.tsv
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import io, phasing
+
+COLUMNS = ("#CHROM", "POS", "REF", "ALT", "PS", "GT", "HP1_REF", "HP1_ALT", "HP1_OTHER", "HP2_REF", "HP2_ALT", "HP2_OTHER",
+           "NONE_REF", "NONE_ALT", "NONE_OTHER")
+_LETTER = {1: "A", 2: "C", 4: "G", 8: "T"}
+
+
+def nearest_sets(cands, table):
+    """A copy of the candidate array whose ps is that of the nearest site of `table` (sorted by pos, not empty) by position; at equal distance
+    the site before."""
+    out = np.array(cands, copy=True)
+    tpos = table["pos"].astype(np.int64)
+    pos = out["pos"].astype(np.int64)
+    after = np.searchsorted(tpos, pos, side="left")           # first table site at or behind the candidate
+    before = after - 1
+    a, b = np.clip(after, 0, len(tpos) - 1), np.clip(before, 0, len(tpos) - 1)
+    take_after = (before < 0) | ((after < len(tpos)) & (tpos[a] - pos < pos - tpos[b]))
+    out["ps"] = table["ps"][np.where(take_after, a, b)]
+    out["h1"] = 0
+    return out
+
+
+def counts_lines(contig, cands, assigned, counts):
+    """The counts file's lines for one contig's candidates (query sites, hap_assign's output, (n, 3, 3) counts)."""
+    lines = []
+    for c, o, t in zip(cands, assigned, counts):
+        gt = ("1|0" if int(o["h1"]) else "0|1") if int(o["ps"]) >= 0 else "0/1"
+        lines.append("\t".join([contig, str(int(c["pos"])), _LETTER[int(c["ref"])], _LETTER[int(c["alt"])], str(int(c["ps"])), gt]
+                               + [str(int(t[r][a])) for r in (1, 2, 0) for a in (0, 1, 2)]) + "\n")
+    return lines
+
+
+def write_vcf(in_vcf, assigned_by_contig, out_fn):
+    """Every row of `in_vcf` to `out_fn` (a name that ends in .gz: bgzip + tabix): the rows of the sites of {contig: hap_assign's output} with
+    ps >= 0 rewritten by phasing.phased_row, every other row byte for byte, the PS header line added unless present.  Returns the number
+    of rows rewritten."""
+    from .io import _open_text
+    phased = {c: {int(s["pos"]): s for s in a if int(s["ps"]) >= 0} for c, a in assigned_by_contig.items()}
+    plain = out_fn[:-3] if out_fn.endswith(".gz") else out_fn
+    n, has_ps = 0, False
+    with _open_text(in_vcf) as f, open(plain, "w") as out:
+        for line in f:
+            if line.startswith("#"):
+                text, has_ps = phasing.header_row(line, has_ps)
+                out.write(text)
+                continue
+            f_ = line.rstrip("\r\n").split("\t")
+            table = phased.get(f_[0])
+            if not table:
+                out.write(line)
+                continue
+            text, done = phasing.phased_row(line, f_, table)
+            out.write(text)
+            n += int(done)
+    if plain != out_fn:
+        from . import sort_vcf
+        sort_vcf.compress_vcf(plain)
+    return n
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Phase the heterozygous SNVs of the final VCF of a phased run from per-haplotype allele counts on MI355X, and report the counts")
+    a = p.add_argument
+    a("-b", "--bam_fn", type=str, required=True, help="the BAM (or flat read archive .npz) the VCF was called from")
+    a("--vcf_fn", type=str, required=True, help="the VCF to phase (<prefix>_enable_phasing.vcf.gz), plain or gzipped")
+    a("--phased_vcf_fn", type=str, required=True,
+      help="what the 30-channel pass read: one phased VCF for all contigs, or a directory that holds phased_<ctg>.vcf.gz")
+    a("-o", "--output_fn", type=str, required=True, help="the phased VCF, all contigs; a name that ends in .gz is bgzipped and tabix-indexed")
+    a("--hap_counts_fn", type=str, default=None, help="receives one line of per-haplotype allele counts per candidate")
+    a("-c", "--ctg_name", type=str, default=None, help="contigs to phase, comma-separated; default: every contig of the VCF (the others' rows are copied)")
+    a("--min_mq", type=int, default=5, help="reads below it are not counted (the tensor build's filter)")
+    a("--min_reads", type=int, default=2, help="fewest haplotype-tagged observations that phase a candidate")
+    a("--min_agree_pct", type=int, default=75, help="fewest per cent of them that agree on the orientation")
+    a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
+    return p
+
+
+def Run(args, log=None):
+    from . import capi, phasedvcf
+    log = log or (lambda m: print(m, file=sys.stderr))
+    for need in (args.bam_fn, args.vcf_fn):
+        if not os.path.isfile(need):
+            sys.exit("[ERROR] file %s not found" % need)
+    if not os.path.exists(args.phased_vcf_fn):
+        sys.exit("[ERROR] file %s not found" % args.phased_vcf_fn)
+    if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
+        sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
+    per = phasing.candidates_from_vcf(args.vcf_fn, None)
+    contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
+    tables = None if os.path.isdir(args.phased_vcf_fn) else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
+    gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
+    eng = None
+    assigned, lines = {}, ["\t".join(COLUMNS) + "\n"]
+    try:
+        for ctg in contigs:
+            cands, skipped = per.get(ctg, (None, None))
+            if tables is None:
+                table = phasedvcf.contig_sites(args.phased_vcf_fn, ctg)
+            else:
+                table = tables[ctg][0] if ctg in tables else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
+            if cands is None or not len(cands) or not len(table):
+                log("[INFO] %s: %d phased sites in the table, %d heterozygous SNV candidates: rows copied unchanged"
+                    % (ctg, len(table), 0 if cands is None else len(cands)))
+                continue
+            if eng is None:
+                eng = capi.Engine(gpu_id)
+                eng.set_params(min_mq=args.min_mq)
+            query = nearest_sets(cands, table)
+            rs = io.load_reads(args.bam_fn, ctg)
+            eng.set_phase_sites(table)
+            eng.load_reads(rs)
+            counts = eng.hap_counts(query)
+            out, st = capi.hap_assign(query, counts, args.min_reads, args.min_agree_pct)
+            assigned[ctg] = out
+            lines += counts_lines(ctg, query, out, counts)
+            log("[INFO] %s: %d reads, %d phased sites in %d sets, %d candidate sites (%s), %d phased, %d with too few tagged reads, %d without agreement -> %s"
+                % (ctg, len(rs), len(table), len(set(table["ps"].tolist())), st["n_sites"],
+                   ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
+                   st["n_phased"], st["n_few_reads"], st["n_disagree"], args.output_fn))
+    finally:
+        if eng is not None:
+            eng.close()
+    n = write_vcf(args.vcf_fn, assigned, args.output_fn)
+    if args.hap_counts_fn:
+        with open(args.hap_counts_fn, "w") as f:
+            f.writelines(lines)
+    return n
+
+
+def main(argv=None):
+    Run(build_parser().parse_args(argv))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -85,37 +85,53 @@ def phased_only(sites_out):
     return np.ascontiguousarray(sites_out[sites_out["ps"] >= 0])
 
 
+def header_row(line, has_ps):
+    """A header line of a VCF that is being phased -> (text to write, has_ps): the ##FORMAT line for PS goes before the #CHROM line unless the
+    header has one."""
+    has_ps = has_ps or line.startswith("##FORMAT=<ID=PS,")
+    if line.startswith("#CHROM") and not has_ps:
+        return PS_HEADER + line, has_ps
+    return line, has_ps
+
+
+def phased_row(line, f_, phased):
+    """One data row (`f_`: its tab-separated fields) -> (text to write, rewritten): the first row on the position of a site of `phased`
+    ({pos: site with ps >= 0}) whose REF and ALT are that site's, FILTER PASS and GT `0/1` or `1/0`, gets GT `0|1` / `1|0`, a PS key appended
+    to FORMAT and its value appended to the sample column, and the site leaves `phased` (a later row on the position stays as it is); every
+    other row comes back byte for byte."""
+    s = phased.get(int(f_[1])) if len(f_) >= 10 and f_[1].isdigit() else None
+    keys = f_[8].split(":") if s is not None else []
+    if (s is None or "GT" not in keys or "PS" in keys or f_[6] != "PASS" or BASE_CODE.get(f_[3].upper()) != int(s["ref"])
+            or BASE_CODE.get(f_[4].upper()) != int(s["alt"])):
+        return line, False
+    vals = f_[9].split(":")
+    if keys.index("GT") >= len(vals) or vals[keys.index("GT")] not in ("0/1", "1/0"):
+        return line, False
+    vals[keys.index("GT")] = "1|0" if int(s["h1"]) else "0|1"
+    f_ = list(f_)
+    f_[8], f_[9] = f_[8] + ":PS", ":".join(vals) + ":%d" % int(s["ps"])
+    del phased[int(f_[1])]
+    return "\t".join(f_) + line[len(line.rstrip("\r\n")):], True
+
+
 def write_phased_vcf(in_vcf, contig, sites_out, out_fn):
     """Write `contig`'s rows of the first pass's VCF `in_vcf` to the gzipped VCF `out_fn`: the first row on the position of a phased site
     (Engine.phase_sites: ps >= 0) whose REF and ALT are that site's gets GT `0|1` / `1|0`, a PS key appended to FORMAT and its value
     appended to the sample column; every other row is written byte for byte as it was.  The header gets a ##FORMAT line for PS before
-    the #CHROM line unless it has one.  Returns the number of rows rewritten."""
+    the #CHROM line unless it has one.  Returns the number of rows rewritten.  (The per-row part is header_row / phased_row, which
+    hap_vcf's writer shares.)"""
     phased = {int(s["pos"]): s for s in sites_out if int(s["ps"]) >= 0}
     n, has_ps = 0, False
     with _open_text(in_vcf) as f, gzip.open(out_fn, "wt") as out:
         for line in f:
             if line.startswith("#"):
-                has_ps = has_ps or line.startswith("##FORMAT=<ID=PS,")
-                if line.startswith("#CHROM") and not has_ps:
-                    out.write(PS_HEADER)
-                out.write(line)
+                text, has_ps = header_row(line, has_ps)
+                out.write(text)
                 continue
             f_ = line.rstrip("\r\n").split("\t")
             if f_[0] != contig:
                 continue
-            s = phased.get(int(f_[1])) if len(f_) >= 10 and f_[1].isdigit() else None
-            keys = f_[8].split(":") if s is not None else []
-            if (s is None or "GT" not in keys or "PS" in keys or f_[6] != "PASS" or BASE_CODE.get(f_[3].upper()) != int(s["ref"])
-                    or BASE_CODE.get(f_[4].upper()) != int(s["alt"])):
-                out.write(line)
-                continue
-            vals = f_[9].split(":")
-            if keys.index("GT") >= len(vals) or vals[keys.index("GT")] not in ("0/1", "1/0"):
-                out.write(line)
-                continue
-            vals[keys.index("GT")] = "1|0" if int(s["h1"]) else "0|1"
-            f_[8], f_[9] = f_[8] + ":PS", ":".join(vals) + ":%d" % int(s["ps"])
-            out.write("\t".join(f_) + line[len(line.rstrip("\r\n")):])
-            del phased[int(f_[1])]                          # (a later row on the position stays as it is)
-            n += 1
+            text, done = phased_row(line, f_, phased)
+            out.write(text)
+            n += int(done)
     return n

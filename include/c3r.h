@@ -115,6 +115,38 @@ int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n);
 /* The tags of the loaded reads, in load order (hp: [cap], cap >= the number of loaded reads; may be NULL), and their statistics (may be
  * NULL).  C3R_EINVAL when no phase sites are set. */
 int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats_t *stats);
+/* The phase set every loaded read's tag was decided in, in load order (ps: [cap], cap >= the number of loaded reads): the ps of the set the
+ * rule above picks — most votes, equal: the earlier first voting site — and -1 for a read whose tag is 0 (no vote, or a tie).  k_haplotag
+ * stores it beside the tag, so it follows the table like the tags do.  C3R_EINVAL when no phase sites are set. */
+int c3r_get_read_phase_sets(c3r_ctx *ctx, int32_t *ps, int64_t cap);
+/* Per-haplotype allele counts at called sites, and the phase of a heterozygous call from them: what phases the FINAL VCF once the reads are
+ * tagged, and, written out, the haplotype support of every call.  SNVs only; a majority rule over CIGAR-position alleles (no realignment,
+ * no base qualities).
+ *
+ * Query sites (c3r_hap_counts): sorted by strictly increasing pos; ref and alt are valid; ps >= 0 is the phase set to count against; h1 is
+ * ignored; validated as in c3r_set_phase_sites (except h1), naming the first bad index.
+ * Voters: as for c3r_phase_links — the loaded reads that the tensor build keeps under the current parameters (read_kept), without the
+ * depth cap: the counts describe the reads the caller sees.
+ * Observation: as in c3r_set_phase_sites — a site under an M / = / X op at a query offset below l_seq; a = 0 when the read's base there is
+ * the site's ref, 1 when it is alt, 2 when it is another one of the codes 1, 2, 4, 8; nothing for any other code (=, N, IUPAC).
+ * Row: t = the read's tag (1 or 2) when the read's phase set (c3r_get_read_phase_sets) equals the site's ps, else t = 0 — untagged reads,
+ * ties and reads tagged in another set.
+ * Counts: every observation adds one to counts[j][t][a], uint32 [n][3][3].  All sums are integers: neither read order nor arrival order
+ * shows.
+ * Assignment (c3r_hap_assign), per site: v1 = counts[j][1][1] + counts[j][2][0] (ALT on haplotype-1 reads, REF on haplotype-2 reads),
+ * v0 = counts[j][1][0] + counts[j][2][1], w = v0 + v1.  The site is accepted iff w >= min_reads, v0 != v1 and
+ * 100 max(v0, v1) >= min_agree_pct w — the agreement test of c3r_phase_resolve, in 64-bit products.  Accepted: ps = the query's ps,
+ * h1 = (v1 > v0).  Otherwise ps = -1, h1 = 0.  The t = 0 row and the a = 2 column never enter the decision: they are reported, not used.
+ *
+ * c3r_hap_counts needs a phase table (C3R_EINVAL without one, whatever n is); no reads loaded: every count is 0; n = 0 succeeds and launches
+ * nothing.  It uploads the sites, clears a device table, runs k_hap_counts (csrc/hapcount_kernels.hpp) on the context's stream and reads
+ * the table back (36 n bytes).  It changes neither the reads' haplotags, nor the table of c3r_set_phase_sites, nor anything a scan reads.
+ * Its device buffers are allocated at the first call and kept.
+ * c3r_hap_assign is host code like c3r_phase_resolve: no context, no device.  p = NULL: the defaults (2, 75).  C3R_EINVAL for
+ * min_reads < 0 or min_agree_pct outside 0 .. 100.  stats may be NULL.  out may be `in`. */
+int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *counts);
+int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts, const c3r_phase_params_t *p, c3r_phase_site_t *out,
+                   c3r_hap_assign_stats_t *stats);
 /* Phasing on the device from read linkage: what stands where `whatshap phase` / `longphase phase` stand in the reference flow
  * (run_clair3_rna:729-767), in two steps.  It is a GREEDY LINKAGE CHAIN, not whatshap's wMEC: every heterozygous SNV gets a block and an
  * orientation from the reads that cover it together with one of the K = C3R_PHASE_LINKS sites before it, once, in table order.

@@ -156,6 +156,14 @@ typedef struct c3r_phase_stats {
     int64_t max_block;      /* sites of the largest block (0: no site; 1: singletons only)                             */
 } c3r_phase_stats_t;
 
+/* What c3r_hap_assign came to.  n_sites = n_phased + n_few_reads + n_disagree. */
+typedef struct c3r_hap_assign_stats {
+    int64_t n_sites;        /* sites in the table                                                                      */
+    int64_t n_phased;       /* accepted: ps and h1 on output                                                           */
+    int64_t n_few_reads;    /* w < min_reads                                                                           */
+    int64_t n_disagree;     /* enough reads, but v0 == v1 or the majority below min_agree_pct                          */
+} c3r_hap_assign_stats_t;
+
 #ifdef __cplusplus
 }
 #endif
