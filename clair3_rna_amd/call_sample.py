@@ -33,6 +33,8 @@ only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line
 `--phase_output` (with --enable_phasing_model and --phased_vcf_fn or --phasing builtin; one process only) adds a step behind the phased pass:
 hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU into
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
+`--phase_indels` (with --phase_output) hands hap_vcf --indels: heterozygous insertions, deletions and rows with two ALT alleles are phased too,
+by CIGAR-position alleles (no realignment, no left-alignment, no base qualities); without it both files are what they were.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
@@ -163,6 +165,10 @@ def build_parser():
            "<prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU (hap_vcf: SNVs only, a majority rule over CIGAR-position "
            "alleles) into <prefix>_enable_phasing_phased.vcf.gz and write the counts to <prefix>_enable_phasing_hap_counts.tsv.  One process only "
            "(not under torch.distributed.run)")
+    a("--phase_indels", action="store_true",
+      help="with --phase_output: handed to hap_vcf as --indels — heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2) are "
+           "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels, no base qualities), and the counts "
+           "file gets the column ALLELES")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
     a("--genotyping_mode_vcf_fn", type=str, default=None)
@@ -328,6 +334,8 @@ def Run(args, log=None):
     """The passes (_run_flow), and with `--phase_output` one further step behind them: hap_vcf on the phased pass's VCF — nothing inside a
     pass changes."""
     if not getattr(args, "phase_output", False):
+        if getattr(args, "phase_indels", False):
+            sys.exit("[ERROR] --phase_indels belongs to --phase_output (it phases the indels of the final VCF): it needs --phase_output")
         return _run_flow(args, log)
     from . import hap_vcf
     builtin = getattr(args, "phasing", None) is not None
@@ -348,7 +356,7 @@ def Run(args, log=None):
     source = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf") if builtin else args.phased_vcf_fn
     hap_vcf.Run(hap_vcf.build_parser().parse_args(
         ["--bam_fn", _indexed_bam(args), "--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext,
-         "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)]
+         "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if getattr(args, "phase_indels", False) else [])
         + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
     return rc
 

@@ -17,7 +17,14 @@ TOKEN_DTYPE = np.dtype([("read_idx", "<u4"), ("indel", "<i4"), ("qpos", "<u4"), 
 PADINS_DTYPE = np.dtype([("read_idx", "<u4"), ("qpos", "<u4"), ("n_bases", "<u4"), ("total", "<u4"), ("pad_mask", "<u8")], align=True)
 # c3r_phase_site_t: one phased heterozygous SNV (phasedvcf.read_phase_sites); ref / alt are BAM 4-bit base codes (A 1, C 2, G 4, T 8)
 PHASE_SITE_DTYPE = np.dtype([("pos", "<i4"), ("ps", "<i4"), ("ref", "u1"), ("alt", "u1"), ("h1", "u1"), ("reserved", "u1")], align=True)
+# c3r_hap_site_t: one heterozygous call with its two alleles (phasing.allele_candidates_from_vcf): per allele the anchor base's code, the
+# event behind it (HAP_EV_*), its length and, for an insertion, the offset of its bases in the pool of inserted bases
+HAP_EV_NONE, HAP_EV_INS, HAP_EV_DEL = 0, 1, 2
+HAP_SITE_DTYPE = np.dtype([("pos", "<i4"), ("ps", "<i4"), ("base_matters", "u1"), ("event_matters", "u1"), ("reserved", "u1", (6,)),
+                           ("a_base", "u1"), ("a_kind", "u1"), ("a_len", "<u2"), ("a_ins_off", "<u4"),
+                           ("b_base", "u1"), ("b_kind", "u1"), ("b_len", "<u2"), ("b_ins_off", "<u4")], align=True)
 assert SITE_DTYPE.itemsize == 52 and TOKEN_DTYPE.itemsize == 16 and PADINS_DTYPE.itemsize == 24 and PHASE_SITE_DTYPE.itemsize == 12
+assert HAP_SITE_DTYPE.itemsize == 32 and HAP_SITE_DTYPE.fields["a_base"][1] == 16 and HAP_SITE_DTYPE.fields["b_ins_off"][1] == 28
 
 C3R_ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EUNSUPPORTED", -6: "EOVERFLOW"}
 
@@ -59,7 +66,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
-           "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign"]
+           "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
+           "c3r_hap_allele_counts"]
 
 _lib = None
 
@@ -105,6 +113,7 @@ def load_library():
     L.c3r_phase_merge.argtypes = [vp, i64, vp, i64, C.POINTER(PhaseParams), vp, C.POINTER(PhaseStats), C.POINTER(i64)]
     L.c3r_get_read_phase_sets.argtypes = [vp, vp, i64]
     L.c3r_hap_counts.argtypes = [vp, vp, i64, vp]
+    L.c3r_hap_allele_counts.argtypes = [vp, vp, i64, vp, i64, vp]
     L.c3r_hap_assign.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(HapAssignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
@@ -304,6 +313,22 @@ class Engine(object):
         a = _phase_site_array(sites)
         counts = np.zeros((len(a), 3, 3), dtype=np.uint32)
         self._chk(self.L.c3r_hap_counts(self.h, _ptr(a), len(a), _ptr(counts)))
+        return counts
+
+    def hap_allele_counts(self, sites, ins_pool=None):
+        """uint32 (n, 3, 3) like hap_counts, for query sites whose two alleles may be SNVs, insertions or deletions (a HAP_SITE_DTYPE array
+        sorted by pos; `ins_pool`: the packed pool of the insertions' bases, uint8 with two codes to a byte as a read's SEQ has them —
+        pack_nibbles — or None when no allele is an insertion): columns — allele A, allele B, anything else (c3r_hap_allele_counts).  Needs a
+        table; leaves tags, table and scans as they are."""
+        a = np.zeros(0, HAP_SITE_DTYPE) if sites is None else np.asarray(sites)
+        if a.dtype != HAP_SITE_DTYPE:
+            raise TypeError("sites must be a capi.HAP_SITE_DTYPE array, got %r" % (a.dtype,))
+        a = np.ascontiguousarray(a)
+        pool = np.zeros(0, np.uint8) if ins_pool is None else np.ascontiguousarray(ins_pool)
+        if pool.dtype != np.uint8 or pool.ndim != 1:
+            raise TypeError("ins_pool must be a one-dimensional uint8 array of packed bases (capi.pack_nibbles)")
+        counts = np.zeros((len(a), 3, 3), dtype=np.uint32)
+        self._chk(self.L.c3r_hap_allele_counts(self.h, _ptr(a), len(a), _ptr(pool) if len(pool) else None, 2 * len(pool), _ptr(counts)))
         return counts
 
     def phase_links(self, sites):
@@ -526,6 +551,33 @@ class Engine(object):
         n = C.c_int(0)
         self._chk(self.L.c3r_get_kernel_stats(self.h, names, ms, cnt, cap, C.byref(n)))
         return {names[i].decode(): dict(total_ms=ms[i], launches=cnt[i]) for i in range(min(n.value, cap))}
+
+
+def pack_nibbles(codes):
+    """4-bit codes, one per element -> uint8 array with two to a byte, the first in the high nibble, as a read's SEQ is packed (an odd
+    number: the last low nibble is 0)."""
+    c = np.zeros(0, np.uint8) if codes is None else np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1)
+    if len(c) and int(c.max()) > 15:
+        raise ValueError("4-bit codes must be 0 .. 15")
+    padded = np.concatenate([c, np.zeros(len(c) % 2, np.uint8)])
+    return np.ascontiguousarray((padded[0::2] << 4) | padded[1::2])
+
+
+def hap_sites_from_snvs(sites):
+    """PHASE_SITE_DTYPE query sites (c3r_hap_counts) -> the same query as a HAP_SITE_DTYPE array (c3r_hap_allele_counts): allele A = (ref, no
+    event), allele B = (alt, no event), the base matters and events do not."""
+    a = _phase_site_array(sites)
+    out = np.zeros(len(a), dtype=HAP_SITE_DTYPE)
+    out["pos"], out["ps"], out["base_matters"], out["a_base"], out["b_base"] = a["pos"], a["ps"], 1, a["ref"], a["alt"]
+    return out
+
+
+def hap_site_keys(sites):
+    """HAP_SITE_DTYPE array -> PHASE_SITE_DTYPE array with its pos and ps and placeholder bases (A, C): what hap_assign takes — its rule
+    reads the counts, pos and ps only, with allele A in the place of REF and allele B in the place of ALT."""
+    out = np.zeros(len(sites), dtype=PHASE_SITE_DTYPE)
+    out["pos"], out["ps"], out["ref"], out["alt"] = sites["pos"], sites["ps"], 1, 2
+    return out
 
 
 def _phase_site_array(sites):

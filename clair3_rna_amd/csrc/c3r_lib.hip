@@ -162,6 +162,7 @@ struct c3r_ctx {
     DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
     DevBuf d_hcsites, d_hcounts;
+    DevBuf d_hasites, d_hapool;               // c3r_hap_allele_counts: its query sites and the pool of inserted bases (the counts share d_hcounts)
 
     // ---- scan state
     int32_t reg_beg0 = 0, reg_end0 = 0;   // first region of the most recent scan (c3r_get_columns)
@@ -730,7 +731,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1192,6 +1193,61 @@ int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint3
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_hcounts.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's site array may go once this returns, and the table is there)
+    return C3R_OK;
+}
+
+int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts) {
+    if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !counts)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
+    if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many query sites");
+    auto base = [](uint8_t c) { return c == 1 || c == 2 || c == 4 || c == 8; };
+    auto pool_at = [&](uint64_t q) { const uint8_t byte = ins_pool[q >> 1]; return (uint8_t)((q & 1) ? (byte & 15) : (byte >> 4)); };
+    for (int64_t i = 0; i < n; ++i) {
+        const c3r_hap_site_t &e = sites[i];
+        if (e.pos < 1) return fail(ctx, C3R_EINVAL, "query site %lld: pos %d is not a 1-based position", (long long)i, e.pos);
+        if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "query site %lld: positions must be strictly increasing (%d after %d)", (long long)i, e.pos, sites[i - 1].pos);
+        if (e.ps < 0) return fail(ctx, C3R_EINVAL, "query site %lld: phase set %d is negative", (long long)i, e.ps);
+        if (e.base_matters > 1 || e.event_matters > 1) return fail(ctx, C3R_EINVAL, "query site %lld: base_matters / event_matters must be 0 or 1", (long long)i);
+        for (const c3r_hap_allele_t *al : {&e.a, &e.b}) {
+            const char which = al == &e.a ? 'A' : 'B';
+            if (!base(al->base)) return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: the base must be a code 1, 2, 4 or 8 (got %d)", (long long)i, which, al->base);
+            if (al->kind > C3R_HAP_EV_DEL) return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: unknown kind %d", (long long)i, which, al->kind);
+            if (al->kind == C3R_HAP_EV_NONE ? al->len != 0 : al->len == 0)
+                return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: an insertion or deletion has a length of 1 or more, any other allele 0 (got %d)", (long long)i, which, al->len);
+            if (al->kind == C3R_HAP_EV_INS) {
+                if ((int64_t)al->ins_off + al->len > pool_bases)
+                    return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: the insertion (%u + %d bases) runs past the pool of %lld bases", (long long)i, which, al->ins_off, al->len, (long long)pool_bases);
+                for (uint32_t j = 0; j < al->len; ++j)
+                    if (!base(pool_at((uint64_t)al->ins_off + j)))
+                        return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: inserted base %u must be a code 1, 2, 4 or 8 (got %d)", (long long)i, which, j, pool_at((uint64_t)al->ins_off + j));
+            }
+        }
+        bool same = e.a.base == e.b.base && e.a.kind == e.b.kind && e.a.len == e.b.len;
+        if (same && e.a.kind == C3R_HAP_EV_INS)
+            for (uint32_t j = 0; j < e.a.len && same; ++j) same = pool_at((uint64_t)e.a.ins_off + j) == pool_at((uint64_t)e.b.ins_off + j);
+        if (same) return fail(ctx, C3R_EINVAL, "query site %lld: the two alleles are the same", (long long)i);
+    }
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads carry no tags to count by");
+    if (n == 0) return C3R_OK;
+    const size_t words = (size_t)n * 9;
+    if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->d_hasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_hapool, ins_pool, (size_t)((pool_bases + 1) / 2))) ||
+        (rc = ensure(ctx, ctx->d_hcounts, words * 4))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_hcounts.p, 0, words * 4, ctx->stream));
+    HapAlleleArgs a;
+    memset(&a, 0, sizeof a);
+    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
+    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_hapool.p;
+    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.counts = (uint32_t *)ctx->d_hcounts.p;
+    {
+        Launch L(ctx, "k_hap_allele_counts");
+        hipLaunchKernelGGL(k_hap_allele_counts, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_hcounts.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's arrays may go once this returns, and the table is there)
     return C3R_OK;
 }
 

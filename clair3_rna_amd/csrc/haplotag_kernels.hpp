@@ -37,8 +37,9 @@ struct HapArgs {
     int32_t *read_ps;                         // [n_reads] the phase set the tag was decided in, -1 when the tag is 0
 };
 
-// first site of [lo, hi) with pos >= p (hi: none)
-__device__ __forceinline__ int hap_lower(const c3r_phase_site_t *sites, int lo, int hi, long long p) {
+// first site of [lo, hi) with pos >= p (hi: none).  Site: any record with a `pos` (c3r_phase_site_t; c3r_hap_site_t in hapcount_kernels.hpp)
+template <class Site>
+__device__ __forceinline__ int hap_lower(const Site *sites, int lo, int hi, long long p) {
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         if ((long long)sites[mid].pos < p) lo = mid + 1; else hi = mid;
@@ -48,7 +49,8 @@ __device__ __forceinline__ int hap_lower(const c3r_phase_site_t *sites, int lo, 
 
 // The same search by the 16 lanes of a read together: sixteen probes a round and a seventeenth of the candidates left after it (64 k sites:
 // four dependent loads where hap_lower takes sixteen).  All lanes of the group call it, with the same arguments, and all return the index.
-__device__ __forceinline__ int hap_lower_group(const c3r_phase_site_t *sites, int lo, int hi, long long p, int gl) {
+template <class Site>
+__device__ __forceinline__ int hap_lower_group(const Site *sites, int lo, int hi, long long p, int gl) {
     const int shift = (int)(threadIdx.x & 63u) & ~(PREP_GRP - 1);              // where the group's lanes lie in the wavefront's ballot
     while (lo < hi) {
         const long long span = hi - lo;                                         // pivot g = lo + (g + 1) * span / 17: in [lo, hi), never decreasing with g

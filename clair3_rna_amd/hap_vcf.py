@@ -13,8 +13,16 @@ unchanged and has no line in the counts file.  One [INFO] line per contig.
 says whether the candidate was phased in it; HP1 / HP2 / NONE are the reads tagged 1, tagged 2 and the others (untagged, tied, or tagged in
 another set), REF / ALT / OTHER the allele the read shows.
 
-It covers SNVs only and is a majority rule over CIGAR-position alleles: no indels, no multi-allelic or homozygous rows, no realignment, no
-base qualities.  Agreement with `whatshap` has not been measured.
+By default it covers SNVs only and is a majority rule over CIGAR-position alleles: no indels, no multi-allelic or homozygous rows, no
+realignment, no base qualities.  Agreement with `whatshap` has not been measured.
+
+--indels (off by default, like `whatshap phase --indels`): the candidates are phasing.allele_candidates_from_vcf's — heterozygous rows whose
+alleles are SNVs, insertions or deletions, GT `0/1` with one ALT or `1/2` with two (`C  T,CGG`, `ACC  A,TCC`) — counted by
+Engine.hap_allele_counts (include/c3r.h: c3r_hap_allele_counts) and written as `0|1` / `1|0` / `1|2` / `2|1`.  The nearest-set rule and the
+assignment are the same.  The counts file's REF / ALT columns then hold the row's strings, its REF / ALT count columns stand for allele A /
+allele B, and one more column ALLELES says which they are: `0,1` or `1,2`.  The alleles are read off the CIGAR position: no realignment, no
+left-alignment of the reads' indels, no base qualities; a homozygous row or one with three or more ALTs stays as it is.  Agreement with
+`whatshap --indels` has not been measured.  Without --indels both files are what they were.
 
     python -m clair3_rna_amd.hap_vcf --bam_fn x.bam --vcf_fn out/output_enable_phasing.vcf.gz \\
         --phased_vcf_fn out/tmp/phased_output/phased_vcf --output_fn out/phased.vcf.gz --hap_counts_fn out/hap_counts.tsv
@@ -29,12 +37,13 @@ from . import io, phasing
 
 COLUMNS = ("#CHROM", "POS", "REF", "ALT", "PS", "GT", "HP1_REF", "HP1_ALT", "HP1_OTHER", "HP2_REF", "HP2_ALT", "HP2_OTHER",
            "NONE_REF", "NONE_ALT", "NONE_OTHER")
+ALLELE_COLUMNS = COLUMNS + ("ALLELES",)                     # --indels
 _LETTER = {1: "A", 2: "C", 4: "G", 8: "T"}
 
 
 def nearest_sets(cands, table):
-    """A copy of the candidate array whose ps is that of the nearest site of `table` (sorted by pos, not empty) by position; at equal distance
-    the site before."""
+    """A copy of the candidate array (PHASE_SITE_DTYPE or HAP_SITE_DTYPE) whose ps is that of the nearest site of `table` (sorted by pos, not
+    empty) by position; at equal distance the site before."""
     out = np.array(cands, copy=True)
     tpos = table["pos"].astype(np.int64)
     pos = out["pos"].astype(np.int64)
@@ -43,7 +52,8 @@ def nearest_sets(cands, table):
     a, b = np.clip(after, 0, len(tpos) - 1), np.clip(before, 0, len(tpos) - 1)
     take_after = (before < 0) | ((after < len(tpos)) & (tpos[a] - pos < pos - tpos[b]))
     out["ps"] = table["ps"][np.where(take_after, a, b)]
-    out["h1"] = 0
+    if "h1" in out.dtype.names:
+        out["h1"] = 0
     return out
 
 
@@ -57,12 +67,30 @@ def counts_lines(contig, cands, assigned, counts):
     return lines
 
 
-def write_vcf(in_vcf, assigned_by_contig, out_fn):
+def allele_counts_lines(contig, cands, strings, assigned, counts):
+    """counts_lines under --indels: candidates of phasing.allele_candidates_from_vcf (query sites and their rows' (REF, ALT) strings),
+    hap_assign's output, (n, 3, 3) counts."""
+    lines = []
+    for c, (ref, alt), o, t in zip(cands, strings, assigned, counts):
+        a, b = ("1", "2") if "," in alt else ("0", "1")
+        gt = (b + "|" + a if int(o["h1"]) else a + "|" + b) if int(o["ps"]) >= 0 else a + "/" + b
+        lines.append("\t".join([contig, str(int(c["pos"])), ref, alt, str(int(c["ps"])), gt]
+                               + [str(int(t[r][k])) for r in (1, 2, 0) for k in (0, 1, 2)] + [a + "," + b]) + "\n")
+    return lines
+
+
+def write_vcf(in_vcf, assigned_by_contig, out_fn, strings_by_contig=None):
     """Every row of `in_vcf` to `out_fn` (a name that ends in .gz: bgzip + tabix): the rows of the sites of {contig: hap_assign's output} with
     ps >= 0 rewritten by phasing.phased_row, every other row byte for byte, the PS header line added unless present.  Returns the number
-    of rows rewritten."""
+    of rows rewritten.  strings_by_contig ({contig: [(REF, ALT)] beside the sites}, --indels): phasing.allele_phased_row rewrites them."""
     from .io import _open_text
-    phased = {c: {int(s["pos"]): s for s in a if int(s["ps"]) >= 0} for c, a in assigned_by_contig.items()}
+    if strings_by_contig is None:
+        phased = {c: {int(s["pos"]): s for s in a if int(s["ps"]) >= 0} for c, a in assigned_by_contig.items()}
+        rewrite = phasing.phased_row
+    else:
+        phased = {c: {int(s["pos"]): (ref, alt, int(s["ps"]), int(s["h1"])) for s, (ref, alt) in zip(a, strings_by_contig[c]) if int(s["ps"]) >= 0}
+                  for c, a in assigned_by_contig.items()}
+        rewrite = phasing.allele_phased_row
     plain = out_fn[:-3] if out_fn.endswith(".gz") else out_fn
     n, has_ps = 0, False
     with _open_text(in_vcf) as f, open(plain, "w") as out:
@@ -76,7 +104,7 @@ def write_vcf(in_vcf, assigned_by_contig, out_fn):
             if not table:
                 out.write(line)
                 continue
-            text, done = phasing.phased_row(line, f_, table)
+            text, done = rewrite(line, f_, table)
             out.write(text)
             n += int(done)
     if plain != out_fn:
@@ -98,6 +126,9 @@ def build_parser():
     a("--min_mq", type=int, default=5, help="reads below it are not counted (the tensor build's filter)")
     a("--min_reads", type=int, default=2, help="fewest haplotype-tagged observations that phase a candidate")
     a("--min_agree_pct", type=int, default=75, help="fewest per cent of them that agree on the orientation")
+    a("--indels", action="store_true",
+      help="also phase heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2), by CIGAR-position alleles: no realignment, no "
+           "left-alignment, no base qualities; the counts file gets the column ALLELES.  Off: SNVs only, both files as they were")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 
@@ -112,22 +143,23 @@ def Run(args, log=None):
         sys.exit("[ERROR] file %s not found" % args.phased_vcf_fn)
     if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
         sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
-    per = phasing.candidates_from_vcf(args.vcf_fn, None)
+    indels = bool(getattr(args, "indels", False))
+    per = phasing.allele_candidates_from_vcf(args.vcf_fn, None) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
     tables = None if os.path.isdir(args.phased_vcf_fn) else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
     eng = None
-    assigned, lines = {}, ["\t".join(COLUMNS) + "\n"]
+    assigned, strings, lines = {}, {}, ["\t".join(ALLELE_COLUMNS if indels else COLUMNS) + "\n"]
     try:
         for ctg in contigs:
-            cands, skipped = per.get(ctg, (None, None))
+            cands, skipped = (per[ctg][0], per[ctg][-1]) if ctg in per else (None, None)
             if tables is None:
                 table = phasedvcf.contig_sites(args.phased_vcf_fn, ctg)
             else:
                 table = tables[ctg][0] if ctg in tables else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
             if cands is None or not len(cands) or not len(table):
-                log("[INFO] %s: %d phased sites in the table, %d heterozygous SNV candidates: rows copied unchanged"
-                    % (ctg, len(table), 0 if cands is None else len(cands)))
+                log("[INFO] %s: %d phased sites in the table, %d heterozygous %s candidates: rows copied unchanged"
+                    % (ctg, len(table), 0 if cands is None else len(cands), "SNV / indel / two-ALT" if indels else "SNV"))
                 continue
             if eng is None:
                 eng = capi.Engine(gpu_id)
@@ -136,10 +168,16 @@ def Run(args, log=None):
             rs = io.load_reads(args.bam_fn, ctg)
             eng.set_phase_sites(table)
             eng.load_reads(rs)
-            counts = eng.hap_counts(query)
-            out, st = capi.hap_assign(query, counts, args.min_reads, args.min_agree_pct)
+            if indels:
+                counts = eng.hap_allele_counts(query, per[ctg][1])
+                out, st = capi.hap_assign(capi.hap_site_keys(query), counts, args.min_reads, args.min_agree_pct)
+                strings[ctg] = per[ctg][2]
+                lines += allele_counts_lines(ctg, query, strings[ctg], out, counts)
+            else:
+                counts = eng.hap_counts(query)
+                out, st = capi.hap_assign(query, counts, args.min_reads, args.min_agree_pct)
+                lines += counts_lines(ctg, query, out, counts)
             assigned[ctg] = out
-            lines += counts_lines(ctg, query, out, counts)
             log("[INFO] %s: %d reads, %d phased sites in %d sets, %d candidate sites (%s), %d phased, %d with too few tagged reads, %d without agreement -> %s"
                 % (ctg, len(rs), len(table), len(set(table["ps"].tolist())), st["n_sites"],
                    ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
@@ -147,7 +185,7 @@ def Run(args, log=None):
     finally:
         if eng is not None:
             eng.close()
-    n = write_vcf(args.vcf_fn, assigned, args.output_fn)
+    n = write_vcf(args.vcf_fn, assigned, args.output_fn, strings if indels else None)
     if args.hap_counts_fn:
         with open(args.hap_counts_fn, "w") as f:
             f.writelines(lines)

@@ -6,16 +6,22 @@ The rule is a greedy linkage chain over the reads that cover two heterozygous SN
 not been measured.
 
 candidates_from_vcf keeps a row when FILTER is PASS, REF and ALT are single letters of ACGT and the first sample's GT is `0/1` or `1/0`; of
-several rows on one position the first is kept; everything else is counted by reason and skipped."""
+several rows on one position the first is kept; everything else is counted by reason and skipped.
+
+allele_candidates_from_vcf / allele_phased_row are the same two steps for the FINAL VCF of a phased run under `hap_vcf --indels`
+(include/c3r.h: c3r_hap_allele_counts states the rule): heterozygous rows whose alleles are SNVs, insertions or deletions, GT `0/1` / `1/0`
+with one ALT or `1/2` / `2/1` with two.  The phasing between the two passes (phase_vcf) stays SNV-only."""
 import gzip
 
 import numpy as np
 
-from .capi import PHASE_SITE_DTYPE
+from .capi import HAP_EV_DEL, HAP_EV_INS, HAP_EV_NONE, HAP_SITE_DTYPE, PHASE_SITE_DTYPE, pack_nibbles
 from .io import _open_text
 from .phasedvcf import BASE_CODE
 
 SKIP_REASONS = ("other_contig", "malformed", "not_pass", "not_snv", "not_het", "duplicate_pos")
+# allele_candidates_from_vcf: the same reasons (not_snv stays 0 there) and three more
+ALLELE_SKIP_REASONS = SKIP_REASONS + ("multi_alt", "complex_allele", "same_alleles")
 PS_HEADER = '##FORMAT=<ID=PS,Number=1,Type=Integer,Description="Phase set identifier">\n'
 
 
@@ -80,6 +86,108 @@ def candidates_from_vcf(vcf_fn, contig):
     return _table(*per[contig])
 
 
+def reduce_allele(ref, alt):
+    """One ALT of a row against its REF (the rule of include/c3r.h) -> (base letter, kind, length, inserted letters), or None when the pair
+    is not an SNV, an insertion or a deletion anchored on POS (letters other than ACGT, a complex allele, an indel longer than 65535)."""
+    r, a = ref.upper(), alt.upper()
+    if not r or not a or set(r + a) - set("ACGT"):
+        return None
+    while len(r) > 1 and len(a) > 1 and r[-1] == a[-1]:
+        r, a = r[:-1], a[:-1]
+    if len(r) == 1 and len(a) == 1:
+        return (a, HAP_EV_NONE, 0, "") if r != a else None
+    if len(r) == 1 and a[0] == r and len(a) - 1 <= 0xffff:
+        return (r, HAP_EV_INS, len(a) - 1, a[1:])
+    if len(a) == 1 and r[0] == a and len(r) - 1 <= 0xffff:
+        return (a, HAP_EV_DEL, len(r) - 1, "")
+    return None
+
+
+def _parse_alleles(lines, contig):
+    """-> {contig: ([(pos, allele A, allele B, REF string, ALT string)] in file order, {reason: rows skipped})}; an allele is
+    reduce_allele's tuple.  The checks of a row, in this order: malformed, not_pass, not_het (GT is none of 0/1, 1/0, 1/2, 2/1, or 1/2 with
+    one ALT), multi_alt (three or more ALTs, or two under GT 0/1), complex_allele (an allele does not reduce), same_alleles (two ALTs that
+    reduce to one allele)."""
+    out = {}
+    other = 0
+    for line in lines:
+        if not line or line[0] == "#":
+            continue
+        f = line.rstrip("\r\n").split("\t")
+        if not f[0] or f == [""]:
+            continue
+        if contig is not None and f[0] != contig:
+            other += 1
+            continue
+        rows, skipped = out.setdefault(f[0], ([], dict.fromkeys(ALLELE_SKIP_REASONS, 0)))
+        if len(f) < 10 or not f[1].isdigit() or int(f[1]) < 1:
+            skipped["malformed"] += 1
+            continue
+        if f[6] != "PASS":
+            skipped["not_pass"] += 1
+            continue
+        keys, vals = f[8].split(":"), f[9].split(":")
+        gt = vals[keys.index("GT")] if "GT" in keys and keys.index("GT") < len(vals) else ""
+        alts = f[4].split(",")
+        two = gt in ("1/2", "2/1")
+        if (gt not in ("0/1", "1/0") and not two) or (two and len(alts) < 2):
+            skipped["not_het"] += 1
+            continue
+        if len(alts) != (2 if two else 1):
+            skipped["multi_alt"] += 1
+            continue
+        reduced = [reduce_allele(f[3], a) for a in alts]
+        if None in reduced:
+            skipped["complex_allele"] += 1
+            continue
+        if two and reduced[0] == reduced[1]:
+            skipped["same_alleles"] += 1
+            continue
+        a, b = reduced if two else ((f[3][0].upper(), HAP_EV_NONE, 0, ""), reduced[0])
+        rows.append((int(f[1]), a, b, f[3], f[4]))
+    if contig is not None:
+        rows, skipped = out.setdefault(contig, ([], dict.fromkeys(ALLELE_SKIP_REASONS, 0)))
+        skipped["other_contig"] = other
+    return out
+
+
+def _allele_table(rows, skipped):
+    rows = sorted(enumerate(rows), key=lambda kr: (kr[1][0], kr[0]))           # by position; rows of one position in file order
+    keep, last = [], None
+    for _, r in rows:
+        if r[0] == last:
+            skipped["duplicate_pos"] += 1
+            continue
+        keep.append(r)
+        last = r[0]
+    sites = np.zeros(len(keep), dtype=HAP_SITE_DTYPE)
+    pool = []
+    for k, (pos, a, b, _, _) in enumerate(keep):
+        s = sites[k]
+        s["pos"] = pos
+        s["base_matters"] = int(any(x[1] == HAP_EV_NONE and x[0] != keep[k][3][0].upper() for x in (a, b)))     # one of them is an SNV
+        s["event_matters"] = int(any(x[1] != HAP_EV_NONE for x in (a, b)))
+        for name, (base, kind, length, ins) in (("a", a), ("b", b)):
+            s[name + "_base"], s[name + "_kind"], s[name + "_len"] = BASE_CODE[base], kind, length
+            if kind == HAP_EV_INS:
+                s[name + "_ins_off"] = len(pool)
+                pool += [BASE_CODE[c] for c in ins]
+    return sites, pack_nibbles(pool), [(r[3], r[4]) for r in keep], skipped
+
+
+def allele_candidates_from_vcf(vcf_fn, contig):
+    """(HAP_SITE_DTYPE array sorted by pos — ps is 0 —, the packed pool of the insertions' bases (capi.pack_nibbles), [(REF string, ALT
+    string)] of the rows as the file spells them, {reason: rows skipped}) for `contig` of a plain or gzipped VCF; contig None: {contig: that
+    tuple} for every contig of the file, in one pass.  A row is kept when FILTER is PASS, its GT is `0/1` / `1/0` with one ALT (A = REF,
+    B = the ALT) or `1/2` / `2/1` with two ALTs (A = the first, B = the second), every ALT reduces to an SNV, an insertion or a deletion
+    anchored on POS (reduce_allele) and the two alleles differ; of several such rows on one position the first is kept."""
+    with _open_text(vcf_fn) as f:
+        per = _parse_alleles(f, contig)
+    if contig is None:
+        return {c: _allele_table(rows, skipped) for c, (rows, skipped) in per.items()}
+    return _allele_table(*per[contig])
+
+
 def phased_only(sites_out):
     """The sites that got a block (ps >= 0): what goes to Engine.set_phase_sites."""
     return np.ascontiguousarray(sites_out[sites_out["ps"] >= 0])
@@ -110,6 +218,27 @@ def phased_row(line, f_, phased):
     vals[keys.index("GT")] = "1|0" if int(s["h1"]) else "0|1"
     f_ = list(f_)
     f_[8], f_[9] = f_[8] + ":PS", ":".join(vals) + ":%d" % int(s["ps"])
+    del phased[int(f_[1])]
+    return "\t".join(f_) + line[len(line.rstrip("\r\n")):], True
+
+
+def allele_phased_row(line, f_, phased):
+    """phased_row for the candidates of allele_candidates_from_vcf.  `phased`: {pos: (REF string, ALT string, ps, h1)} of the accepted
+    candidates.  The first row on such a position whose REF and ALT are those strings, FILTER PASS, without a PS key and with GT `0/1` /
+    `1/0` (one ALT) or `1/2` / `2/1` (two ALTs) gets GT A|B — `0|1`, `1|2` — when h1 is 0 and B|A — `1|0`, `2|1` — when it is 1, and PS as
+    phased_row writes it; the site leaves `phased`.  Every other row comes back byte for byte."""
+    s = phased.get(int(f_[1])) if len(f_) >= 10 and f_[1].isdigit() else None
+    keys = f_[8].split(":") if s is not None else []
+    if s is None or "GT" not in keys or "PS" in keys or f_[6] != "PASS" or f_[3] != s[0] or f_[4] != s[1]:
+        return line, False
+    vals = f_[9].split(":")
+    two = "," in s[1]
+    if keys.index("GT") >= len(vals) or vals[keys.index("GT")] not in (("1/2", "2/1") if two else ("0/1", "1/0")):
+        return line, False
+    a, b = ("1", "2") if two else ("0", "1")
+    vals[keys.index("GT")] = b + "|" + a if int(s[3]) else a + "|" + b
+    f_ = list(f_)
+    f_[8], f_[9] = f_[8] + ":PS", ":".join(vals) + ":%d" % int(s[2])
     del phased[int(f_[1])]
     return "\t".join(f_) + line[len(line.rstrip("\r\n")):], True
 

@@ -120,8 +120,9 @@ int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats
  * stores it beside the tag, so it follows the table like the tags do.  C3R_EINVAL when no phase sites are set. */
 int c3r_get_read_phase_sets(c3r_ctx *ctx, int32_t *ps, int64_t cap);
 /* Per-haplotype allele counts at called sites, and the phase of a heterozygous call from them: what phases the FINAL VCF once the reads are
- * tagged, and, written out, the haplotype support of every call.  SNVs only; a majority rule over CIGAR-position alleles (no realignment,
- * no base qualities).
+ * tagged, and, written out, the haplotype support of every call.  c3r_hap_counts: biallelic SNVs only; c3r_hap_allele_counts (below):
+ * SNVs, insertions, deletions and sites with two ALT alleles.  Both are a majority rule over CIGAR-position alleles (no realignment, no
+ * base qualities).
  *
  * Query sites (c3r_hap_counts): sorted by strictly increasing pos; ref and alt are valid; ps >= 0 is the phase set to count against; h1 is
  * ignored; validated as in c3r_set_phase_sites (except h1), naming the first bad index.
@@ -147,6 +148,38 @@ int c3r_get_read_phase_sets(c3r_ctx *ctx, int32_t *ps, int64_t cap);
 int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *counts);
 int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts, const c3r_phase_params_t *p, c3r_phase_site_t *out,
                    c3r_hap_assign_stats_t *stats);
+/* The same counts for a heterozygous call whose two alleles may be SNVs, insertions or deletions: `0/1` rows with an indel ALT and `1/2` rows
+ * (`C  T,CGG`, `ACC  A,TCC`).  Opt-in (hap_vcf --indels), like `whatshap phase --indels`.  The alleles are read off the CIGAR position: no
+ * realignment, no left-alignment of the reads' indels, no base qualities; agreement with `whatshap --indels` is not measured.  This is where
+ * the rule is stated; phasing.allele_candidates_from_vcf, csrc/hapcount_kernels.hpp and tests/hapalleleref.py restate it.
+ *
+ * Alleles of a VCF row: REF r and an ALT a, upper-cased, letters of ACGT only; the common SUFFIX is stripped while both are longer than one
+ * letter (only suffixes: the anchor is always POS).  Then: one letter each and different — an SNV (base = the ALT letter, event NONE); r
+ * one letter, a longer and starting with r — an insertion (base = r[0], event INS(the rest of a)); a one letter, r longer and starting with
+ * a — a deletion (base = r[0], event DEL(len(r) - 1)); anything else — the row is skipped (`complex_allele`).  The REF allele is (r[0], NONE).
+ * GT 0/1 or 1/0 with one ALT: A = REF, B = the ALT; GT 1/2 or 2/1 with two ALTs that both reduce and differ: A = the first, B = the second.
+ * base_matters = one of A, B is an SNV; event_matters = one of them is an insertion or a deletion.
+ *
+ * Observation of a read at a site with anchor P, on the read's NORMALISED CIGAR (H, empty ops and pads dropped — a pad survives, as an op that
+ * consumes nothing, only directly before a D that does not follow an I —, = and X folded into M, equal neighbours merged): P must lie under an
+ * M op (first reference base x, first query base y, length len) at offset dd with q = y + dd < l_seq, else nothing (a P under D or N:
+ * nothing).  b = the read's 4-bit code at q.  Event: dd < len - 1: NONE.  dd = len - 1: by the next op — an I directly followed by a D:
+ * OTHER (the `+<ins>-<del>` column; equals no allele's event); an I of n bases that do not all lie below l_seq: no observation; an I of n
+ * bases: INS(the codes at y + len .. y + len + n - 1); a D of n: DEL(n); anything else (N, S, the pad before a D, the read's end): NONE.
+ * Where event_matters is 0 the event is not looked at (an insertion cut off by a short SEQ then does not drop the base before it).
+ * base_matters and b not one of 1, 2, 4, 8: no observation.  The read shows allele (B, E) when (base_matters is 0 or b == B) and
+ * (event_matters is 0 or the event equals E — INS: the same length and the same codes).  Column = 0 for A, else 1 for B, else 2.
+ * On a site whose alleles are REF and one SNV this is c3r_hap_counts' rule: events are ignored.
+ * Voters, row and counts are those of c3r_hap_counts, and c3r_hap_assign runs on the table with "REF" read as allele A and "ALT" as allele B
+ * (it reads pos and ps only): accepted with h1 = 0 the GT is A|B (0|1, 1|2), with h1 = 1 it is B|A (1|0, 2|1).
+ *
+ * ins_pool: the inserted bases of all INS alleles, 4-bit packed like a read's SEQ (base 2k in the high nibble of byte k), pool_bases of them
+ * (NULL when 0).  Preconditions and side effects are c3r_hap_counts': it needs a phase table; n = 0 launches nothing; no reads loaded: every
+ * count is 0; it changes nothing a scan or the tags read; its device buffers are allocated at the first call and kept
+ * (k_hap_allele_counts, csrc/hapcount_kernels.hpp).  C3R_EINVAL, naming the first bad index, for an unsorted or repeated pos, pos < 1,
+ * ps < 0, a flag other than 0 / 1, a base code (of an allele or in the pool of an insertion) outside 1, 2, 4, 8, an unknown kind, an indel
+ * of length 0 (or a length on kind NONE), an insertion that runs past the pool, or two equal alleles. */
+int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts);
 /* Phasing on the device from read linkage: what stands where `whatshap phase` / `longphase phase` stand in the reference flow
  * (run_clair3_rna:729-767), in two steps.  It is a GREEDY LINKAGE CHAIN, not whatshap's wMEC: every heterozygous SNV gets a block and an
  * orientation from the reads that cover it together with one of the K = C3R_PHASE_LINKS sites before it, once, in table order.

@@ -129,6 +129,31 @@ static_assert(sizeof(c3r_phase_site_t) == 12, "c3r_phase_site_t must be 12 bytes
 _Static_assert(sizeof(c3r_phase_site_t) == 12, "c3r_phase_site_t must be 12 bytes");
 #endif
 
+/* One allele of a query site of c3r_hap_allele_counts (include/c3r.h): the base on the anchor position and the event behind it. */
+#define C3R_HAP_EV_NONE 0 /* nothing follows the anchor base                                          */
+#define C3R_HAP_EV_INS 1  /* `len` inserted bases follow it: nibbles ins_off .. ins_off + len - 1 of the pool */
+#define C3R_HAP_EV_DEL 2  /* `len` deleted reference bases follow it                                  */
+typedef struct c3r_hap_allele {
+    uint8_t base;         /* BAM 4-bit code of the anchor base, one of 1, 2, 4, 8                    */
+    uint8_t kind;         /* C3R_HAP_EV_*                                                            */
+    uint16_t len;         /* INS / DEL: length >= 1; NONE: 0                                         */
+    uint32_t ins_off;     /* INS: offset of its first base in the pool, in bases; else 0             */
+} c3r_hap_allele_t;
+/* One query site of c3r_hap_allele_counts: a heterozygous call of the final VCF with its two alleles, A and B. */
+typedef struct c3r_hap_site {
+    int32_t pos;          /* 1-based position = the anchor of both alleles                           */
+    int32_t ps;           /* phase set to count against, >= 0                                        */
+    uint8_t base_matters; /* 1: one of the two alleles is an SNV — the read's anchor base is compared */
+    uint8_t event_matters;/* 1: one of them is an insertion or a deletion — the read's event is compared */
+    uint8_t reserved[6];  /* set to 0                                                                */
+    c3r_hap_allele_t a, b;
+} c3r_hap_site_t;
+#ifdef __cplusplus
+static_assert(sizeof(c3r_hap_allele_t) == 8 && sizeof(c3r_hap_site_t) == 32, "c3r_hap_site_t must be 32 bytes");
+#else
+_Static_assert(sizeof(c3r_hap_allele_t) == 8 && sizeof(c3r_hap_site_t) == 32, "c3r_hap_site_t must be 32 bytes");
+#endif
+
 /* What the haplotagging of the loaded reads came to (c3r_get_haplotags).  n_reads = n_hp1 + n_hp2 + n_no_vote + n_tie. */
 typedef struct c3r_haplotag_stats {
     int64_t n_reads;      /* loaded reads (all of them vote, whatever the filters say)               */
