@@ -35,6 +35,9 @@ hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
 `--phase_indels` (with --phase_output) hands hap_vcf --indels: heterozygous insertions, deletions and rows with two ALT alleles are phased too,
 by CIGAR-position alleles (no realignment, no left-alignment, no base qualities); without it both files are what they were.
+`--haplotagged_bam` (same conditions as --phase_output, and combinable with it) adds the step the reference's "Haplotag the BAM" commands stand
+for: haplotag_bam writes <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai for the contigs the run processed — every record of the
+contig, with the HP / PS tags the GPU computed from the phase table the second pass read; without the flag nothing changes.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
@@ -193,6 +196,10 @@ def build_parser():
     a("--mpileup_compat", type=str, default=mpileup_compat.env_default(), choices=list(mpileup_compat.CHOICES),
       help="which samtools mpileup text the tensor build restates: auto = ask `--samtools --version` (>= 1.11 -> 1, <= 1.10 -> 0, not "
            "runnable -> 1); 0 = samtools <= 1.10; 1 = samtools >= 1.11.  Default: $C3R_MPILEUP_COMPAT, else auto")
+    a("--haplotagged_bam", action="store_true",
+      help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: after the passes, write the haplotagged BAM of every "
+           "processed contig with the tags the GPU computed to <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai (haplotag_bam: the "
+           "files the reference's `whatshap haplotag` + `samtools index` step leaves).  One process only.  Off: no file more and no byte different")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else LOCAL_RANK under torch.distributed.run, else 0")
     a("--gpu_precision", type=str, default=_env_precision(), choices=["f32", "f16x3", "f16+f8", "auto"],
       help="network arithmetic (c3r_set_precision): f16x3 = fp32-equivalent split-f16 (default); auto = the faster fp8-corrected path where a "
@@ -331,21 +338,30 @@ def _indexed_bam(args):
 
 
 def Run(args, log=None):
-    """The passes (_run_flow), and with `--phase_output` one further step behind them: hap_vcf on the phased pass's VCF — nothing inside a
-    pass changes."""
-    if not getattr(args, "phase_output", False):
-        if getattr(args, "phase_indels", False):
-            sys.exit("[ERROR] --phase_indels belongs to --phase_output (it phases the indels of the final VCF): it needs --phase_output")
+    """The passes (_run_flow), and with `--phase_output` / `--haplotagged_bam` one further step each behind them: hap_vcf on the phased pass's
+    VCF, haplotag_bam on the BAM — nothing inside a pass changes."""
+    phase_output, tagged_bam = getattr(args, "phase_output", False), getattr(args, "haplotagged_bam", False)
+    if not phase_output and getattr(args, "phase_indels", False):
+        sys.exit("[ERROR] --phase_indels belongs to --phase_output (it phases the indels of the final VCF): it needs --phase_output")
+    if not phase_output and not tagged_bam:
         return _run_flow(args, log)
-    from . import hap_vcf
     builtin = getattr(args, "phasing", None) is not None
-    if not args.enable_phasing_model:
-        sys.exit("[ERROR] --phase_output needs --enable_phasing_model (it phases the 30-channel pass's VCF)")
-    if not builtin and not getattr(args, "phased_vcf_fn", None):
-        sys.exit("[ERROR] --phase_output needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("[ERROR] --phase_output runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the pass without it and then "
-                 "`python -m clair3_rna_amd.hap_vcf --bam_fn ... --vcf_fn <prefix>_enable_phasing.vcf.gz --phased_vcf_fn ... --output_fn ...`")
+    if phase_output:
+        if not args.enable_phasing_model:
+            sys.exit("[ERROR] --phase_output needs --enable_phasing_model (it phases the 30-channel pass's VCF)")
+        if not builtin and not getattr(args, "phased_vcf_fn", None):
+            sys.exit("[ERROR] --phase_output needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("[ERROR] --phase_output runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the pass without it and then "
+                     "`python -m clair3_rna_amd.hap_vcf --bam_fn ... --vcf_fn <prefix>_enable_phasing.vcf.gz --phased_vcf_fn ... --output_fn ...`")
+    if tagged_bam:
+        if not args.enable_phasing_model:
+            sys.exit("[ERROR] --haplotagged_bam needs --enable_phasing_model (it writes the tags the 30-channel pass called with)")
+        if not builtin and not getattr(args, "phased_vcf_fn", None):
+            sys.exit("[ERROR] --haplotagged_bam needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("[ERROR] --haplotagged_bam runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the pass without it and then "
+                     "`python -m clair3_rna_amd.haplotag_bam --bam_fn ... --phased_vcf_fn ... --output_dir <output_dir>/tmp/phased_output/phased_bam`")
     rc = _run_flow(args, log)
     if rc:
         return rc
@@ -354,10 +370,26 @@ def Run(args, log=None):
     if not os.path.isfile(stem + ext):                        # (no contig found: the pass wrote nothing)
         return rc
     source = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf") if builtin else args.phased_vcf_fn
-    hap_vcf.Run(hap_vcf.build_parser().parse_args(
-        ["--bam_fn", _indexed_bam(args), "--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext,
-         "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if getattr(args, "phase_indels", False) else [])
-        + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
+    gpu = ["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else []
+    if phase_output:
+        from . import hap_vcf
+        hap_vcf.Run(hap_vcf.build_parser().parse_args(
+            ["--bam_fn", _indexed_bam(args), "--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext,
+             "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if getattr(args, "phase_indels", False) else [])
+            + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + gpu), log)
+    if tagged_bam:
+        # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed
+        from . import haplotag_bam
+        contigs, _ = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn),
+                                 args.chunk_size, args.chunk_num)
+        bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
+        if os.path.isdir(bam_dir):                            # (files of an earlier run in this directory, for contigs this run did not process)
+            for name in os.listdir(bam_dir):
+                if name.endswith(".bam") or name.endswith(".bam.bai"):
+                    os.remove(os.path.join(bam_dir, name))
+        haplotag_bam.Run(haplotag_bam.build_parser().parse_args(
+            ["--bam_fn", _indexed_bam(args), "--phased_vcf_fn", source, "--output_dir", bam_dir,
+             "--ctg_name", ",".join(contigs)] + gpu), log)
     return rc
 
 

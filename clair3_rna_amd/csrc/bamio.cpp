@@ -1,4 +1,4 @@
-// bamio.cpp — libc3r_io.so: BAM / BGZF / BAI reader producing the flat read records of c3r_load_reads.
+// bamio.cpp — libc3r_io.so: BAM / BGZF / BAI reader producing the flat read records of c3r_load_reads, and the writer of the haplotagged BAM.
 // C ABI in include/c3r_io.h.  Host-only (g++ -O2 -pthread -lz).
 //
 // What it replaces: the input side of `samtools mpileup <bam> -r ctg:beg-end --output-extra HP`
@@ -9,6 +9,8 @@
 //   full load ......... block table from the BGZF headers, blocks inflated by a thread pool in batches, records parsed
 //                       in file order with early exit once the contig is passed
 //   index build ....... one pass over the records with their virtual offsets (`samtools index` equivalent)
+//   haplotagged BAM ... the same pass over one contig's blocks, every record copied with its HP / PS aux fields replaced by the
+//                       caller's tags, deflated by vcfio.cpp's block compressor (`whatshap haplotag` equivalent; the tags are the device's)
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -29,6 +31,7 @@
 
 #include "../../include/c3r.h"
 #include "../../include/c3r_io.h"
+#include "bgzf_out.hpp"
 #include <sched.h>
 
 // CPUs this process may run on (its affinity mask: one process per GPU is pinned to its share of the node, shard.host_budget), not the
@@ -211,6 +214,7 @@ struct c3r_bam {
     std::vector<int64_t> lens;
     uint64_t first_record_voff = 0;     // virtual offset of the first alignment
     size_t header_bytes = 0;            // uncompressed size of header + reference list
+    std::string text;                   // the header text (l_text bytes): the haplotagged writer copies it
     bool has_bai = false;
     std::vector<RefIndex> bai;
     int n_threads = 1;
@@ -250,9 +254,18 @@ inline int malformed_in(RecSink &o, int32_t pos, const char *what) {
     return 2;
 }
 
-// Append one alignment (pointer to the 32 fixed bytes after block_size) if it belongs to (tid, [beg,end)).
-// Returns 1 appended, 0 skipped, 2 = stop: past the region (sorted input) or a malformed record (o.malformed).
-int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, int64_t beg, int64_t end) {
+// What the keep rule reads off one alignment: the fixed fields c3r_read_t takes, the CIGAR that counts (the record's own, or the CG:B,I
+// array behind the two-op placeholder), the HP tag, and where the packed sequence lies.
+struct RecView {
+    int32_t pos; uint32_t flag, mapq, l_seq, n_cig, hp;
+    const uint8_t *cig; size_t s0, nb;
+};
+
+// THE keep rule — the one place that says which alignments (pointer to the 32 fixed bytes after block_size) of (tid, [beg,end)) are
+// read records: shared by the fetch (take_record_into) and by the haplotagged writer, which pairs its tag arrays with the records
+// this function keeps.  Returns 1 kept (v filled), 0 skipped, 2 = stop: past the region (sorted input) or a malformed record
+// (*bad_what set, v.pos filled).
+int view_record(const uint8_t *r, size_t block_size, int tid, int64_t beg, int64_t end, RecView &v, const char **bad_what) {
     if (block_size < 32) return 0;
     const int32_t ref_id = le32s(r), pos = le32s(r + 4);
     const uint32_t l_read_name = r[8], mapq = r[9];
@@ -262,8 +275,9 @@ int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, i
     if (ref_id != tid) return (ref_id > tid || ref_id < 0) ? 2 : 0;
     if (pos < 0) return 0;
     if (end > 0 && pos >= end) return 2;
+    v.pos = pos;
     const size_t c0 = 32 + l_read_name, s0 = c0 + 4 * (size_t)n_cig, nb = ((size_t)l_seq + 1) / 2, a0 = s0 + nb + l_seq;
-    if (a0 > block_size) return malformed_in(o, pos, "name / CIGAR / sequence longer than the record");
+    if (a0 > block_size) { *bad_what = "name / CIGAR / sequence longer than the record"; return 2; }
     const uint8_t *cig = r + c0;
     // aux: HP (any integer type) and CG:B,I (real CIGAR of reads with > 65535 ops, SAM spec §4.2.2)
     uint32_t hp = 0; const uint8_t *cg = nullptr; uint32_t cg_n = 0;
@@ -281,7 +295,7 @@ int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, i
                 if (p + 5 > block_size) { p = block_size; continue; }
                 const uint8_t sub = r[p]; const uint32_t cnt = le32(r + p + 1);
                 const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-                if ((size_t)cnt * es > block_size - (p + 5)) return malformed_in(o, pos, "B-array tag longer than the record");
+                if ((size_t)cnt * es > block_size - (p + 5)) { *bad_what = "B-array tag longer than the record"; return 2; }
                 if (t0 == 'C' && t1 == 'G' && sub == 'I') { cg = r + p + 5; cg_n = cnt; }
                 p += 5 + (size_t)cnt * es;
                 continue;
@@ -290,13 +304,13 @@ int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, i
         }
         if (p + sz > block_size) break;
         if (t0 == 'H' && t1 == 'P' && ty != 'A' && ty != 'f') {
-            int64_t v = 0;
+            int64_t x = 0;
             switch (ty) {
-                case 'c': v = (int8_t)r[p]; break;  case 'C': v = r[p]; break;
-                case 's': v = (int16_t)le16(r + p); break;  case 'S': v = le16(r + p); break;
-                case 'i': v = le32s(r + p); break;  case 'I': v = le32(r + p); break;
+                case 'c': x = (int8_t)r[p]; break;  case 'C': x = r[p]; break;
+                case 's': x = (int16_t)le16(r + p); break;  case 'S': x = le16(r + p); break;
+                case 'i': x = le32s(r + p); break;  case 'I': x = le32(r + p); break;
             }
-            hp = (v > 0 && v < 256) ? (uint32_t)v : 0;
+            hp = (x > 0 && x < 256) ? (uint32_t)x : 0;
         }
         p += sz;
     }
@@ -308,15 +322,26 @@ int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, i
         if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4;
     }
     if ((int64_t)pos + std::max<int64_t>(rlen, 1) <= beg) return 0;
+    v.flag = flag; v.mapq = mapq; v.l_seq = l_seq; v.n_cig = n_cig; v.hp = hp; v.cig = cig; v.s0 = s0; v.nb = nb;
+    return 1;
+}
+
+// Append one alignment if view_record keeps it.  Returns 1 appended, 0 skipped, 2 = stop (o.malformed when the record was malformed).
+int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, int64_t beg, int64_t end) {
+    RecView v;
+    const char *bad = nullptr;
+    const int rc = view_record(r, block_size, tid, beg, end, v, &bad);
+    if (bad) return malformed_in(o, v.pos, bad);
+    if (rc != 1) return rc;
     c3r_read_t rec;
     memset(&rec, 0, sizeof rec);
-    rec.pos = pos; rec.cigar_off = (uint32_t)o.cigar->size(); rec.n_cigar = n_cig; rec.l_seq = l_seq; rec.seq_off = (uint64_t)o.seq->size();
-    rec.flag = (uint16_t)flag; rec.mapq = (uint8_t)mapq; rec.hp = (uint8_t)hp;
+    rec.pos = v.pos; rec.cigar_off = (uint32_t)o.cigar->size(); rec.n_cigar = v.n_cig; rec.l_seq = v.l_seq; rec.seq_off = (uint64_t)o.seq->size();
+    rec.flag = (uint16_t)v.flag; rec.mapq = (uint8_t)v.mapq; rec.hp = (uint8_t)v.hp;
     o.reads->push_back(rec);
     const size_t cb = o.cigar->size();
-    o.cigar->resize(cb + n_cig);
-    for (uint32_t k = 0; k < n_cig; ++k) (*o.cigar)[cb + k] = le32(cig + 4 * k);
-    o.seq->insert(o.seq->end(), r + s0, r + s0 + nb);
+    o.cigar->resize(cb + v.n_cig);
+    for (uint32_t k = 0; k < v.n_cig; ++k) (*o.cigar)[cb + k] = le32(v.cig + 4 * k);
+    o.seq->insert(o.seq->end(), r + v.s0, r + v.s0 + v.nb);
     return 1;
 }
 
@@ -384,6 +409,7 @@ int parse_header(c3r_bam *b) {
     if (cur.read(h, 4) != 1) return failb(b, C3R_EINVAL, "%s: truncated header", b->path.c_str());
     const int32_t n_ref = le32s(h);
     if (l_text < 0 || n_ref < 0) return failb(b, C3R_EINVAL, "%s: negative header length / reference count", b->path.c_str());
+    b->text.assign((const char *)tmp.data(), tmp.size());
     size_t total = 12 + (size_t)std::max(l_text, 0);
     for (int i = 0; i < n_ref; ++i) {
         if (cur.read(h, 4) != 1) return failb(b, C3R_EINVAL, "%s: truncated reference list", b->path.c_str());
@@ -439,6 +465,18 @@ int load_bai(c3r_bam *b, const std::string &p) {
     } while (0);
     m.close();
     return rc;
+}
+
+// end0 <= 0 of a fetch: the whole contig
+inline int64_t whole_contig_end(const c3r_bam *b, int tid) { return std::max<int64_t>(b->lens[(size_t)tid], (int64_t)1 << 29); }
+
+// The file range (virtual offsets) the index gives for a contig's placed records: the metadata pseudo-bin, else the span of its chunks.
+// false: the contig has no bin at all — it holds no placed record.
+bool contig_span(const RefIndex &ri, uint64_t *lo, uint64_t *hi) {
+    if (ri.n_mapped >= 0) { *lo = ri.off_beg; *hi = ri.off_end; return true; }
+    *lo = ~0ull; *hi = 0;
+    for (auto &kv : ri.bins) for (auto &c : kv.second) { *lo = std::min(*lo, c.first); *hi = std::max(*hi, c.second); }
+    return !ri.bins.empty();
 }
 
 struct BlockRef { size_t off, payload, bsize, isize; };
@@ -694,7 +732,7 @@ int c3r_bam_fetch(c3r_bam *b, const char *contig, int64_t beg0, int64_t end0, in
     int rc = C3R_OK;
     if (tid >= 0) {
         if (beg0 < 0) beg0 = 0;
-        if (end0 <= 0) end0 = std::max<int64_t>(b->lens[(size_t)tid], (int64_t)1 << 29);
+        if (end0 <= 0) end0 = whole_contig_end(b, tid);
         if (b->has_bai) {
             rc = fetch_indexed(b, tid, beg0, end0);
         } else {
@@ -725,10 +763,9 @@ int c3r_bam_contig_weight(c3r_bam *b, int i, int64_t *n_mapped, int64_t *file_by
     if (b->has_bai && (size_t)i < b->bai.size()) {
         const RefIndex &ri = b->bai[(size_t)i];
         nm = ri.n_mapped;
-        uint64_t lo = ri.off_beg, hi = ri.off_end;
+        uint64_t lo, hi;
+        contig_span(ri, &lo, &hi);
         if (ri.n_mapped < 0) {             // no pseudo-bin: the span of the contig's chunks
-            lo = ~0ull; hi = 0;
-            for (auto &kv : ri.bins) for (auto &c : kv.second) { lo = std::min(lo, c.first); hi = std::max(hi, c.second); }
             // `samtools index` writes the pseudo-bin only for references that HAVE records: a contig without a single bin (chrY, chrM or a
             // decoy under --include_all_ctgs) holds no read — 0 mapped reads, 0 bytes, not "unknown" (which would push the whole deal of a
             // sample from mapped reads down to compressed bytes)
@@ -807,3 +844,190 @@ int c3r_bam_index_build(const char *bam_path, const char *bai_path) {
 }
 
 }  // extern "C"
+
+// ---- haplotagged output: the contig's records with the device's HP / PS tags (include/c3r_io.h: c3r_bam_write_haplotagged)
+namespace {
+
+inline void put16(std::vector<uint8_t> &v, uint32_t x) { v.push_back((uint8_t)x); v.push_back((uint8_t)(x >> 8)); }
+inline void put32(std::vector<uint8_t> &v, uint32_t x) { put16(v, x & 0xffff); put16(v, x >> 16); }
+
+// One alignment (the block_size bytes after the length field) appended to `out` without its HP / PS / PC aux fields, whatever their
+// type; every other byte in place.  Strict where the keep rule is lenient, since what it cannot walk it cannot copy faithfully: an aux
+// field of unknown type, one that runs past the record, an unterminated string are malformed.
+// Returns 0 nothing removed, 1 something removed, -1 malformed (*what says why).
+int strip_phase_tags(const uint8_t *r, size_t bs, std::vector<uint8_t> &out, const char **what) {
+    if (bs < 32) { *what = "record shorter than its fixed fields"; return -1; }
+    const size_t a0 = 32 + (size_t)r[8] + 4 * (size_t)le16(r + 12) + ((size_t)le32(r + 16) + 1) / 2 + (size_t)le32(r + 16);
+    if (a0 > bs) { *what = "name / CIGAR / sequence longer than the record"; return -1; }
+    out.insert(out.end(), r, r + a0);
+    int removed = 0;
+    for (size_t p = a0; p < bs;) {
+        const size_t f0 = p;
+        if (p + 3 > bs) { *what = "aux field cut short"; return -1; }
+        const uint8_t t0 = r[p], t1 = r[p + 1], ty = r[p + 2];
+        p += 3;
+        switch (ty) {
+            case 'A': case 'c': case 'C': p += 1; break;
+            case 's': case 'S': p += 2; break;
+            case 'i': case 'I': case 'f': p += 4; break;
+            case 'Z': case 'H': {
+                const void *z = p < bs ? memchr(r + p, 0, bs - p) : nullptr;
+                if (!z) { *what = "unterminated string aux field"; return -1; }
+                p = (size_t)((const uint8_t *)z - r) + 1;
+                break;
+            }
+            case 'B': {
+                if (p + 5 > bs) { *what = "aux field cut short"; return -1; }
+                const uint8_t sub = r[p];
+                const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+                if (!es) { *what = "B-array aux field of unknown element type"; return -1; }
+                if ((size_t)le32(r + p + 1) * es > bs - (p + 5)) { *what = "B-array tag longer than the record"; return -1; }
+                p += 5 + (size_t)le32(r + p + 1) * es;
+                break;
+            }
+            default: *what = "aux field of unknown type"; return -1;
+        }
+        if (p > bs) { *what = "aux field cut short"; return -1; }
+        if ((t0 == 'H' && t1 == 'P') || (t0 == 'P' && (t1 == 'S' || t1 == 'C'))) removed = 1;
+        else out.insert(out.end(), r + f0, r + p);
+    }
+    return removed;
+}
+
+// The uncompressed stream of the output file, cut into BGZF blocks every BLK bytes and written as it grows.
+struct BgzfSink {
+    FILE *f = nullptr; int threads = 1;
+    std::vector<uint8_t> pend;              // bytes not yet in a block
+    static constexpr size_t ROUND = 256;    // blocks deflated per round
+    bool flush(bool all) {
+        const size_t nb = all ? (pend.size() + c3r_io::BLK - 1) / c3r_io::BLK : pend.size() / c3r_io::BLK;
+        if (nb == 0) return true;
+        const size_t take = std::min(pend.size(), nb * c3r_io::BLK);
+        std::vector<uint8_t> gz; std::vector<uint64_t> co;
+        if (!c3r_io::bgzf_compress(pend.data(), take, threads, gz, co)) return false;
+        if (fwrite(gz.data(), 1, gz.size(), f) != gz.size()) return false;
+        pend.erase(pend.begin(), pend.begin() + (long)take);
+        return true;
+    }
+    bool grown() { return pend.size() < ROUND * c3r_io::BLK || flush(false); }
+};
+
+}  // namespace
+
+extern "C" int c3r_bam_header_text(c3r_bam *b, const char **text, int64_t *n_bytes) {
+    if (!b) return C3R_EINVAL;
+    if (text) *text = b->text.data();
+    if (n_bytes) *n_bytes = (int64_t)b->text.size();
+    return C3R_OK;
+}
+
+extern "C" int c3r_bam_write_haplotagged(c3r_bam *b, const char *contig, const c3r_read_t *reads, const uint8_t *hp, const int32_t *ps,
+                                         int64_t n_reads, const char *out_path, const char *pg_line, int threads, int64_t *counts) {
+    if (!b) return C3R_EINVAL;
+    if (!contig || !out_path || n_reads < 0) return failb(b, C3R_EINVAL, "c3r_bam_write_haplotagged: null contig / output path or negative n_reads");
+    const bool paired = !(n_reads == 0 && !reads && !hp && !ps);       // (no arrays at all: the records go out untagged, nothing is checked)
+    if (paired && n_reads > 0 && (!reads || !hp || !ps)) return failb(b, C3R_EINVAL, "c3r_bam_write_haplotagged: %lld reads without their arrays", (long long)n_reads);
+    int tid = -1;
+    for (size_t i = 0; i < b->names.size(); ++i) if (b->names[i] == contig) { tid = (int)i; break; }
+    if (tid < 0) return failb(b, C3R_EINVAL, "%s: no contig %s in the header", b->path.c_str(), contig);
+    for (int64_t k = 0; k < n_reads; ++k) {
+        if (hp[k] > 2) return failb(b, C3R_EINVAL, "c3r_bam_write_haplotagged: hp[%lld] = %d is no haplotype (0, 1, 2)", (long long)k, (int)hp[k]);
+        if (hp[k] && ps[k] < 0) return failb(b, C3R_EINVAL, "c3r_bam_write_haplotagged: hp[%lld] = %d without a phase set (ps = %d)", (long long)k, (int)hp[k], ps[k]);
+    }
+    if (pg_line && (strchr(pg_line, '\n') || strncmp(pg_line, "@PG\t", 4) != 0))
+        return failb(b, C3R_EINVAL, "c3r_bam_write_haplotagged: pg_line must be one @PG line without its newline");
+
+    BgzfSink sink;
+    sink.threads = c3r_io::deflate_threads(threads);
+    sink.f = fopen(out_path, "wb");
+    if (!sink.f) return failb(b, C3R_EINVAL, "%s: cannot write", out_path);
+    {   // header: the input's text (+ the @PG line) and its reference dictionary
+        std::string text = b->text;
+        if (pg_line) {
+            while (!text.empty() && text.back() == '\0') text.pop_back();       // (some writers pad the text with NULs)
+            if (!text.empty() && text.back() != '\n') text += '\n';
+            text += pg_line; text += '\n';
+        }
+        std::vector<uint8_t> &o = sink.pend;
+        o.insert(o.end(), {'B', 'A', 'M', 1});
+        put32(o, (uint32_t)text.size());
+        o.insert(o.end(), text.begin(), text.end());
+        put32(o, (uint32_t)b->names.size());
+        for (size_t i = 0; i < b->names.size(); ++i) {
+            put32(o, (uint32_t)b->names[i].size() + 1);
+            o.insert(o.end(), b->names[i].begin(), b->names[i].end()); o.push_back(0);
+            put32(o, (uint32_t)b->lens[i]);
+        }
+    }
+    int64_t n_written = 0, n_tagged = 0, n_stripped = 0, n_unpaired = 0, k = 0;
+    int rc = C3R_OK;
+    bool past = false;                                  // the fetch stopped here (a position beyond the region): nothing further is paired
+    const int64_t end0 = whole_contig_end(b, tid);
+    std::vector<uint8_t> rec;
+    auto visit = [&](const uint8_t *r, size_t bs, uint64_t, uint64_t) {
+        if (bs < 32) return true;
+        const int32_t ref_id = le32s(r);
+        if (ref_id != tid) return !(ref_id > tid || ref_id < 0);      // sorted input: the contig is over
+        const char *what = nullptr;
+        rec.clear();
+        const int removed = strip_phase_tags(r, bs, rec, &what);
+        if (removed < 0) { rc = failb(b, C3R_EINVAL, "%s: malformed alignment record at position %d (%s)", b->path.c_str(), le32s(r + 4) + 1, what); return false; }
+        RecView v;
+        const int keep = past ? 0 : view_record(r, bs, tid, 0, end0, v, &what);
+        if (keep == 2) {
+            if (what) { rc = failb(b, C3R_EINVAL, "%s: malformed alignment record at position %d (%s)", b->path.c_str(), v.pos + 1, what); return false; }
+            past = true;
+        }
+        uint32_t tag = 0;
+        if (keep == 1 && paired) {
+            if (k >= n_reads) { rc = failb(b, C3R_EINVAL, "%s: %s holds more read records than the %lld handed in (record %lld at position %d)", b->path.c_str(), contig, (long long)n_reads, (long long)k, v.pos + 1); return false; }
+            const c3r_read_t &q = reads[k];
+            if (q.pos != v.pos || q.flag != v.flag || q.mapq != v.mapq || q.l_seq != v.l_seq) {
+                rc = failb(b, C3R_EINVAL, "%s: reads[%lld] (pos %d, flag %u, mapq %u, l_seq %u) is not record %lld of %s (pos %d, flag %u, mapq %u, l_seq %u)", b->path.c_str(),
+                           (long long)k, q.pos, (unsigned)q.flag, (unsigned)q.mapq, q.l_seq, (long long)k, contig, v.pos, v.flag, v.mapq, v.l_seq);
+                return false;
+            }
+            tag = hp[k];
+            if (tag) {
+                const uint32_t set = (uint32_t)ps[k];
+                rec.insert(rec.end(), {'H', 'P', 'C', (uint8_t)tag, 'P', 'S'});
+                if (set < 256) { rec.push_back('C'); rec.push_back((uint8_t)set); }
+                else if (set < 65536) { rec.push_back('S'); put16(rec, set); }
+                else { rec.push_back('I'); put32(rec, set); }
+            }
+            ++k;
+        }
+        if (keep != 1) ++n_unpaired;
+        put32(sink.pend, (uint32_t)rec.size());                        // block_size
+        sink.pend.insert(sink.pend.end(), rec.begin(), rec.end());
+        ++n_written; n_tagged += tag != 0; n_stripped += removed;
+        if (!sink.grown()) { rc = failb(b, C3R_EINVAL, "%s: write failed", out_path); return false; }
+        return true;
+    };
+    int src = C3R_OK;
+    if (b->has_bai) {
+        // the contig's placed records lie in [lo, hi); records of the contig without a position sort before them, behind the last
+        // placed record of the contigs before: the pass starts there
+        uint64_t lo, hi, from = b->first_record_voff, plo, phi;
+        if (contig_span(b->bai[(size_t)tid], &lo, &hi) && hi > lo) {
+            for (int t = tid - 1; t >= 0; --t) if (contig_span(b->bai[(size_t)t], &plo, &phi) && phi > plo) { from = phi; break; }
+            if (from > lo) from = lo;
+            std::vector<BlockRef> blocks;
+            bool truncated = false;
+            src = list_blocks(b, (size_t)(from >> 16), (size_t)(hi >> 16) + ((hi & 0xffff) ? 1 : 0), blocks);
+            if (src == C3R_OK) src = scan_blocks(b, blocks, (size_t)(from & 0xffff), visit, &truncated);
+            if (src == C3R_OK && rc == C3R_OK && truncated) src = failb(b, C3R_EINVAL, "%s: the index does not match the file (a record of %s runs past its range)", b->path.c_str(), contig);
+        }
+    } else {
+        src = scan_all(b, visit);
+    }
+    if (rc == C3R_OK) rc = src;
+    if (rc == C3R_OK && paired && k != n_reads)
+        rc = failb(b, C3R_EINVAL, "%s: %s holds %lld read records, %lld were handed in (reads[%lld] has no record)", b->path.c_str(), contig, (long long)k, (long long)n_reads, (long long)k);
+    if (rc == C3R_OK && !(sink.flush(true) && fwrite(c3r_io::BGZF_EOF, 1, sizeof c3r_io::BGZF_EOF, sink.f) == sizeof c3r_io::BGZF_EOF))
+        rc = failb(b, C3R_EINVAL, "%s: write failed", out_path);
+    if (fclose(sink.f) != 0 && rc == C3R_OK) rc = failb(b, C3R_EINVAL, "%s: write failed", out_path);
+    if (rc != C3R_OK) { remove(out_path); return rc; }
+    if (counts) { counts[0] = n_written; counts[1] = n_tagged; counts[2] = n_stripped; counts[3] = n_unpaired; }
+    return C3R_OK;
+}

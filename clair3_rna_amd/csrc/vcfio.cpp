@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/c3r_io.h"
+#include "bgzf_out.hpp"
 #include <sched.h>
 
 // CPUs this process may run on (its affinity mask: one process per GPU is pinned to its share of the node, shard.host_budget), not the
@@ -185,10 +186,15 @@ int c3r_vcf_merge(const char *rows, int64_t n_bytes, int qual, int show_ref, con
 
 }  // extern "C"
 
-namespace {
+namespace c3r_io {
 const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-const size_t BLK = 0xff00;
+int deflate_threads(int threads) { return threads > 0 ? threads : (int)std::min(32u, std::max(1u, usable_cpus())); }
+}  // namespace c3r_io
+using c3r_io::BGZF_EOF;
+using c3r_io::BLK;
+using c3r_io::bgzf_compress;
 
+namespace {
 bool deflate_block(const uint8_t *src, size_t n, std::vector<uint8_t> &dst) {
     z_stream zs; memset(&zs, 0, sizeof zs);
     if (deflateInit2(&zs, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
@@ -210,8 +216,10 @@ bool deflate_block(const uint8_t *src, size_t n, std::vector<uint8_t> &dst) {
     return true;
 }
 
+}  // namespace
+
 // data -> BGZF (blocks of 0xff00 bytes, deflated on `threads` threads) in `out`; coffs[i] = file offset of block i
-bool bgzf_compress(const uint8_t *data, size_t n, int threads, std::vector<uint8_t> &out, std::vector<uint64_t> &coffs) {
+bool c3r_io::bgzf_compress(const uint8_t *data, size_t n, int threads, std::vector<uint8_t> &out, std::vector<uint64_t> &coffs) {
     const size_t nb = (n + BLK - 1) / BLK;
     std::vector<std::vector<uint8_t>> blocks(nb);
     std::atomic<size_t> next(0);
@@ -237,6 +245,7 @@ bool bgzf_compress(const uint8_t *data, size_t n, int threads, std::vector<uint8
     return true;
 }
 
+namespace {
 inline int reg2bin_vcf(int64_t beg, int64_t end) {
     --end;
     if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
@@ -373,7 +382,7 @@ int c3r_vcfz_open(const char *gz_path, int threads, c3r_vcfz **out) {
     *out = nullptr;
     c3r_vcfz *z = new c3r_vcfz();
     z->gz_path = gz_path;
-    z->threads = threads > 0 ? threads : (int)std::min(32u, std::max(1u, usable_cpus()));
+    z->threads = c3r_io::deflate_threads(threads);
     z->f = fopen(gz_path, "wb");
     if (!z->f) { delete z; return C3R_EINVAL; }
     *out = z;
@@ -412,7 +421,7 @@ int c3r_vcfz_piece_make(const char *text, int64_t n, int threads, c3r_vcfz_piece
     c3r_vcfz_piece *p = new c3r_vcfz_piece();
     p->n = (uint64_t)n;
     std::vector<uint64_t> co;
-    const int nt = threads > 0 ? threads : (int)std::min(32u, std::max(1u, usable_cpus()));
+    const int nt = c3r_io::deflate_threads(threads);
     if (n && !bgzf_compress((const uint8_t *)text, (size_t)n, nt, p->gz, co)) { delete p; return C3R_EINVAL; }
     const uint64_t gz_end = (uint64_t)p->gz.size() << 16;
     auto rel = [&](uint64_t u) { return u < (uint64_t)n ? (co[(size_t)(u / BLK)] << 16) | (u % BLK) : gz_end; };

@@ -1,5 +1,5 @@
 /* c3r_io.h — C ABI of libc3r_io.so: BAM/BGZF/BAI -> the flat read records c3r_load_reads takes; merged, bgzipped,
- * tabix-indexed VCF out.
+ * tabix-indexed VCF out; the haplotagged BAM of a contig out.
  *
  * Replaces the input side of the reference's `samtools mpileup <bam> -r ctg:beg-end` subprocess
  * (src/create_tensor_pileup.py:436-451; region set-up :409-428): open the BAM, use its .bai to find the
@@ -52,6 +52,40 @@ int c3r_bam_copy(c3r_bam *b, c3r_read_t *reads, uint32_t *cigar, uint8_t *seq);
 /* `samtools index` equivalent (samtools is not a dependency of this path): write a .bai for a
  * coordinate-sorted BAM. */
 int c3r_bam_index_build(const char *bam_path, const char *bai_path);
+
+/* The header text (l_text bytes, not terminated; points into the handle, valid until close): what a caller builds the @PG line of
+ * c3r_bam_write_haplotagged from. */
+int c3r_bam_header_text(c3r_bam *b, const char **text, int64_t *n_bytes);
+
+/* The haplotagged BAM of one contig: what `whatshap haplotag` / `longphase haplotag` + `samtools index` leave per contig in the
+ * reference's phased flow (run_clair3_rna:769-801: phased_bam/<ctg>.bam), with the tags the device computed (c3r_get_haplotags,
+ * c3r_get_read_phase_sets) instead of an external tool's.  The index is c3r_bam_index_build's job.
+ *
+ * The file: the input's header text and reference dictionary, unchanged but for `pg_line` (one "@PG\t..." line without its newline;
+ * NULL: none) appended to the text; then EVERY record of `contig` (ref_id = its index) in file order, the ones c3r_bam_fetch skips
+ * included; no record of another contig, none of the unplaced tail; then the 28-byte BGZF EOF block.  A contig without records
+ * gives header + EOF, a valid empty BAM.  (Through an index the pass covers the file range the index gives the contig, from the
+ * end of the contig before: in a coordinate-sorted file that is every record of the contig.)
+ *
+ * Pairing: reads[k], hp[k], ps[k] belong to the k-th record that c3r_bam_fetch(b, contig, 0, 0, ...) returns — the writer applies the
+ * fetch's own keep rule (one function in csrc/bamio.cpp) and checks pos, flag, mapq and l_seq of every such record against reads[k].
+ * C3R_EINVAL, a message that names the index, and NO output file: a mismatch of one of those fields; more or fewer kept records than
+ * n_reads; hp[k] > 2; hp[k] != 0 with ps[k] < 0.  n_reads = 0 with all three arrays NULL is allowed: nothing is paired, the records go
+ * out untagged.
+ *
+ * Aux fields: HP, PS and PC of any type are removed from every record of the contig, paired or not (a stale tag beside a fresh one
+ * would mislead).  Where hp[k] is 1 or 2, `HP:C:<hp>` and then PS in the smallest unsigned type that holds ps[k] (C / S / I) are
+ * appended behind the remaining fields; block_size follows.  Every other byte of the record is the input's, in the input's order:
+ * name, bin, the placeholder CIGAR with its CG array, qualities, the other aux fields.  A record whose aux area cannot be walked to
+ * its end (a field cut short, an unterminated string, an unknown type, a B array longer than the record) is C3R_EINVAL, never a
+ * silent pass-through.
+ *
+ * Blocks: the payload is cut every 0xff00 bytes wherever that falls (records straddle blocks), deflated on `threads` threads
+ * (<= 0: as c3r_vcf_compress) by the compressor the VCF writer uses, written in order; the bytes do not depend on `threads`.
+ * counts[4] (may be NULL) = records written, records tagged, records an old HP / PS / PC was removed from, records passed through
+ * unpaired (the ones the keep rule skips). */
+int c3r_bam_write_haplotagged(c3r_bam *b, const char *contig, const c3r_read_t *reads, const uint8_t *hp, const int32_t *ps, int64_t n_reads,
+                              const char *out_path, const char *pg_line, int threads, int64_t *counts);
 
 /* ---- output side (csrc/vcfio.cpp): what `sort_vcf` does after the per-chunk calls (src/sort_vcf.py:123-292).
  *
