@@ -164,6 +164,9 @@ def env_precision(default="f16x3"):
     return v
 
 
+CTG_END_MAX = 2147482590          # C3R_CTG_END_MAX (include/c3r.h, "coordinates"): the last ctg_end a scan accepts
+
+
 def default_params():
     p = Params()
     load_library().c3r_default_params(C.byref(p))

@@ -842,6 +842,7 @@ void c3r_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
 int c3r_set_reference(c3r_ctx *ctx, int64_t ref_start, const char *ref, int64_t len) {
     if (!ctx || !ref || len < 0 || ref_start < 1) return C3R_EINVAL;
+    if (ref_start - 1 + len > INT32_MAX) return fail(ctx, C3R_EINVAL, "reference slice ends beyond 2^31");          // (the kernels index it by 32-bit offsets)
     ctx->last_scan_pruned = false;       // (c3r_get_columns completes a pruned scan with the arguments of that scan: stale now)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // The slice is upper-cased straight into a page-locked buffer the context keeps (one pass over the caller's bytes, on threads for a
@@ -895,6 +896,7 @@ int c3r_set_reference(c3r_ctx *ctx, int64_t ref_start, const char *ref, int64_t 
 
 int c3r_set_reference_view(c3r_ctx *ctx, int64_t ref_start, const char *ref_upper, int64_t len) {
     if (!ctx || !ref_upper || len < 0 || ref_start < 1) return C3R_EINVAL;
+    if (ref_start - 1 + len > INT32_MAX) return fail(ctx, C3R_EINVAL, "reference slice ends beyond 2^31");          // (the kernels index it by 32-bit offsets)
     ctx->last_scan_pruned = false;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // Nothing is copied on the host: the decoder reads the caller's bytes (kept alive and unchanged by the caller, see c3r.h) and the
@@ -1511,7 +1513,8 @@ int c3r_pileup_scan_regions(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_
     if (ctx->ref_len == 0) return fail(ctx, C3R_EINVAL, "c3r_set_reference must be called before c3r_pileup_scan");
     for (int r = 0; r < n_regions; ++r) {
         if (ctg_ends[r] < ctg_starts[r]) return C3R_EINVAL;
-        if (ctg_ends[r] + C3R_WINDOW > INT32_MAX - 1) return fail(ctx, C3R_EINVAL, "region beyond 2^31");
+        // (the scan kernels add up to two tiles and a flank to a region position in plain int: C3R_CTG_END_MAX leaves them 1024, include/c3r.h)
+        if (ctg_ends[r] > C3R_CTG_END_MAX) return fail(ctx, C3R_EINVAL, "region %d ends beyond C3R_CTG_END_MAX = %lld (2^31 - 1 - 33 - 1024)", r, (long long)C3R_CTG_END_MAX);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (n_candidates) *n_candidates = 0;

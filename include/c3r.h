@@ -67,6 +67,24 @@ void c3r_default_params(c3r_params_t *p);
  * (including the reference's shared pre-fill column, [[0]*C]*33, that padding edits in place). */
 int c3r_set_params(c3r_ctx *ctx, const c3r_params_t *p);
 
+/* ---- coordinates --------------------------------------------------------------------------- */
+/* Positions are 32-bit on the device.  The accepted domain, and what refuses a value outside it (C3R_EINVAL with a message):
+ *   reads (c3r_load_reads): pos is 0-based and >= 0; the 0-based EXCLUSIVE end pos + reference length of the CIGAR is at most INT32_MAX
+ *     (2,147,483,647), i.e. a read's last base lies on 1-based 2,147,483,647 at most — "read <i> ends beyond 2^31".  One CIGAR op holds 2^28 - 1.
+ *   regions (c3r_pileup_scan, c3r_pileup_scan_regions): 1-based, ctg_start <= ctg_end <= C3R_CTG_END_MAX = 2,147,482,590 — "region <r> ends
+ *     beyond C3R_CTG_END_MAX".  The rows of a region reach ctg_end + 33, and the kernels add up to two tiles of 256 positions and a flank of 16 to
+ *     a row's position in 32-bit arithmetic: the limit leaves them 1024 below INT32_MAX.  A start below 34 is clamped (rows begin at 1).
+ *     Reads may lie, and end, above the last accepted region end; a scan never looks at more of them than its rows.
+ *   reference slice (c3r_set_reference, c3r_set_reference_view): 1-based ref_start >= 1 and ref_start - 1 + len <= INT32_MAX — "reference slice
+ *     ends beyond 2^31".
+ *   BED intervals (c3r_set_bed): 0-based half-open int32 pairs, 0 <= start < end <= INT32_MAX; they are only compared with row positions.
+ *   genotyping sites (c3r_set_sites): 1-based int32, 1 .. INT32_MAX; only compared.
+ *   phase sites and query sites (c3r_set_phase_sites, c3r_hap_counts, c3r_hap_allele_counts, c3r_phase_links, c3r_phase_unit_links): 1-based
+ *     int32 pos, 1 .. INT32_MAX, compared with read positions in 64-bit arithmetic; ps is a name (a position by convention), -1 or 0 .. INT32_MAX.
+ * GRCh38 chr1 is 248,956,422 bp; BAI indexing ends at 2^29.  tests/test_gpu_coords.py runs the kernels at chr1 scale, at 2^28 and on the last
+ * accepted and first refused values above. */
+#define C3R_CTG_END_MAX 2147482590LL          /* INT32_MAX - 33 - 1024 */
+
 /* ---- inputs -------------------------------------------------------------------------------- */
 /* Hand over one contig's aligned reads, sorted by pos (BAM order), as flat host-resident records.  Replaces the BAM side of
  * `samtools mpileup <bam> -r ...` (src/create_tensor_pileup.py:446-451): the records are copied to the device as they are and

@@ -124,7 +124,8 @@ def _rand_cigar(rng, want_q, pads=True):
     return "".join("%d%s" % lo for lo in ops), qlen
 
 
-def _case(seed, phased, pads=True):
+def _case(seed, phased, pads=True, info=None):
+    """info: a dict that receives `hot`, the 0-based centre of the pile (place() puts it on a chosen coordinate)."""
     import random
     import re
     rng = random.Random(seed)
@@ -138,6 +139,8 @@ def _case(seed, phased, pads=True):
     recs = []
     n_reads = rng.randint(25, 90)
     hot = rng.randint(30, L - 120)
+    if info is not None:
+        info["hot"] = hot
     for _ in range(n_reads):
         pos = max(1, int(rng.gauss(hot, 40)))
         cg, qlen = _rand_cigar(rng, 0, pads)
@@ -156,6 +159,105 @@ def _case(seed, phased, pads=True):
     return ref, recs
 
 
+# ---- coordinates: the same cases translated to chromosome scale and to the end of the accepted domain (tests/test_coords_ref.py: the references do
+# not depend on the translation; tests/test_gpu_coords.py: neither does the engine).  A translation is an int, or f(L, hot) -> int for one that
+# depends on the case (L: the length of its reference, hot: the 0-based centre of its pile).
+INT32_MAX = 2 ** 31 - 1
+CTG_END_MAX = 2147482590            # C3R_CTG_END_MAX (include/c3r.h): the last ctg_end a scan accepts; a read may END on INT32_MAX (0-based, exclusive)
+CHR1_LEN = 248956422                # GRCh38 chr1
+K_LOW = 1000                        # magnitude as in every other test: only the phases against bins and tiles move
+
+
+def K_CHR1(L, hot):
+    """the case's last reference base sits on the last base of chr1"""
+    return CHR1_LEN - L
+
+
+def K_2_28(L, hot):
+    """the centre of the pile sits on 0-based 2^28 (the length limit of one CIGAR op: no human contig reaches it, the accepted domain does)"""
+    return (1 << 28) - hot
+
+
+def K_TOP(L, hot):
+    """the scan of the whole case ends on the last accepted ctg_end"""
+    return CTG_END_MAX - L
+
+
+def k_plus(K, phi):
+    """K + phi: the reads' phase against the bins (pos >> 5)"""
+    if not callable(K):
+        return K + phi
+    return lambda L, hot: K(L, hot) + phi
+
+
+PHIS = (0, 1, 31)                   # reads against bins
+FRONTS = (0, 1, 223, 255)           # tile starts (ctg_start - 34) against reads, bins (32) and coarse bins (256); spans are 224 positions
+
+
+def shift_records(recs, K):
+    return recs if K == 0 else [dict(r, pos=r["pos"] + K) for r in recs]
+
+
+def place(ref, recs, shift, front, hot, seed):
+    """A case at its coordinates: (K, records with pos + K, reference slice with `front` random bases before the case's first base, 1-based
+    position `first` of the slice's first base = 1 + K - front).  A scan of the whole case runs from `first` to first + len(slice) - 1: nothing
+    covers the front positions, they only move the first tile's p0 = first - 34 (front > 0 requires K >= front + 34: no clamp at 1).  Engine and
+    oracle get the same slice; the front bases show only where head/tail calling prints the reference under a window that begins before the case."""
+    import random
+    K = shift(len(ref), hot) if callable(shift) else int(shift)
+    if front:
+        assert K >= front + 34, (K, front)
+        rng = random.Random(911 * seed + front)
+        ref = "".join(rng.choice("ACGT") for _ in range(front)) + ref
+    return K, shift_records(recs, K), ref, 1 + K - front
+
+
+def placed_case(seed, phased, shift=0, front=0, pads=True):
+    """(ReadSet, reference slice, first, last, records) of _case(seed) at its coordinates (place)."""
+    from clair3_rna_amd.reads import ReadSet
+    info = {}
+    ref, recs = _case(seed, phased=phased, pads=pads, info=info)
+    K, recs, ref, first = place(ref, recs, shift, front, info["hot"], seed)
+    return ReadSet.from_records(recs), ref, first, first + len(ref) - 1, recs
+
+
+def shift_readset(rs, K):
+    """The same reads K positions further (CIGARs and bases shared)."""
+    from clair3_rna_amd.reads import ReadSet
+    reads = rs.reads.copy()
+    assert int(reads["pos"].max(initial=0)) + K <= INT32_MAX
+    reads["pos"] += K
+    return ReadSet(reads, rs.cigar, rs.seq)
+
+
+def readset_end(rs):
+    """The largest 0-based exclusive end of the reads' alignments."""
+    best = 0
+    for r in rs.reads:
+        c = rs.cigar[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["n_cigar"])]
+        best = max(best, int(r["pos"]) + int(sum(int(x) >> 4 for x in c if "MIDNSHP=X"[int(x) & 15] in "MDN=X")))
+    return best
+
+
+def shift_sites(sites, K, ps=False):
+    """A site table (PHASE_SITE_DTYPE / HAP_SITE_DTYPE) K positions further; ps (phase-set names) stay unless ps=True."""
+    out = sites.copy()
+    out["pos"] += K
+    if ps:
+        out["ps"] = np.where(out["ps"] >= 0, out["ps"] + K, out["ps"])
+    return out
+
+
+def shift_lines(lines, K, field=1):
+    """Tab-separated lines with the position field moved by K (the oracle's lines and mpileup rows, VCF rows)."""
+    out = []
+    for l in lines:
+        f = l.split("\t")
+        f[field] = str(int(f[field]) + K)
+        out.append("\t".join(f))
+    return out
+
+
 def _scanned(on_scan, eng, exp):
     """on_scan(eng, exp): a caller's look at the engine after a scan (Engine.scan_counts(): which kernels built the spans; it stands until the
     next scan, the raw re-run behind tensors(rescaled=False) and columns() leave it alone); exp is the oracle's result for that scan, or a list
@@ -164,9 +266,11 @@ def _scanned(on_scan, eng, exp):
         on_scan(eng, exp)
 
 
-def fuzz_match_oracle(eng, seeds, kw, case_base, on_scan=None):
+def fuzz_match_oracle(eng, seeds, kw, case_base, on_scan=None, shift=0, front=0):
     """The random read sets case_base + seed through the engine with the parameters kw: every line equals the oracle's, and (18 channels,
-    no splice padding) every column of the scan equals generate_tensor on the oracle's mpileup row.  Returns (cases, lines) seen."""
+    no splice padding) every column of the scan equals generate_tensor on the oracle's mpileup row.  Returns (cases, lines) seen.
+    shift, front (here and in the helpers below): the case translated by place() — reads, reference slice, region, BED intervals and sites move
+    together; the defaults are the case as generated."""
     from clair3_rna_amd import capi
     from clair3_rna_amd.reads import ReadSet
     channels = kw.get("channels", 18)
@@ -179,14 +283,13 @@ def fuzz_match_oracle(eng, seeds, kw, case_base, on_scan=None):
         okw["snp_af"] = okw.pop("snp_min_af")
     n_cases, n_lines = 0, 0
     for seed in seeds:
-        ref, recs = _case(case_base + seed, phased=(channels == 30))
-        rs = ReadSet.from_records(recs)
+        rs, ref, first, last, recs = placed_case(case_base + seed, channels == 30, shift, front)
         eng.params = capi.default_params()
         eng.set_bed(0, None); eng.set_bed(1, None)
         eng.set_params(min_coverage=kw.get("min_coverage", 2), **{k: v for k, v in kw.items() if k != "min_coverage"})
-        exp = oracle_chunk(rs, ref, 1, 1, len(ref), channels=channels, min_coverage=kw.get("min_coverage", 2),
+        exp = oracle_chunk(rs, ref, first, first, last, channels=channels, min_coverage=kw.get("min_coverage", 2),
                            **{k: v for k, v in okw.items() if k != "min_coverage"})
-        got = engine_chunk(eng, rs, ref, 1, 1, len(ref))
+        got = engine_chunk(eng, rs, ref, first, first, last)
         _scanned(on_scan, eng, exp)
         assert got["lines"] == exp["lines"], (seed, recs, first_diff(got["lines"], exp["lines"]))
         if channels == 18 and not kw.get("splice_padding"):
@@ -196,7 +299,7 @@ def fuzz_match_oracle(eng, seeds, kw, case_base, on_scan=None):
             for row in rows:
                 f = row.split("\t")
                 pos = int(f[1])
-                o = orc.generate_tensor(f[4], ref[pos - 1].upper(), pos, ref.upper(), 1, snp_af=okw.get("snp_af", 0.08))
+                o = orc.generate_tensor(f[4], ref[pos - first].upper(), pos, ref.upper(), first, snp_af=okw.get("snp_af", 0.08))
                 i = pos - col["region_start"]
                 assert col["cols"][i].tolist() == o["tensor"], (seed, pos, f[4], recs)
                 assert col["depth"][i] == o["depth"], (seed, pos)
@@ -207,7 +310,7 @@ def fuzz_match_oracle(eng, seeds, kw, case_base, on_scan=None):
     return n_cases, n_lines
 
 
-def fuzz_samtools_1_11(eng, seeds, kw, case_base, on_scan=None):
+def fuzz_samtools_1_11(eng, seeds, kw, case_base, on_scan=None, shift=0, front=0):
     """The same with c3r_params_t.mpileup_compat = 1 (pads inside insertions, a deletion right behind an insertion).  Returns
     (lines, columns that show an insertion with a deletion behind it, padded alleles, cases the pad table refused)."""
     import re
@@ -218,14 +321,13 @@ def fuzz_samtools_1_11(eng, seeds, kw, case_base, on_scan=None):
     n_lines, n_both, n_padded, n_refused = 0, 0, 0, 0
     eng.load_reads(ReadSet.from_records([]))
     for seed in seeds:
-        ref, recs = _case(case_base + seed, phased=(channels == 30), pads=True)
-        rs = ReadSet.from_records(recs)
+        rs, ref, first, last, recs = placed_case(case_base + seed, channels == 30, shift, front)
         eng.params = capi.default_params()
         eng.set_bed(0, None); eng.set_bed(1, None)
         eng.set_params(min_coverage=2, mpileup_compat=1, **kw)
-        exp = oracle_chunk(rs, ref, 1, 1, len(ref), channels=channels, min_coverage=2, mpileup_compat=1, **okw)
+        exp = oracle_chunk(rs, ref, first, first, last, channels=channels, min_coverage=2, mpileup_compat=1, **okw)
         try:
-            got = engine_chunk(eng, rs, ref, 1, 1, len(ref))
+            got = engine_chunk(eng, rs, ref, first, first, last)
             _scanned(on_scan, eng, exp)
         except capi.C3RError as e:
             # the documented limit of the pad table (c3r_padins_t: a 64-bit mask per run of I and P ops); the generator reaches it on a few seeds
@@ -238,8 +340,8 @@ def fuzz_samtools_1_11(eng, seeds, kw, case_base, on_scan=None):
         n_padded += sum(1 for l in exp["lines"] if re.search(r" I[ACGT][A-Z=]*[*#]", l.split("\t")[4]))
         if seed % 20 == 0:                      # the same reads with the <= 1.10 text: the records are rebuilt when the parameter changes
             eng.set_params(min_coverage=2, mpileup_compat=0, **kw)
-            n0 = eng.scan(1, len(ref))
-            old = oracle_chunk(rs, ref, 1, 1, len(ref), channels=channels, min_coverage=2, **okw)
+            n0 = eng.scan(first, last)
+            old = oracle_chunk(rs, ref, first, first, last, channels=channels, min_coverage=2, **okw)
             _scanned(on_scan, eng, old)
             assert n0 == len(old["lines"])
     eng.params = capi.default_params()
@@ -247,51 +349,70 @@ def fuzz_samtools_1_11(eng, seeds, kw, case_base, on_scan=None):
     return n_lines, n_both, n_padded, n_refused
 
 
-def fuzz_filters_and_regions(eng, seeds, mode, case_base, rng_base, head_tail=None, on_scan=None):
+def filters_case(seed, mode, case_base, rng_base, head_tail=None, shift=0, front=0):
+    """The inputs of one case of fuzz_filters_and_regions at their coordinates (place): dict(rs, ref, ref_start, a, b, lbed, cbed, sites, ht).
+    The random draws are made in the case's own coordinates and translated afterwards, so a case is the same case at every translation."""
+    import random
+    from clair3_rna_amd.reads import ReadSet
+    rng = random.Random(rng_base + seed)
+    info = {}
+    ref, recs = _case(case_base + seed, phased=False, info=info)
+    if mode == "deep":              # replicate the reads: depth 150-400 with identical alleles (I1/D1 multiplicities, rescale)
+        rep = rng.randint(6, 9)
+        recs = [dict(r) for r in recs for _ in range(rep)]
+        recs.sort(key=lambda r: r["pos"])
+    L = len(ref)
+
+    def intervals(k):
+        out = []
+        for _ in range(k):
+            a = rng.randint(0, L - 2)
+            out.append((a, min(L, a + rng.choice([1, 2, 5, 17, 33, 60, 150]))))
+        return out
+    lbed = intervals(rng.randint(1, 6)) if mode in ("lbed", "both_beds") else None
+    cbed = intervals(rng.randint(1, 6)) if mode in ("cbed", "both_beds") else None
+    sites = sorted(set(rng.randint(1, L) for _ in range(rng.randint(1, 25)))) if mode == "sites" else None
+    ref_start, a, b = 1, 1, L
+    if mode == "subregion":
+        a = rng.randint(2, L // 2); b = rng.randint(a, L)
+        ref_start = rng.randint(1, max(1, a - 49))   # the slice starts before the region's halo and its windows (the
+                                                     # reference fetches ctg_start - 1000: every row and flank is covered)
+    if mode == "sites":
+        a, b = min(sites), max(sites)
+    ht = seed % 2 if head_tail is None else int(head_tail)
+    K, recs, ref, first = place(ref, recs, shift, front, info["hot"], case_base + seed)
+    if K:
+        lbed = lbed and [(x + K, y + K) for x, y in lbed]
+        cbed = cbed and [(x + K, y + K) for x, y in cbed]
+        sites = sites and [x + K for x in sites]
+    # (the slice: `front` more bases before ref_start; the region: `front` more positions before a)
+    return dict(rs=ReadSet.from_records(recs), ref=ref[ref_start - 1:], ref_start=ref_start + K - front, a=a + K - front, b=b + K,
+                lbed=lbed, cbed=cbed, sites=sites, ht=ht)
+
+
+def filters_oracle(c):
+    return oracle_chunk(c["rs"], c["ref"], c["ref_start"], c["a"], c["b"], lbed=c["lbed"], bed=c["cbed"], sites=c["sites"], min_coverage=2,
+                        head_tail=bool(c["ht"]))
+
+
+def fuzz_filters_and_regions(eng, seeds, mode, case_base, rng_base, head_tail=None, on_scan=None, shift=0, front=0):
     """The random read sets through the -l BED, the confident BED, a genotyping site list, a sub-region with a shifted reference slice,
     and at depths that cross the 216 rescale threshold.  head_tail: None = on for the odd seeds, else that value for every case.
     Returns the lines seen."""
-    import random
     from clair3_rna_amd import capi
-    from clair3_rna_amd.reads import ReadSet
     n_lines = 0
     for seed in seeds:
-        rng = random.Random(rng_base + seed)
-        ref, recs = _case(case_base + seed, phased=False)
-        if mode == "deep":              # replicate the reads: depth 150-400 with identical alleles (I1/D1 multiplicities, rescale)
-            rep = rng.randint(6, 9)
-            recs = [dict(r) for r in recs for _ in range(rep)]
-            recs.sort(key=lambda r: r["pos"])
-        rs = ReadSet.from_records(recs)
-        L = len(ref)
-
-        def intervals(k):
-            out = []
-            for _ in range(k):
-                a = rng.randint(0, L - 2)
-                out.append((a, min(L, a + rng.choice([1, 2, 5, 17, 33, 60, 150]))))
-            return out
-        lbed = intervals(rng.randint(1, 6)) if mode in ("lbed", "both_beds") else None
-        cbed = intervals(rng.randint(1, 6)) if mode in ("cbed", "both_beds") else None
-        sites = sorted(set(rng.randint(1, L) for _ in range(rng.randint(1, 25)))) if mode == "sites" else None
-        ref_start, a, b = 1, 1, L
-        if mode == "subregion":
-            a = rng.randint(2, L // 2); b = rng.randint(a, L)
-            ref_start = rng.randint(1, max(1, a - 49))   # the slice starts before the region's halo and its windows (the
-                                                         # reference fetches ctg_start - 1000: every row and flank is covered)
-        if mode == "sites":
-            a, b = min(sites), max(sites)
-        ht = seed % 2 if head_tail is None else int(head_tail)
+        c = filters_case(seed, mode, case_base, rng_base, head_tail, shift, front)
+        lbed, cbed, sites = c["lbed"], c["cbed"], c["sites"]
         eng.params = capi.default_params()
         eng.set_bed(0, lbed); eng.set_bed(1, cbed)
         if sites is not None:
             eng.set_sites(sites)
-        eng.set_params(min_coverage=2, genotyping_mode=int(sites is not None), head_tail=ht)
-        refslice = ref[ref_start - 1:]
-        exp = oracle_chunk(rs, refslice, ref_start, a, b, lbed=lbed, bed=cbed, sites=sites, min_coverage=2, head_tail=bool(ht))
-        got = engine_chunk(eng, rs, refslice, ref_start, a, b)
+        eng.set_params(min_coverage=2, genotyping_mode=int(sites is not None), head_tail=c["ht"])
+        exp = filters_oracle(c)
+        got = engine_chunk(eng, c["rs"], c["ref"], c["ref_start"], c["a"], c["b"])
         _scanned(on_scan, eng, exp)
-        assert got["lines"] == exp["lines"], (mode, seed, lbed, cbed, sites, (ref_start, a, b), first_diff(got["lines"], exp["lines"]))
+        assert got["lines"] == exp["lines"], (mode, seed, lbed, cbed, sites, (c["ref_start"], c["a"], c["b"]), first_diff(got["lines"], exp["lines"]))
         assert np.array_equal(got["X"], exp["X"]), (mode, seed)
         n_lines += len(exp["lines"])
     eng.params = capi.default_params()
@@ -300,7 +421,7 @@ def fuzz_filters_and_regions(eng, seeds, mode, case_base, rng_base, head_tail=No
     return n_lines
 
 
-def fuzz_decode_rows_and_regions(eng, seeds, compat, case_base, rng_base, on_scan=None):
+def fuzz_decode_rows_and_regions(eng, seeds, compat, case_base, rng_base, on_scan=None, shift=0, front=0):
     """On the random read sets: (1) c3r_call_rows (C++: tokens -> ordered alt_info -> decode -> row text) equals the Python path fed with the
     ORACLE's alt_info strings; (2) a multi-region scan over random chunk boundaries equals successive scans.  Returns (rows, genotypes seen)."""
     import random
@@ -314,16 +435,15 @@ def fuzz_decode_rows_and_regions(eng, seeds, compat, case_base, rng_base, on_sca
     seeds = list(seeds)
     for seed in seeds:
         rng = random.Random(rng_base + seed)
-        ref, recs = _case(case_base + seed, phased=False, pads=True)
-        rs = ReadSet.from_records(recs)
-        L = len(ref)
+        rs, ref, first, last, recs = placed_case(case_base + seed, False, shift, front)
+        L, K = last - first + 1 - front, first + front - 1          # (the case's own length; its translation)
         eng.params = capi.default_params()
         eng.set_bed(0, None); eng.set_bed(1, None)
         if seed == seeds[0]:
             eng.load_reads(ReadSet.from_records([]))
         eng.set_params(min_coverage=2, mpileup_compat=compat)
-        exp = oracle_chunk(rs, ref, 1, 1, L, min_coverage=2, mpileup_compat=compat)
-        got = engine_chunk(eng, rs, ref, 1, 1, L)
+        exp = oracle_chunk(rs, ref, first, first, last, min_coverage=2, mpileup_compat=compat)
+        got = engine_chunk(eng, rs, ref, first, first, last)
         _scanned(on_scan, eng, exp)
         assert got["lines"] == exp["lines"]
         if exp["lines"]:
@@ -338,6 +458,7 @@ def fuzz_decode_rows_and_regions(eng, seeds, compat, case_base, rng_base, on_sca
             kinds.update(r.split("\t")[9].split(":")[0] for r in py)
         # random chunking of the same contig
         cuts = sorted(set([1, L] + [rng.randint(2, L - 1) for _ in range(rng.randint(1, 5))]))
+        cuts = [first] + [c + K for c in cuts[1:]]
         chunks = [(cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
         eng.begin_batch()
         for a, b in chunks:
@@ -353,7 +474,7 @@ def fuzz_decode_rows_and_regions(eng, seeds, compat, case_base, rng_base, on_sca
     return n_rows, kinds
 
 
-def fuzz_depth_cap(eng, seeds, channels, case_base, rng_base, splice_padding=None, head_tail=None, on_scan=None):
+def fuzz_depth_cap(eng, seeds, channels, case_base, rng_base, splice_padding=None, head_tail=None, on_scan=None, shift=0, front=0):
     """samtools mpileup -d on replicated random read sets, small caps: the engine equals the oracle for the region and for its two halves
     (a two-region scan equals two successive scans equals the per-region oracle).  splice_padding / head_tail: None = by the seed's
     low bits, else that value for every case.  Returns the cases in which the cap changed the output."""
@@ -363,12 +484,14 @@ def fuzz_depth_cap(eng, seeds, channels, case_base, rng_base, splice_padding=Non
     n_dropped_cases = 0
     for seed in seeds:
         rng = random.Random(rng_base + seed)
-        ref, recs = _case(case_base + seed, phased=(channels == 30))
+        info = {}
+        ref, recs = _case(case_base + seed, phased=(channels == 30), info=info)
         rep = rng.randint(3, 7)
         recs = [dict(r) for r in recs for _ in range(rep)]
         recs.sort(key=lambda r: r["pos"])
-        rs = ReadSet.from_records(recs)
         L = len(ref)
+        K, recs, ref, first = place(ref, recs, shift, front, info["hot"], case_base + seed)
+        rs = ReadSet.from_records(recs)
         cap = rng.choice([8, 20, 60, 150])
         sp = seed % 2 if splice_padding is None else int(splice_padding)
         ht = (seed // 2) % 2 if head_tail is None else int(head_tail)
@@ -378,17 +501,18 @@ def fuzz_depth_cap(eng, seeds, channels, case_base, rng_base, splice_padding=Non
         eng.set_bed(0, None); eng.set_bed(1, None)
         eng.set_params(channels=channels, **kw)
         a = rng.randint(1, L // 3); b = rng.randint(2 * L // 3, L)
-        exp = oracle_chunk(rs, ref, 1, a, b, max_depth=cap, **okw)
-        got = engine_chunk(eng, rs, ref, 1, a, b)
+        a, b = a + K - front, b + K
+        exp = oracle_chunk(rs, ref, first, a, b, max_depth=cap, **okw)
+        got = engine_chunk(eng, rs, ref, first, a, b)
         _scanned(on_scan, eng, exp)
-        nocap = oracle_chunk(rs, ref, 1, a, b, max_depth=0, **okw)
+        nocap = oracle_chunk(rs, ref, first, a, b, max_depth=0, **okw)
         n_dropped_cases += int(exp["lines"] != nocap["lines"])
         assert got["lines"] == exp["lines"], (seed, cap, first_diff(got["lines"], exp["lines"]))
         assert np.array_equal(got["X"], exp["X"])
         # the same through a two-region scan (masks are per region)
         mid = (a + b) // 2
-        e1 = oracle_chunk(rs, ref, 1, a, mid, max_depth=cap, **okw)
-        e2 = oracle_chunk(rs, ref, 1, mid, b, max_depth=cap, **okw)
+        e1 = oracle_chunk(rs, ref, first, a, mid, max_depth=cap, **okw)
+        e2 = oracle_chunk(rs, ref, first, mid, b, max_depth=cap, **okw)
         eng.begin_batch()
         eng.scan(a, mid); _scanned(on_scan, eng, e1)
         eng.scan(mid, b); _scanned(on_scan, eng, e2)
@@ -402,6 +526,78 @@ def fuzz_depth_cap(eng, seeds, channels, case_base, rng_base, splice_padding=Non
     eng.params = capi.default_params()
     eng.set_params()
     return n_dropped_cases
+
+
+# ---- the deep routes (tests/test_gpu_deep_routes.py, tests/test_gpu_coords.py): environment variables that the library reads at every scan
+NEVER = str(1 << 30)
+ROUTES = {
+    # every listed span: k_fused_deep, no arrival-order buffer — a span above 3072 events walks its records again
+    "deep_walk_twice": dict(C3R_DEEP_MIN="1", C3R_SPLIT_MIN=NEVER, C3R_EVWG="0"),
+    # every listed span: k_fused_deep, events taken from the workgroup's buffer (up to 49152)
+    "deep_event_buffer": dict(C3R_DEEP_MIN="1", C3R_SPLIT_MIN=NEVER, C3R_EVWG="1"),
+    # every listed span: k_deep_walk in 64-record slices, alleles from k_deep_alleles' table (the soak of tests/evidence/README.md)
+    "giant_slices": dict(C3R_DEEP_MIN="1", C3R_SPLIT_MIN="1", C3R_GIANT="1", C3R_EVWG="1", C3R_SPLIT_CUS="1000000000", C3R_SPLIT_SLICE="64"),
+    # the natural thresholds
+    "default": dict(),
+    # (control) every span: k_fused_tiles
+    "tiles_only": dict(C3R_DEEP_MIN=NEVER),
+}
+ROUTE_VARS = sorted(set(k for r in ROUTES.values() for k in r))
+SLICE, MAX_SLICES, SLOTS = 64, 32, 256         # C3R_SPLIT_SLICE above; GIANT_MAX_HELP; GIANT_SLOTS
+
+
+def _set_route(monkeypatch, route):
+    for k in ROUTE_VARS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in ROUTES[route].items():
+        monkeypatch.setenv(k, v)
+
+
+def routed_get(monkeypatch, engines):
+    """The body of a test module's `routed` fixture.  routed(route) -> the route's engine: a context of its own, created after the route's
+    variables are set, kept in the module's `engines` (which the module closes at its end)."""
+    def get(route, fresh=False):
+        from clair3_rna_amd import capi
+        _set_route(monkeypatch, route)
+        if fresh:
+            return capi.Engine(0)
+        if route not in engines:
+            engines[route] = capi.Engine(0)
+        return engines[route]
+    return get
+
+
+def _most_aligned(exp):
+    """The most reads that show a base or a deletion on one position (each is a record of the span that holds the position)."""
+    best = 0
+    for row in exp["rows"]:
+        f = row.split("\t")
+        if int(f[3]) > best:                       # (mpileup's own depth counts ref-skips too: an upper bound, so look closer only then)
+            b = f[4]
+            best = max(best, int(f[3]) - b.count("<") - b.count(">"))
+    return best
+
+
+def route_check(route, seen=None):
+    """on_scan(eng, exp) for the fuzz helpers above: the assertions on Engine.scan_counts() that hold after EVERY scan of a route."""
+    def on_scan(eng, exp):
+        c = eng.scan_counts()
+        exps = [e for e in (exp if isinstance(exp, list) else [exp]) if e is not None]
+        if any(e["lines"] for e in exps):
+            assert c["listed"] > 0, (route, c)
+        if route in ("deep_walk_twice", "deep_event_buffer"):
+            assert c["deep"] == c["listed"] and c["giant"] == 0 and c["slices"] == 0, (route, c)
+        elif route == "giant_slices":
+            assert c["deep"] == c["listed"] and c["giant"] == c["listed"] and c["slices"] >= min(c["giant"], SLOTS), (route, c)
+            if c["giant"] <= SLOTS and any(_most_aligned(e) > SLICE for e in exps):
+                assert c["slices"] > c["giant"], (route, c)
+        elif route == "tiles_only":
+            assert c["deep"] == 0 and c["giant"] == 0 and c["slices"] == 0, (route, c)
+        if seen is not None:
+            for k in c:
+                seen[k] = seen.get(k, 0) + c[k]
+            seen["scans"] = seen.get("scans", 0) + 1
+    return on_scan
 
 
 # ---- read sets sized for the thresholds of the deep-span kernels (tests/test_gpu_deep_routes.py) ------------------------------------------

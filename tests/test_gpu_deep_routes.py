@@ -21,22 +21,9 @@ from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-NEVER = str(1 << 30)
-ROUTES = {
-    # every listed span: k_fused_deep, no arrival-order buffer — a span above 3072 events walks its records again
-    "deep_walk_twice": dict(C3R_DEEP_MIN="1", C3R_SPLIT_MIN=NEVER, C3R_EVWG="0"),
-    # every listed span: k_fused_deep, events taken from the workgroup's buffer (up to 49152)
-    "deep_event_buffer": dict(C3R_DEEP_MIN="1", C3R_SPLIT_MIN=NEVER, C3R_EVWG="1"),
-    # every listed span: k_deep_walk in 64-record slices, alleles from k_deep_alleles' table (the soak of tests/evidence/README.md)
-    "giant_slices": dict(C3R_DEEP_MIN="1", C3R_SPLIT_MIN="1", C3R_GIANT="1", C3R_EVWG="1", C3R_SPLIT_CUS="1000000000", C3R_SPLIT_SLICE="64"),
-    # the natural thresholds
-    "default": dict(),
-    # (control) every span: k_fused_tiles
-    "tiles_only": dict(C3R_DEEP_MIN=NEVER),
-}
-ROUTE_VARS = sorted(set(k for r in ROUTES.values() for k in r))
+ROUTES, ROUTE_VARS, _set_route, route_check, _most_aligned = H.ROUTES, H.ROUTE_VARS, H._set_route, H.route_check, H._most_aligned          # shared with tests/test_gpu_coords.py (tests/helpers.py)
 FORCED = ["deep_walk_twice", "deep_event_buffer", "giant_slices"]
-SLICE, MAX_SLICES, SLOTS = 64, 32, 256         # C3R_SPLIT_SLICE above; GIANT_MAX_HELP; GIANT_SLOTS
+SLICE, MAX_SLICES, SLOTS = H.SLICE, H.MAX_SLICES, H.SLOTS         # C3R_SPLIT_SLICE of the route; GIANT_MAX_HELP; GIANT_SLOTS
 
 _engines = {}
 
@@ -49,58 +36,10 @@ def _close_engines():
     _engines.clear()
 
 
-def _set_route(monkeypatch, route):
-    for k in ROUTE_VARS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in ROUTES[route].items():
-        monkeypatch.setenv(k, v)
-
-
 @pytest.fixture
 def routed(monkeypatch):
     """routed(route) -> the route's engine: a context of its own, created after the route's variables are set, closed at the end of the module."""
-    def get(route, fresh=False):
-        from clair3_rna_amd import capi
-        _set_route(monkeypatch, route)
-        if fresh:
-            return capi.Engine(0)
-        if route not in _engines:
-            _engines[route] = capi.Engine(0)
-        return _engines[route]
-    return get
-
-
-def _most_aligned(exp):
-    """The most reads that show a base or a deletion on one position (each is a record of the span that holds the position)."""
-    best = 0
-    for row in exp["rows"]:
-        f = row.split("\t")
-        if int(f[3]) > best:                       # (mpileup's own depth counts ref-skips too: an upper bound, so look closer only then)
-            b = f[4]
-            best = max(best, int(f[3]) - b.count("<") - b.count(">"))
-    return best
-
-
-def route_check(route, seen=None):
-    """on_scan(eng, exp) for tests/helpers.py: the assertions on Engine.scan_counts() that hold after EVERY scan of a route."""
-    def on_scan(eng, exp):
-        c = eng.scan_counts()
-        exps = [e for e in (exp if isinstance(exp, list) else [exp]) if e is not None]
-        if any(e["lines"] for e in exps):
-            assert c["listed"] > 0, (route, c)
-        if route in ("deep_walk_twice", "deep_event_buffer"):
-            assert c["deep"] == c["listed"] and c["giant"] == 0 and c["slices"] == 0, (route, c)
-        elif route == "giant_slices":
-            assert c["deep"] == c["listed"] and c["giant"] == c["listed"] and c["slices"] >= min(c["giant"], SLOTS), (route, c)
-            if c["giant"] <= SLOTS and any(_most_aligned(e) > SLICE for e in exps):
-                assert c["slices"] > c["giant"], (route, c)
-        elif route == "tiles_only":
-            assert c["deep"] == 0 and c["giant"] == 0 and c["slices"] == 0, (route, c)
-        if seen is not None:
-            for k in c:
-                seen[k] = seen.get(k, 0) + c[k]
-            seen["scans"] = seen.get("scans", 0) + 1
-    return on_scan
+    return H.routed_get(monkeypatch, _engines)
 
 
 def _swept(route, seen):
