@@ -168,6 +168,11 @@ def build_parser():
            "<prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU (hap_vcf: SNVs only, a majority rule over CIGAR-position "
            "alleles) into <prefix>_enable_phasing_phased.vcf.gz and write the counts to <prefix>_enable_phasing_hap_counts.tsv.  One process only "
            "(not under torch.distributed.run)")
+    a("--haplotag_indels", action="store_true",
+      help="with --phased_vcf_fn: haplotag the reads from the phased insertions, deletions and two-ALT rows (`1|2`) of the phased VCF too, not "
+           "from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows that --phase_output --phase_indels and `whatshap "
+           "phase --indels` write.  Not with --phasing builtin (the phasing between the passes is SNV-only): run with --phase_output "
+           "--phase_indels first, then rerun with --phased_vcf_fn <prefix>_enable_phasing_phased.vcf.gz --haplotag_indels")
     a("--phase_indels", action="store_true",
       help="with --phase_output: handed to hap_vcf as --indels — heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2) are "
            "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels, no base qualities), and the counts "
@@ -343,6 +348,13 @@ def Run(args, log=None):
     phase_output, tagged_bam = getattr(args, "phase_output", False), getattr(args, "haplotagged_bam", False)
     if not phase_output and getattr(args, "phase_indels", False):
         sys.exit("[ERROR] --phase_indels belongs to --phase_output (it phases the indels of the final VCF): it needs --phase_output")
+    tag_indels = getattr(args, "haplotag_indels", False)
+    if tag_indels and getattr(args, "phasing", None) is not None:
+        sys.exit("[ERROR] --haplotag_indels changes nothing under --phasing builtin: the phasing between the passes is SNV-only, so the table the "
+                 "reads are haplotagged from holds no indel.  The two-step way: 1. run with --phase_output --phase_indels; 2. rerun with "
+                 "--phased_vcf_fn <prefix>_enable_phasing_phased.vcf.gz --haplotag_indels")
+    if tag_indels and not getattr(args, "phased_vcf_fn", None):
+        sys.exit("[ERROR] --haplotag_indels needs --phased_vcf_fn (it widens the table the reads are haplotagged from)")
     if not phase_output and not tagged_bam:
         return _run_flow(args, log)
     builtin = getattr(args, "phasing", None) is not None
@@ -376,7 +388,7 @@ def Run(args, log=None):
         hap_vcf.Run(hap_vcf.build_parser().parse_args(
             ["--bam_fn", _indexed_bam(args), "--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext,
              "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if getattr(args, "phase_indels", False) else [])
-            + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + gpu), log)
+            + (["--haplotag_indels"] if tag_indels else []) + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + gpu), log)
     if tagged_bam:
         # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed
         from . import haplotag_bam
@@ -389,7 +401,7 @@ def Run(args, log=None):
                     os.remove(os.path.join(bam_dir, name))
         haplotag_bam.Run(haplotag_bam.build_parser().parse_args(
             ["--bam_fn", _indexed_bam(args), "--phased_vcf_fn", source, "--output_dir", bam_dir,
-             "--ctg_name", ",".join(contigs)] + gpu), log)
+             "--ctg_name", ",".join(contigs)] + (["--haplotag_indels"] if tag_indels else []) + gpu), log)
     return rc
 
 
@@ -636,7 +648,13 @@ def _run_pass(args, log=None):
                        mpileup_compat=compat)
         if phase is not None:                        # (--phased_vcf_fn; without it a context never holds a table)
             eng.load_reads(_empty_reads())           # (the previous contig's reads are done with: a new table would tag them again first)
-            eng.set_phase_sites(phase)               # before the reads: they are tagged while they are prepared
+            if isinstance(phase, tuple):             # (--haplotag_indels: phasedvcf.contig_alleles' table)
+                eng.set_phase_alleles(*phase[:4])
+                log("[INFO] %s: %d phased sites in the table of --haplotag_indels, %d with an insertion or deletion, %d with two ALTs"
+                    % (ctg, len(phase[0]), phase[4].kept["indel"], phase[4].kept["two_alt"]))
+                phase = phase[0]
+            else:
+                eng.set_phase_sites(phase)           # before the reads: they are tagged while they are prepared
             if not len(phase):
                 rs.reads["hp"] = 0                   # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
         t = [time()]
@@ -709,12 +727,15 @@ def _run_pass(args, log=None):
         """--phased_vcf_fn: the contig's site table, read on a fetch thread.  One VCF for the whole sample is parsed once, by the
         first thread that asks; a directory is read file by file."""
         from . import phasedvcf
+        tag_indels = getattr(args, "haplotag_indels", False)
         if os.path.isdir(phased_vcf_fn):
-            return phasedvcf.contig_sites(phased_vcf_fn, ctg)
+            return phasedvcf.contig_alleles(phased_vcf_fn, ctg) if tag_indels else phasedvcf.contig_sites(phased_vcf_fn, ctg)
         with phase_lock:
             if not phase_all:
-                phase_all.append(phasedvcf.read_all_phase_sites(phased_vcf_fn))
+                phase_all.append(phasedvcf.read_all_phase_alleles(phased_vcf_fn) if tag_indels else phasedvcf.read_all_phase_sites(phased_vcf_fn))
         hit = phase_all[0].get(ctg)
+        if tag_indels:
+            return hit or phasedvcf.empty_alleles()
         return hit[0] if hit else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
     t_setup = time() - t_all
     # contigs fetched (or being fetched) but not yet through their context: every context busy + every fetch thread running ahead.

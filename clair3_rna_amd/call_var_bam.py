@@ -115,6 +115,10 @@ def build_parser():
       help="with --enable_phasing_model True: a phased VCF (`whatshap phase` / `longphase phase`, plain or gzipped), or a directory that holds "
            "phased_<ctg>.vcf.gz; the reads of --bam_fn are haplotagged on the GPU from its phased heterozygous SNVs (HP tags of the BAM are "
            "ignored), so the BAM needs no `whatshap haplotag` pass")
+    a('--haplotag_indels', action='store_true',
+      help="with --phased_vcf_fn: the reads are haplotagged from the phased insertions, deletions and two-ALT rows (`1|2`) of the phased VCF "
+           "too, not from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows `--phase_output --phase_indels` and "
+           "`whatshap phase --indels` write.  Alleles are read off the CIGAR position: no realignment, no left-alignment, no base qualities")
     a('--minCoverage', type=int, default=4)
     a('--minMQ', type=int, default=5)
     a('--minBQ', type=int, default=0)
@@ -163,6 +167,9 @@ def Run(args, engine=None):
     phased_vcf_fn = getattr(args, "phased_vcf_fn", None)
     if phased_vcf_fn and not args.enable_phasing_model:
         sys.exit("[ERROR] --phased_vcf_fn needs --enable_phasing_model True (haplotags only enter the 30-channel tensors)")
+    haplotag_indels = getattr(args, "haplotag_indels", False)
+    if haplotag_indels and not phased_vcf_fn:
+        sys.exit("[ERROR] --haplotag_indels needs --phased_vcf_fn (it widens the table the reads are haplotagged from)")
     for need in (args.bam_fn, args.ref_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
@@ -197,11 +204,19 @@ def Run(args, engine=None):
     phase_sites = None
     if phased_vcf_fn:
         from . import phasedvcf
-        phase_sites = phasedvcf.contig_sites(phased_vcf_fn, ctg)
+        if haplotag_indels:
+            phase_sites, phase_h1, phase_pool, phase_pool_bases, phase_skipped = phasedvcf.contig_alleles(phased_vcf_fn, ctg)
+            print("[INFO] %s: %d phased sites in the table of --haplotag_indels, %d with an insertion or deletion, %d with two ALTs"
+                  % (ctg, len(phase_sites), phase_skipped.kept["indel"], phase_skipped.kept["two_alt"]), file=sys.stderr)
+        else:
+            phase_sites = phasedvcf.contig_sites(phased_vcf_fn, ctg)
         if engine is not None:
             from .reads import ReadSet
             engine.load_reads(ReadSet.from_records([]))      # (a caller's engine may still hold a chunk's reads: a new table would tag them again first)
-    eng.set_phase_sites(phase_sites)
+    if haplotag_indels:
+        eng.set_phase_alleles(phase_sites, phase_h1, phase_pool, phase_pool_bases)
+    else:
+        eng.set_phase_sites(phase_sites)
     eng.set_params(channels=channels, min_mq=args.minMQ, min_coverage=args.minCoverage, snp_min_af=args.snp_min_af,
                    indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
                    splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(sites is not None),

@@ -67,7 +67,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
            "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
-           "c3r_hap_allele_counts"]
+           "c3r_hap_allele_counts", "c3r_set_phase_alleles"]
 
 _lib = None
 
@@ -114,6 +114,7 @@ def load_library():
     L.c3r_get_read_phase_sets.argtypes = [vp, vp, i64]
     L.c3r_hap_counts.argtypes = [vp, vp, i64, vp]
     L.c3r_hap_allele_counts.argtypes = [vp, vp, i64, vp, i64, vp]
+    L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
     L.c3r_hap_assign.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(HapAssignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
@@ -289,6 +290,28 @@ class Engine(object):
             raise TypeError("phase sites must be a capi.PHASE_SITE_DTYPE array, got %r" % (a.dtype,))
         a = np.ascontiguousarray(a)
         self._chk(self.L.c3r_set_phase_sites(self.h, _ptr(a), len(a)))
+
+    def set_phase_alleles(self, sites, h1, pool=None, pool_bases=None):
+        """set_phase_sites for a table that may hold phased insertions, deletions and two-ALT sites beside the SNVs (c3r_set_phase_alleles;
+        phasedvcf.read_phase_alleles): `sites` a HAP_SITE_DTYPE array sorted by pos with ps >= 0, `h1` a uint8 array of the same length — 0:
+        allele A on haplotype 1 (GT 0|1, 1|2), 1: allele B (GT 1|0, 2|1) —, `pool` the packed pool of the insertions' bases (pack_nibbles;
+        None when no allele is an insertion) and `pool_bases` the number of bases in it (None: two per byte).  It replaces the table of
+        set_phase_sites, and that call replaces this one's; None or an empty array clears the table.  Reads that are already loaded are
+        tagged at once."""
+        a = np.zeros(0, HAP_SITE_DTYPE) if sites is None else np.asarray(sites)
+        if a.dtype != HAP_SITE_DTYPE:
+            raise TypeError("sites must be a capi.HAP_SITE_DTYPE array, got %r" % (a.dtype,))
+        a = np.ascontiguousarray(a)
+        h = np.zeros(0, np.uint8) if h1 is None else np.ascontiguousarray(h1)
+        if h.dtype != np.uint8 or h.shape != (len(a),):
+            raise TypeError("h1 must be a uint8 array with one entry per site")
+        pl = np.zeros(0, np.uint8) if pool is None else np.ascontiguousarray(pool)
+        if pl.dtype != np.uint8 or pl.ndim != 1:
+            raise TypeError("pool must be a one-dimensional uint8 array of packed bases (capi.pack_nibbles)")
+        nb = 2 * len(pl) if pool_bases is None else int(pool_bases)
+        if nb < 0 or (nb + 1) // 2 > len(pl):
+            raise ValueError("pool_bases = %d does not fit a pool of %d bytes" % (nb, len(pl)))
+        self._chk(self.L.c3r_set_phase_alleles(self.h, _ptr(a), _ptr(h) if len(h) else None, len(a), _ptr(pl) if nb else None, nb))
 
     def haplotags(self):
         """(uint8[n] tags of the loaded reads in load order, dict(n_reads, n_hp1, n_hp2, n_no_vote, n_tie, n_votes)); an error while no

@@ -156,8 +156,11 @@ struct c3r_ctx {
     // haplotagging (c3r_set_phase_sites): the contig's phased SNVs and, once reads have been loaded under them, the reads' tags
     // (tag | votes << 2 per read, k_haplotag) and the phase set each tag was decided in.  Nothing is allocated or launched while the table
     // is empty.
+    // c3r_set_phase_alleles: the same for a table of SNVs, indels and two-ALT sites (k_haplotag_alleles).  One table at a time: n_phase counts
+    // the sites of whichever is set, phase_alleles says which; d_phasea holds c3r_hap_site_t with h1 in reserved[0], d_phasepool the inserted bases.
     int64_t n_phase = 0;
-    DevBuf d_phase, d_hptag, d_hpps;
+    bool phase_alleles = false;
+    DevBuf d_phase, d_hptag, d_hpps, d_phasea, d_phasepool;
     // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
     DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
@@ -571,13 +574,24 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     // takes every read's hp from the header this kernel writes it to (nothing here waits for the device)
     if (ctx->n_phase > 0) {
         if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16)) || (rc = ensure(ctx, ctx->d_hpps, (size_t)n * 4 + 16))) return rc;
-        HapArgs h;
-        memset(&h, 0, sizeof h);
-        h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
-        h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_phase_site_t *)ctx->d_phase.p; h.n_sites = (int32_t)ctx->n_phase;
-        h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p;
-        Launch L(ctx, "k_haplotag");
-        hipLaunchKernelGGL(k_haplotag, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
+        if (!ctx->phase_alleles) {
+            HapArgs h;
+            memset(&h, 0, sizeof h);
+            h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
+            h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_phase_site_t *)ctx->d_phase.p; h.n_sites = (int32_t)ctx->n_phase;
+            h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p;
+            Launch L(ctx, "k_haplotag");
+            hipLaunchKernelGGL(k_haplotag, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
+        } else {
+            HapAlleleTagArgs h;
+            memset(&h, 0, sizeof h);
+            h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
+            h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.n_sites = (int32_t)ctx->n_phase;
+            h.pool = (const uint8_t *)ctx->d_phasepool.p;
+            h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p;
+            Launch L(ctx, "k_haplotag_alleles");
+            hipLaunchKernelGGL(k_haplotag_alleles, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
+        }
     }
     // ---- second pass (nothing below waits for the device): every record into its bin
     if ((rc = ensure(ctx, ctx->d_recs, (size_t)hs.n_rec * sizeof(PileRec) + 64))) return rc;
@@ -731,7 +745,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -965,6 +979,7 @@ int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n) 
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's array may go once this returns)
     }
     ctx->n_phase = n;
+    ctx->phase_alleles = false;                                   // (one table at a time: this one replaces c3r_set_phase_alleles')
     // reads already loaded: their tables again, from the records the device holds (what c3r_set_params does for new filters)
     ctx->host_cache.reset();
     return ::refilter(ctx);
@@ -1135,7 +1150,7 @@ int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulink
 
 int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats_t *stats) {
     if (!ctx) return C3R_EINVAL;
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads carry their records' own hp");
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry their records' own hp");
     const int64_t n = ctx->n_reads;
     if (hp && cap < n) return fail(ctx, C3R_EOVERFLOW, "haplotags of %lld reads do not fit %lld slots", (long long)n, (long long)cap);
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1159,7 +1174,7 @@ int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats
 
 int c3r_get_read_phase_sets(c3r_ctx *ctx, int32_t *ps, int64_t cap) {
     if (!ctx || cap < 0) return C3R_EINVAL;
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads have no phase set");
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads have no phase set");
     const int64_t n = ctx->n_reads;
     if (n && (!ps || cap < n)) return fail(ctx, C3R_EOVERFLOW, "phase sets of %lld reads do not fit %lld slots", (long long)n, (long long)cap);
     if (n == 0) return C3R_OK;
@@ -1174,7 +1189,7 @@ int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint3
     if (int rc = check_phase_sites(ctx, "query site", sites, n, false)) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (sites[i].ps < 0) return fail(ctx, C3R_EINVAL, "query site %lld: phase set %d is negative", (long long)i, sites[i].ps);
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads carry no tags to count by");
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
     if (n == 0) return C3R_OK;
     const size_t words = (size_t)n * 9;
     if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)
@@ -1198,37 +1213,67 @@ int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint3
     return C3R_OK;
 }
 
-int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts) {
-    if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !counts)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
-    if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many query sites");
+// The checks of a table of c3r_hap_site_t: c3r_hap_allele_counts' (h1 = NULL) and c3r_set_phase_alleles' (the same and h1 <= 1).
+static int check_hap_sites(c3r_ctx *ctx, const char *what, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, const uint8_t *h1) {
+    if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many %ss", what);
     auto base = [](uint8_t c) { return c == 1 || c == 2 || c == 4 || c == 8; };
     auto pool_at = [&](uint64_t q) { const uint8_t byte = ins_pool[q >> 1]; return (uint8_t)((q & 1) ? (byte & 15) : (byte >> 4)); };
     for (int64_t i = 0; i < n; ++i) {
         const c3r_hap_site_t &e = sites[i];
-        if (e.pos < 1) return fail(ctx, C3R_EINVAL, "query site %lld: pos %d is not a 1-based position", (long long)i, e.pos);
-        if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "query site %lld: positions must be strictly increasing (%d after %d)", (long long)i, e.pos, sites[i - 1].pos);
-        if (e.ps < 0) return fail(ctx, C3R_EINVAL, "query site %lld: phase set %d is negative", (long long)i, e.ps);
-        if (e.base_matters > 1 || e.event_matters > 1) return fail(ctx, C3R_EINVAL, "query site %lld: base_matters / event_matters must be 0 or 1", (long long)i);
+        if (e.pos < 1) return fail(ctx, C3R_EINVAL, "%s %lld: pos %d is not a 1-based position", what, (long long)i, e.pos);
+        if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "%s %lld: positions must be strictly increasing (%d after %d)", what, (long long)i, e.pos, sites[i - 1].pos);
+        if (e.ps < 0) return fail(ctx, C3R_EINVAL, "%s %lld: phase set %d is negative", what, (long long)i, e.ps);
+        if (e.base_matters > 1 || e.event_matters > 1) return fail(ctx, C3R_EINVAL, "%s %lld: base_matters / event_matters must be 0 or 1", what, (long long)i);
         for (const c3r_hap_allele_t *al : {&e.a, &e.b}) {
             const char which = al == &e.a ? 'A' : 'B';
-            if (!base(al->base)) return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: the base must be a code 1, 2, 4 or 8 (got %d)", (long long)i, which, al->base);
-            if (al->kind > C3R_HAP_EV_DEL) return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: unknown kind %d", (long long)i, which, al->kind);
+            if (!base(al->base)) return fail(ctx, C3R_EINVAL, "%s %lld: allele %c: the base must be a code 1, 2, 4 or 8 (got %d)", what, (long long)i, which, al->base);
+            if (al->kind > C3R_HAP_EV_DEL) return fail(ctx, C3R_EINVAL, "%s %lld: allele %c: unknown kind %d", what, (long long)i, which, al->kind);
             if (al->kind == C3R_HAP_EV_NONE ? al->len != 0 : al->len == 0)
-                return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: an insertion or deletion has a length of 1 or more, any other allele 0 (got %d)", (long long)i, which, al->len);
+                return fail(ctx, C3R_EINVAL, "%s %lld: allele %c: an insertion or deletion has a length of 1 or more, any other allele 0 (got %d)", what, (long long)i, which, al->len);
             if (al->kind == C3R_HAP_EV_INS) {
                 if ((int64_t)al->ins_off + al->len > pool_bases)
-                    return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: the insertion (%u + %d bases) runs past the pool of %lld bases", (long long)i, which, al->ins_off, al->len, (long long)pool_bases);
+                    return fail(ctx, C3R_EINVAL, "%s %lld: allele %c: the insertion (%u + %d bases) runs past the pool of %lld bases", what, (long long)i, which, al->ins_off, al->len, (long long)pool_bases);
                 for (uint32_t j = 0; j < al->len; ++j)
                     if (!base(pool_at((uint64_t)al->ins_off + j)))
-                        return fail(ctx, C3R_EINVAL, "query site %lld: allele %c: inserted base %u must be a code 1, 2, 4 or 8 (got %d)", (long long)i, which, j, pool_at((uint64_t)al->ins_off + j));
+                        return fail(ctx, C3R_EINVAL, "%s %lld: allele %c: inserted base %u must be a code 1, 2, 4 or 8 (got %d)", what, (long long)i, which, j, pool_at((uint64_t)al->ins_off + j));
             }
         }
         bool same = e.a.base == e.b.base && e.a.kind == e.b.kind && e.a.len == e.b.len;
         if (same && e.a.kind == C3R_HAP_EV_INS)
             for (uint32_t j = 0; j < e.a.len && same; ++j) same = pool_at((uint64_t)e.a.ins_off + j) == pool_at((uint64_t)e.b.ins_off + j);
-        if (same) return fail(ctx, C3R_EINVAL, "query site %lld: the two alleles are the same", (long long)i);
+        if (same) return fail(ctx, C3R_EINVAL, "%s %lld: the two alleles are the same", what, (long long)i);
+        if (h1 && h1[i] > 1) return fail(ctx, C3R_EINVAL, "%s %lld: h1 must be 0 (allele A on haplotype 1) or 1 (allele B on haplotype 1)", what, (long long)i);
     }
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites): the reads carry no tags to count by");
+    return C3R_OK;
+}
+
+int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases) {
+    if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !h1)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
+    if (int rc = check_hap_sites(ctx, "phase allele site", sites, n, ins_pool, pool_bases, h1)) return rc;
+    if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->last_scan_pruned = false;
+    if (n) {
+        std::vector<c3r_hap_site_t> t(sites, sites + n);          // the device's table: h1 rides in reserved[0], the rest of `reserved` is 0
+        for (int64_t i = 0; i < n; ++i) { memset(t[(size_t)i].reserved, 0, sizeof t[(size_t)i].reserved); t[(size_t)i].reserved[0] = h1[i]; }
+        // From here on the buffers of an allele table set before are being overwritten: a device failure (C3R_ENOMEM, C3R_EHIP) must not leave
+        // half of the new table under the old count, so the context holds NO table until both copies have landed.
+        if (ctx->phase_alleles) { ctx->n_phase = 0; ctx->phase_alleles = false; }
+        int rc;
+        if ((rc = upload(ctx, ctx->d_phasea, t.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_phasepool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's arrays, and `t`, may go once this returns)
+    }
+    ctx->n_phase = n;
+    ctx->phase_alleles = n > 0;                                   // (one table at a time: this one replaces c3r_set_phase_sites')
+    // reads already loaded: their tables again, from the records the device holds (as c3r_set_phase_sites does)
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
+int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts) {
+    if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !counts)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
+    if (int rc = check_hap_sites(ctx, "query site", sites, n, ins_pool, pool_bases, nullptr)) return rc;
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
     if (n == 0) return C3R_OK;
     const size_t words = (size_t)n * 9;
     if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)

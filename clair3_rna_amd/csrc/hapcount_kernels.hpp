@@ -91,13 +91,7 @@ struct HapAlleleArgs {
     uint32_t *counts;                         // [n_sites][3][3] row (0, haplotype 1, 2) x allele (A, B, other), zero on entry
 };
 
-constexpr uint32_t HAP_EV_OTHER = 3u;         // an insertion with a deletion at once behind it: equals no allele's kind
-
-__device__ __forceinline__ uint32_t hap_nibble(const uint8_t *p, unsigned long long q) {
-    const uint32_t byte = p[q >> 1];
-    return (q & 1) ? (byte & 15u) : (byte >> 4);
-}
-
+// (HAP_EV_OTHER and hap_nibble: haplotag_kernels.hpp, where k_haplotag_alleles takes the same observation)
 __global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts(const HapAlleleArgs a) {
     const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
     const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));

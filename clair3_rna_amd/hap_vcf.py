@@ -129,6 +129,9 @@ def build_parser():
     a("--indels", action="store_true",
       help="also phase heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2), by CIGAR-position alleles: no realignment, no "
            "left-alignment, no base qualities; the counts file gets the column ALLELES.  Off: SNVs only, both files as they were")
+    a("--haplotag_indels", action="store_true",
+      help="tag the reads from the phased insertions, deletions and two-ALT rows of --phased_vcf_fn too, not from its biallelic SNVs alone "
+           "(what the 30-channel pass did when it ran with this flag; include/c3r.h: c3r_set_phase_alleles)")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 
@@ -146,14 +149,23 @@ def Run(args, log=None):
     indels = bool(getattr(args, "indels", False))
     per = phasing.allele_candidates_from_vcf(args.vcf_fn, None) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
-    tables = None if os.path.isdir(args.phased_vcf_fn) else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
+    tag_indels = bool(getattr(args, "haplotag_indels", False))
+    if os.path.isdir(args.phased_vcf_fn):
+        tables = None
+    else:
+        tables = phasedvcf.read_all_phase_alleles(args.phased_vcf_fn) if tag_indels else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
     eng = None
     assigned, strings, lines = {}, {}, ["\t".join(ALLELE_COLUMNS if indels else COLUMNS) + "\n"]
     try:
         for ctg in contigs:
             cands, skipped = (per[ctg][0], per[ctg][-1]) if ctg in per else (None, None)
-            if tables is None:
+            if tag_indels:                                   # (the table's pos / ps serve nearest_sets and the log as the SNV table's do)
+                full = phasedvcf.contig_alleles(args.phased_vcf_fn, ctg) if tables is None else tables.get(ctg) or phasedvcf.empty_alleles()
+                table = full[0]
+                log("[INFO] %s: --haplotag_indels: %d phased sites in the table, %d with an insertion or deletion, %d with two ALTs"
+                    % (ctg, len(table), full[4].kept["indel"], full[4].kept["two_alt"]))
+            elif tables is None:
                 table = phasedvcf.contig_sites(args.phased_vcf_fn, ctg)
             else:
                 table = tables[ctg][0] if ctg in tables else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
@@ -166,7 +178,10 @@ def Run(args, log=None):
                 eng.set_params(min_mq=args.min_mq)
             query = nearest_sets(cands, table)
             rs = io.load_reads(args.bam_fn, ctg)
-            eng.set_phase_sites(table)
+            if tag_indels:
+                eng.set_phase_alleles(*full[:4])
+            else:
+                eng.set_phase_sites(table)
             eng.load_reads(rs)
             if indels:
                 counts = eng.hap_allele_counts(query, per[ctg][1])

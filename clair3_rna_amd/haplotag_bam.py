@@ -18,7 +18,8 @@ The tag rule is the one of include/c3r.h (c3r_set_phase_sites): ALL loaded reads
 supplementary alignments and MAPQ 0 included); every phased heterozygous SNV a read covers is one vote of unit weight for the haplotype
 whose allele the read shows at the CIGAR position; the read's set is the one with the most votes.  No realignment, no base qualities, no
 indels, no tagging of a supplementary alignment after its primary.  Agreement with `whatshap haplotag` / `longphase haplotag` has not been
-measured.
+measured.  --haplotag_indels: the phased insertions, deletions and two-ALT rows of the phased VCF vote too (c3r_set_phase_alleles:
+phasedvcf.contig_alleles -> Engine.set_phase_alleles), still as CIGAR-position alleles without left-alignment.
 
     python -m clair3_rna_amd.haplotag_bam --bam_fn x.bam --phased_vcf_fn out/tmp/phased_output/phased_vcf \\
         --output_dir out/tmp/phased_output/phased_bam
@@ -63,6 +64,9 @@ def build_parser():
       help="what the 30-channel pass read: one phased VCF for all contigs, or a directory that holds phased_<ctg>.vcf.gz")
     a("-o", "--output_dir", type=str, required=True, help="receives <ctg>.bam and <ctg>.bam.bai")
     a("-c", "--ctg_name", type=str, default=None, help="contigs, comma-separated; default: every contig of the BAM header.  A contig without a record gets no file")
+    a("--haplotag_indels", action="store_true",
+      help="tag the reads from the phased insertions, deletions and two-ALT rows of --phased_vcf_fn too, not from its biallelic SNVs alone "
+           "(include/c3r.h: c3r_set_phase_alleles): the tags of a 30-channel pass that ran with this flag")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     a("--threads", type=int, default=0, help="BGZF inflate / deflate threads; default: the CPUs this process may run on, 32 at the most")
     return p
@@ -84,7 +88,11 @@ def Run(args, log=None):
     threads = int(getattr(args, "threads", 0) or 0)
     command = getattr(args, "command", None) or " ".join(sys.argv)
     os.makedirs(args.output_dir, exist_ok=True)
-    tables = None if os.path.isdir(args.phased_vcf_fn) else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
+    tag_indels = bool(getattr(args, "haplotag_indels", False))
+    if os.path.isdir(args.phased_vcf_fn):
+        tables = None
+    else:
+        tables = phasedvcf.read_all_phase_alleles(args.phased_vcf_fn) if tag_indels else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
     done, eng = {}, None
     with bamio.BamFile(args.bam_fn, threads=threads) as bf:
@@ -95,7 +103,11 @@ def Run(args, log=None):
                 if ctg not in in_bam:
                     log("[INFO] %s: not in the header of %s: no file" % (ctg, args.bam_fn))
                     continue
-                if tables is None:
+                full = None
+                if tag_indels:
+                    full = phasedvcf.contig_alleles(args.phased_vcf_fn, ctg) if tables is None else tables.get(ctg) or phasedvcf.empty_alleles()
+                    table = full[0]
+                elif tables is None:
                     table = phasedvcf.contig_sites(args.phased_vcf_fn, ctg)
                 else:
                     table = tables[ctg][0] if ctg in tables else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
@@ -106,7 +118,10 @@ def Run(args, log=None):
                     if eng is None:
                         eng = capi.Engine(gpu_id)
                         eng.set_params()
-                    eng.set_phase_sites(table)
+                    if tag_indels:
+                        eng.set_phase_alleles(*full[:4])
+                    else:
+                        eng.set_phase_sites(table)
                     eng.load_reads(rs)
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()
                 elif rs is not None:                               # (no read record: nothing to launch; the contig's other records still go out)
@@ -131,7 +146,8 @@ def Run(args, log=None):
                 done[ctg] = st
                 log("[INFO] %s: %d records, %d HP1, %d HP2, %d untagged, %d unpaired (not read records: copied, never tagged), %d phased sites%s -> %s"
                     % (ctg, st["records"], st["hp1"], st["hp2"], st["records"] - st["tagged"] - st["unpaired"], st["unpaired"], len(table),
-                       "" if len(table) else " (nothing phased on this contig: every read untagged)", out))
+                       (" (--haplotag_indels: %d with an insertion or deletion, %d with two ALTs)" % (full[4].kept["indel"], full[4].kept["two_alt"]) if tag_indels else "")
+                       + ("" if len(table) else " (nothing phased on this contig: every read untagged)"), out))
         finally:
             if eng is not None:
                 eng.close()

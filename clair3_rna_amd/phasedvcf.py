@@ -3,14 +3,22 @@
 
 A row is kept when its REF and ALT are single characters of ACGTacgt and the first sample's GT is exactly `0|1` or `1|0`; `ps` is the integer
 PS FORMAT field (0 when it is absent or `.`); FILTER is ignored; of several rows on one position the first is kept.  Everything else is
-counted by reason and skipped: haplotagging here votes on biallelic SNVs only (no indels, no multi-allelic sites)."""
+counted by reason and skipped: that table votes on biallelic SNVs only (no indels, no multi-allelic sites).
+
+read_phase_alleles / read_all_phase_alleles / contig_alleles are the same for the table of capi.Engine.set_phase_alleles (include/c3r.h:
+c3r_set_phase_alleles; --haplotag_indels): a row is kept when the first sample's GT is exactly `0|1` / `1|0` with one ALT (allele A = REF,
+B = the ALT) or `1|2` / `2|1` with two ALTs (A = the first, B = the second) and every ALT reduces to an SNV, an insertion or a deletion
+anchored on POS (phasing._parse_alleles and reduce_allele: one row loop and one implementation of that rule for both files); h1 is 1 for `1|0` and `2|1`.  PS, FILTER and rows that share a
+position are treated as above.  On a file of biallelic SNV rows the kept positions, ps and orientation are read_phase_sites'."""
 import numpy as np
 
-from .capi import PHASE_SITE_DTYPE
+from .capi import HAP_EV_INS, HAP_SITE_DTYPE, PHASE_SITE_DTYPE
 from .io import _open_text
 
 BASE_CODE = {"A": 1, "C": 2, "G": 4, "T": 8}                 # BAM 4-bit codes (reads.NT16)
 SKIP_REASONS = ("other_contig", "malformed", "not_snv", "not_phased_het", "duplicate_pos")
+# read_phase_alleles: the same reasons (not_snv stays 0 there) and three more, with the meanings they have in phasing.py
+ALLELE_SKIP_REASONS = SKIP_REASONS + ("multi_alt", "complex_allele", "same_alleles")
 
 
 def contig_file(path, contig):
@@ -101,3 +109,53 @@ def read_all_phase_sites(vcf_fn):
     with _open_text(vcf_fn) as f:
         per = _parse(f, None)
     return {c: _table(rows, skipped) for c, (rows, skipped) in per.items()}
+
+
+# ---- the table of Engine.set_phase_alleles: SNVs, insertions, deletions and two-ALT rows
+def _allele_table(rows, skipped):
+    """read_phase_alleles' tuple from the rows of phasing._parse_alleles(phased=True): (pos, allele A, allele B, REF, ALT, ps, h1)."""
+    from . import phasing                                    # (phasing imports this module: not at import time)
+    keep = phasing._first_rows(rows, skipped)
+    sites, pool = phasing._allele_sites(keep)                 # (flags and pool: as for hap_vcf --indels)
+    sites["ps"] = [r[5] for r in keep]
+    h1 = np.array([r[6] for r in keep], dtype=np.uint8)
+    pool_bases = int(sum(int(sites[n + "_len"][sites[n + "_kind"] == HAP_EV_INS].sum()) for n in "ab"))
+    return sites, h1, pool, pool_bases, Skipped(skipped, indel=int((sites["event_matters"] != 0).sum()), two_alt=sum("," in r[4] for r in keep))
+
+
+class Skipped(dict):
+    """{reason: rows skipped} of an allele table, with `kept`: dict(indel = the sites kept with an insertion or deletion among their two
+    alleles, two_alt = the sites kept from rows with two ALTs) — what the drivers' [INFO] lines count.  Compares like the plain dict."""
+
+    def __init__(self, skipped, indel=0, two_alt=0):
+        dict.__init__(self, skipped)
+        self.kept = dict(indel=indel, two_alt=two_alt)
+
+
+def empty_alleles():
+    """The empty table of set_phase_alleles: (sites, h1, pool, pool_bases, skipped)."""
+    return np.zeros(0, dtype=HAP_SITE_DTYPE), np.zeros(0, np.uint8), np.zeros(0, np.uint8), 0, Skipped(dict.fromkeys(ALLELE_SKIP_REASONS, 0))
+
+
+def read_phase_alleles(vcf_fn, contig):
+    """(HAP_SITE_DTYPE array sorted by pos, uint8 h1 per site, packed pool of the insertions' bases, number of bases in the pool, {reason: rows
+    skipped}) for `contig` of a plain or gzipped VCF: the arguments of Engine.set_phase_alleles."""
+    from . import phasing
+    with _open_text(vcf_fn) as f:
+        rows, skipped = phasing._parse_alleles(f, contig, phased=True)[contig]
+    return _allele_table(rows, skipped)
+
+
+def read_all_phase_alleles(vcf_fn):
+    """{contig: read_phase_alleles' tuple} for every contig of the file, in one pass."""
+    from . import phasing
+    with _open_text(vcf_fn) as f:
+        per = phasing._parse_alleles(f, None, phased=True)
+    return {c: _allele_table(*v) for c, v in per.items()}
+
+
+def contig_alleles(path, contig):
+    """read_phase_alleles' tuple for `contig` from a phased VCF or a directory of per-contig ones (contig_file); the empty table when nothing
+    was phased there."""
+    fn = contig_file(path, contig)
+    return read_phase_alleles(fn, contig) if fn else empty_alleles()

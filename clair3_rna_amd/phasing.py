@@ -103,11 +103,17 @@ def reduce_allele(ref, alt):
     return None
 
 
-def _parse_alleles(lines, contig):
+def _parse_alleles(lines, contig, phased=False):
     """-> {contig: ([(pos, allele A, allele B, REF string, ALT string)] in file order, {reason: rows skipped})}; an allele is
     reduce_allele's tuple.  The checks of a row, in this order: malformed, not_pass, not_het (GT is none of 0/1, 1/0, 1/2, 2/1, or 1/2 with
     one ALT), multi_alt (three or more ALTs, or two under GT 0/1), complex_allele (an allele does not reduce), same_alleles (two ALTs that
-    reduce to one allele)."""
+    reduce to one allele).
+    phased (phasedvcf.read_phase_alleles: the rows of a PHASED VCF, the table that tags the reads): the same loop with the GTs 0|1, 1|0,
+    1|2, 2|1 (reason not_phased_het), FILTER ignored, the reasons of phasedvcf.ALLELE_SKIP_REASONS, and two more elements in a row: ps — the
+    integer PS field, 0 when it is absent or `.`, malformed when it is anything else — and h1 — 1 for 1|0 and 2|1."""
+    from . import phasedvcf
+    reasons = phasedvcf.ALLELE_SKIP_REASONS if phased else ALLELE_SKIP_REASONS
+    sep, not_het = ("|", "not_phased_het") if phased else ("/", "not_het")
     out = {}
     other = 0
     for line in lines:
@@ -119,19 +125,19 @@ def _parse_alleles(lines, contig):
         if contig is not None and f[0] != contig:
             other += 1
             continue
-        rows, skipped = out.setdefault(f[0], ([], dict.fromkeys(ALLELE_SKIP_REASONS, 0)))
+        rows, skipped = out.setdefault(f[0], ([], dict.fromkeys(reasons, 0)))
         if len(f) < 10 or not f[1].isdigit() or int(f[1]) < 1:
             skipped["malformed"] += 1
             continue
-        if f[6] != "PASS":
+        if not phased and f[6] != "PASS":
             skipped["not_pass"] += 1
             continue
         keys, vals = f[8].split(":"), f[9].split(":")
         gt = vals[keys.index("GT")] if "GT" in keys and keys.index("GT") < len(vals) else ""
         alts = f[4].split(",")
-        two = gt in ("1/2", "2/1")
-        if (gt not in ("0/1", "1/0") and not two) or (two and len(alts) < 2):
-            skipped["not_het"] += 1
+        two = gt in ("1" + sep + "2", "2" + sep + "1")
+        if (gt not in ("0" + sep + "1", "1" + sep + "0") and not two) or (two and len(alts) < 2):
+            skipped[not_het] += 1
             continue
         if len(alts) != (2 if two else 1):
             skipped["multi_alt"] += 1
@@ -144,14 +150,22 @@ def _parse_alleles(lines, contig):
             skipped["same_alleles"] += 1
             continue
         a, b = reduced if two else ((f[3][0].upper(), HAP_EV_NONE, 0, ""), reduced[0])
-        rows.append((int(f[1]), a, b, f[3], f[4]))
+        row = (int(f[1]), a, b, f[3], f[4])
+        if phased:
+            ps = vals[keys.index("PS")] if "PS" in keys and keys.index("PS") < len(vals) else "."
+            if ps not in (".", "") and not (ps.isdigit() and int(ps) < 2 ** 31):
+                skipped["malformed"] += 1
+                continue
+            row += (0 if ps in (".", "") else int(ps), 1 if gt in ("1|0", "2|1") else 0)
+        rows.append(row)
     if contig is not None:
-        rows, skipped = out.setdefault(contig, ([], dict.fromkeys(ALLELE_SKIP_REASONS, 0)))
+        rows, skipped = out.setdefault(contig, ([], dict.fromkeys(reasons, 0)))
         skipped["other_contig"] = other
     return out
 
 
-def _allele_table(rows, skipped):
+def _first_rows(rows, skipped):
+    """The rows sorted by position, of several on one position the first of the file; the others are counted as duplicate_pos."""
     rows = sorted(enumerate(rows), key=lambda kr: (kr[1][0], kr[0]))           # by position; rows of one position in file order
     keep, last = [], None
     for _, r in rows:
@@ -160,9 +174,20 @@ def _allele_table(rows, skipped):
             continue
         keep.append(r)
         last = r[0]
+    return keep
+
+
+def _allele_table(rows, skipped):
+    keep = _first_rows(rows, skipped)
+    sites, pool = _allele_sites(keep)
+    return sites, pool, [(r[3], r[4]) for r in keep], skipped
+
+
+def _allele_sites(keep):
+    """(HAP_SITE_DTYPE array with ps = 0, packed pool of the insertions' bases) of the kept rows of _parse_alleles."""
     sites = np.zeros(len(keep), dtype=HAP_SITE_DTYPE)
     pool = []
-    for k, (pos, a, b, _, _) in enumerate(keep):
+    for k, (pos, a, b, *_) in enumerate(keep):
         s = sites[k]
         s["pos"] = pos
         s["base_matters"] = int(any(x[1] == HAP_EV_NONE and x[0] != keep[k][3][0].upper() for x in (a, b)))     # one of them is an SNV
@@ -172,7 +197,7 @@ def _allele_table(rows, skipped):
             if kind == HAP_EV_INS:
                 s[name + "_ins_off"] = len(pool)
                 pool += [BASE_CODE[c] for c in ins]
-    return sites, pack_nibbles(pool), [(r[3], r[4]) for r in keep], skipped
+    return sites, pack_nibbles(pool)
 
 
 def allele_candidates_from_vcf(vcf_fn, contig):

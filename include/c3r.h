@@ -79,7 +79,7 @@ int c3r_set_params(c3r_ctx *ctx, const c3r_params_t *p);
  *     ends beyond 2^31".
  *   BED intervals (c3r_set_bed): 0-based half-open int32 pairs, 0 <= start < end <= INT32_MAX; they are only compared with row positions.
  *   genotyping sites (c3r_set_sites): 1-based int32, 1 .. INT32_MAX; only compared.
- *   phase sites and query sites (c3r_set_phase_sites, c3r_hap_counts, c3r_hap_allele_counts, c3r_phase_links, c3r_phase_unit_links): 1-based
+ *   phase sites and query sites (c3r_set_phase_sites, c3r_set_phase_alleles, c3r_hap_counts, c3r_hap_allele_counts, c3r_phase_links, c3r_phase_unit_links): 1-based
  *     int32 pos, 1 .. INT32_MAX, compared with read positions in 64-bit arithmetic; ps is a name (a position by convention), -1 or 0 .. INT32_MAX.
  * GRCh38 chr1 is 248,956,422 bp; BAI indexing ends at 2^29.  tests/test_gpu_coords.py runs the kernels at chr1 scale, at 2^28 and on the last
  * accepted and first refused values above. */
@@ -198,6 +198,34 @@ int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts
  * ps < 0, a flag other than 0 / 1, a base code (of an allele or in the pool of an insertion) outside 1, 2, 4, 8, an unknown kind, an indel
  * of length 0 (or a length on kind NONE), an insertion that runs past the pool, or two equal alleles. */
 int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts);
+/* Haplotagging from a table that also holds phased insertions, deletions and two-ALT sites (`0|1` rows with an indel ALT, `1|2` rows): what
+ * `--phase_output --phase_indels` and `whatshap phase --indels` write.  Opt-in (--haplotag_indels).  It is c3r_set_phase_sites with the
+ * observation of c3r_hap_allele_counts in the place of "the read's base is ref or alt" — the two contracts above, joined, and nothing else:
+ *  Table: sites sorted by strictly increasing pos, ps >= 0; alleles A and B, base_matters, event_matters and the pool exactly as in
+ *   c3r_hap_allele_counts.  h1[j] = 0: allele A lies on haplotype 1 (GT 0|1 or 1|2); h1[j] = 1: allele B does (GT 1|0 or 2|1).
+ *  Voters: c3r_set_phase_sites' — every loaded read, whatever excl_flags / min_mq say (not read_kept).
+ *  Observation: the column of c3r_hap_allele_counts at the site (normalised CIGAR, the event behind the anchor as defined there): columns 0
+ *   (A) and 1 (B) vote, column 2 (another allele) and no observation do not; the vote is for haplotype 1 when the column equals h1[j],
+ *   else for haplotype 2.
+ *  Decision: c3r_set_phase_sites', unchanged — votes per phase set, the set with the most votes (equal: the one whose first voting site
+ *   comes first in the table), hp = 1 / 2 / 0 from c1 against c2; the winning set is kept for c3r_get_read_phase_sets.
+ * On a table whose sites are all REF-and-one-SNV this IS c3r_set_phase_sites' rule, bit for bit (tags, sets and statistics): there the
+ * column is 0 for ref, 1 for alt, and 2 or nothing for every other code.
+ * Limits, as for both parents: the alleles are read off the CIGAR position — no realignment, no left-alignment of the reads' indels, no
+ * base qualities; a read whose aligner placed an indel one repeat unit away from the VCF's anchor shows "another allele" and does not
+ * vote.  Agreement with `whatshap haplotag` (which, as far as we recall and have not checked, reads indel rows of a phased VCF too) is
+ * not measured.
+ * One table at a time: this call replaces the table of c3r_set_phase_sites and that call replaces this one's; n = 0 on either clears the
+ * table (nothing is launched then and the records' own hp count again).  Valid before or after c3r_load_reads with the same result (the
+ * tags are rebuilt as c3r_set_phase_sites rebuilds them); the caller's arrays may go once the call returns (the device holds a copy
+ * with h1 folded into the site records).  c3r_load_reads runs k_haplotag_alleles (csrc/haplotag_kernels.hpp) in k_haplotag's place
+ * while this table is the one set.  c3r_get_haplotags, c3r_get_read_phase_sets, c3r_hap_counts and c3r_hap_allele_counts treat either
+ * table as "a phase table is set".  C3R_EINVAL, naming the first bad index, for everything c3r_hap_allele_counts refuses and for
+ * h1 > 1; after such a refusal (and only then) the table set before stays in force.  A device failure while the new table is copied
+ * (C3R_ENOMEM, C3R_EHIP) is different: where the table before was an allele table its buffers are the ones being overwritten, so the
+ * context then holds no table at all (the getters answer as without one) until a setter succeeds; a table of c3r_set_phase_sites, which
+ * lives in buffers of its own, stays. */
+int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases);
 /* Phasing on the device from read linkage: what stands where `whatshap phase` / `longphase phase` stand in the reference flow
  * (run_clair3_rna:729-767), in two steps.  It is a GREEDY LINKAGE CHAIN, not whatshap's wMEC: every heterozygous SNV gets a block and an
  * orientation from the reads that cover it together with one of the K = C3R_PHASE_LINKS sites before it, once, in table order.
