@@ -416,6 +416,52 @@ struct Launch {
     }
 };
 
+// ---- the kernels that hold the loaded reads against a site table (haplotag_kernels.hpp, hapcount_kernels.hpp, phase_kernels.hpp)
+// What c3r_load_reads left on the device, as the base of such a kernel's (zeroed) arguments.
+template <class Args>
+Args read_args(const c3r_ctx *ctx, int n) {
+    Args a;
+    memset(&a, 0, sizeof a);
+    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = n; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
+    a.seq = (const uint8_t *)ctx->d_seq.p;
+    return a;
+}
+// One launch of such a kernel: a group of PREP_GRP lanes per read.
+template <class Args>
+void launch_per_read(c3r_ctx *ctx, const char *label, void (*kernel)(Args), const Args &a) {
+    Launch L(ctx, label);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
+}
+// A table of `words` 32-bit counters that one such launch adds to: zeroed in `buf`, filled by launch(the table on the device), copied to
+// `out`.  Waits for the device: the arrays the caller handed in may go once this returns, and the table is there.
+template <class LaunchOn>
+int counter_table(c3r_ctx *ctx, DevBuf &buf, size_t words, uint32_t *out, LaunchOn &&launch) {
+    if (int rc = ensure(ctx, buf, words * 4)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(buf.p, 0, words * 4, ctx->stream));
+    launch((uint32_t *)buf.p);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, buf.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return C3R_OK;
+}
+
+// c3r_hap_counts and c3r_hap_allele_counts once their n query sites are checked: the counts of `kernel` by the tags of the phase table
+// that is set.  upload_sites(args) puts the query table on the device and into the arguments.
+template <class Args, class Upload>
+int hap_count_table(c3r_ctx *ctx, const char *label, void (*kernel)(Args), int64_t n, uint32_t *counts, Upload &&upload_sites) {
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
+    if (n == 0) return C3R_OK;
+    const size_t words = (size_t)n * 9;
+    if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Args a = read_args<Args>(ctx, ctx->n_reads);
+    if (int rc = upload_sites(a)) return rc;
+    a.n_sites = (int32_t)n;
+    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    return counter_table(ctx, ctx->d_hcounts, words, counts, [&](uint32_t *t) { a.counts = t; launch_per_read(ctx, label, kernel, a); });
+}
+
 }  // namespace
 static int device_excl_scan(c3r_ctx *ctx, int32_t *d, int n, int32_t *d_total);
 namespace {
@@ -574,23 +620,15 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     // takes every read's hp from the header this kernel writes it to (nothing here waits for the device)
     if (ctx->n_phase > 0) {
         if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16)) || (rc = ensure(ctx, ctx->d_hpps, (size_t)n * 4 + 16))) return rc;
+        auto tag_args = [&](auto h) { h.hp_reads = (DevRead *)ctx->d_reads.p; h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p; h.n_sites = (int32_t)ctx->n_phase; return h; };
         if (!ctx->phase_alleles) {
-            HapArgs h;
-            memset(&h, 0, sizeof h);
-            h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
-            h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_phase_site_t *)ctx->d_phase.p; h.n_sites = (int32_t)ctx->n_phase;
-            h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p;
-            Launch L(ctx, "k_haplotag");
-            hipLaunchKernelGGL(k_haplotag, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
+            HapArgs h = tag_args(read_args<HapArgs>(ctx, n));
+            h.sites = (const c3r_phase_site_t *)ctx->d_phase.p;
+            launch_per_read(ctx, "k_haplotag", k_haplotag, h);
         } else {
-            HapAlleleTagArgs h;
-            memset(&h, 0, sizeof h);
-            h.reads = (DevRead *)ctx->d_reads.p; h.n_reads = n; h.serial = (const uint8_t *)ctx->d_serial.p; h.cigars = (const uint32_t *)ctx->d_rawcig.p;
-            h.seq = (const uint8_t *)ctx->d_seq.p; h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.n_sites = (int32_t)ctx->n_phase;
-            h.pool = (const uint8_t *)ctx->d_phasepool.p;
-            h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p;
-            Launch L(ctx, "k_haplotag_alleles");
-            hipLaunchKernelGGL(k_haplotag_alleles, dim3((unsigned)((n + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, h);
+            HapAlleleTagArgs h = tag_args(read_args<HapAlleleTagArgs>(ctx, n));
+            h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.pool = (const uint8_t *)ctx->d_phasepool.p;
+            launch_per_read(ctx, "k_haplotag_alleles", k_haplotag_alleles, h);
         }
     }
     // ---- second pass (nothing below waits for the device): every record into its bin
@@ -967,22 +1005,28 @@ static int check_phase_sites(c3r_ctx *ctx, const char *what, const c3r_phase_sit
     return C3R_OK;
 }
 
+// The close of c3r_set_phase_sites and c3r_set_phase_alleles: the table on the device counts from here (one table at a time: either call
+// replaces the other's), and the reads already loaded get their tables again, from the records the device holds (what c3r_set_params
+// does for new filters).
+static int phase_table_set(c3r_ctx *ctx, int64_t n, bool alleles) {
+    ctx->n_phase = n;
+    ctx->phase_alleles = alleles && n > 0;
+    ctx->last_scan_pruned = false;
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
 int c3r_set_phase_sites(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n) {
     if (!ctx || n < 0 || (n && !sites)) return C3R_EINVAL;
     if (int rc = check_phase_sites(ctx, "phase site", sites, n, true)) return rc;
     if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ctx->last_scan_pruned = false;
     if (n) {
         int rc = upload(ctx, ctx->d_phase, sites, (size_t)n);
         if (rc) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's array may go once this returns)
     }
-    ctx->n_phase = n;
-    ctx->phase_alleles = false;                                   // (one table at a time: this one replaces c3r_set_phase_alleles')
-    // reads already loaded: their tables again, from the records the device holds (what c3r_set_params does for new filters)
-    ctx->host_cache.reset();
-    return ::refilter(ctx);
+    return phase_table_set(ctx, n, false);
 }
 
 int c3r_phase_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *links) {
@@ -992,22 +1036,11 @@ int c3r_phase_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint
     const size_t words = (size_t)n * C3R_PHASE_LINKS * 2;
     if (ctx->n_reads == 0) { memset(links, 0, words * 4); return C3R_OK; }               // (no voters: nothing to launch)
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = upload(ctx, ctx->d_plsites, sites, (size_t)n)) || (rc = ensure(ctx, ctx->d_links, words * 4))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_links.p, 0, words * 4, ctx->stream));
-    LinkArgs a;
-    memset(&a, 0, sizeof a);
-    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
-    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_phase_site_t *)ctx->d_plsites.p; a.n_sites = (int32_t)n;
-    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.links = (uint32_t *)ctx->d_links.p;
-    {
-        Launch L(ctx, "k_phase_links");
-        hipLaunchKernelGGL(k_phase_links, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(links, ctx->d_links.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's site array may go once this returns, and the table is there)
-    return C3R_OK;
+    if (int rc = upload(ctx, ctx->d_plsites, sites, (size_t)n)) return rc;
+    LinkArgs a = read_args<LinkArgs>(ctx, ctx->n_reads);
+    a.sites = (const c3r_phase_site_t *)ctx->d_plsites.p; a.n_sites = (int32_t)n;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    return counter_table(ctx, ctx->d_links, words, links, [&](uint32_t *t) { a.links = t; launch_per_read(ctx, "k_phase_links", k_phase_links, a); });
 }
 
 int c3r_phase_resolve(const c3r_phase_site_t *in, int64_t n, const uint32_t *links, const c3r_phase_params_t *p, c3r_phase_site_t *out, c3r_phase_stats_t *stats) {
@@ -1091,22 +1124,12 @@ int c3r_phase_unit_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n,
     if (U < 2 || ctx->n_reads == 0) { if (words) memset(ulinks, 0, words * 4); return C3R_OK; }      // (nothing to link, or no voters: nothing to launch)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = upload(ctx, ctx->d_plsites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_unitof, unit_of.data(), (size_t)n)) || (rc = ensure(ctx, ctx->d_links, words * 4))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_links.p, 0, words * 4, ctx->stream));
-    UnitLinkArgs a;
-    memset(&a, 0, sizeof a);
-    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
-    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_phase_site_t *)ctx->d_plsites.p; a.n_sites = (int32_t)n;
+    if ((rc = upload(ctx, ctx->d_plsites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_unitof, unit_of.data(), (size_t)n))) return rc;
+    UnitLinkArgs a = read_args<UnitLinkArgs>(ctx, ctx->n_reads);
+    a.sites = (const c3r_phase_site_t *)ctx->d_plsites.p; a.n_sites = (int32_t)n;
     a.unit_of = (const int32_t *)ctx->d_unitof.p; a.n_units = (int32_t)U;
-    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.ulinks = (uint32_t *)ctx->d_links.p;
-    {
-        Launch L(ctx, "k_phase_unit_links");
-        hipLaunchKernelGGL(k_phase_unit_links, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ulinks, ctx->d_links.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (unit_of and the caller's site array may go once this returns, and the table is there)
-    return C3R_OK;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    return counter_table(ctx, ctx->d_links, words, ulinks, [&](uint32_t *t) { a.ulinks = t; launch_per_read(ctx, "k_phase_unit_links", k_phase_unit_links, a); });   // (unit_of lives until it returns)
 }
 
 int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulinks, int64_t n_units, const c3r_phase_params_t *p, c3r_phase_site_t *out,
@@ -1189,28 +1212,11 @@ int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint3
     if (int rc = check_phase_sites(ctx, "query site", sites, n, false)) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (sites[i].ps < 0) return fail(ctx, C3R_EINVAL, "query site %lld: phase set %d is negative", (long long)i, sites[i].ps);
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
-    if (n == 0) return C3R_OK;
-    const size_t words = (size_t)n * 9;
-    if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = upload(ctx, ctx->d_hcsites, sites, (size_t)n)) || (rc = ensure(ctx, ctx->d_hcounts, words * 4))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_hcounts.p, 0, words * 4, ctx->stream));
-    HapCountArgs a;
-    memset(&a, 0, sizeof a);
-    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
-    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_phase_site_t *)ctx->d_hcsites.p; a.n_sites = (int32_t)n;
-    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
-    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.counts = (uint32_t *)ctx->d_hcounts.p;
-    {
-        Launch L(ctx, "k_hap_counts");
-        hipLaunchKernelGGL(k_hap_counts, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_hcounts.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's site array may go once this returns, and the table is there)
-    return C3R_OK;
+    return hap_count_table(ctx, "k_hap_counts", k_hap_counts, n, counts, [&](HapCountArgs &a) {
+        if (int rc = upload(ctx, ctx->d_hcsites, sites, (size_t)n)) return rc;
+        a.sites = (const c3r_phase_site_t *)ctx->d_hcsites.p;
+        return (int)C3R_OK;
+    });
 }
 
 // The checks of a table of c3r_hap_site_t: c3r_hap_allele_counts' (h1 = NULL) and c3r_set_phase_alleles' (the same and h1 <= 1).
@@ -1252,7 +1258,6 @@ int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8
     if (int rc = check_hap_sites(ctx, "phase allele site", sites, n, ins_pool, pool_bases, h1)) return rc;
     if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ctx->last_scan_pruned = false;
     if (n) {
         std::vector<c3r_hap_site_t> t(sites, sites + n);          // the device's table: h1 rides in reserved[0], the rest of `reserved` is 0
         for (int64_t i = 0; i < n; ++i) { memset(t[(size_t)i].reserved, 0, sizeof t[(size_t)i].reserved); t[(size_t)i].reserved[0] = h1[i]; }
@@ -1263,39 +1268,18 @@ int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8
         if ((rc = upload(ctx, ctx->d_phasea, t.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_phasepool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // (the caller's arrays, and `t`, may go once this returns)
     }
-    ctx->n_phase = n;
-    ctx->phase_alleles = n > 0;                                   // (one table at a time: this one replaces c3r_set_phase_sites')
-    // reads already loaded: their tables again, from the records the device holds (as c3r_set_phase_sites does)
-    ctx->host_cache.reset();
-    return ::refilter(ctx);
+    return phase_table_set(ctx, n, true);
 }
 
 int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !counts)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "query site", sites, n, ins_pool, pool_bases, nullptr)) return rc;
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
-    if (n == 0) return C3R_OK;
-    const size_t words = (size_t)n * 9;
-    if (ctx->n_reads == 0) { memset(counts, 0, words * 4); return C3R_OK; }              // (no voters: nothing to launch)
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = upload(ctx, ctx->d_hasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_hapool, ins_pool, (size_t)((pool_bases + 1) / 2))) ||
-        (rc = ensure(ctx, ctx->d_hcounts, words * 4))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_hcounts.p, 0, words * 4, ctx->stream));
-    HapAlleleArgs a;
-    memset(&a, 0, sizeof a);
-    a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = ctx->n_reads; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
-    a.seq = (const uint8_t *)ctx->d_seq.p; a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_hapool.p;
-    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
-    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags; a.counts = (uint32_t *)ctx->d_hcounts.p;
-    {
-        Launch L(ctx, "k_hap_allele_counts");
-        hipLaunchKernelGGL(k_hap_allele_counts, dim3((unsigned)((ctx->n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_hcounts.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's arrays may go once this returns, and the table is there)
-    return C3R_OK;
+    return hap_count_table(ctx, "k_hap_allele_counts", k_hap_allele_counts, n, counts, [&](HapAlleleArgs &a) {
+        int rc;
+        if ((rc = upload(ctx, ctx->d_hasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_hapool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
+        a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.pool = (const uint8_t *)ctx->d_hapool.p;
+        return (int)C3R_OK;
+    });
 }
 
 int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts, const c3r_phase_params_t *p, c3r_phase_site_t *out,

@@ -21,127 +21,63 @@
 
 namespace c3r {
 
-struct HapCountArgs {
-    const DevRead *reads; int32_t n_reads;    // headers of k_prep<false>; read only
-    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
-    const uint32_t *cigars;
-    const uint8_t *seq;                       // 4-bit packed bases
-    const c3r_phase_site_t *sites; int32_t n_sites;       // query sites (h1 is not read)
+// What the two counting kernels take beside their table.
+struct HapTableArgs : ReadArgs {
     const uint32_t *tags;                     // [n_reads] k_haplotag's: tag in the low two bits
     const int32_t *read_ps;                   // [n_reads] k_haplotag's: the set the tag was decided in, -1 when the tag is 0
     int32_t min_mq, excl_flags;               // the voters: read_kept
-    uint32_t *counts;                         // [n_sites][3][3] row (0, haplotype 1, 2) x allele (ref, alt, other), zero on entry
+    uint32_t *counts;                         // [n_sites][3][3] row (0, haplotype 1, 2) x column (ref / A, alt / B, other), zero on entry
+};
+
+// The body of k_hap_counts and k_hap_allele_counts: one walk of the group's read, one add per site where
+// column(site, R, the read's bases, walk_sites' arguments) gives 0, 1 or 2 (more: nothing).  compat_plain: ReadInfo::compat of a read of
+// the plain walk.  All lanes of a group take the same way through it (whole groups leave: the ballots of the searches stay inside a group).
+template <class Args, class Column>
+__device__ __forceinline__ void hap_count_read(const Args &a, bool compat_plain, Column &&column) {
+    const GroupAt g;
+    const int gl = g.gl, i = g.i;
+    if (i >= a.n_reads) return;
+    const DevRead d = a.reads[i];
+    if (!read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) return;
+    const SiteRange r = read_sites(a.sites, a.n_sites, d, gl);
+    if (r.lo >= r.hi) return;
+    const bool serial = a.serial[i] != 0;
+    const ReadInfo R(d, i, a.cigars, compat_plain && !serial ? 1 : 0);
+    const uint8_t *rseq = a.seq + R.seq_off;
+    const uint32_t tag = a.tags[i] & 3u;
+    const int32_t set = tag ? a.read_ps[i] : -1;
+    walk_sites(R, gl, serial, a.sites, r.lo, r.hi, [&](int s, const auto &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = column(e, R, rseq, q, last, iq, cx);
+        if (al > 2u) return;
+        const uint32_t row = e.ps == set ? tag : 0u;                   // (set = -1 equals no query ps: they are >= 0)
+        __hip_atomic_fetch_add(&a.counts[(size_t)s * 9 + row * 3 + al], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
+}
+
+struct HapCountArgs : HapTableArgs {
+    const c3r_phase_site_t *sites; int32_t n_sites;       // query sites (h1 is not read)
 };
 
 __global__ __launch_bounds__(PREP_THREADS) void k_hap_counts(const HapCountArgs a) {
-    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
-    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
-    if (i >= a.n_reads) return;                                        // (whole groups leave: the ballots of the searches stay inside a group)
-    const DevRead d = a.reads[i];
-    if (!read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) return;
-    // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
-    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
-    if (lo >= hi) return;
-    ReadInfo R;
-    R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
-    R.compat = 0; R.padbit = 0;
-    const uint32_t tag = a.tags[i] & 3u;
-    const int32_t set = tag ? a.read_ps[i] : -1;
-    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &) __attribute__((always_inline)) {
-        if (op != C3R_CIG_M) return;
-        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
-            const c3r_phase_site_t e = a.sites[s];
-            const long long dd = (long long)e.pos - 1 - x;
-            if (dd >= (long long)len) break;
-            const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
-            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-            const uint32_t byte = a.seq[R.seq_off + (q >> 1)], b = (q & 1) ? (byte & 15u) : (byte >> 4);
-            if (b != 1u && b != 2u && b != 4u && b != 8u) continue;    // (=, N, IUPAC: nothing)
-            const uint32_t al = b == e.ref ? 0u : b == e.alt ? 1u : 2u;
-            const uint32_t row = e.ps == set ? tag : 0u;               // (set = -1 equals no query ps: they are >= 0)
-            __hip_atomic_fetch_add(&a.counts[(size_t)s * 9 + row * 3 + al], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
-    if (a.serial[i] == 0) walk_plain_ops(R, gl, on_op);
-    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+    hap_count_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+        const uint32_t b = hap_nibble(rseq, q);
+        return hap_is_acgt(b) ? snv_column(e, b) : HAP_NOTHING;
+    });
 }
 
 // ---- k_hap_allele_counts: the same table for sites whose two alleles may be SNVs, insertions or deletions (c3r_hap_allele_counts) ----------
 // The rule is stated in include/c3r.h and restated, independently of this file, by tests/hapalleleref.py.  k_hap_counts' shape: 16 lanes per
-// read, the two group searches, one walk, one relaxed add per observation, no LDS, no barrier, nothing reduced across lanes.  The lane that
-// holds an M op decides everything for the sites under it: the read's base on the anchor, and — on the op's LAST base only — the event
-// behind it from the op's neighbours (OpCtx): an I (nop; its bases start at query offset y + len of the same read), a D, or an I with a D
-// at once behind it (n2op), which is the `+<ins>-<del>` column and matches no allele.  A pad kept before a D, an N, an S and the read's end
-// are no event.  Adjacent M-like ops of a plain CIGAR (`3M2=`) are one op of the normalised form: the first one's last base sees nop = M,
-// no event, which is what the merged op says.
-// n2op: walk_serial_ops always fills it; walk_plain_ops fills it only with ReadInfo::compat set, so the kernel sets compat = 1 for the
-// reads of the plain walk (there it costs the loads of two more neighbours next to an insertion and nothing else) and leaves it 0 for
-// the serial walk, where compat would also run mpileup_compat's scan of the pads inside insertions, which this rule does not know.
-// Insertions are compared nibble by nibble: the read's offset and the pool's have independent parity.
-struct HapAlleleArgs {
-    const DevRead *reads; int32_t n_reads;    // headers of k_prep<false>; read only
-    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
-    const uint32_t *cigars;
-    const uint8_t *seq;                       // 4-bit packed bases
+// read, the two group searches, one walk, one relaxed add per observation, no LDS, no barrier, nothing reduced across lanes.  The column is
+// hap_observe's (haplotag_kernels.hpp, where k_haplotag_alleles takes the same observation).
+struct HapAlleleArgs : HapTableArgs {
     const c3r_hap_site_t *sites; int32_t n_sites;
     const uint8_t *pool;                      // the alleles' inserted bases, 4-bit packed like seq (never read when no allele is an insertion)
-    const uint32_t *tags;                     // [n_reads] k_haplotag's: tag in the low two bits
-    const int32_t *read_ps;                   // [n_reads] k_haplotag's: the set the tag was decided in, -1 when the tag is 0
-    int32_t min_mq, excl_flags;               // the voters: read_kept
-    uint32_t *counts;                         // [n_sites][3][3] row (0, haplotype 1, 2) x allele (A, B, other), zero on entry
 };
 
-// (HAP_EV_OTHER and hap_nibble: haplotag_kernels.hpp, where k_haplotag_alleles takes the same observation)
 __global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts(const HapAlleleArgs a) {
-    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
-    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
-    if (i >= a.n_reads) return;                                        // (whole groups leave: the ballots of the searches stay inside a group)
-    const DevRead d = a.reads[i];
-    if (!read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) return;
-    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
-    if (lo >= hi) return;
-    const bool serial = a.serial[i] != 0;
-    ReadInfo R;
-    R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
-    R.compat = serial ? 0 : 1; R.padbit = 0;                           // (compat: n2op in the plain walk, see above)
-    const uint8_t *rseq = a.seq + R.seq_off;
-    const uint32_t tag = a.tags[i] & 3u;
-    const int32_t set = tag ? a.read_ps[i] : -1;
-    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) __attribute__((always_inline)) {
-        if (op != C3R_CIG_M) return;
-        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
-            const c3r_hap_site_t e = a.sites[s];
-            const long long dd = (long long)e.pos - 1 - x;
-            if (dd >= (long long)len) break;
-            const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
-            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-            const uint32_t b = hap_nibble(rseq, q);
-            if (e.base_matters && b != 1u && b != 2u && b != 4u && b != 8u) continue;      // (=, N, IUPAC: nothing)
-            uint32_t ek = C3R_HAP_EV_NONE, en = 0;
-            const unsigned long long iq = (unsigned long long)y + len;              // query offset of the bases of an insertion behind this op
-            if (e.event_matters && dd == (long long)len - 1) {
-                if (cx.nop == C3R_CIG_I) {
-                    if (cx.n2op == C3R_CIG_D) ek = HAP_EV_OTHER;
-                    else if (iq + cx.nlen > R.l_seq) continue;         // (SEQ ends inside the insertion: nothing)
-                    else { ek = C3R_HAP_EV_INS; en = cx.nlen; }
-                } else if (cx.nop == C3R_CIG_D) { ek = C3R_HAP_EV_DEL; en = cx.nlen; }
-            }
-            auto shows = [&](const c3r_hap_allele_t &al) __attribute__((always_inline)) {
-                if (e.base_matters && b != al.base) return false;
-                if (!e.event_matters) return true;
-                if (ek != al.kind || en != al.len) return false;       // (NONE: both lengths are 0)
-                if (ek != C3R_HAP_EV_INS) return true;
-                for (uint32_t j = 0; j < en; ++j)
-                    if (hap_nibble(rseq, iq + j) != hap_nibble(a.pool, (unsigned long long)al.ins_off + j)) return false;
-                return true;
-            };
-            const uint32_t al = shows(e.a) ? 0u : shows(e.b) ? 1u : 2u;
-            const uint32_t row = e.ps == set ? tag : 0u;               // (set = -1 equals no query ps: they are >= 0)
-            __hip_atomic_fetch_add(&a.counts[(size_t)s * 9 + row * 3 + al], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
-    if (!serial) walk_plain_ops(R, gl, on_op);
-    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+    hap_count_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+    });
 }
 
 }  // namespace c3r

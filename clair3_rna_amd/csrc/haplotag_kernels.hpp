@@ -20,6 +20,9 @@
 //      number above it, so any number of sets — interleaved as they may be — is exact in P + 1 walks with no storage.
 // The set the tag was decided in is kept beside the tag (read_ps): k_hap_counts (hapcount_kernels.hpp) counts a read on a haplotype only at
 // the sites of that set.
+//
+// The pieces that every kernel which holds reads against a sorted site table shares are here as well (hapcount_kernels.hpp and
+// phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,17 +31,22 @@
 
 namespace c3r {
 
-struct HapArgs {
-    DevRead *reads; int32_t n_reads;          // headers of k_prep<false>; hp is overwritten
+// ---- shared by the six per-read kernels over a site table (this file, hapcount_kernels.hpp, phase_kernels.hpp) -------------------------------
+// What c3r_load_reads left on the device: the base of every such kernel's arguments (c3r_lib.hip: read_args fills it).
+struct ReadArgs {
+    const DevRead *reads; int32_t n_reads;    // headers of k_prep<false>
     const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
     const uint32_t *cigars;
     const uint8_t *seq;                       // 4-bit packed bases
-    const c3r_phase_site_t *sites; int32_t n_sites;
-    uint32_t *tags;                           // [n_reads] tag | votes of the read on all phase sets << 2
-    int32_t *read_ps;                         // [n_reads] the phase set the tag was decided in, -1 when the tag is 0
 };
 
-// first site of [lo, hi) with pos >= p (hi: none).  Site: any record with a `pos` (c3r_phase_site_t; c3r_hap_site_t in hapcount_kernels.hpp)
+// Where a thread stands: its lane in the 16-lane group, the group's slot in the workgroup and the group's read (may lie past n_reads).
+struct GroupAt {
+    int gl, slot, i;
+    __device__ __forceinline__ GroupAt() : gl((int)threadIdx.x & (PREP_GRP - 1)), slot((int)threadIdx.x / PREP_GRP), i((int)(blockIdx.x * PREP_READS) + slot) {}
+};
+
+// first site of [lo, hi) with pos >= p (hi: none).  Site: any record with a `pos` (c3r_phase_site_t, c3r_hap_site_t)
 template <class Site>
 __device__ __forceinline__ int hap_lower(const Site *sites, int lo, int hi, long long p) {
     while (lo < hi) {
@@ -64,6 +72,83 @@ __device__ __forceinline__ int hap_lower_group(const Site *sites, int lo, int hi
     return lo;
 }
 
+// The sites [lo, hi) a base of read d can lie on: 0-based pos - 1 in [d.pos, d.end).  Every kernel calls it once per read; all lanes of the
+// group call it together, with the same arguments, and all get the range (nothing here leaves the kernel: k_phase_links' threads stay).
+struct SiteRange { int lo, hi; };
+template <class Site>
+__device__ __forceinline__ SiteRange read_sites(const Site *sites, int n_sites, const DevRead &d, int gl) {
+    SiteRange r;
+    r.lo = hap_lower_group(sites, 0, n_sites, (long long)d.pos + 1, gl);
+    r.hi = hap_lower_group(sites, r.lo, n_sites, (long long)d.end + 1, gl);
+    return r;
+}
+
+__device__ __forceinline__ uint32_t hap_nibble(const uint8_t *p, unsigned long long q) {
+    const uint32_t byte = p[q >> 1];
+    return (q & 1) ? (byte & 15u) : (byte >> 4);
+}
+
+// One walk of a read over the sites [lo, hi) (k_phase_links: a window of them) that its M ops cover: every M op searches its own stretch once.
+// on_site(site index, site, query offset of the read's base there, is it the op's last base, query offset behind the op — where an
+// insertion's bases start —, the op's neighbours) runs in the lane that holds the op.  Every kernel's walk; all lanes of the group come here together.
+template <class Site, class OnSite>
+__device__ __forceinline__ void walk_sites(const ReadInfo &R, int gl, bool serial, const Site *sites, int lo, int hi, OnSite &&on_site) {
+    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) __attribute__((always_inline)) {
+        if (op != C3R_CIG_M) return;
+        for (int s = hap_lower(sites, lo, hi, x + 1); s < hi; ++s) {
+            const Site e = sites[s];
+            const long long dd = (long long)e.pos - 1 - x;
+            if (dd >= (long long)len) break;
+            const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
+            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
+            on_site(s, e, q, dd == (long long)len - 1, (unsigned long long)y + len, cx);
+        }
+    };
+    if (!serial) walk_plain_ops(R, gl, on_op);
+    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+}
+
+// The column of a biallelic SNV that base b shows: 0 ref, 1 alt, 2 neither (k_hap_counts: `other` for A, C, G, T; the others: nothing).
+__device__ __forceinline__ uint32_t snv_column(const c3r_phase_site_t &e, uint32_t b) { return b == e.ref ? 0u : b == e.alt ? 1u : 2u; }
+__device__ __forceinline__ bool hap_is_acgt(uint32_t b) { return b == 1u || b == 2u || b == 4u || b == 8u; }      // (not =, N, IUPAC)
+
+// The column of an allele site (SNV, insertion, deletion, two-ALT; the rule of include/c3r.h) that the read shows: 0 allele A, 1 allele B,
+// 2 another allele, HAP_NOTHING no observation.  The lane that holds the M op decides: the read's base on the anchor and — on the op's LAST
+// base only — the event behind it from the op's neighbours: an I (its bases start at query offset iq of the same read), a D, or an I with
+// a D at once behind it (n2op), which is the `+<ins>-<del>` column and matches no allele.  A pad kept before a D, an N, an S and the read's
+// end are no event.  Adjacent M-like ops of a plain CIGAR (`3M2=`) are one op of the normalised form: the first one's last base sees
+// nop = M, no event, which is what the merged op says.  Insertions are compared nibble by nibble: the read's offset and the pool's have
+// independent parity.  walk_sites' arguments; called by k_hap_allele_counts (2 is a column) and k_haplotag_alleles (2 is no vote).
+// n2op: walk_serial_ops always fills it; walk_plain_ops fills it only with ReadInfo::compat set, so both kernels set compat = 1 for the
+// reads of the plain walk (there it costs the loads of two more neighbours next to an insertion and nothing else) and leave it 0 for
+// the serial walk, where compat would also run mpileup_compat's scan of the pads inside insertions, which this rule does not know.
+constexpr uint32_t HAP_EV_OTHER = 3u;         // an insertion with a deletion at once behind it: equals no allele's kind
+constexpr uint32_t HAP_NOTHING = 3u;
+__device__ __forceinline__ uint32_t hap_observe(const c3r_hap_site_t &e, const uint8_t *rseq, uint32_t l_seq, const uint8_t *pool, unsigned long long q, bool last,
+                                                unsigned long long iq, const OpCtx &cx) {
+    const uint32_t b = hap_nibble(rseq, q);
+    if (e.base_matters && !hap_is_acgt(b)) return HAP_NOTHING;
+    uint32_t ek = C3R_HAP_EV_NONE, en = 0;
+    if (e.event_matters && last) {
+        if (cx.nop == C3R_CIG_I) {
+            if (cx.n2op == C3R_CIG_D) ek = HAP_EV_OTHER;
+            else if (iq + cx.nlen > l_seq) return HAP_NOTHING;         // (SEQ ends inside the insertion)
+            else { ek = C3R_HAP_EV_INS; en = cx.nlen; }
+        } else if (cx.nop == C3R_CIG_D) { ek = C3R_HAP_EV_DEL; en = cx.nlen; }
+    }
+    auto shows = [&](const c3r_hap_allele_t &al) __attribute__((always_inline)) {
+        if (e.base_matters && b != al.base) return false;
+        if (!e.event_matters) return true;
+        if (ek != al.kind || en != al.len) return false;               // (NONE: both lengths are 0)
+        if (ek != C3R_HAP_EV_INS) return true;
+        for (uint32_t j = 0; j < en; ++j)
+            if (hap_nibble(rseq, iq + j) != hap_nibble(pool, (unsigned long long)al.ins_off + j)) return false;
+        return true;
+    };
+    return shows(e.a) ? 0u : shows(e.b) ? 1u : 2u;
+}
+
+// ---- the tags ---------------------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t HAP_NONE = 0xffffffffu;    // no phase set (ps is an int32 >= 0)
 
 // What one walk over a read gathers in one lane, and in all lanes of the group after reduce().
@@ -72,6 +157,17 @@ struct HapTally {
     uint32_t first;           // table index of the first voting site of those (HAP_NONE: none)
     uint32_t ps_min, ps_max;  // smallest / largest phase set above `cur` that holds a vote (ps_min HAP_NONE: none)
     __device__ __forceinline__ void clear() { c1 = 0; c2 = 0; first = HAP_NONE; ps_min = HAP_NONE; ps_max = 0; }
+    // one vote of site s, phase set ps.  cur = HAP_NONE: every vote counts and ps_min / ps_max span all sets; else only the votes of set
+    // `cur` count and ps_min is the next set above it.  (hap_walk, hap_walk_alleles)
+    __device__ __forceinline__ void vote(uint32_t cur, uint32_t ps, bool hap1, int s) {
+        if (cur == HAP_NONE) { ps_min = min(ps_min, ps); ps_max = max(ps_max, ps); }
+        else {
+            if (ps > cur) ps_min = min(ps_min, ps);
+            if (ps != cur) return;
+        }
+        if (hap1) c1 += 1; else c2 += 1;
+        first = min(first, (uint32_t)s);
+    }
     __device__ __forceinline__ void reduce() {
 #pragma unroll
         for (int off = PREP_GRP / 2; off > 0; off >>= 1) {
@@ -84,59 +180,35 @@ struct HapTally {
     }
 };
 
-// One walk: the votes of the sites [lo, hi) that the read's M ops cover.  cur = HAP_NONE: every vote counts and ps_min / ps_max span all
-// sets; else only the votes of set `cur` count and ps_min is the next set above it.  All lanes of the group come here together.
-__device__ __forceinline__ HapTally hap_walk(const ReadInfo &R, int gl, bool serial, const HapArgs &a, int lo, int hi, uint32_t cur) {
-    HapTally t;
-    t.clear();
-    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &) __attribute__((always_inline)) {
-        if (op != C3R_CIG_M) return;
-        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
-            const c3r_phase_site_t e = a.sites[s];
-            const long long d = (long long)e.pos - 1 - x;
-            if (d >= (long long)len) break;
-            const unsigned long long q = (unsigned long long)y + (unsigned long long)d;
-            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-            const uint32_t byte = a.seq[R.seq_off + (q >> 1)], b = (q & 1) ? (byte & 15u) : (byte >> 4);
-            if (b != e.ref && b != e.alt) continue;
-            const uint32_t ps = (uint32_t)e.ps;
-            if (cur == HAP_NONE) { t.ps_min = min(t.ps_min, ps); t.ps_max = max(t.ps_max, ps); }
-            else {
-                if (ps > cur) t.ps_min = min(t.ps_min, ps);
-                if (ps != cur) continue;
-            }
-            const uint32_t allele = b == e.alt ? 1u : 0u;
-            if (allele == e.h1) t.c1 += 1; else t.c2 += 1;
-            t.first = min(t.first, (uint32_t)s);
-        }
-    };
-    if (!serial) walk_plain_ops(R, gl, on_op);
-    else if (gl == 0) (void)walk_serial_ops(R, on_op);
-    t.reduce();
-    return t;
-}
+// What the two tagging kernels take beside their table.
+struct HapTagArgs : ReadArgs {
+    DevRead *hp_reads;                        // the same headers as `reads`, to write: hp is overwritten
+    uint32_t *tags;                           // [n_reads] tag | votes of the read on all phase sets << 2
+    int32_t *read_ps;                         // [n_reads] the phase set the tag was decided in, -1 when the tag is 0
+};
 
-__global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
-    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
-    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
-    if (i >= a.n_reads) return;                                        // (whole groups leave: the shuffles below stay inside a group)
+// The tag of the group's read from walk(R, gl, serial, lo, hi, cur) -> HapTally, the reduced votes of one walk (steps 1 to 3 above), and
+// lane 0's three stores.  compat_plain: ReadInfo::compat of a read of the plain walk.  The body of k_haplotag and k_haplotag_alleles; all
+// lanes of a group take the same way through it (whole groups leave: the shuffles stay inside a group).
+template <class Args, class Walk>
+__device__ __forceinline__ void hap_tag_read(const Args &a, bool compat_plain, Walk &&walk) {
+    const GroupAt g;
+    const int gl = g.gl, i = g.i;
+    if (i >= a.n_reads) return;
     const DevRead d = a.reads[i];
-    // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
-    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
+    const SiteRange r = read_sites(a.sites, a.n_sites, d, gl);
     uint32_t tag = 0, votes = 0, set = HAP_NONE;
-    if (lo < hi) {
-        ReadInfo R;
-        R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
-        R.compat = 0; R.padbit = 0;
+    if (r.lo < r.hi) {
         const bool serial = a.serial[i] != 0;
-        HapTally t = hap_walk(R, gl, serial, a, lo, hi, HAP_NONE);
+        const ReadInfo R(d, i, a.cigars, compat_plain && !serial ? 1 : 0);
+        HapTally t = walk(R, gl, serial, r.lo, r.hi, HAP_NONE);
         votes = t.c1 + t.c2;
         set = t.ps_min;                                                // (one set, or no vote: HAP_NONE)
         if (votes && t.ps_min != t.ps_max) {
             // several phase sets: one walk each, in the order of their numbers; the set with the most votes wins, the earlier first site among equals
             uint32_t best_n = 0, best_first = HAP_NONE, b1 = 0, b2 = 0;
             for (uint32_t cur = t.ps_min; cur != HAP_NONE;) {
-                const HapTally u = hap_walk(R, gl, serial, a, lo, hi, cur);
+                const HapTally u = walk(R, gl, serial, r.lo, r.hi, cur);
                 const uint32_t n = u.c1 + u.c2;
                 if (n > best_n || (n == best_n && u.first < best_first)) { best_n = n; best_first = u.first; b1 = u.c1; b2 = u.c2; set = cur; }
                 cur = u.ps_min;
@@ -146,124 +218,60 @@ __global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
         tag = t.c1 > t.c2 ? 1u : t.c2 > t.c1 ? 2u : 0u;
     }
     if (gl == 0) {
-        a.reads[i].hp = (uint8_t)tag;
+        a.hp_reads[i].hp = (uint8_t)tag;
         a.tags[i] = tag | (votes << 2);
         a.read_ps[i] = tag ? (int32_t)set : -1;
     }
+}
+
+struct HapArgs : HapTagArgs {
+    const c3r_phase_site_t *sites; int32_t n_sites;
+};
+
+// One walk: the votes of the sites [lo, hi) that the read's M ops cover.  All lanes of the group come here together.
+__device__ __forceinline__ HapTally hap_walk(const ReadInfo &R, int gl, bool serial, const HapArgs &a, int lo, int hi, uint32_t cur) {
+    HapTally t;
+    t.clear();
+    const uint8_t *rseq = a.seq + R.seq_off;
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+        const uint32_t al = snv_column(e, hap_nibble(rseq, q));
+        if (al != 2u) t.vote(cur, (uint32_t)e.ps, al == e.h1, s);
+    });
+    t.reduce();
+    return t;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
+    hap_tag_read(a, false, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) { return hap_walk(R, gl, serial, a, lo, hi, cur); });
 }
 
 // ---- k_haplotag_alleles: the same tags from a table whose sites may be SNVs, insertions, deletions and two-ALT sites (c3r_set_phase_alleles) --
 // The rule is stated in include/c3r.h and restated, independently of this file, by tests/hapindelref.py.  k_haplotag's shape — 16 lanes per
 // read, the two group searches, the walks folded through HapTally, one further walk per phase set in the order of the sets' numbers, no LDS,
-// no barrier, no atomics — with k_hap_allele_counts' observation (hapcount_kernels.hpp) in the place of the nibble compare: the lane that
-// holds an M op decides, the event behind the anchor is read from OpCtx on the op's last base only, compat = 1 on the plain walk so that
-// n2op is filled and 0 on the serial walk, insertions compared nibble by nibble against the pool.  Columns A and B vote — for haplotype 1
-// when the column equals the site's h1 —, column 2 and no observation do not.  The observation is written out here a second time and not
-// shared with k_hap_allele_counts: that kernel's text, and with it its registers, stay as they were.
+// no barrier, no atomics — with hap_observe in the place of the nibble compare.  Columns A and B vote — for haplotype 1 when the column
+// equals the site's h1 —, column 2 and no observation do not.
 // The table on the device is the caller's with one change: c3r_set_phase_alleles puts h1 into reserved[0] of its copy of every site, so
 // that a site is one 32-byte load.
-constexpr uint32_t HAP_EV_OTHER = 3u;         // an insertion with a deletion at once behind it: equals no allele's kind
-
-__device__ __forceinline__ uint32_t hap_nibble(const uint8_t *p, unsigned long long q) {
-    const uint32_t byte = p[q >> 1];
-    return (q & 1) ? (byte & 15u) : (byte >> 4);
-}
-
-struct HapAlleleTagArgs {
-    DevRead *reads; int32_t n_reads;          // headers of k_prep<false>; hp is overwritten
-    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
-    const uint32_t *cigars;
-    const uint8_t *seq;                       // 4-bit packed bases
+struct HapAlleleTagArgs : HapTagArgs {
     const c3r_hap_site_t *sites; int32_t n_sites;         // reserved[0] holds h1
     const uint8_t *pool;                      // the alleles' inserted bases, 4-bit packed like seq (never read when no allele is an insertion)
-    uint32_t *tags;                           // [n_reads] tag | votes of the read on all phase sets << 2
-    int32_t *read_ps;                         // [n_reads] the phase set the tag was decided in, -1 when the tag is 0
 };
 
-// hap_walk for the allele table; R.compat is set by the caller (1: plain walk, 0: serial walk).
+// hap_walk for the allele table
 __device__ __forceinline__ HapTally hap_walk_alleles(const ReadInfo &R, int gl, bool serial, const HapAlleleTagArgs &a, int lo, int hi, uint32_t cur) {
     HapTally t;
     t.clear();
     const uint8_t *rseq = a.seq + R.seq_off;
-    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) __attribute__((always_inline)) {
-        if (op != C3R_CIG_M) return;
-        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
-            const c3r_hap_site_t e = a.sites[s];
-            const long long dd = (long long)e.pos - 1 - x;
-            if (dd >= (long long)len) break;
-            const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
-            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-            const uint32_t b = hap_nibble(rseq, q);
-            if (e.base_matters && b != 1u && b != 2u && b != 4u && b != 8u) continue;      // (=, N, IUPAC: nothing)
-            uint32_t ek = C3R_HAP_EV_NONE, en = 0;
-            const unsigned long long iq = (unsigned long long)y + len;              // query offset of the bases of an insertion behind this op
-            if (e.event_matters && dd == (long long)len - 1) {
-                if (cx.nop == C3R_CIG_I) {
-                    if (cx.n2op == C3R_CIG_D) ek = HAP_EV_OTHER;
-                    else if (iq + cx.nlen > R.l_seq) continue;         // (SEQ ends inside the insertion: nothing)
-                    else { ek = C3R_HAP_EV_INS; en = cx.nlen; }
-                } else if (cx.nop == C3R_CIG_D) { ek = C3R_HAP_EV_DEL; en = cx.nlen; }
-            }
-            auto shows = [&](const c3r_hap_allele_t &al) __attribute__((always_inline)) {
-                if (e.base_matters && b != al.base) return false;
-                if (!e.event_matters) return true;
-                if (ek != al.kind || en != al.len) return false;       // (NONE: both lengths are 0)
-                if (ek != C3R_HAP_EV_INS) return true;
-                for (uint32_t j = 0; j < en; ++j)
-                    if (hap_nibble(rseq, iq + j) != hap_nibble(a.pool, (unsigned long long)al.ins_off + j)) return false;
-                return true;
-            };
-            const uint32_t allele = shows(e.a) ? 0u : shows(e.b) ? 1u : 2u;
-            if (allele == 2u) continue;                                // (another allele: no vote)
-            const uint32_t ps = (uint32_t)e.ps;
-            if (cur == HAP_NONE) { t.ps_min = min(t.ps_min, ps); t.ps_max = max(t.ps_max, ps); }
-            else {
-                if (ps > cur) t.ps_min = min(t.ps_min, ps);
-                if (ps != cur) continue;
-            }
-            if (allele == e.reserved[0]) t.c1 += 1; else t.c2 += 1;
-            t.first = min(t.first, (uint32_t)s);
-        }
-    };
-    if (!serial) walk_plain_ops(R, gl, on_op);
-    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_hap_site_t &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+        if (al < 2u) t.vote(cur, (uint32_t)e.ps, al == e.reserved[0], s);
+    });
     t.reduce();
     return t;
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles(const HapAlleleTagArgs a) {
-    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
-    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
-    if (i >= a.n_reads) return;                                        // (whole groups leave: the shuffles below stay inside a group)
-    const DevRead d = a.reads[i];
-    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
-    uint32_t tag = 0, votes = 0, set = HAP_NONE;
-    if (lo < hi) {
-        const bool serial = a.serial[i] != 0;
-        ReadInfo R;
-        R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
-        R.compat = serial ? 0 : 1; R.padbit = 0;                       // (compat: n2op in the plain walk, as in k_hap_allele_counts)
-        HapTally t = hap_walk_alleles(R, gl, serial, a, lo, hi, HAP_NONE);
-        votes = t.c1 + t.c2;
-        set = t.ps_min;                                                // (one set, or no vote: HAP_NONE)
-        if (votes && t.ps_min != t.ps_max) {
-            // several phase sets: k_haplotag's loop — one walk each, in the order of their numbers; most votes, the earlier first site among equals
-            uint32_t best_n = 0, best_first = HAP_NONE, b1 = 0, b2 = 0;
-            for (uint32_t cur = t.ps_min; cur != HAP_NONE;) {
-                const HapTally u = hap_walk_alleles(R, gl, serial, a, lo, hi, cur);
-                const uint32_t n = u.c1 + u.c2;
-                if (n > best_n || (n == best_n && u.first < best_first)) { best_n = n; best_first = u.first; b1 = u.c1; b2 = u.c2; set = cur; }
-                cur = u.ps_min;
-            }
-            t.c1 = b1; t.c2 = b2;
-        }
-        tag = t.c1 > t.c2 ? 1u : t.c2 > t.c1 ? 2u : 0u;
-    }
-    if (gl == 0) {
-        a.reads[i].hp = (uint8_t)tag;
-        a.tags[i] = tag | (votes << 2);
-        a.read_ps[i] = tag ? (int32_t)set : -1;
-    }
+    hap_tag_read(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) { return hap_walk_alleles(R, gl, serial, a, lo, hi, cur); });
 }
 
 }  // namespace c3r

@@ -29,11 +29,7 @@ constexpr int PHASE_K = C3R_PHASE_LINKS, PHASE_WIN = 256, PHASE_STEP = PHASE_WIN
 static_assert(PHASE_WIN == 16 * PREP_GRP, "a group clears its slab with one 16-byte store per lane");
 static_assert(PHASE_K >= 1 && PHASE_K < PHASE_WIN, "windows overlap by K sites");
 
-struct LinkArgs {
-    const DevRead *reads; int32_t n_reads;    // headers of k_prep<false>; read only
-    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
-    const uint32_t *cigars;
-    const uint8_t *seq;                       // 4-bit packed bases
+struct LinkArgs : ReadArgs {
     const c3r_phase_site_t *sites; int32_t n_sites;       // candidate sites (ps and h1 are not read)
     int32_t min_mq, excl_flags;               // the voters: read_kept
     uint32_t *links;                          // [n_sites][PHASE_K][2] cis / trans, zero on entry
@@ -42,27 +38,27 @@ struct LinkArgs {
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) {
     __shared__ uint4 s_obs4[PREP_READS][PHASE_WIN / 16];
     __shared__ int s_nwin;
-    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1), slot = tid / PREP_GRP;
-    const int i = (int)(blockIdx.x * PREP_READS) + slot;
+    const GroupAt g;
+    const int gl = g.gl, slot = g.slot, i = g.i;
     uint8_t *const obs = reinterpret_cast<uint8_t *>(s_obs4[slot]);
-    if (tid == 0) s_nwin = 0;
+    if (threadIdx.x == 0) s_nwin = 0;
     __syncthreads();
-    int lo = 0, hi = 0, nwin = 0;
+    SiteRange r = {0, 0};
+    int nwin = 0;
     bool serial = false;
-    ReadInfo R;
-    R.cig = a.cigars; R.pos = 0; R.n_cig = 0; R.l_seq = 0; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = 0; R.compat = 0; R.padbit = 0;
+    ReadInfo R(DevRead{}, i, a.cigars, 0);                             // (an empty read until the group's own is known to vote)
     if (i < a.n_reads) {                                               // (whole groups take the branch: the ballots and shuffles below stay inside a group)
         const DevRead d = a.reads[i];
         if (read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) {
-            // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
-            lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl);
-            hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
-            const int m = hi - lo;
+            r = read_sites(a.sites, a.n_sites, d, gl);
+            const int m = r.hi - r.lo;
             nwin = m < 2 ? 0 : m <= PHASE_WIN ? 1 : 1 + (m - PHASE_WIN + PHASE_STEP - 1) / PHASE_STEP;
-            R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.seq_off = d.seq_off;
+            R = ReadInfo(d, i, a.cigars, 0);
             serial = a.serial[i] != 0;
         }
     }
+    const int lo = r.lo, hi = r.hi;
+    const uint8_t *rseq = a.seq + R.seq_off;
     if (gl == 0 && nwin > 0) atomicMax(&s_nwin, nwin);
     __syncthreads();
     const int nwin_wg = s_nwin;
@@ -72,20 +68,10 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) 
         if (mine) s_obs4[slot][gl] = make_uint4(0, 0, 0, 0);
         __syncthreads();
         if (mine) {
-            auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &) __attribute__((always_inline)) {
-                if (op != C3R_CIG_M) return;
-                for (int s = hap_lower(a.sites, ws, we, x + 1); s < we; ++s) {
-                    const c3r_phase_site_t e = a.sites[s];
-                    const long long d = (long long)e.pos - 1 - x;
-                    if (d >= (long long)len) break;
-                    const unsigned long long q = (unsigned long long)y + (unsigned long long)d;
-                    if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-                    const uint32_t byte = a.seq[R.seq_off + (q >> 1)], b = (q & 1) ? (byte & 15u) : (byte >> 4);
-                    if (b == e.ref) obs[s - ws] = 1; else if (b == e.alt) obs[s - ws] = 2;
-                }
-            };
-            if (!serial) walk_plain_ops(R, gl, on_op);
-            else if (gl == 0) (void)walk_serial_ops(R, on_op);
+            walk_sites(R, gl, serial, a.sites, ws, we, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+                const uint32_t al = snv_column(e, hap_nibble(rseq, q));
+                if (al != 2u) obs[s - ws] = (uint8_t)(al + 1u);
+            });
         }
         __syncthreads();
         if (mine) {
@@ -116,11 +102,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) 
 // the K units before the current one is two bit masks in registers — bit k: unit u - k was observed (not tied) / with haplotype 2 —
 // shifted by the distance to the next unit, so a tied unit or one the read does not touch leaves a hole and no link spans more than K
 // unit numbers.  Lane k - 1 of the group adds the link to unit u - k (relaxed, agent scope: integer sums, arrival order never shows).
-struct UnitLinkArgs {
-    const DevRead *reads; int32_t n_reads;    // headers of k_prep<false>; read only
-    const uint8_t *serial;                    // [n_reads] != 0: the read takes the serial walk
-    const uint32_t *cigars;
-    const uint8_t *seq;                       // 4-bit packed bases
+struct UnitLinkArgs : ReadArgs {
     const c3r_phase_site_t *sites; int32_t n_sites;       // the chain's table: ref, alt and h1 are read, ps never (it holds -1)
     const int32_t *unit_of;                   // [n_sites] unit of every site, -1: singleton
     int32_t n_units;
@@ -150,41 +132,29 @@ struct UnitTally {
 __device__ __forceinline__ UnitTally unit_walk(const ReadInfo &R, int gl, bool serial, const UnitLinkArgs &a, int lo, int hi, int32_t cur) {
     UnitTally t;
     t.c1 = 0; t.c2 = 0; t.u_min = UNIT_NONE; t.u_max = -1;
-    auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &) __attribute__((always_inline)) {
-        if (op != C3R_CIG_M) return;
-        for (int s = hap_lower(a.sites, lo, hi, x + 1); s < hi; ++s) {
-            const c3r_phase_site_t e = a.sites[s];
-            const long long d = (long long)e.pos - 1 - x;
-            if (d >= (long long)len) break;
-            const unsigned long long q = (unsigned long long)y + (unsigned long long)d;
-            if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-            const int32_t u = a.unit_of[s];
-            if (u < 0 || u < cur) continue;
-            const uint32_t byte = a.seq[R.seq_off + (q >> 1)], b = (q & 1) ? (byte & 15u) : (byte >> 4);
-            if (b != e.ref && b != e.alt) continue;
-            if (u > cur) { t.u_min = min(t.u_min, u); t.u_max = max(t.u_max, u); continue; }
-            const uint32_t allele = b == e.alt ? 1u : 0u;              // (u == cur)
-            if (allele == e.h1) t.c1 += 1; else t.c2 += 1;
-        }
-    };
-    if (!serial) walk_plain_ops(R, gl, on_op);
-    else if (gl == 0) (void)walk_serial_ops(R, on_op);
+    const uint8_t *rseq = a.seq + R.seq_off;
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+        const int32_t u = a.unit_of[s];
+        if (u < 0 || u < cur) return;
+        const uint32_t al = snv_column(e, hap_nibble(rseq, q));
+        if (al == 2u) return;
+        if (u > cur) { t.u_min = min(t.u_min, u); t.u_max = max(t.u_max, u); return; }
+        if (al == e.h1) t.c1 += 1; else t.c2 += 1;                     // (u == cur)
+    });
     t.reduce();
     return t;
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLinkArgs a) {
-    const int tid = (int)threadIdx.x, gl = tid & (PREP_GRP - 1);
-    const int i = (int)(blockIdx.x * PREP_READS + (tid / PREP_GRP));
+    const GroupAt g;
+    const int gl = g.gl, i = g.i;
     if (i >= a.n_reads) return;                                        // (whole groups leave: the shuffles below stay inside a group)
     const DevRead d = a.reads[i];
     if (!read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) return;
-    // the sites a base of the read can lie on: 0-based pos - 1 in [d.pos, d.end)
-    const int lo = hap_lower_group(a.sites, 0, a.n_sites, (long long)d.pos + 1, gl), hi = hap_lower_group(a.sites, lo, a.n_sites, (long long)d.end + 1, gl);
+    const SiteRange r = read_sites(a.sites, a.n_sites, d, gl);
+    const int lo = r.lo, hi = r.hi;
     if (hi - lo < 2) return;                                           // (two units take two sites)
-    ReadInfo R;
-    R.cig = a.cigars + d.cig_off; R.pos = d.pos; R.n_cig = d.n_cig; R.l_seq = d.l_seq; R.read_idx = (uint32_t)i; R.wbits = 0; R.seq_off = d.seq_off;
-    R.compat = 0; R.padbit = 0;
+    const ReadInfo R(d, i, a.cigars, 0);
     const bool serial = a.serial[i] != 0;
     const UnitTally all = unit_walk(R, gl, serial, a, lo, hi, -1);
     if (all.u_min >= all.u_max) return;                                // no unit observed (UNIT_NONE, -1) or one

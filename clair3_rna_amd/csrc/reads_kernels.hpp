@@ -142,6 +142,10 @@ struct ReadInfo {
     uint64_t seq_off;
     int32_t compat;                           // c3r_params_t::mpileup_compat
     uint32_t padbit;                          // PR_INS_PADS when a run of I ops of this read holds pads (mpileup_compat = 1), else 0
+    ReadInfo() = default;
+    // a prepared read as the kernels over a site table walk it (haplotag_kernels.hpp): no PileRec bits
+    __device__ __forceinline__ ReadInfo(const DevRead &d, int i, const uint32_t *cigars, int32_t compat_)
+        : cig(cigars + d.cig_off), pos(d.pos), n_cig(d.n_cig), l_seq(d.l_seq), read_idx((uint32_t)i), wbits(0), seq_off(d.seq_off), compat(compat_), padbit(0) {}
 };
 // an op's neighbours in the normalised CIGAR (15 = none)
 struct OpCtx { uint32_t prev, prev2, nop, nlen, n2op, n2len; };

@@ -191,6 +191,28 @@ def test_reads_that_take_the_serial_walk(eng, seed):
     assert int(_check(eng, only, table).sum()) > 0
 
 
+@pytest.mark.parametrize("cigar", ["8M", "4M0D4M"], ids=["plain_walk", "serial_walk"])
+def test_a_query_offset_at_or_beyond_l_seq(eng, cigar):
+    """SEQ shorter than the CIGAR claims: two units of two sites each under one 8M op, one read per haplotype pattern, whole (l_seq 8), cut
+    so that the second unit's sites lie at (l_seq 5) or beyond (4) the end of SEQ, and cut between the second unit's two sites (6), where
+    the nibble left behind the end says the opposite of the site before it: counted, it would tie the unit and take the link away."""
+    assert _takes_serial_walk(cigar) == (cigar != "8M")
+    table = P.make_sites([(p, "A", "C") for p in (2, 3, 6, 7)])
+    table["ps"], table["h1"] = [2, 2, 6, 6], [0, 0, 1, 1]
+    patterns = ["AAAAAAAA", "ACCAAAAA", "AAAAACCA", "ACCAACCA"]
+    whole, cut, between = [(s, 8) for s in patterns], [(s, n) for n in (5, 4) for s in patterns], [("AAAAAACA", 6), ("AAAAACAA", 6)]
+
+    def rs_of(rows):
+        rs = _readset([(0, cigar, s) for s, _ in rows])
+        rs.reads["l_seq"][:] = [n for _, n in rows]          # (the nibbles behind the end stay where they are)
+        return rs
+    # the restatement alone: the whole reads link the two units, the cut ones link nothing
+    assert M.unit_links(rs_of(whole), table)[1, 0].tolist() == [2, 2] and int(M.unit_links(rs_of(cut), table).sum()) == 0
+    assert M.unit_links(rs_of(between), table)[1, 0].tolist() == [1, 1]
+    exp = _check(eng, rs_of(whole + cut + between), table)
+    assert exp[1, 0].tolist() == [3, 3] and int(exp.sum()) == 6
+
+
 def test_one_unit_pair_under_five_thousand_reads(eng):
     rng = random.Random(6)
     recs = [(100, "2M", rng.choice(["AG", "AG", "CT", "CT", "AT", "CG", "NG", "AA"])) for _ in range(5000)]

@@ -18,7 +18,7 @@ Per load, written to --out (appended):
 that one (three of each), every child on the same reads under the same table (saved by this process): the extra store against the
 run-to-run spread.
 --ab counts (with --parent_root): instead, k_hap_counts of that tree against k_hap_counts and k_hap_allele_counts of this one on the same
-SNV-only query, and k_hap_allele_counts on an INDEL query of the same size (indel_query: the insertions and deletions that most reads show
+SNV-only query, and k_hap_allele_counts (that tree's too, where it has the kernel) on an INDEL query of the same size (indel_query: the insertions and deletions that most reads show
 behind an M op, each as a 0/1 site), in alternating child processes on the reads, table and queries that this process saved.  This
 process skips its own kernel and wall-time sections then: the children are the measurement."""
 import argparse
@@ -157,6 +157,8 @@ def counts_ab(name, rounds, parent_root, scratch, rs, table, query):
             runs.setdefault((who, g[0]), []).append(float(np.mean([float(v) for v in g[1:]])))
     for (who, label), title in ((("parent", "HAP_COUNTS_MS"), "parent commit  k_hap_counts                     "),
                                 (("this", "HAP_COUNTS_MS"), "this commit    k_hap_counts                     "),
+                                (("parent", "HAP_ALLELE_SNV_MS"), "parent commit  k_hap_allele_counts, SNV query   "),
+                                (("parent", "HAP_ALLELE_INDEL_MS"), "parent commit  k_hap_allele_counts, indel query "),
                                 (("this", "HAP_ALLELE_SNV_MS"), "this commit    k_hap_allele_counts, SNV query   "),
                                 (("this", "HAP_ALLELE_INDEL_MS"), "this commit    k_hap_allele_counts, indel query ")):
         lines.append("   %s ms per launch, alternating processes (mean of %d calls each): %s" % (title, rounds, " ".join("%.4f" % v for v in runs.get((who, label), []))))
