@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/c3r.h"
@@ -39,6 +40,9 @@ struct DevBuf {
 };
 
 struct KStat { double ms = 0; int64_t n = 0; };
+
+// what a fused scan reads back: the head of its control block (totals, overflow bits, span counts) and the allocator words
+struct ScanReadback { ScanCtl ctl; unsigned long long alloc[ALLOC_SHARDS * ALLOC_STRIDE]; };
 
 }  // namespace
 
@@ -132,7 +136,7 @@ struct c3r_ctx {
     DevBuf d_winidx;                       // [resident candidates] row of the i-th site's window in d_tensors (the fused path writes windows as they arrive)
     DevBuf d_rawidx, d_export;             // c3r_get_tensors: index of a raw re-run, windows gathered into position order
     DevBuf d_tokexp, d_tokoff;             // c3r_get_tokens: tokens gathered into site order, their offsets there
-    int32_t *h_scan = nullptr;             // pinned: what a fused scan reads back (totals, overflow flags)
+    ScanReadback *h_scan = nullptr;        // pinned
     int32_t scan_counts[4] = {0, 0, 0, 0}; // the last scan's spans: listed, deep, giant, slices listed for k_deep_walk (c3r_get_scan_counts)
     bool last_fused = false;
     std::vector<int64_t> last_starts, last_ends;
@@ -724,7 +728,46 @@ void merge_intervals(std::vector<int32_t> &iv) {
 
 }  // namespace
 
-static int list_grid() { static const int v = [] { const char *e = getenv("C3R_LIST_GRID"); return e && atoi(e) > 0 ? atoi(e) : LIST_GRID; }(); return v; }
+// Developer knobs of the scan path: environment variables, never needed in production.  Read once per entry into the scan code
+// — c3r_pileup_scan_regions, c3r_get_columns, the raw re-run of c3r_get_tensors — and passed down, so a test may change them between two scans.
+struct ScanKnobs {
+    int abl, deep_min, split_min, split_slice, split_cus, giant_wgs, list_grid;
+    int evwg, giant;              // 0: never, 1: from the first scan on, -1 (unset, or anything else): once a scan of the context has met such a span
+    bool dbg, no_shift, no_fuse, no_prune, no_giant_tab, legacy_eager, one_shard, deep_serial, cap_all;
+};
+static ScanKnobs read_scan_knobs(const c3r_ctx *ctx) {
+    const auto set = [](const char *e) { return e != nullptr; };
+    const auto is1 = [](const char *e) { return e && *e == '1'; };
+    const auto at_least_1 = [](const char *e, int dflt) { return e ? std::max(1, atoi(e)) : dflt; };
+    const auto never_or_now = [](const char *e) { return !e ? -1 : *e == '0' ? 0 : *e == '1' ? 1 : -1; };
+    ScanKnobs k;
+    { const char *e = getenv("C3R_SCAN_ABL"); k.abl = e ? atoi(e) : 0; }       // ablation bits of the diagnostic build (ScanArgs::abl)
+    k.dbg = set(getenv("C3R_SCAN_DBG"));                                       // phase clocks of the tile kernels, printed after the scan
+    k.deep_min = at_least_1(getenv("C3R_DEEP_MIN"), DEEP_MIN_RECORDS);         // records from which a span is k_fused_deep's
+    k.split_min = at_least_1(getenv("C3R_SPLIT_MIN"), SPLIT_MIN_RECORDS);      // records from which a span is giant
+    k.split_slice = at_least_1(getenv("C3R_SPLIT_SLICE"), GIANT_SLICE);        // records per slice of a giant span
+    k.split_cus = at_least_1(getenv("C3R_SPLIT_CUS"), ctx->n_cu > 0 ? ctx->n_cu : 256);   // the CU count of the share rule (giant_on)
+    k.no_shift = is1(getenv("C3R_NO_SHIFT"));                                  // spans on the regions' fixed grid
+    k.no_fuse = set(getenv("C3R_NO_FUSE"));                                    // the plain mode through the column store
+    k.no_prune = set(getenv("C3R_NO_PRUNE"));                                  // the column store scans intron-only tiles too
+    k.evwg = never_or_now(getenv("C3R_EVWG"));                                 // k_fused_deep's per-workgroup event buffers
+    k.giant = never_or_now(getenv("C3R_GIANT"));                               // the giant-span pool
+    k.no_giant_tab = set(getenv("C3R_NO_GIANT_TAB"));                          // giant spans' alleles counted by the span's own workgroup
+    k.legacy_eager = is1(getenv("C3R_LEGACY_EAGER"));                          // 30 channels: op / segment tables before the first flagged column
+    k.one_shard = set(getenv("C3R_ONE_SHARD"));                                // one allocator however large the scan
+    k.deep_serial = set(getenv("C3R_DEEP_SERIAL"));                            // k_fused_deep behind k_fused_tiles on one stream
+    k.giant_wgs = at_least_1(getenv("C3R_GIANT_WGS"), 2);                      // workgroups per CU of k_deep_walk / k_deep_alleles
+    { const char *e = getenv("C3R_LIST_GRID"); k.list_grid = e && atoi(e) > 0 ? atoi(e) : LIST_GRID; }   // workgroups of the column store's tile kernels
+    k.cap_all = is1(getenv("C3R_CAP_ALL"));                                    // the depth-cap rule over every read, not only the hot zones (A/B aid)
+    return k;
+}
+
+// f(std::integral_constant<int, C>) for the context's channel count: picks the instance of a kernel templated on it
+template <class F>
+static void with_channels(const c3r_ctx *ctx, F &&f) {
+    if (ctx->prm.channels == C3R_CH) f(std::integral_constant<int, C3R_CH>{});
+    else f(std::integral_constant<int, C3R_CH_PHASED>{});
+}
 
 extern "C" {
 
@@ -1324,13 +1367,11 @@ static int run_gather(c3r_ctx *ctx, int rescale, void *dst, bool with_sites, boo
         // in-place column edits, candidate after candidate: runs once per scan and also keeps the raw windows
         g.raw = (int32_t *)ctx->d_raw.p; g.skipmax = (const int32_t *)ctx->d_skipmax.p;
         Launch L(ctx, "k_splice_gather");
-        if (ctx->prm.channels == C3R_CH) hipLaunchKernelGGL(k_splice_gather<C3R_CH>, dim3(blocks), dim3(256), 0, ctx->stream, g);
-        else hipLaunchKernelGGL(k_splice_gather<C3R_CH_PHASED>, dim3(blocks), dim3(256), 0, ctx->stream, g);
+        with_channels(ctx, [&](auto c) { hipLaunchKernelGGL(k_splice_gather<decltype(c)::value>, dim3(blocks), dim3(256), 0, ctx->stream, g); });
         return C3R_OK;
     }
     Launch L(ctx, "k_gather");
-    if (ctx->prm.channels == C3R_CH) hipLaunchKernelGGL(k_gather<C3R_CH>, dim3(blocks), dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL(k_gather<C3R_CH_PHASED>, dim3(blocks), dim3(256), 0, ctx->stream, g);
+    with_channels(ctx, [&](auto c) { hipLaunchKernelGGL(k_gather<decltype(c)::value>, dim3(blocks), dim3(256), 0, ctx->stream, g); });
     return C3R_OK;
 }
 
@@ -1382,7 +1423,7 @@ static size_t event_capacity(const c3r_ctx *ctx, int n_regions, const int64_t *c
 // entered with the list it would hold there: the kept reads from before the zone that reach into it.  A contig with one 20,000x locus
 // costs a counting pass over its read headers and a heap over that locus' reads, not a heap over every read of every region.
 constexpr int PLP_POOL_EXTRA = 1;      // nodes of htslib's pool that are not reads: the list's empty tail
-static int depth_cap_mask(c3r_ctx *ctx, int n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, const uint32_t **d_drop, int *drop_words_out) {
+static int depth_cap_mask(c3r_ctx *ctx, const ScanKnobs &kn, int n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, const uint32_t **d_drop, int *drop_words_out) {
     *d_drop = nullptr;
     const int drop_words = (int)(((size_t)ctx->n_reads + 31) / 32);
     *drop_words_out = drop_words;
@@ -1421,7 +1462,7 @@ static int depth_cap_mask(c3r_ctx *ctx, int n_regions, const int64_t *ctg_starts
         }
     }
     if (zones.empty()) return C3R_OK;
-    if (const char *e = getenv("C3R_CAP_ALL")) if (*e == '1') { zones.clear(); zones.push_back({(int64_t)R.front().pos, top + 1}); }     // (A/B aid: the rule over every read, as before round 5)
+    if (kn.cap_all) { zones.clear(); zones.push_back({(int64_t)R.front().pos, top + 1}); }     // (A/B aid: the rule over every read, as before round 5)
     ctx->h_drop.assign((size_t)n_regions * drop_words, 0u);
     bool any = false;
     auto first_at_or_after = [&](int64_t p) {           // first read with pos >= p (reads are sorted by pos)
@@ -1507,10 +1548,10 @@ static int af_table(c3r_ctx *ctx) {
     return C3R_OK;
 }
 
-// the inputs every tile kernel sees (the output side is filled in by the two scan paths)
-static void scan_inputs(c3r_ctx *ctx, ScanArgs &a, const uint32_t *d_drop, int drop_words, int n_tiles) {
+// the inputs every tile kernel sees, the regions' depth-cap masks among them (the output side is filled in by the two scan paths)
+static int scan_inputs(c3r_ctx *ctx, const ScanKnobs &kn, ScanArgs &a, int n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int n_tiles) {
     memset(&a, 0, sizeof a);
-    a.drop = d_drop; a.drop_words = drop_words;
+    if (int rc = depth_cap_mask(ctx, kn, n_regions, ctg_starts, ctg_ends, &a.drop, &a.drop_words)) return rc;
     a.reads = (const DevRead *)ctx->d_reads.p; a.seq = (const uint8_t *)ctx->d_seq.p; a.n_reads = ctx->n_reads; a.compat = ctx->prm.mpileup_compat;
     a.recs = (const PileRec *)ctx->d_recs.p; a.rec_off = (const uint32_t *)ctx->d_binoff.p; a.rtab = (const int4 *)ctx->d_rtab.p; a.bins = ctx->bins;
     a.n_tiles = n_tiles;
@@ -1523,79 +1564,74 @@ static void scan_inputs(c3r_ctx *ctx, ScanArgs &a, const uint32_t *d_drop, int d
     a.snp_af = ctx->prm.snp_min_af; a.indel_af = ctx->prm.indel_min_af; a.af_tab = (const uint32_t *)ctx->d_aftab.p;
     a.head_tail = ctx->prm.head_tail; a.splice = ctx->prm.splice_padding;
     if (ctx->padins && !ctx->padins->empty()) { a.padins = (const c3r_padins_t *)ctx->d_padins.p; a.n_padins = (int32_t)ctx->padins->size(); }
-    { const char *e = getenv("C3R_SCAN_ABL"); a.abl = e ? atoi(e) : 0; }
-    { const char *e = getenv("C3R_DEEP_MIN"); a.deep_min = e ? std::max(1, atoi(e)) : DEEP_MIN_RECORDS; }
-    { const char *e = getenv("C3R_SPLIT_MIN"); a.split_min = e ? std::max(1, atoi(e)) : SPLIT_MIN_RECORDS; }
-    { const char *e = getenv("C3R_SPLIT_SLICE"); a.split_slice = e ? std::max(1, atoi(e)) : GIANT_SLICE; }
-    { const char *e = getenv("C3R_NO_SHIFT"); a.no_shift = (e && *e == '1') ? 1 : 0; }
+    a.abl = kn.abl; a.deep_min = kn.deep_min; a.split_min = kn.split_min; a.split_slice = kn.split_slice; a.no_shift = kn.no_shift ? 1 : 0;
+    return C3R_OK;
 }
 
-static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates, bool columns_only);
-static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates, bool raw_rerun);
-
-int c3r_pileup_scan(c3r_ctx *ctx, int64_t ctg_start, int64_t ctg_end, int64_t *n_candidates) {
-    return c3r_pileup_scan_regions(ctx, 1, &ctg_start, &ctg_end, n_candidates);
-}
-
-int c3r_pileup_scan_regions(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates) {
-    if (!ctx || n_regions < 1 || !ctg_starts || !ctg_ends) return C3R_EINVAL;
-    if (ctx->ref_len == 0) return fail(ctx, C3R_EINVAL, "c3r_set_reference must be called before c3r_pileup_scan");
-    for (int r = 0; r < n_regions; ++r) {
-        if (ctg_ends[r] < ctg_starts[r]) return C3R_EINVAL;
-        // (the scan kernels add up to two tiles and a flank to a region position in plain int: C3R_CTG_END_MAX leaves them 1024, include/c3r.h)
-        if (ctg_ends[r] > C3R_CTG_END_MAX) return fail(ctx, C3R_EINVAL, "region %d ends beyond C3R_CTG_END_MAX = %lld (2^31 - 1 - 33 - 1024)", r, (long long)C3R_CTG_END_MAX);
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n_candidates) *n_candidates = 0;
-    { const int rc_af = af_table(ctx); if (rc_af) return rc_af; }
-    ctx->last_starts.assign(ctg_starts, ctg_starts + n_regions); ctx->last_ends.assign(ctg_ends, ctg_ends + n_regions);
-    ctx->last_scan_pruned = false;
-    memset(ctx->scan_counts, 0, sizeof ctx->scan_counts);          // (a fused scan that succeeds fills them in)
-    // The plain mode runs in one fused tile kernel (k_fused_tiles).  Head/tail calling (the end-of-stream rule needs the last row of the
-    // whole region), splice padding (in-place column edits, candidate after candidate) and genotyping mode (candidates in intron-only
-    // spans) keep the column store and its selection / compaction / gather kernels.
-    const bool fused = !ctx->prm.head_tail && !ctx->prm.splice_padding && !ctx->prm.genotyping_mode && !getenv("C3R_NO_FUSE");
-    ctx->last_fused = fused;
-    return fused ? scan_fused(ctx, n_regions, ctg_starts, ctg_ends, n_candidates, false)
-                 : scan_column_store(ctx, n_regions, ctg_starts, ctg_ends, n_candidates, false);
-}
-
-// ---- the column-store path: columns, depth and flags of every position go to HBM (k_scan_tiles), then window selection, ordered
-// compaction, gather and tokens as separate kernels, with two host read-backs for sizes.  columns_only: c3r_get_columns after a
-// fused scan — the columns and flags of the given region, nothing else is touched.
-static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates, bool columns_only) {
-    const int C = ctx->prm.channels;
-    // per region, rows: 1-based [max(1, ctg_start-33), ctg_end+33]  (src/create_tensor_pileup.py:411-415); slots: the regions
-    // back to back, each padded to whole tiles plus one guard tile (pileup_kernels.hpp, TileGeo)
-    std::vector<int64_t> key;
-    key.push_back(-1);                                                 // (geometry of the column store)
+// ---- what the two scan routes share
+// The tile geometry of a scan.  Per region, rows: 1-based [max(1, ctg_start-33), ctg_end+33]  (src/create_tensor_pileup.py:411-415), cut into
+// tiles of `step` positions; the slots of tile t are t * TILE + (p - p0).  guard_tile: the column store's layout — an empty tile behind every region
+// (pileup_kernels.hpp, TileGeo); without: the fused path's spans.  Rebuilt and uploaded only when the regions or the layout have changed; then
+// regb takes the regions' [beg0, end0).  geo_key is empty while h_geo or d_geo are not what a key says (a failure below, or in the caller's own upload).
+static int scan_geometry(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int step, bool guard_tile, std::vector<int2> *regb = nullptr) {
+    std::vector<int64_t> key{guard_tile ? -1 : -2};                    // (which of the two layouts, then the regions)
     for (int r = 0; r < n_regions; ++r) { key.push_back(ctg_starts[r]); key.push_back(ctg_ends[r]); }
-    bool geo_changed = key != ctx->geo_key;
-    if (geo_changed) {
+    if (key != ctx->geo_key) {
+        ctx->geo_key.clear();
         ctx->h_geo.clear();
         for (int r = 0; r < n_regions; ++r) {
             int64_t es = ctg_starts[r] - C3R_WINDOW, ee = ctg_ends[r] + C3R_WINDOW;
             if (es < 1) es = 1;
             const int32_t beg0 = (int32_t)(es - 1), end0 = (int32_t)ee;
-            for (int32_t p0 = beg0; p0 < end0; p0 += TILE) ctx->h_geo.push_back(TileGeo{p0, std::min(p0 + TILE, end0), r, 0});
-            ctx->h_geo.push_back(TileGeo{end0, end0, r, 0});          // guard tile
+            for (int32_t p0 = beg0; p0 < end0; p0 += step) ctx->h_geo.push_back(TileGeo{p0, std::min(p0 + step, end0), r, 0});
+            if (guard_tile) ctx->h_geo.push_back(TileGeo{end0, end0, r, 0});
+            if (regb) regb->push_back(make_int2(beg0, end0));
             if (r == 0) { ctx->reg_beg0 = beg0; ctx->reg_end0 = end0; }
         }
         if ((int64_t)ctx->h_geo.size() * TILE > INT32_MAX - TILE) return fail(ctx, C3R_EINVAL, "regions too large for one scan (2^31 slots)");
+        if (int rc = upload(ctx, ctx->d_geo, ctx->h_geo.data(), ctx->h_geo.size())) return rc;
         ctx->geo_key = key;
     }
     ctx->n_regions = n_regions;
+    ctx->n_pos = (int64_t)ctx->h_geo.size() * TILE;
+    return C3R_OK;
+}
+
+// a scan that produces candidates starts here: outside a batch the resident totals start over
+static void scan_output_begin(c3r_ctx *ctx) {
+    if (!ctx->batching) { ctx->n_cand = 0; ctx->n_tok = 0; ctx->n_rows = 0; ctx->n_tokspace = 0; }
+    ctx->last_cand = 0; ctx->last_base = ctx->n_cand; ctx->tokens_ready = false;
+}
+
+// C3R_SCAN_DBG: the phase clocks of the tile kernels (timing aid, off in production)
+static int scan_dbg_buffer(c3r_ctx *ctx, const ScanKnobs &kn, ScanArgs &a) {
+    if (!kn.dbg) return C3R_OK;                                       // (a.dbg is null: scan_inputs)
+    if (int rc = ensure(ctx, ctx->d_dbg, 32 * 8)) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg.p, 0, 32 * 8, ctx->stream));
+    a.dbg = (unsigned long long *)ctx->d_dbg.p;
+    return C3R_OK;
+}
+
+// bytes of a resident window: int16 (a caller sees int32: c3r_get_tensors) unless the context has met a position too deep for it
+static size_t window_bytes(const c3r_ctx *ctx) { return (size_t)C3R_WINDOW * ctx->prm.channels * (ctx->win32 ? sizeof(int32_t) : sizeof(int16_t)); }
+
+// the two refusals that either route may end in
+static int refuse_depth16_in_batch(c3r_ctx *ctx) { return fail(ctx, C3R_EOVERFLOW, "a position is covered by more than 32,767 reads and the batch already holds 16-bit windows: scan this region first, or alone"); }
+static int refuse_event_scratch(c3r_ctx *ctx, size_t ev_cap) { return fail(ctx, C3R_EOVERFLOW, "internal: indel-event scratch too small (%zu records) — nothing was written past it", ev_cap); }
+
+// ---- the column-store path: columns, depth and flags of every position go to HBM (k_scan_tiles), then window selection, ordered
+// compaction, gather and tokens as separate kernels, with two host read-backs for sizes.  columns_only: c3r_get_columns after a
+// fused scan — the columns and flags of the given region, nothing else is touched.
+static int scan_column_store(c3r_ctx *ctx, const ScanKnobs &kn, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates, bool columns_only) {
+    const int C = ctx->prm.channels;
+    int rc;
+    if ((rc = scan_geometry(ctx, n_regions, ctg_starts, ctg_ends, TILE, true))) return rc;
     const int n_tiles = (int)ctx->h_geo.size();
-    ctx->n_pos = (int64_t)n_tiles * TILE;
-    if (!columns_only) {
-        if (!ctx->batching) { ctx->n_cand = 0; ctx->n_tok = 0; ctx->n_rows = 0; ctx->n_tokspace = 0; }
-        ctx->last_cand = 0; ctx->last_base = ctx->n_cand; ctx->tokens_ready = false;
-    }
+    if (!columns_only) scan_output_begin(ctx);
     const int64_t base_cand = ctx->n_cand, base_row = ctx->n_rows, base_tok = ctx->n_tokspace;
     const int64_t n_pos = ctx->n_pos;
     const int n_cblocks = (int)((n_pos + CMP_BLOCK - 1) / CMP_BLOCK);
-    int rc;
-    if (geo_changed && (rc = upload(ctx, ctx->d_geo, ctx->h_geo.data(), ctx->h_geo.size()))) return rc;
+    const int grid = std::min(n_tiles, kn.list_grid);
     if ((rc = ensure(ctx, ctx->d_lastrow, (size_t)n_regions * 4 + 16))) return rc;
     if ((rc = ensure(ctx, ctx->d_cols, (size_t)n_pos * C * 4))) return rc;
     if ((rc = ensure(ctx, ctx->d_depth, (size_t)n_pos * 4))) return rc;
@@ -1603,7 +1639,7 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
     if ((rc = ensure(ctx, ctx->d_flags, (size_t)n_pos))) return rc;
     const size_t ev_cap = event_capacity(ctx, n_regions, ctg_starts, ctg_ends, n_tiles, 1);
     if ((rc = ensure(ctx, ctx->d_ev, ev_cap * sizeof(EvRec)))) return rc;
-    if ((rc = ensure(ctx, ctx->d_small, 64))) return rc;
+    if ((rc = ensure(ctx, ctx->d_small, sizeof(ColCtl)))) return rc;
     if ((rc = ensure(ctx, ctx->d_tile_cols, (size_t)n_tiles + 16))) return rc;
     if ((rc = ensure(ctx, ctx->d_tile_rng, (size_t)n_tiles * 16 + 16))) return rc;
     if ((rc = ensure(ctx, ctx->d_tile_list, (size_t)n_tiles * 4 + 16))) return rc;
@@ -1611,47 +1647,33 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
     if ((rc = ensure(ctx, ctx->d_tile_cand, (size_t)n_tiles * 8 + 16))) return rc;
     if ((rc = ensure(ctx, ctx->d_blockcnt, (size_t)(n_cblocks + 1) * 4))) return rc;
     if (ctx->prm.splice_padding && (rc = ensure(ctx, ctx->d_skipmax, (size_t)n_pos * 4))) return rc;
-    // d_small: [0..7] ev_cursor (u64), [8..11] event-scratch overflow flag, [12..15] n_cand, [16..19] n_tok, [20..23] n_tile_list,
-    //          [24..27] n_tile_list2 (pruned intron-only tiles), [28..31] tokens written, [32..35] tokens that found no slot (k_tile_tokens)
-    int32_t init[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_small.p, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+    ColCtl *const ctl = (ColCtl *)ctx->d_small.p;                 // (device memory: only its fields' addresses are taken here)
+    const ColCtl init{};
+    HIPCHK(ctx, hipMemcpyAsync(ctl, &init, offsetof(ColCtl, unused), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_lastrow.p, 0xff, (size_t)n_regions * 4, ctx->stream));      // -1
     HIPCHK(ctx, hipMemsetAsync(ctx->d_flags.p, 0, (size_t)n_pos, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cols.p, 0, (size_t)n_tiles, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cand.p, 0, (size_t)n_tiles * 8, ctx->stream));
 
-    const uint32_t *d_drop = nullptr;
-    int drop_words = 0;
-    if ((rc = depth_cap_mask(ctx, n_regions, ctg_starts, ctg_ends, &d_drop, &drop_words))) return rc;
-
     ScanArgs a;
-    scan_inputs(ctx, a, d_drop, drop_words, n_tiles);
+    if ((rc = scan_inputs(ctx, kn, a, n_regions, ctg_starts, ctg_ends, n_tiles))) return rc;
     a.tile_cols = (uint8_t *)ctx->d_tile_cols.p;
     a.tile_rng = (int4 *)ctx->d_tile_rng.p; a.tile_list = (int32_t *)ctx->d_tile_list.p;
-    a.n_tile_list = (int32_t *)((char *)ctx->d_small.p + 20);
+    a.n_tile_list = &ctl->n_tile_list;
     // rows of intron-only tiles far from every aligned segment only matter to the end-of-stream rule (head/tail), to splice
     // padding and to genotyping sites: in the plain mode they are left out of the scan
-    a.prune = (!columns_only && !ctx->prm.head_tail && !ctx->prm.splice_padding && !ctx->prm.genotyping_mode && !getenv("C3R_NO_PRUNE")) ? 1 : 0;
-    a.tile_list2 = (int32_t *)ctx->d_tile_list2.p; a.n_tile_list2 = (int32_t *)((char *)ctx->d_small.p + 24);
-    a.dbg = nullptr;
-    if (getenv("C3R_SCAN_DBG")) {
-        if ((rc = ensure(ctx, ctx->d_dbg, 32 * 8))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg.p, 0, 32 * 8, ctx->stream));
-        a.dbg = (unsigned long long *)ctx->d_dbg.p;
-    }
+    a.prune = (!columns_only && !ctx->prm.head_tail && !ctx->prm.splice_padding && !ctx->prm.genotyping_mode && !kn.no_prune) ? 1 : 0;
+    a.tile_list2 = (int32_t *)ctx->d_tile_list2.p; a.n_tile_list2 = &ctl->n_tile_list2;
+    if ((rc = scan_dbg_buffer(ctx, kn, a))) return rc;
     a.cols = (int32_t *)ctx->d_cols.p; a.depth = (int32_t *)ctx->d_depth.p; a.ncov = (int32_t *)ctx->d_ncov.p; a.flags = (uint8_t *)ctx->d_flags.p;
-    a.ev = (EvRec *)ctx->d_ev.p; a.ev_cursor = (unsigned long long *)ctx->d_small.p; a.last_row = (int32_t *)ctx->d_lastrow.p;
-    a.ev_cap = (unsigned long long)ev_cap; a.ev_overflow = (int32_t *)((char *)ctx->d_small.p + 8);
+    a.ev = (EvRec *)ctx->d_ev.p; a.ev_cursor = &ctl->ev_cursor; a.last_row = (int32_t *)ctx->d_lastrow.p;
+    a.ev_cap = (unsigned long long)ev_cap; a.ev_overflow = &ctl->ev_overflow;
     a.skipmax = (int32_t *)ctx->d_skipmax.p;
     if (!columns_only) { ctx->last_scan = a; ctx->last_scan_pruned = a.prune && a.n_reads > 0; }
     if (a.n_reads > 0) {
-        Launch L(ctx, "k_tile_ranges");
-        hipLaunchKernelGGL(k_tile_ranges, dim3((n_tiles + 255) / 256), dim3(256), 0, ctx->stream, a);
-    }
-    if (a.n_reads > 0) {
+        { Launch L(ctx, "k_tile_ranges"); hipLaunchKernelGGL(k_tile_ranges, dim3((n_tiles + 255) / 256), dim3(256), 0, ctx->stream, a); }
         Launch L(ctx, "k_scan_tiles");
-        if (C == C3R_CH) hipLaunchKernelGGL(k_scan_tiles<C3R_CH>, dim3(std::min(n_tiles, list_grid())), dim3(SCAN_THREADS), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(k_scan_tiles<C3R_CH_PHASED>, dim3(std::min(n_tiles, list_grid())), dim3(SCAN_THREADS), 0, ctx->stream, a);
+        with_channels(ctx, [&](auto c) { hipLaunchKernelGGL(k_scan_tiles<decltype(c)::value>, dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, a); });
     }
     if (a.n_reads > 0 && C == C3R_CH_PHASED) {
         if ((rc = ensure_legacy_tables(ctx))) return rc;
@@ -1661,20 +1683,20 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
         f.cigar = (const uint32_t *)ctx->d_cigar.p; f.seq = a.seq; f.flags = a.flags; f.cols = a.cols; f.min_mq = a.min_mq; f.excl_flags = a.excl_flags;
         f.drop = a.drop; f.drop_words = a.drop_words;
         Launch L(ctx, "k_phase_recompute");
-        hipLaunchKernelGGL(k_phase_recompute, dim3(std::min(n_tiles, list_grid())), dim3(TILE), 0, ctx->stream, f);
+        hipLaunchKernelGGL(k_phase_recompute, dim3(grid), dim3(TILE), 0, ctx->stream, f);
     }
     if (a.n_reads > 0 && a.splice) {
         HIPCHK(ctx, hipMemsetAsync(ctx->d_skipmax.p, 0, (size_t)n_pos * 4, ctx->stream));
         Launch L(ctx, "k_skip_counts");
-        hipLaunchKernelGGL(k_skip_counts, dim3(std::min(n_tiles, list_grid())), dim3(SCAN_THREADS), 0, ctx->stream, a);
+        hipLaunchKernelGGL(k_skip_counts, dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, a);
     }
     // candidates live in tiles that hold aligned bases — except in genotyping mode, where any row of the site list is one
     const uint8_t *heavy = ctx->prm.genotyping_mode ? nullptr : (const uint8_t *)ctx->d_tile_cols.p;
     {
         Launch L(ctx, "k_select");
-        hipLaunchKernelGGL(k_select, dim3(std::min(n_tiles, list_grid())), dim3(TILE), 0, ctx->stream, (uint8_t *)ctx->d_flags.p,
+        hipLaunchKernelGGL(k_select, dim3(grid), dim3(TILE), 0, ctx->stream, (uint8_t *)ctx->d_flags.p,
                            (int)n_pos, (const TileGeo *)ctx->d_geo.p, ctx->prm.head_tail, (const int32_t *)ctx->d_lastrow.p, heavy,
-                           (const int32_t *)ctx->d_tile_list.p, (const int32_t *)((char *)ctx->d_small.p + 20));
+                           (const int32_t *)ctx->d_tile_list.p, (const int32_t *)&ctl->n_tile_list);
     }
     if (columns_only) { HIPCHK(ctx, hipGetLastError()); return C3R_OK; }
     {
@@ -1682,11 +1704,9 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
         hipLaunchKernelGGL(k_compact_count, dim3(n_cblocks), dim3(CMP_THREADS), 0, ctx->stream, (const uint8_t *)ctx->d_flags.p, (int)n_pos,
                            (int32_t *)ctx->d_blockcnt.p, heavy);
     }
-    {
-        if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_blockcnt.p, n_cblocks, (int32_t *)((char *)ctx->d_small.p + 12)))) return rc;
-    }
-    int32_t flag_cand[2] = {0, 0};       // event-scratch overflow flag, n_cand
-    HIPCHK(ctx, hipMemcpyAsync(flag_cand, (char *)ctx->d_small.p + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_blockcnt.p, n_cblocks, &ctl->n_cand))) return rc;
+    ColCtl h{};                          // host copy: the words read back below, and no others
+    HIPCHK(ctx, hipMemcpyAsync(&h.ev_overflow, &ctl->ev_overflow, offsetof(ColCtl, n_tok) - offsetof(ColCtl, ev_overflow), hipMemcpyDeviceToHost, ctx->stream));   // ev_overflow, n_cand
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     if (a.dbg) {
@@ -1696,18 +1716,18 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
         fprintf(stderr, "[k_scan_tiles] %llu heavy tiles; per tile: segments in range %.1f, listed %.1f, ops %.1f; us per tile: zero %.2f | cover+list+walk %.2f | scans %.2f | events %.2f | gates %.2f | store %.2f | first-seen %.2f\n",
                 d[15], d[13] / nt, d[12] / nt, d[14] / nt, d[0] / nt / 100, d[1] / nt / 100, d[2] / nt / 100, d[3] / nt / 100, d[4] / nt / 100, d[5] / nt / 100, d[6] / nt / 100);
     }
-    if ((flag_cand[0] & 2) && !ctx->win32) {
+    if ((h.ev_overflow & EV_OVF_DEPTH16) && !ctx->win32) {
         ctx->last_scan_pruned = false;
         if (columns_only) { /* columns are int32 anyway */ }
-        else if (base_row != 0) return fail(ctx, C3R_EOVERFLOW, "a position is covered by more than 32,767 reads and the batch already holds 16-bit windows: scan this region first, or alone");
-        else { ctx->win32 = true; return scan_column_store(ctx, n_regions, ctg_starts, ctg_ends, n_candidates, columns_only); }
+        else if (base_row != 0) return refuse_depth16_in_batch(ctx);
+        else { ctx->win32 = true; return scan_column_store(ctx, kn, n_regions, ctg_starts, ctg_ends, n_candidates, columns_only); }
     }
-    if (flag_cand[0] & 1) { ctx->last_scan_pruned = false; return fail(ctx, C3R_EOVERFLOW, "internal: indel-event scratch too small (%zu records) — nothing was written past it", ev_cap); }
-    const int32_t n_cand = flag_cand[1];
+    if (h.ev_overflow & EV_OVF_SCRATCH) { ctx->last_scan_pruned = false; return refuse_event_scratch(ctx, ev_cap); }
+    const int32_t n_cand = h.n_cand;
     ctx->last_cand = n_cand;
     if (n_candidates) *n_candidates = n_cand;
     if (n_cand == 0) return C3R_OK;
-    const size_t tbytes = (size_t)C3R_WINDOW * C * (ctx->win32 ? sizeof(int32_t) : sizeof(int16_t));          // the resident windows are int16 (a caller sees int32: c3r_get_tensors)
+    const size_t tbytes = window_bytes(ctx);
     if ((rc = ensure(ctx, ctx->d_cand, (size_t)n_cand * 4))) return rc;
     if ((rc = ensure_keep(ctx, ctx->d_tensors, (size_t)(base_row + n_cand) * tbytes, (size_t)base_row * tbytes))) return rc;
     if ((rc = ensure_keep(ctx, ctx->d_sites_out, (size_t)(base_cand + n_cand) * sizeof(c3r_site_t), (size_t)base_cand * sizeof(c3r_site_t)))) return rc;
@@ -1724,12 +1744,11 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
     {
         // token SLOTS per candidate (the gates' bound of the reads with something to say, TileOut::cov) -> first slots; [n_cand] = their total
         HIPCHK(ctx, hipMemsetAsync((int32_t *)ctx->d_tokcnt.p + n_cand, 0, 4, ctx->stream));
-        if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_tokcnt.p, (int)n_cand + 1, (int32_t *)((char *)ctx->d_small.p + 16)))) return rc;
+        if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_tokcnt.p, (int)n_cand + 1, &ctl->n_tok))) return rc;
     }
-    int32_t n_tok = 0;                   // slots
-    HIPCHK(ctx, hipMemcpyAsync(&n_tok, (char *)ctx->d_small.p + 16, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = ensure_keep(ctx, ctx->d_tok, std::max<size_t>((size_t)(base_tok + n_tok) * sizeof(c3r_token_t), 16),
+    HIPCHK(ctx, hipMemcpyAsync(&h.n_tok, &ctl->n_tok, sizeof h.n_tok, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // (h.n_tok: slots)
+    if ((rc = ensure_keep(ctx, ctx->d_tok, std::max<size_t>((size_t)(base_tok + h.n_tok) * sizeof(c3r_token_t), 16),
                           (size_t)base_tok * sizeof(c3r_token_t)))) return rc;
     {
         TileTokArgs t;
@@ -1737,18 +1756,17 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
         t.cand_idx = (const int32_t *)ctx->d_cand.p; t.tile_cand = (const int2 *)ctx->d_tile_cand.p;
         t.tok_off = (const int32_t *)ctx->d_tokcnt.p; t.sites = (c3r_site_t *)ctx->d_sites_out.p + base_cand;
         t.tok = (c3r_token_t *)ctx->d_tok.p; t.tok_base = (int32_t)base_tok;     // (sized exactly above)
-        t.totals = (int32_t *)((char *)ctx->d_small.p + 28);
+        t.totals = &ctl->tok_written;                                             // ([1]: tok_lost)
         Launch L(ctx, "k_tokens");
-        hipLaunchKernelGGL(k_tile_tokens, dim3(std::min(n_tiles, list_grid())), dim3(SCAN_THREADS), 0, ctx->stream, t);
+        hipLaunchKernelGGL(k_tile_tokens, dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, t);
     }
-    int32_t tok_done[2] = {0, 0};        // tokens written, tokens that found no slot
-    HIPCHK(ctx, hipMemcpyAsync(tok_done, (char *)ctx->d_small.p + 28, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&h.tok_written, &ctl->tok_written, offsetof(ColCtl, unused) - offsetof(ColCtl, tok_written), hipMemcpyDeviceToHost, ctx->stream));   // tok_written, tok_lost
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (tok_done[1]) return fail(ctx, C3R_EOVERFLOW, "internal: %d tokens found no slot (the gates' bound of a site's tokens was too small)", tok_done[1]);
+    if (h.tok_lost) return fail(ctx, C3R_EOVERFLOW, "internal: %d tokens found no slot (the gates' bound of a site's tokens was too small)", h.tok_lost);
     ctx->tokens_ready = true;
     ctx->n_cand = base_cand + n_cand;
-    ctx->n_tok += tok_done[0];
-    ctx->n_rows = base_row + n_cand; ctx->n_tokspace = base_tok + n_tok;
+    ctx->n_tok += h.tok_written;
+    ctx->n_rows = base_row + n_cand; ctx->n_tokspace = base_tok + h.n_tok;
     HIPCHK(ctx, hipGetLastError());
     return C3R_OK;
 }
@@ -1758,92 +1776,58 @@ static int scan_column_store(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg
 // kernels never write past them, and when the totals say something did not fit the buffers grow and the scan is repeated (the first
 // pass of a context; steady-state passes run once, without talking to the host in between).
 // raw_rerun: c3r_get_tensors(rescaled = 0) — the same scan again, un-rescaled windows only, into d_raw.
-static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates, bool raw_rerun) {
+static int scan_fused(c3r_ctx *ctx, const ScanKnobs &kn, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates, bool raw_rerun) {
     const int C = ctx->prm.channels;
-    // per region, rows: 1-based [max(1, ctg_start-33), ctg_end+33]  (src/create_tensor_pileup.py:411-415), cut into spans of FUSE_IN
-    // positions; a span's slots are tile * TILE + (p - p0)
-    std::vector<int64_t> key;
-    key.push_back(-2);                                                 // (geometry of the fused path)
-    for (int r = 0; r < n_regions; ++r) { key.push_back(ctg_starts[r]); key.push_back(ctg_ends[r]); }
-    const bool geo_changed = key != ctx->geo_key;
     int rc;
-    if (geo_changed) {
-        ctx->h_geo.clear();
-        std::vector<int2> regb((size_t)n_regions);
-        for (int r = 0; r < n_regions; ++r) {
-            int64_t es = ctg_starts[r] - C3R_WINDOW, ee = ctg_ends[r] + C3R_WINDOW;
-            if (es < 1) es = 1;
-            const int32_t beg0 = (int32_t)(es - 1), end0 = (int32_t)ee;
-            for (int32_t p0 = beg0; p0 < end0; p0 += FUSE_IN) ctx->h_geo.push_back(TileGeo{p0, std::min(p0 + FUSE_IN, end0), r, 0});
-            regb[(size_t)r] = make_int2(beg0, end0);
-            if (r == 0) { ctx->reg_beg0 = beg0; ctx->reg_end0 = end0; }
-        }
-        if ((int64_t)ctx->h_geo.size() * TILE > INT32_MAX - TILE) { ctx->geo_key.clear(); return fail(ctx, C3R_EINVAL, "regions too large for one scan (2^31 slots)"); }
-        ctx->geo_key = key;
-        if ((rc = upload(ctx, ctx->d_geo, ctx->h_geo.data(), ctx->h_geo.size())) || (rc = upload(ctx, ctx->d_regb, regb.data(), regb.size()))) { ctx->geo_key.clear(); return rc; }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));               // (regb is a temporary)
+    std::vector<int2> regb;
+    if ((rc = scan_geometry(ctx, n_regions, ctg_starts, ctg_ends, FUSE_IN, false, &regb))) return rc;
+    if (!regb.empty()) {                                              // (the geometry is new)
+        if ((rc = upload(ctx, ctx->d_regb, regb.data(), regb.size()))) { ctx->geo_key.clear(); return rc; }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));               // (the copy reads regb)
     }
-    ctx->n_regions = n_regions;
     const int n_tiles = (int)ctx->h_geo.size();
-    ctx->n_pos = (int64_t)n_tiles * TILE;
-    if (!raw_rerun) {
-        if (!ctx->batching) { ctx->n_cand = 0; ctx->n_tok = 0; ctx->n_rows = 0; ctx->n_tokspace = 0; }
-        ctx->last_cand = 0; ctx->last_base = ctx->n_cand; ctx->tokens_ready = false;
-    }
+    if (!raw_rerun) scan_output_begin(ctx);
     const int64_t base_cand = raw_rerun ? 0 : ctx->n_cand, base_row = raw_rerun ? 0 : ctx->n_rows, base_tok = raw_rerun ? 0 : ctx->n_tokspace;
     if (ctx->n_reads == 0 || n_tiles == 0) return C3R_OK;
     const size_t ev_cap = event_capacity(ctx, n_regions, ctg_starts, ctg_ends, n_tiles, 2);
     const int nblk = (n_tiles + 255) / 256;
-    // d_lb: [0] ticket of k_tile_ranges_fused, [4] ticket of k_deep_alleles, [8] candidates, [12] tokens (k_order_spans), [16] overflow
-    // bits, [20] listed spans, [24..31] event-scratch cursor, [32] event-scratch overflow, [36] rows handed out, [40] ticket of
-    // k_order_spans, [44] deep spans listed, [48] ticket of k_fused_deep, [52] giant spans met, [56] their slices listed, [60] ticket of k_deep_walk, [64..] the TICKET_Q ticket words of k_fused_tiles, 256 bytes apart, then the ALLOC_SHARDS allocator words (tokens << 32 |
-    // rows), 256 bytes apart; then look-back words: one per block of 256 spans for k_tile_ranges_fused, then the same for k_order_spans
-    const size_t lb_alloc = 64 + (size_t)TICKET_Q * TICKET_STRIDE * 4;
-    const size_t lb_head = lb_alloc + (size_t)ALLOC_SHARDS * ALLOC_STRIDE * 8;
-    const size_t lb_bytes = lb_head + (size_t)nblk * 24;         // (look-back words: k_tile_ranges_fused' sums, k_order_spans', k_tile_ranges_fused' run starts)
-    if ((rc = ensure(ctx, ctx->d_ev, ev_cap * sizeof(EvRec))) || (rc = ensure(ctx, ctx->d_lb, lb_bytes)) || (rc = ensure(ctx, ctx->d_tile_rng, (size_t)n_tiles * 16 + 16)) ||
+    const ScanCtlLayout lay(nblk);                                // (pileup_kernels.hpp, ScanCtl: the control block's head and what follows it)
+    if ((rc = ensure(ctx, ctx->d_ev, ev_cap * sizeof(EvRec))) || (rc = ensure(ctx, ctx->d_lb, lay.bytes)) || (rc = ensure(ctx, ctx->d_tile_rng, (size_t)n_tiles * 16 + 16)) ||
         (rc = ensure(ctx, ctx->d_tile_list, (size_t)n_tiles * 4 + 16)) ||
         (rc = ensure(ctx, ctx->d_span, (size_t)n_tiles * sizeof(int4) + 16)) || (rc = ensure(ctx, ctx->d_spanbase, (size_t)n_tiles * 4 + 16)) ||
         (rc = ensure(ctx, ctx->d_spanrec, (size_t)n_tiles * sizeof(SpanRec) + 16)) || (rc = ensure(ctx, ctx->d_deep, (size_t)n_tiles * 4 + 16)))
         return rc;
-    if (!ctx->h_scan) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_scan, 64 + (size_t)ALLOC_SHARDS * ALLOC_STRIDE * 8, hipHostMallocDefault));
-    const uint32_t *d_drop = nullptr;
-    int drop_words = 0;
-    if ((rc = depth_cap_mask(ctx, n_regions, ctg_starts, ctg_ends, &d_drop, &drop_words))) return rc;
-    char *lb = (char *)ctx->d_lb.p;
+    if (!ctx->h_scan) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_scan, sizeof(ScanReadback), hipHostMallocDefault));
+    const ScanReadback &h = *ctx->h_scan;
+    char *const lb = (char *)ctx->d_lb.p;
+    ScanCtl *const ctl = (ScanCtl *)lb;                           // (device memory: only its fields' addresses are taken here)
     FusedArgs f;
     memset(&f, 0, sizeof f);
     ScanArgs &a = f.a;
-    scan_inputs(ctx, a, d_drop, drop_words, n_tiles);
-    a.tile_rng = (int4 *)ctx->d_tile_rng.p; a.tile_list = (int32_t *)ctx->d_tile_list.p; a.n_tile_list = (int32_t *)(lb + 20);
-    a.ev = (EvRec *)ctx->d_ev.p; a.ev_cursor = (unsigned long long *)(lb + 24); a.ev_cap = (unsigned long long)ev_cap; a.ev_overflow = (int32_t *)(lb + 32);
-    if (getenv("C3R_SCAN_DBG")) {          // phase clocks of tile_columns (timing aid, off in production)
-        if ((rc = ensure(ctx, ctx->d_dbg, 32 * 8))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg.p, 0, 32 * 8, ctx->stream));
-        a.dbg = (unsigned long long *)ctx->d_dbg.p;
-    }
+    if ((rc = scan_inputs(ctx, kn, a, n_regions, ctg_starts, ctg_ends, n_tiles))) return rc;
+    a.tile_rng = (int4 *)ctx->d_tile_rng.p; a.tile_list = (int32_t *)ctx->d_tile_list.p; a.n_tile_list = &ctl->n_listed;
+    a.ev = (EvRec *)ctx->d_ev.p; a.ev_cursor = &ctl->ev_cursor; a.ev_cap = (unsigned long long)ev_cap; a.ev_overflow = &ctl->ev_overflow;
+    if ((rc = scan_dbg_buffer(ctx, kn, a))) return rc;
     f.span_rec = (const SpanRec *)ctx->d_spanrec.p;
     // the deep kernel's per-workgroup event buffers (every event of a span in arrival order: a span that outgrows the LDS store is bucketed from there
     // instead of walking its records again): 300 MB, so only for a context that has met a deep span (its first such scan walks twice)
     const int deep_grid = std::min(n_tiles, ctx->n_cu > 0 ? ctx->n_cu : 256);
-    const char *evwg_env = getenv("C3R_EVWG");          // (tests) 0: never, 1: from the first scan on
-    if ((ctx->seen_deep || (evwg_env && *evwg_env == '1')) && !(evwg_env && *evwg_env == '0')) {
+    if ((ctx->seen_deep || kn.evwg == 1) && kn.evwg != 0) {
         if ((rc = ensure(ctx, ctx->d_evwg, (size_t)deep_grid * DEEP_EVG_CAP * sizeof(EvRec)))) return rc;
         a.ev_wg = (EvRec *)ctx->d_evwg.p; a.ev_wg_cap = DEEP_EVG_CAP;
     }
     // giant spans (k_deep_walk, k_deep_alleles): 64 accumulator slots + the slice list (2 MB), a pool of 12 M events (288 MB) and their allele table
     // (192 MB), for a context that has met one
-    const char *giant_env = getenv("C3R_GIANT");        // (tests) 0: never, 1: from the first scan on
     const size_t giant_acc_bytes = (size_t)GIANT_SLOTS * GIANT_STRIDE * 4 + 16;          // (+ the pool's cursor: cleared with the slots)
-    a.n_giant = (int32_t *)(lb + 52); a.n_help = (int32_t *)(lb + 56);
-    if ((ctx->seen_giant || (giant_env && *giant_env == '1')) && !(giant_env && *giant_env == '0')) {
+    a.n_giant = &ctl->n_giant; a.n_help = &ctl->n_help;
+    if ((ctx->seen_giant || kn.giant == 1) && kn.giant != 0) {
         if ((rc = ensure(ctx, ctx->d_giant, giant_acc_bytes + (size_t)GIANT_SLOTS * GIANT_MAX_HELP * sizeof(int4))) ||
             (rc = ensure(ctx, ctx->d_giant_ev, (size_t)GIANT_POOL_EVENTS * sizeof(EvRec)))) return rc;
         a.giant_acc = (int32_t *)ctx->d_giant.p; a.help_list = (int4 *)((char *)ctx->d_giant.p + giant_acc_bytes); a.giant_ev = (EvRec *)ctx->d_giant_ev.p;
         a.giant_pool = GIANT_POOL_EVENTS; a.n_giant_ev = (int32_t *)((char *)ctx->d_giant.p + giant_acc_bytes - 16);
         a.deep_recs = (unsigned long long *)((char *)ctx->d_giant.p + giant_acc_bytes - 8);
-        { const char *e = getenv("C3R_SPLIT_CUS"); a.split_cus = e ? std::max(1, atoi(e)) : (ctx->n_cu > 0 ? ctx->n_cu : 256); }
-        if (!getenv("C3R_NO_GIANT_TAB")) {
+        a.split_cus = kn.split_cus;
+        if (!kn.no_giant_tab) {
             // (the allele table is all-zero between scans: cleared here when it is new, by k_fused_deep as it reads afterwards)
             const size_t tab_bytes = (size_t)GIANT_POOL_EVENTS * 2 * sizeof(uint2);
             const bool fresh = ctx->d_giant_tab.cap < tab_bytes;
@@ -1852,23 +1836,22 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
             a.giant_tab = (uint2 *)ctx->d_giant_tab.p;
         }
     }
-    f.ticket = (int32_t *)(lb + 64); f.alloc = (unsigned long long *)(lb + lb_alloc); f.overflow = (int32_t *)(lb + 16);
+    f.ticket = (int32_t *)(lb + lay.ticket); f.alloc = (unsigned long long *)(lb + lay.alloc); f.overflow = &ctl->overflow;
     f.rescale = raw_rerun ? 0 : 1; f.max_depth = ctx->prm.max_depth_rescale;
     f.span_info = (int4 *)ctx->d_span.p;
     // 30 channels: the per-read op / segment tables behind the ordered recompute of a flagged column (an IUPAC read base, an indel right
     // behind a ref-skip) are built only for a context that has met such a column: aligners emit neither, and the tables cost 0.12 ms of
-    // a 0.7-ms MAS-Seq chr20 pass.  Without them a flagged column raises bit 2 of the scan's flags and the scan is repeated with them.
-    const bool env_eager = [] { const char *e = getenv("C3R_LEGACY_EAGER"); return e && *e == '1'; }();
-    if (C == C3R_CH_PHASED && (ctx->legacy_wanted || env_eager) && (rc = ensure_legacy_tables(ctx))) return rc;
+    // a 0.7-ms MAS-Seq chr20 pass.  Without them a flagged column raises FUSED_OVF_ORDER_TABLES and the scan is repeated with them.
+    if (C == C3R_CH_PHASED && (ctx->legacy_wanted || kn.legacy_eager) && (rc = ensure_legacy_tables(ctx))) return rc;
     const bool have_tables = C == C3R_CH_PHASED && ctx->legacy_valid;
     f.ph.reads = a.reads; f.ph.rsegs = have_tables ? (const DevSeg *)ctx->d_rsegs.p : nullptr; f.ph.rseg_first = have_tables ? (const uint32_t *)ctx->d_rseg_first.p : nullptr;
     f.ph.cigar = (const uint32_t *)ctx->d_cigar.p; f.ph.seq = a.seq;
     f.ph.min_mq = a.min_mq; f.ph.excl_flags = a.excl_flags; f.ph.drop = a.drop; f.ph.drop_words = a.drop_words;
-    const size_t tbytes = (size_t)C3R_WINDOW * C * (ctx->win32 ? sizeof(int32_t) : sizeof(int16_t));          // the resident windows are int16 (a caller sees int32: c3r_get_tensors)
+    const size_t tbytes = window_bytes(ctx);
     // What this scan may write.  A small scan has one allocator and dense output: whatever the buffers can take beyond what the batch
     // already holds.  A large one hands rows and token slots out through ALLOC_SHARDS sub-allocators of equal size, sized from what the
     // previous large scan needed; when a shard runs over, the scan is repeated with what the counters say it needs.
-    const int nsh = raw_rerun ? ctx->last_shards : ((n_tiles >= 4096 && !getenv("C3R_ONE_SHARD")) ? ALLOC_SHARDS : 1);
+    const int nsh = raw_rerun ? ctx->last_shards : ((n_tiles >= 4096 && !kn.one_shard) ? ALLOC_SHARDS : 1);
     int64_t want_c, want_t;            // per shard
     if (raw_rerun) { want_c = ctx->last_shard_rows; want_t = 0; }
     else if (nsh == 1) {
@@ -1907,34 +1890,30 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
         f.cand_cap = (int32_t)rows;
         z.meta = f.meta; z.span_info = f.span_info; z.span_base = (const int32_t *)ctx->d_spanbase.p; z.alloc = f.alloc; z.n_shards = nsh; z.shard_rows = f.shard_rows; z.overflow = f.overflow;
         z.ref = a.ref; z.ref_beg0 = a.ref_beg0; z.ref_len = a.ref_len;
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_lb.p, 0, lb_bytes, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_lb.p, 0, lay.bytes, ctx->stream));
         if (a.giant_acc) HIPCHK(ctx, hipMemsetAsync(a.giant_acc, 0, giant_acc_bytes, ctx->stream));
         {
             Launch L(ctx, "k_tile_ranges");
-            hipLaunchKernelGGL(k_tile_ranges_fused, dim3(nblk), dim3(256), 0, ctx->stream, a, (int32_t *)lb, (unsigned long long *)(lb + lb_head), nblk, (const int2 *)ctx->d_regb.p,
-                               (SpanRec *)ctx->d_spanrec.p, (int32_t *)ctx->d_deep.p, (int32_t *)(lb + 44), (unsigned long long *)(lb + lb_head + (size_t)nblk * 16));
+            hipLaunchKernelGGL(k_tile_ranges_fused, dim3(nblk), dim3(256), 0, ctx->stream, a, &ctl->ticket_ranges, (unsigned long long *)(lb + lay.lb_ranges), nblk, (const int2 *)ctx->d_regb.p,
+                               (SpanRec *)ctx->d_spanrec.p, (int32_t *)ctx->d_deep.p, &ctl->n_deep, (unsigned long long *)(lb + lay.lb_runs));
         }
         // the deep spans k_fused_tiles leaves out go to k_fused_deep: one workgroup of sixteen wavefronts per CU, spans by ticket (no deep span: the
         // workgroups leave at once).  The two kernels share nothing but the allocators and run side by side, the deep one on its own stream; under
         // the profiler (one kernel at a time, each timed on the context's stream) they run one after the other.
-        const bool side = !ctx->profiling && !getenv("C3R_DEEP_SERIAL");
+        const bool side = !ctx->profiling && !kn.deep_serial;
         // the giant spans' walks and allele counts, slice by slice on every CU (two workgroups each: the allele pass is round trips), before the deep
         // kernel takes the spans
-        static const int wg_mul = [] { const char *e = getenv("C3R_GIANT_WGS"); return e ? std::max(1, atoi(e)) : 2; }();
-        const int help_grid = (ctx->n_cu > 0 ? ctx->n_cu : 256) * wg_mul;
-        auto launch_walk = [&](hipStream_t st) {
-            WalkArgs w{(const SpanRec *)ctx->d_spanrec.p, (int32_t *)(lb + 60)};
-            if (C == C3R_CH) hipLaunchKernelGGL(k_deep_walk<C3R_CH>, dim3(help_grid), dim3(DEEP_THREADS), 0, st, a, w);
-            else hipLaunchKernelGGL(k_deep_walk<C3R_CH_PHASED>, dim3(help_grid), dim3(DEEP_THREADS), 0, st, a, w);
-        };
-        auto launch_alleles = [&](hipStream_t st) {
-            if (C == C3R_CH) hipLaunchKernelGGL(k_deep_alleles<C3R_CH>, dim3(help_grid), dim3(DEEP_THREADS), 0, st, a, (int32_t *)(lb + 4));
-            else hipLaunchKernelGGL(k_deep_alleles<C3R_CH_PHASED>, dim3(help_grid), dim3(DEEP_THREADS), 0, st, a, (int32_t *)(lb + 4));
-        };
-        auto launch_deep = [&](hipStream_t st) {
-            DeepArgs d{(const int32_t *)ctx->d_deep.p, (const int32_t *)(lb + 44), (int32_t *)(lb + 48)};
-            if (C == C3R_CH) hipLaunchKernelGGL(k_fused_deep<C3R_CH>, dim3(deep_grid), dim3(DEEP_THREADS), 0, st, f, d);
-            else hipLaunchKernelGGL(k_fused_deep<C3R_CH_PHASED>, dim3(deep_grid), dim3(DEEP_THREADS), 0, st, f, d);
+        const int help_grid = (ctx->n_cu > 0 ? ctx->n_cu : 256) * kn.giant_wgs;
+        auto launch_deep_kernels = [&](hipStream_t st) {          // (the timers: under the profiler only, where st is the context's stream)
+            WalkArgs w{(const SpanRec *)ctx->d_spanrec.p, &ctl->ticket_walk};
+            DeepArgs d{(const int32_t *)ctx->d_deep.p, &ctl->n_deep, &ctl->ticket_deep};
+            with_channels(ctx, [&](auto c) {
+                constexpr int CH = decltype(c)::value;
+                if (a.giant_acc) { Launch L(ctx, "k_deep_walk"); hipLaunchKernelGGL(k_deep_walk<CH>, dim3(help_grid), dim3(DEEP_THREADS), 0, st, a, w); }
+                if (a.giant_tab) { Launch L(ctx, "k_deep_alleles"); hipLaunchKernelGGL(k_deep_alleles<CH>, dim3(help_grid), dim3(DEEP_THREADS), 0, st, a, &ctl->ticket_alleles); }
+                Launch L(ctx, "k_fused_deep");
+                hipLaunchKernelGGL(k_fused_deep<CH>, dim3(deep_grid), dim3(DEEP_THREADS), 0, st, f, d);
+            });
         };
         if (side) {
             if (!ctx->deep_stream) {
@@ -1948,40 +1927,32 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
             }
             HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
             HIPCHK(ctx, hipStreamWaitEvent(ctx->deep_stream, ctx->ev_fork, 0));
-            if (a.giant_acc) launch_walk(ctx->deep_stream);
-            if (a.giant_tab) launch_alleles(ctx->deep_stream);
-            launch_deep(ctx->deep_stream);
+            launch_deep_kernels(ctx->deep_stream);
             HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->deep_stream));
         }
         {
             Launch L(ctx, "k_fused_tiles");
             const int grid = std::min(n_tiles, 2048);
-            if (C == C3R_CH) hipLaunchKernelGGL(k_fused_tiles<C3R_CH>, dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, f);
-            else hipLaunchKernelGGL(k_fused_tiles<C3R_CH_PHASED>, dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, f);
+            with_channels(ctx, [&](auto c) { hipLaunchKernelGGL(k_fused_tiles<decltype(c)::value>, dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, f); });
         }
         if (side) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        else {
-            if (a.giant_acc) { Launch L(ctx, "k_deep_walk"); launch_walk(ctx->stream); }
-            if (a.giant_tab) { Launch L(ctx, "k_deep_alleles"); launch_alleles(ctx->stream); }
-            Launch L(ctx, "k_fused_deep");
-            launch_deep(ctx->stream);
-        }
+        else launch_deep_kernels(ctx->stream);
         {
             Launch L(ctx, "k_order_sites");
-            hipLaunchKernelGGL(k_order_spans, dim3(nblk), dim3(256), 0, ctx->stream, (const int4 *)ctx->d_span.p, (const int32_t *)(lb + 20), (int32_t *)(lb + 40),
-                               (unsigned long long *)(lb + lb_head + (size_t)nblk * 8), (int32_t *)ctx->d_spanbase.p, (int32_t *)(lb + 8));
+            hipLaunchKernelGGL(k_order_spans, dim3(nblk), dim3(256), 0, ctx->stream, (const int4 *)ctx->d_span.p, (const int32_t *)&ctl->n_listed, &ctl->ticket_order,
+                               (unsigned long long *)(lb + lay.lb_order), (int32_t *)ctx->d_spanbase.p, &ctl->n_cand /* totals: n_cand, n_tok */);
             hipLaunchKernelGGL(k_finalize_sites, dim3((unsigned)std::min<int64_t>((rows + 15) / 16 + 1, 8192)), dim3(256), 0, ctx->stream, z);
         }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scan, lb + 8, 52, hipMemcpyDeviceToHost, ctx->stream));          // (.. [9]: deep spans listed, [11]: giant spans met, [12]: their slices)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scan + 16, lb + lb_alloc, (size_t)ALLOC_SHARDS * ALLOC_STRIDE * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&ctx->h_scan->ctl, ctl, sizeof(ScanCtl), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scan->alloc, lb + lay.alloc, sizeof h.alloc, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipGetLastError());
-        n_cand = ctx->h_scan[0]; n_tok = ctx->h_scan[1];
-        if (ctx->h_scan[9] > 0) ctx->seen_deep = true;
-        if (ctx->h_scan[9] > 0 && ctx->h_scan[11] != 0) ctx->seen_giant = true;
+        n_cand = h.ctl.n_cand; n_tok = h.ctl.n_tok;
+        if (h.ctl.n_deep > 0) ctx->seen_deep = true;
+        if (h.ctl.n_deep > 0 && h.ctl.n_giant != 0) ctx->seen_giant = true;
         int64_t need_c = 0, need_t = 0;          // the fullest shard
         for (int sh = 0; sh < nsh; ++sh) {
-            const unsigned long long v = ((const unsigned long long *)(ctx->h_scan + 16))[(size_t)sh * ALLOC_STRIDE];
+            const unsigned long long v = h.alloc[(size_t)sh * ALLOC_STRIDE];
             need_c = std::max<int64_t>(need_c, (int64_t)(uint32_t)v); need_t = std::max<int64_t>(need_t, (int64_t)(v >> 32));
         }
         if (a.dbg && a.giant_acc) {
@@ -1990,7 +1961,7 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
             for (int g = 0; g < GIANT_SLOTS; ++g)
                 HIPCHK(ctx, hipMemcpy(&evn[g], a.giant_acc + (size_t)g * GIANT_STRIDE + GIANT_META, 4, hipMemcpyDeviceToHost));
             std::sort(evn.begin(), evn.end(), std::greater<int32_t>());
-            fprintf(stderr, "[giant spans] %d met; events per slot, largest first:", ctx->h_scan[11]);
+            fprintf(stderr, "[giant spans] %d met; events per slot, largest first:", h.ctl.n_giant);
             for (int g = 0; g < GIANT_SLOTS && evn[g] > 0; ++g) fprintf(stderr, " %d", evn[g]);
             fprintf(stderr, "\n");
         }
@@ -2004,7 +1975,7 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
             fprintf(stderr, "   LDS event store: leader search (thread 0) %.2f | wait for the others %.2f us\n", d[16] / nt / 100, d[17] / nt / 100);
             if (d[18]) fprintf(stderr, "   k_fused_deep: the longest span took %.1f us (%llu records in range)\n", (double)(d[18] >> 24) / 100.0, (d[18] & 0xffffffull) << 4);
         }
-        if ((ctx->h_scan[2] & 4) && !f.ph.rsegs) {
+        if ((h.ctl.overflow & FUSED_OVF_ORDER_TABLES) && !f.ph.rsegs) {
             // a flagged column and no tables yet: build them (this context keeps doing so from now on) and run the scan again
             ctx->legacy_wanted = true;
             if ((rc = ensure_legacy_tables(ctx))) return rc;
@@ -2012,16 +1983,16 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
             --attempt;
             continue;
         }
-        if ((ctx->h_scan[6] & 2) && !ctx->win32 && !raw_rerun) {
-            if (base_row != 0) return fail(ctx, C3R_EOVERFLOW, "a position is covered by more than 32,767 reads and the batch already holds 16-bit windows: scan this region first, or alone");
+        if ((h.ctl.ev_overflow & EV_OVF_DEPTH16) && !ctx->win32 && !raw_rerun) {
+            if (base_row != 0) return refuse_depth16_in_batch(ctx);
             ctx->win32 = true;                 // (16-bit windows cannot hold this scan's counts: once more, with int32 windows)
-            return scan_fused(ctx, n_regions, ctg_starts, ctg_ends, n_candidates, false);
+            return scan_fused(ctx, kn, n_regions, ctg_starts, ctg_ends, n_candidates, false);
         }
-        if (ctx->h_scan[6] & 1) return fail(ctx, C3R_EOVERFLOW, "internal: indel-event scratch too small (%zu records) — nothing was written past it", ev_cap);
-        if (ctx->h_scan[2] & 8) return fail(ctx, C3R_EOVERFLOW, "internal: tokens found no slot (the gates' bound of a site's tokens was too small)");
+        if (h.ctl.ev_overflow & EV_OVF_SCRATCH) return refuse_event_scratch(ctx, ev_cap);
+        if (h.ctl.overflow & FUSED_OVF_TOKEN_LOST) return fail(ctx, C3R_EOVERFLOW, "internal: tokens found no slot (the gates' bound of a site's tokens was too small)");
         if (n_cand < 0 || n_tok < 0) return fail(ctx, C3R_EOVERFLOW, "too many candidates or tokens for one scan");
         if (raw_rerun) {
-            if (ctx->h_scan[2] & 1) {
+            if (h.ctl.overflow & FUSED_OVF_SHARD) {
                 // a shard ran over: which workgroup takes a span depends on dynamic tickets and stealing across queues, so the shards' loads
                 // differ from run to run and a shard that fitted in the scan itself may not fit now — grow and repeat like the scan does
                 // (d_raw / d_rawidx are private to the re-run)
@@ -2032,7 +2003,7 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
             if (n_cand != ctx->last_cand) return fail(ctx, C3R_EINVAL, "internal: the raw re-run found %d candidates, the scan %lld", n_cand, (long long)ctx->last_cand);
             return C3R_OK;
         }
-        if (need_c <= want_c && need_t <= want_t && !(ctx->h_scan[2] & 1)) {
+        if (need_c <= want_c && need_t <= want_t && !(h.ctl.overflow & FUSED_OVF_SHARD)) {
             if (nsh > 1) { ctx->hint_rows = (int32_t)std::min<int64_t>(need_c + need_c / 4 + 64, INT32_MAX / nsh); ctx->hint_toks = (int32_t)std::min<int64_t>(need_t + need_t / 4 + 2048, INT32_MAX / nsh); }
             break;
         }
@@ -2041,7 +2012,7 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
         want_t = std::max<int64_t>(want_t, need_t + need_t / 4 + 1024);
     }
     ctx->last_cand = n_cand; ctx->last_shards = nsh; ctx->last_shard_rows = (int32_t)want_c;
-    ctx->scan_counts[0] = ctx->h_scan[3]; ctx->scan_counts[1] = ctx->h_scan[9]; ctx->scan_counts[2] = ctx->h_scan[11]; ctx->scan_counts[3] = ctx->h_scan[12];
+    ctx->scan_counts[0] = h.ctl.n_listed; ctx->scan_counts[1] = h.ctl.n_deep; ctx->scan_counts[2] = h.ctl.n_giant; ctx->scan_counts[3] = h.ctl.n_help;
     if (n_candidates) *n_candidates = n_cand;
     ctx->tokens_ready = true;
     ctx->n_cand = base_cand + n_cand;
@@ -2049,8 +2020,36 @@ static int scan_fused(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts
     // (one allocator: dense output, the next scan of the batch appends; several: the scan's whole row / token space is taken)
     ctx->n_rows = base_row + (nsh == 1 ? (int64_t)n_cand : want_c * nsh);
     // (token SLOTS: what the allocators handed out — a site reserves the gates' bound and n_tok counts what was written)
-    ctx->n_tokspace = base_tok + (nsh == 1 ? (int64_t)(((const unsigned long long *)(ctx->h_scan + 16))[0] >> 32) : want_t * nsh);
+    ctx->n_tokspace = base_tok + (nsh == 1 ? (int64_t)(h.alloc[0] >> 32) : want_t * nsh);
     return C3R_OK;
+}
+
+int c3r_pileup_scan_regions(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_starts, const int64_t *ctg_ends, int64_t *n_candidates) {
+    if (!ctx || n_regions < 1 || !ctg_starts || !ctg_ends) return C3R_EINVAL;
+    if (ctx->ref_len == 0) return fail(ctx, C3R_EINVAL, "c3r_set_reference must be called before c3r_pileup_scan");
+    for (int r = 0; r < n_regions; ++r) {
+        if (ctg_ends[r] < ctg_starts[r]) return C3R_EINVAL;
+        // (the scan kernels add up to two tiles and a flank to a region position in plain int: C3R_CTG_END_MAX leaves them 1024, include/c3r.h)
+        if (ctg_ends[r] > C3R_CTG_END_MAX) return fail(ctx, C3R_EINVAL, "region %d ends beyond C3R_CTG_END_MAX = %lld (2^31 - 1 - 33 - 1024)", r, (long long)C3R_CTG_END_MAX);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n_candidates) *n_candidates = 0;
+    { const int rc_af = af_table(ctx); if (rc_af) return rc_af; }
+    ctx->last_starts.assign(ctg_starts, ctg_starts + n_regions); ctx->last_ends.assign(ctg_ends, ctg_ends + n_regions);
+    ctx->last_scan_pruned = false;
+    memset(ctx->scan_counts, 0, sizeof ctx->scan_counts);          // (a fused scan that succeeds fills them in)
+    // The plain mode runs in one fused tile kernel (k_fused_tiles).  Head/tail calling (the end-of-stream rule needs the last row of the
+    // whole region), splice padding (in-place column edits, candidate after candidate) and genotyping mode (candidates in intron-only
+    // spans) keep the column store and its selection / compaction / gather kernels.
+    const ScanKnobs kn = read_scan_knobs(ctx);
+    const bool fused = !ctx->prm.head_tail && !ctx->prm.splice_padding && !ctx->prm.genotyping_mode && !kn.no_fuse;
+    ctx->last_fused = fused;
+    return fused ? scan_fused(ctx, kn, n_regions, ctg_starts, ctg_ends, n_candidates, false)
+                 : scan_column_store(ctx, kn, n_regions, ctg_starts, ctg_ends, n_candidates, false);
+}
+
+int c3r_pileup_scan(c3r_ctx *ctx, int64_t ctg_start, int64_t ctg_end, int64_t *n_candidates) {
+    return c3r_pileup_scan_regions(ctx, 1, &ctg_start, &ctg_end, n_candidates);
 }
 
 int c3r_batch_begin(c3r_ctx *ctx) {
@@ -2095,7 +2094,7 @@ int c3r_get_tensors(c3r_ctx *ctx, int rescaled, int32_t *tensors, int64_t cap_si
         if (ctx->last_base != 0 || ctx->last_cand != ctx->n_cand)
             return fail(ctx, C3R_EINVAL, "raw tensors are only available for a single (non-batched) scan");
         if (ctx->last_fused) {               // the fused path keeps no columns: the scan runs again, un-rescaled windows only
-            int rc = scan_fused(ctx, (int32_t)ctx->last_starts.size(), ctx->last_starts.data(), ctx->last_ends.data(), nullptr, true);
+            int rc = scan_fused(ctx, read_scan_knobs(ctx), (int32_t)ctx->last_starts.size(), ctx->last_starts.data(), ctx->last_ends.data(), nullptr, true);
             if (rc) return rc;
             idx = (const int32_t *)ctx->d_rawidx.p;
         } else {
@@ -2148,9 +2147,9 @@ int c3r_get_tokens(c3r_ctx *ctx, c3r_token_t *tokens, int64_t cap_tokens) {
     // site order (see c3r_get_sites): offsets = exclusive sums of the sites' token counts, then one wavefront per site copies its run
     const int n = (int)ctx->n_cand;
     int rc;
-    if ((rc = ensure(ctx, ctx->d_tokoff, (size_t)(n + 2) * 4)) || (rc = ensure(ctx, ctx->d_tokexp, (size_t)ctx->n_tok * sizeof(c3r_token_t))) || (rc = ensure(ctx, ctx->d_small, 64))) return rc;
+    if ((rc = ensure(ctx, ctx->d_tokoff, (size_t)(n + 2) * 4)) || (rc = ensure(ctx, ctx->d_tokexp, (size_t)ctx->n_tok * sizeof(c3r_token_t))) || (rc = ensure(ctx, ctx->d_small, sizeof(ColCtl)))) return rc;
     hipLaunchKernelGGL(k_site_ntok, dim3((unsigned)(n / 256 + 1)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p, n, (int32_t *)ctx->d_tokoff.p);
-    if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_tokoff.p, n + 1, (int32_t *)((char *)ctx->d_small.p + 48)))) return rc;
+    if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_tokoff.p, n + 1, &((ColCtl *)ctx->d_small.p)->export_toks))) return rc;
     hipLaunchKernelGGL(k_export_tokens, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 8192)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p,
                        (const int32_t *)ctx->d_tokoff.p, n, (const c3r_token_t *)ctx->d_tok.p, (c3r_token_t *)ctx->d_tokexp.p);
     HIPCHK(ctx, hipMemcpyAsync(tokens, ctx->d_tokexp.p, (size_t)ctx->n_tok * sizeof(c3r_token_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2178,11 +2177,12 @@ int c3r_get_columns(c3r_ctx *ctx, int64_t *region_start, int64_t *n_pos, int32_t
     if (!cols && !depth && !flags) return C3R_OK;
     if (cap_pos < npos0) return fail(ctx, C3R_EOVERFLOW, "need room for %lld positions", (long long)npos0);
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    const ScanKnobs kn = read_scan_knobs(ctx);
     if (ctx->last_fused) {
         // the fused path never materialises columns: build those of the scan's first region now, through the column store
         if (ctx->last_starts.empty()) return fail(ctx, C3R_EINVAL, "no scan yet");
         int rc = af_table(ctx);
-        if (!rc) rc = scan_column_store(ctx, 1, ctx->last_starts.data(), ctx->last_ends.data(), nullptr, true);
+        if (!rc) rc = scan_column_store(ctx, kn, 1, ctx->last_starts.data(), ctx->last_ends.data(), nullptr, true);
         ctx->geo_key.clear();                // (the device now holds the column store's geometry)
         if (rc) return rc;
     }
@@ -2190,8 +2190,7 @@ int c3r_get_columns(c3r_ctx *ctx, int64_t *region_start, int64_t *n_pos, int32_t
         // the scan skipped intron-only tiles that no candidate window can reach: compute their row flags now
         ScanArgs a = ctx->last_scan;
         a.tile_list = a.tile_list2; a.n_tile_list = a.n_tile_list2;
-        if (ctx->prm.channels == C3R_CH) hipLaunchKernelGGL(k_scan_tiles<C3R_CH>, dim3(std::min((int)a.n_tiles, list_grid())), dim3(SCAN_THREADS), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(k_scan_tiles<C3R_CH_PHASED>, dim3(std::min((int)a.n_tiles, list_grid())), dim3(SCAN_THREADS), 0, ctx->stream, a);
+        with_channels(ctx, [&](auto c) { hipLaunchKernelGGL(k_scan_tiles<decltype(c)::value>, dim3(std::min((int)a.n_tiles, kn.list_grid)), dim3(SCAN_THREADS), 0, ctx->stream, a); });
         ctx->last_scan_pruned = false;
         HIPCHK(ctx, hipGetLastError());
     }
@@ -2493,15 +2492,15 @@ int c3r_rows_begin_ex(c3r_ctx *ctx, int drop_ref_calls, const c3r_read_t *host_r
     bool packed = false;
     if (drop_ref_calls) {
         int rc0;
-        if ((rc0 = ensure(ctx, ctx->d_keep, (size_t)(n_all + 2) * 4)) || (rc0 = ensure(ctx, ctx->d_small, 64))) { delete r; return rc0; }
+        if ((rc0 = ensure(ctx, ctx->d_keep, (size_t)(n_all + 2) * 4)) || (rc0 = ensure(ctx, ctx->d_small, sizeof(ColCtl)))) { delete r; return rc0; }
         hipLaunchKernelGGL(k_row_keep, dim3((unsigned)(n_all / 256 + 1)), dim3(256), 0, ctx->stream, d_sites_src, d_probs_src, (int)n_all, (int32_t *)ctx->d_keep.p);
-        if ((rc0 = device_excl_scan(ctx, (int32_t *)ctx->d_keep.p, (int)n_all + 1, (int32_t *)((char *)ctx->d_small.p + 52)))) { delete r; return rc0; }
+        if ((rc0 = device_excl_scan(ctx, (int32_t *)ctx->d_keep.p, (int)n_all + 1, &((ColCtl *)ctx->d_small.p)->n_keep))) { delete r; return rc0; }
         int32_t n_keep = 0;
         // (the keep decision reads the probabilities: the layer-2 time-out word is checked with the same wait, before the count is acted on —
         // a timed-out batch whose garbage looks like RefCalls must fail, not come back as an empty snapshot)
         int32_t *lstm_st0 = nullptr;
         if ((rc0 = queue_lstm_status(ctx, &lstm_st0))) { delete r; return rc0; }
-        if (hipMemcpyAsync(&n_keep, (char *)ctx->d_small.p + 52, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        if (hipMemcpyAsync(&n_keep, &((ColCtl *)ctx->d_small.p)->n_keep, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             delete r; return fail(ctx, C3R_EHIP, "reading the number of kept sites failed");
         }
         if ((rc0 = check_lstm_status(ctx, lstm_st0))) { delete r; return rc0; }

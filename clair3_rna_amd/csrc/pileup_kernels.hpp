@@ -137,6 +137,12 @@ struct TileGeo {
 };
 static_assert(sizeof(TileGeo) == 16, "TileGeo must be 16 bytes");
 
+// bits of *ScanArgs::ev_overflow: raised by the tile kernels, tested by the host after the scan's read-back
+enum EvOverflow : int32_t {
+    EV_OVF_SCRATCH = 1,           // a tile's events found no room in the event scratch (it skipped them)
+    EV_OVF_DEPTH16 = 2,           // a position covered by 32768 reads or more — its counts may not fit the 16-bit windows
+};
+
 struct ScanArgs {
     const DevRead *reads;
     const uint8_t *seq;
@@ -201,7 +207,7 @@ struct ScanArgs {
     // all decide by this after the list kernel has finished (giant_on).
     unsigned long long *deep_recs;
     int32_t split_cus;            // compute units (env C3R_SPLIT_CUS)
-    int32_t *ev_overflow;         // bit 0: the event scratch; bit 1: a position covered by 32768 reads or more — its counts may not fit the 16-bit windows
+    int32_t *ev_overflow;         // EvOverflow bits
     int32_t *last_row;            // [n_regions] atomicMax of the last SLOT (index into the position arrays) with a row
     const uint32_t *drop;         // mpileup depth cap: [n_regions][drop_words] bit per read = discarded in that region; null: none
     int32_t drop_words;
@@ -996,7 +1002,7 @@ __device__ __forceinline__ TileOut tile_columns(const ScanArgs &a, TileMem<C, EV
     int tot, ev_total;
     const int2 ex = block_excl_scan2<NT>(my_cov_d, nev, M.scan_slot[0], &tot, &ev_total);
     const int my_cov = (C3R_ABL(a) & 256) ? 1 : ex.x + my_cov_d;
-    if (pos_thread && my_cov >= 32768) atomicOr(a.ev_overflow, 2);          // (every count of a column is a count of reads that cover it: below this, the windows fit int16)
+    if (pos_thread && my_cov >= 32768) atomicOr(a.ev_overflow, EV_OVF_DEPTH16);         // (every count of a column is a count of reads that cover it: below this, the windows fit int16)
     if (pos_thread) M.evoff[tid] = ex.y;
     C3R_PHASE(2);
     if (C3R_ABL(a) & 524288) { __syncthreads(); __syncthreads(); __syncthreads(); __syncthreads(); }
@@ -1171,7 +1177,7 @@ __device__ __forceinline__ TileOut tile_columns(const ScanArgs &a, TileMem<C, EV
             if (evb + ev_units + tab_units > a.ev_cap) {
                 // cannot happen with the host's sizing (c3r_pileup_scan_regions); if it ever does, no write leaves the buffer and the
                 // scan call fails instead of corrupting device memory
-                if (tid == 0) atomicOr(a.ev_overflow, 1);
+                if (tid == 0) atomicOr(a.ev_overflow, EV_OVF_SCRATCH);
             } else {
                 events(a.ev + evb);
             }
@@ -2150,6 +2156,61 @@ constexpr int TICKET_Q = 16, TICKET_STRIDE = 64;     // ticket words 256 bytes a
 constexpr int ALLOC_SHARDS = 16, ALLOC_STRIDE = 32;  // (u64 words)
 struct CandMeta { int32_t slot, depth, ncov, tpre, span, pos0; };      // per arrived candidate: slot (tile * TILE + offset), depth, its tokens (the slots reserved until the token pass has counted), token slots of the
                                                                        // span's earlier candidates, list index of its span, its 0-based position
+// bits of *FusedArgs::overflow: raised by the span kernels, tested by k_finalize_sites and by the host after the scan's read-back
+enum FusedOverflow : int32_t {
+    FUSED_OVF_SHARD = 1,          // a span's candidates or tokens did not fit into its shard (nothing was written past it): grow and repeat
+    FUSED_OVF_ORDER_TABLES = 4,   // 30 channels: a flagged column and no op / segment tables yet: build them and repeat
+    FUSED_OVF_TOKEN_LOST = 8,     // a token found no slot (the gates' bound of a site's tokens was too small): the scan fails
+};
+// The fused scan's control block on the device (c3r_ctx::d_lb), cleared before every attempt.  The kernels take pointers to single words of it;
+// the host forms them from these fields and reads the 64-byte head back by name.
+struct ScanCtl {
+    int32_t ticket_ranges;        // ticket of k_tile_ranges_fused
+    int32_t ticket_alleles;       // ticket of k_deep_alleles
+    int32_t n_cand, n_tok;        // candidates, tokens (k_order_spans' totals[0], [1])
+    int32_t overflow;             // FusedOverflow bits (FusedArgs::overflow)
+    int32_t n_listed;             // listed spans (ScanArgs::n_tile_list)
+    unsigned long long ev_cursor; // event-scratch cursor (ScanArgs::ev_cursor)
+    int32_t ev_overflow;          // EvOverflow bits (ScanArgs::ev_overflow)
+    int32_t rows_out;             // rows handed out
+    int32_t ticket_order;         // ticket of k_order_spans
+    int32_t n_deep;               // deep spans listed
+    int32_t ticket_deep;          // ticket of k_fused_deep
+    int32_t n_giant, n_help;      // giant spans met, their slices listed (ScanArgs::n_giant, ::n_help)
+    int32_t ticket_walk;          // ticket of k_deep_walk
+};
+static_assert(sizeof(ScanCtl) == 64 && offsetof(ScanCtl, ticket_ranges) == 0 && offsetof(ScanCtl, ticket_alleles) == 4 && offsetof(ScanCtl, n_cand) == 8 &&
+              offsetof(ScanCtl, n_tok) == 12 && offsetof(ScanCtl, overflow) == 16 && offsetof(ScanCtl, n_listed) == 20 && offsetof(ScanCtl, ev_cursor) == 24 &&
+              offsetof(ScanCtl, ev_overflow) == 32 && offsetof(ScanCtl, rows_out) == 36 && offsetof(ScanCtl, ticket_order) == 40 && offsetof(ScanCtl, n_deep) == 44 &&
+              offsetof(ScanCtl, ticket_deep) == 48 && offsetof(ScanCtl, n_giant) == 52 && offsetof(ScanCtl, n_help) == 56 && offsetof(ScanCtl, ticket_walk) == 60,
+              "ScanCtl layout");
+// ... and what follows the head, byte offsets from the block's start for a scan of nblk blocks of 256 spans: k_fused_tiles' TICKET_Q ticket words,
+// the ALLOC_SHARDS allocator words, then three arrays of look-back words, one word per block each
+struct ScanCtlLayout {
+    size_t ticket, alloc, lb_ranges, lb_order, lb_runs, bytes;
+    constexpr explicit ScanCtlLayout(int nblk)
+        : ticket(sizeof(ScanCtl)), alloc(ticket + (size_t)TICKET_Q * TICKET_STRIDE * 4), lb_ranges(alloc + (size_t)ALLOC_SHARDS * ALLOC_STRIDE * 8),   // k_tile_ranges_fused' sums
+          lb_order(lb_ranges + (size_t)nblk * 8),      // k_order_spans'
+          lb_runs(lb_order + (size_t)nblk * 8),        // k_tile_ranges_fused' run starts
+          bytes(lb_runs + (size_t)nblk * 8) {}
+};
+// The column store's control block (c3r_ctx::d_small, 64 bytes); a scan clears it up to `unused`.  The two words behind are targets of
+// device_excl_scan for callers outside the scan.
+struct ColCtl {
+    unsigned long long ev_cursor; // event-scratch cursor (ScanArgs::ev_cursor)
+    int32_t ev_overflow;          // EvOverflow bits
+    int32_t n_cand, n_tok;        // candidates; token slots of all candidates
+    int32_t n_tile_list;          // tiles that hold aligned bases
+    int32_t n_tile_list2;         // pruned intron-only tiles
+    int32_t tok_written, tok_lost;   // k_tile_tokens' totals[0], [1]: tokens written, tokens that found no slot
+    int32_t unused[3];
+    int32_t export_toks;          // c3r_get_tokens: the tokens of all sites
+    int32_t n_keep;               // c3r_rows_begin_ex(drop_ref_calls): the rows kept
+    int32_t unused2[2];
+};
+static_assert(sizeof(ColCtl) == 64 && offsetof(ColCtl, ev_cursor) == 0 && offsetof(ColCtl, ev_overflow) == 8 && offsetof(ColCtl, n_cand) == 12 && offsetof(ColCtl, n_tok) == 16 &&
+              offsetof(ColCtl, n_tile_list) == 20 && offsetof(ColCtl, n_tile_list2) == 24 && offsetof(ColCtl, tok_written) == 28 && offsetof(ColCtl, tok_lost) == 32 &&
+              offsetof(ColCtl, unused) == 36 && offsetof(ColCtl, export_toks) == 48 && offsetof(ColCtl, n_keep) == 52, "ColCtl layout");
 struct FusedArgs {
     ScanArgs a;                   // tile_list: spans with aligned bases, ascending; tile_rng: reads / segments of the span + flanks
     int32_t *ticket;              // [TICKET_Q * TICKET_STRIDE] tickets handed out per queue
@@ -2157,7 +2218,7 @@ struct FusedArgs {
     unsigned long long *alloc;    // [n_shards * ALLOC_STRIDE] per shard: tokens << 32 | rows handed out so far
     int32_t n_shards;             // 1 for small scans (dense output), ALLOC_SHARDS for large ones
     int32_t shard_rows, shard_toks;   // rows / token slots a shard owns: shard s hands out rows [s * shard_rows, (s + 1) * shard_rows)
-    int32_t *overflow;            // bit 0: a span's candidates or tokens did not fit into its shard (nothing was written past it)
+    int32_t *overflow;            // FusedOverflow bits
     int32_t cand_cap;             // = n_shards * shard_rows
     int32_t rescale, max_depth;   // A5: windows with depth > 1.5 x max_depth are rescaled
     void *tensors;                // [cand_cap][33][C], rows in arrival order: int16 (x16: the resident, rescaled windows — a count never exceeds the reads that
@@ -2192,7 +2253,7 @@ __device__ __forceinline__ void fused_span(const FusedArgs &f, TileMem<C, EVL> &
             // a column whose haplotype channels depend on the ORDER of the reads (see k_phase_recompute): redone in place, one thread
             // per flagged column
             if (o.is_row && M.odd[tid]) {
-                if (!f.ph.rsegs) atomicOr(f.overflow, 4);         // no op / segment tables yet: the host builds them and repeats the scan
+                if (!f.ph.rsegs) atomicOr(f.overflow, FUSED_OVF_ORDER_TABLES);        // no op / segment tables yet: the host builds them and repeats the scan
                 else {
                     int cnt[12];
                     phase_column(f.ph, x0 + tid, rng.x, rng.y, tg.region, cnt);
@@ -2235,7 +2296,7 @@ __device__ __forceinline__ void fused_span(const FusedArgs &f, TileMem<C, EVL> &
         __syncthreads();
         const int row0 = S.row0, tok0 = S.tok0;
         const bool fits = S.fits != 0;
-        if (nc > 0 && !fits && tid == 0) atomicOr(f.overflow, 1);
+        if (nc > 0 && !fits && tid == 0) atomicOr(f.overflow, FUSED_OVF_SHARD);
         if (nc > 0 && fits) {
         if (emit) {
             CandMeta m;
@@ -2340,7 +2401,7 @@ __device__ __forceinline__ void fused_span(const FusedArgs &f, TileMem<C, EVL> &
                 f.meta[row0 + k].ncov = n;                                  // (the site's n_tok: what was written, not what was reserved)
                 if (n) atomicAdd(&f.span_info[b].z, n);                     // the span's tokens: k_order_spans sums them into the scan's total
             }, f.tok, (long long)f.tok_base + (long long)(shard + 1) * f.shard_toks, emit);
-            if (lost && tid == 0) atomicOr(f.overflow, 8);
+            if (lost && tid == 0) atomicOr(f.overflow, FUSED_OVF_TOKEN_LOST);
         }
         }
         if (C3R_DBG(a) && tid == 0) atomicAdd(&C3R_DBG(a)[dbg_slot], wall_clock64() - t_tail);

@@ -24,6 +24,30 @@ ROUTE_CONST(c3r::GIANT_SLOTS == 256, "GIANT_SLOTS, the giant spans of a scan tha
 ROUTE_CONST(c3r::FUSE_IN == 224 && c3r::TILE == 256 && C3R_FLANK == 16, "FUSE_IN / TILE / C3R_FLANK, the positions of a span,");
 ROUTE_CONST(c3r::OP_CHOP == 30, "OP_CHOP, the positions of one record,");
 
+// The scans' control blocks (pileup_kernels.hpp: ScanCtl + ScanCtlLayout for c3r_ctx::d_lb, ColCtl for ::d_small).  The kernels take pointers to single
+// words and the host reads the blocks back by field: every field stays on the byte it had when the host addressed it by number.
+#define CTL_AT(S, field, off) static_assert(offsetof(c3r::S, field) == off, #S "::" #field " has moved")
+static_assert(sizeof(c3r::ScanCtl) == 64 && sizeof(c3r::ColCtl) == 64, "the control blocks' heads are 64 bytes");
+CTL_AT(ScanCtl, ticket_ranges, 0);  CTL_AT(ScanCtl, ticket_alleles, 4); CTL_AT(ScanCtl, n_cand, 8);        CTL_AT(ScanCtl, n_tok, 12);
+CTL_AT(ScanCtl, overflow, 16);      CTL_AT(ScanCtl, n_listed, 20);      CTL_AT(ScanCtl, ev_cursor, 24);    CTL_AT(ScanCtl, ev_overflow, 32);
+CTL_AT(ScanCtl, rows_out, 36);      CTL_AT(ScanCtl, ticket_order, 40);  CTL_AT(ScanCtl, n_deep, 44);       CTL_AT(ScanCtl, ticket_deep, 48);
+CTL_AT(ScanCtl, n_giant, 52);       CTL_AT(ScanCtl, n_help, 56);        CTL_AT(ScanCtl, ticket_walk, 60);
+CTL_AT(ColCtl, ev_cursor, 0);       CTL_AT(ColCtl, ev_overflow, 8);     CTL_AT(ColCtl, n_cand, 12);        CTL_AT(ColCtl, n_tok, 16);
+CTL_AT(ColCtl, n_tile_list, 20);    CTL_AT(ColCtl, n_tile_list2, 24);   CTL_AT(ColCtl, tok_written, 28);   CTL_AT(ColCtl, tok_lost, 32);
+CTL_AT(ColCtl, unused, 36);         CTL_AT(ColCtl, export_toks, 48);    CTL_AT(ColCtl, n_keep, 52);
+// (k_order_spans and k_tile_tokens write totals[0] and totals[1] through one pointer)
+static_assert(offsetof(c3r::ScanCtl, n_tok) == offsetof(c3r::ScanCtl, n_cand) + 4 && offsetof(c3r::ColCtl, tok_lost) == offsetof(c3r::ColCtl, tok_written) + 4, "totals[0], [1]");
+static_assert(c3r::EV_OVF_SCRATCH == 1 && c3r::EV_OVF_DEPTH16 == 2, "EvOverflow bits");
+static_assert(c3r::FUSED_OVF_SHARD == 1 && c3r::FUSED_OVF_ORDER_TABLES == 4 && c3r::FUSED_OVF_TOKEN_LOST == 8, "FusedOverflow bits");
+static_assert(c3r::TICKET_Q == 16 && c3r::TICKET_STRIDE == 64 && c3r::ALLOC_SHARDS == 16 && c3r::ALLOC_STRIDE == 32, "ticket / allocator words, 256 bytes apart");
+constexpr bool scan_ctl_layout_ok(int nblk) {
+    const c3r::ScanCtlLayout L(nblk);
+    const size_t alloc = 64 + (size_t)c3r::TICKET_Q * c3r::TICKET_STRIDE * 4, head = alloc + (size_t)c3r::ALLOC_SHARDS * c3r::ALLOC_STRIDE * 8;
+    return L.ticket == 64 && L.alloc == alloc && L.lb_ranges == head && L.lb_order == head + (size_t)nblk * 8 && L.lb_runs == head + (size_t)nblk * 16 &&
+           L.bytes == 64 + (size_t)c3r::TICKET_Q * c3r::TICKET_STRIDE * 4 + (size_t)c3r::ALLOC_SHARDS * c3r::ALLOC_STRIDE * 8 + (size_t)nblk * 24;
+}
+static_assert(scan_ctl_layout_ok(1) && scan_ctl_layout_ok(2) && scan_ctl_layout_ok(257) && scan_ctl_layout_ok(8191), "ScanCtlLayout");
+
 int main() {
     const uint32_t N = 8 * 1024;
     std::vector<int> seen(N, 0);
@@ -55,6 +79,6 @@ int main() {
             }
             if (at != n) { printf("n %d G %d: the slices end at %d\n", n, G, at); return 1; }
         }
-    printf("cnt_at ok (swizzle %d), giant slices ok\n", (int)C3R_CNT_SWZ);
+    printf("cnt_at ok (swizzle %d), giant slices ok, scan control blocks ok\n", (int)C3R_CNT_SWZ);
     return 0;
 }

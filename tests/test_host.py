@@ -178,7 +178,7 @@ def test_bin_counter_layout_is_a_permutation_that_keeps_groups_and_separates_nei
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-function",
                            os.path.join(ROOT, "tests", "c", "layout_check.hip"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and out.stdout.startswith("cnt_at ok") and "giant slices ok" in out.stdout, out.stdout + out.stderr
+    assert out.returncode == 0 and out.stdout.startswith("cnt_at ok") and "giant slices ok" in out.stdout and "scan control blocks ok" in out.stdout, out.stdout + out.stderr
 
 
 def test_bench_dump_outputs_samples_within_its_budget(tmp_path):
