@@ -30,6 +30,9 @@ linkage on the GPU, a greedy linkage chain, not whatshap's wMEC (include/c3r.h: 
 <output_dir>/tmp/phased_output/phased_vcf, then the run with --phased_vcf_fn on that directory (<prefix>_enable_phasing.vcf.gz).
 `--phase_merge_levels N` (default 0: off) is handed to phase_vcf as --merge_levels: up to N levels of the block-merge stage after the chain.  One process
 only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line — run the three steps as three commands there.
+`--phasing_indels` (with --phasing builtin; default off, as `whatshap phase --indels` is) hands phase_vcf --indels: heterozygous insertions, deletions and
+1/2 rows are phased between the passes too (include/c3r.h: c3r_phase_allele_links; CIGAR-position alleles, no realignment), and the second pass — and
+--phase_output / --haplotagged_bam behind it — reads the directory with the allele table, as `--phased_vcf_fn DIR --haplotag_indels` does.
 `--phase_output` (with --enable_phasing_model and --phased_vcf_fn or --phasing builtin; one process only) adds a step behind the phased pass:
 hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU into
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
@@ -168,6 +171,10 @@ def build_parser():
            "<prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU (hap_vcf: SNVs only, a majority rule over CIGAR-position "
            "alleles) into <prefix>_enable_phasing_phased.vcf.gz and write the counts to <prefix>_enable_phasing_hap_counts.tsv.  One process only "
            "(not under torch.distributed.run)")
+    a("--phasing_indels", action="store_true",
+      help="with --phasing builtin: the phasing between the passes links heterozygous insertions, deletions and 1/2 rows too (phase_vcf "
+           "--indels: alleles read off the CIGAR position, no realignment, a greedy chain), and the second pass — and --phase_output / "
+           "--haplotagged_bam behind it — haplotags the reads from all of them.  Off by default, as `whatshap phase --indels` is")
     a("--haplotag_indels", action="store_true",
       help="with --phased_vcf_fn: haplotag the reads from the phased insertions, deletions and two-ALT rows (`1|2`) of the phased VCF too, not "
            "from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows that --phase_output --phase_indels and `whatshap "
@@ -352,9 +359,14 @@ def Run(args, log=None):
     if tag_indels and getattr(args, "phasing", None) is not None:
         sys.exit("[ERROR] --haplotag_indels changes nothing under --phasing builtin: the phasing between the passes is SNV-only, so the table the "
                  "reads are haplotagged from holds no indel.  The two-step way: 1. run with --phase_output --phase_indels; 2. rerun with "
-                 "--phased_vcf_fn <prefix>_enable_phasing_phased.vcf.gz --haplotag_indels")
+                 "--phased_vcf_fn <prefix>_enable_phasing_phased.vcf.gz --haplotag_indels.  In one command, without --haplotag_indels: "
+                 "--phasing builtin --phasing_indels phases the indels between the passes and tags the reads from them")
     if tag_indels and not getattr(args, "phased_vcf_fn", None):
         sys.exit("[ERROR] --haplotag_indels needs --phased_vcf_fn (it widens the table the reads are haplotagged from)")
+    if getattr(args, "phasing_indels", False):
+        if getattr(args, "phasing", None) is None:
+            sys.exit("[ERROR] --phasing_indels belongs to the built-in phasing (it phases indels and 1/2 rows between the passes): it needs --phasing builtin")
+        tag_indels = True                                     # (the steps behind the passes read phase_vcf --indels' directory with the allele table)
     if not phase_output and not tagged_bam:
         return _run_flow(args, log)
     builtin = getattr(args, "phasing", None) is not None
@@ -407,7 +419,8 @@ def Run(args, log=None):
 
 def _run_flow(args, log=None):
     """One pass (_run_pass), or with `--phasing builtin` the three steps of the phased flow one after the other: the unphased pass, phase_vcf
-    on the file it wrote, the 30-channel pass with --phased_vcf_fn on phase_vcf's directory — nothing inside a pass changes."""
+    on the file it wrote, the 30-channel pass with --phased_vcf_fn on phase_vcf's directory — nothing inside a pass changes.
+    --phasing_indels: phase_vcf --indels, and the second pass reads its directory as under --haplotag_indels."""
     if getattr(args, "phasing", None) is None:
         if getattr(args, "phase_merge_levels", 0):
             sys.exit("[ERROR] --phase_merge_levels belongs to the built-in phasing: it needs --phasing builtin")
@@ -444,11 +457,14 @@ def _run_flow(args, log=None):
     if os.path.isfile(vcf_fn):                                # (no contig found: the first pass wrote nothing, and neither will the second)
         phase_vcf.Run(phase_vcf.build_parser().parse_args(
             ["--bam_fn", bam_fn, "--vcf_fn", vcf_fn, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(merge_levels)]
+            + (["--indels"] if getattr(args, "phasing_indels", False) else [])
             + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
     else:
         os.makedirs(phased_dir, exist_ok=True)
     second = copy.copy(args)
     second.phasing, second.phased_vcf_fn = None, phased_dir
+    if getattr(args, "phasing_indels", False):
+        second.haplotag_indels = True                         # (the table of c3r_set_phase_alleles, as --phased_vcf_fn DIR --haplotag_indels)
     return _run_pass(second, log)
 
 

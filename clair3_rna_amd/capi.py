@@ -67,7 +67,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
            "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
-           "c3r_hap_allele_counts", "c3r_set_phase_alleles"]
+           "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links"]
 
 _lib = None
 
@@ -114,6 +114,8 @@ def load_library():
     L.c3r_get_read_phase_sets.argtypes = [vp, vp, i64]
     L.c3r_hap_counts.argtypes = [vp, vp, i64, vp]
     L.c3r_hap_allele_counts.argtypes = [vp, vp, i64, vp, i64, vp]
+    L.c3r_phase_allele_links.argtypes = [vp, vp, i64, vp, i64, vp]
+    L.c3r_phase_allele_unit_links.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
     L.c3r_hap_assign.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(HapAssignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
@@ -398,6 +400,50 @@ class Engine(object):
         st["merge_levels_run"], st["merge_units_joined"] = levels, joined
         return out, st
 
+    def phase_allele_links(self, sites, pool=None, pool_bases=None):
+        """phase_links over a table that may hold insertions, deletions and two-ALT sites beside the SNVs (c3r_phase_allele_links): `sites` a
+        HAP_SITE_DTYPE array sorted by pos (ps is ignored), `pool` the packed pool of the insertions' bases (pack_nibbles; None when no allele
+        is an insertion), `pool_bases` the number of bases in it (None: two per byte).  uint32 (n, PHASE_LINKS, 2) cis / trans by allele
+        index (A 0, B 1).  Needs no table; leaves tags, a table that is set and every scan as they are."""
+        a, pl, nb = _hap_site_array(sites), *_pool_args(pool, pool_bases)
+        links = np.zeros((len(a), PHASE_LINKS, 2), dtype=np.uint32)
+        self._chk(self.L.c3r_phase_allele_links(self.h, _ptr(a), len(a), _ptr(pl) if nb else None, nb, _ptr(links)))
+        return links
+
+    def phase_allele_unit_links(self, sites, h1, pool=None, pool_bases=None):
+        """phase_unit_links over the allele table (c3r_phase_allele_unit_links): `sites` with ps = -1 or >= 1 as the chain leaves it, `h1` a
+        uint8 array of the same length (0: allele A lies on haplotype 1).  uint32 (U, PHASE_LINKS, 2)."""
+        a, pl, nb = _hap_site_array(sites), *_pool_args(pool, pool_bases)
+        h = np.zeros(0, np.uint8) if h1 is None else np.ascontiguousarray(h1)
+        if h.dtype != np.uint8 or h.shape != (len(a),):
+            raise TypeError("h1 must be a uint8 array with one entry per site")
+        ulinks = np.zeros((len(a), PHASE_LINKS, 2), dtype=np.uint32)          # (U <= n)
+        u = C.c_int64(0)
+        self._chk(self.L.c3r_phase_allele_unit_links(self.h, _ptr(a), _ptr(h) if len(h) else None, len(a), _ptr(pl) if nb else None, nb,
+                                                     _ptr(ulinks), len(a), C.byref(u)))
+        return np.ascontiguousarray(ulinks[:u.value])
+
+    def phase_allele_sites(self, sites, pool=None, min_reads=2, min_agree_pct=75, merge_levels=0, pool_bases=None):
+        """phase_sites over the allele table: phase_allele_links, the greedy chain of phase_resolve on the pseudo-table of the sites (pos, ps,
+        h1: all the rule reads), then up to merge_levels levels of phase_allele_unit_links + phase_merge.  -> (int32 ps per site, -1: the
+        site stays unphased; uint8 h1 per site, 0: allele A lies on haplotype 1; the statistics dict of phase_sites)."""
+        if int(merge_levels) < 0:
+            raise ValueError("merge_levels must be >= 0, got %r" % (merge_levels,))
+        a = _hap_site_array(sites)
+        out, st = phase_resolve(hap_site_keys(a), self.phase_allele_links(a, pool, pool_bases), min_reads, min_agree_pct)
+        if int(merge_levels) > 0:
+            levels = joined = 0
+            while levels < int(merge_levels):
+                t = a.copy()
+                t["ps"] = out["ps"]
+                out, st, n = phase_merge(out, self.phase_allele_unit_links(t, np.ascontiguousarray(out["h1"]), pool, pool_bases), min_reads, min_agree_pct)
+                levels += 1
+                joined += n
+                if n == 0:
+                    break
+            st["merge_levels_run"], st["merge_units_joined"] = levels, joined
+        return np.ascontiguousarray(out["ps"]), np.ascontiguousarray(out["h1"]), st
+
     # ---- tensor build
     def scan(self, ctg_start, ctg_end):
         n = C.c_int64(0)
@@ -604,6 +650,24 @@ def hap_site_keys(sites):
     out = np.zeros(len(sites), dtype=PHASE_SITE_DTYPE)
     out["pos"], out["ps"], out["ref"], out["alt"] = sites["pos"], sites["ps"], 1, 2
     return out
+
+
+def _hap_site_array(sites):
+    a = np.zeros(0, HAP_SITE_DTYPE) if sites is None else np.asarray(sites)
+    if a.dtype != HAP_SITE_DTYPE:
+        raise TypeError("sites must be a capi.HAP_SITE_DTYPE array, got %r" % (a.dtype,))
+    return np.ascontiguousarray(a)
+
+
+def _pool_args(pool, pool_bases):
+    """(the packed pool as a contiguous uint8 array, the number of bases in it): pool_bases None means two per byte."""
+    pl = np.zeros(0, np.uint8) if pool is None else np.ascontiguousarray(pool)
+    if pl.dtype != np.uint8 or pl.ndim != 1:
+        raise TypeError("pool must be a one-dimensional uint8 array of packed bases (capi.pack_nibbles)")
+    nb = 2 * len(pl) if pool_bases is None else int(pool_bases)
+    if nb < 0 or (nb + 1) // 2 > len(pl):
+        raise ValueError("pool_bases = %d does not fit a pool of %d bytes" % (nb, len(pl)))
+    return pl, nb
 
 
 def _phase_site_array(sites):

@@ -170,6 +170,7 @@ struct c3r_ctx {
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
     DevBuf d_hcsites, d_hcounts;
     DevBuf d_hasites, d_hapool;               // c3r_hap_allele_counts: its query sites and the pool of inserted bases (the counts share d_hcounts)
+    DevBuf d_pasites, d_papool;               // c3r_phase_allele_links / c3r_phase_allele_unit_links: their candidate sites and pool (the links share d_links, the units d_unitof)
 
     // ---- scan state
     int32_t reg_beg0 = 0, reg_end0 = 0;   // first region of the most recent scan (c3r_get_columns)
@@ -826,7 +827,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1262,8 +1263,9 @@ int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint3
     });
 }
 
-// The checks of a table of c3r_hap_site_t: c3r_hap_allele_counts' (h1 = NULL) and c3r_set_phase_alleles' (the same and h1 <= 1).
-static int check_hap_sites(c3r_ctx *ctx, const char *what, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, const uint8_t *h1) {
+// The checks of a table of c3r_hap_site_t: c3r_hap_allele_counts' (h1 = NULL) and c3r_set_phase_alleles' (the same and h1 <= 1).  any_ps:
+// ps is not looked at (c3r_phase_allele_links, which ignores it, and c3r_phase_allele_unit_links, which has a rule of its own for it).
+static int check_hap_sites(c3r_ctx *ctx, const char *what, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, const uint8_t *h1, bool any_ps = false) {
     if (n >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many %ss", what);
     auto base = [](uint8_t c) { return c == 1 || c == 2 || c == 4 || c == 8; };
     auto pool_at = [&](uint64_t q) { const uint8_t byte = ins_pool[q >> 1]; return (uint8_t)((q & 1) ? (byte & 15) : (byte >> 4)); };
@@ -1271,7 +1273,7 @@ static int check_hap_sites(c3r_ctx *ctx, const char *what, const c3r_hap_site_t 
         const c3r_hap_site_t &e = sites[i];
         if (e.pos < 1) return fail(ctx, C3R_EINVAL, "%s %lld: pos %d is not a 1-based position", what, (long long)i, e.pos);
         if (i > 0 && e.pos <= sites[i - 1].pos) return fail(ctx, C3R_EINVAL, "%s %lld: positions must be strictly increasing (%d after %d)", what, (long long)i, e.pos, sites[i - 1].pos);
-        if (e.ps < 0) return fail(ctx, C3R_EINVAL, "%s %lld: phase set %d is negative", what, (long long)i, e.ps);
+        if (!any_ps && e.ps < 0) return fail(ctx, C3R_EINVAL, "%s %lld: phase set %d is negative", what, (long long)i, e.ps);
         if (e.base_matters > 1 || e.event_matters > 1) return fail(ctx, C3R_EINVAL, "%s %lld: base_matters / event_matters must be 0 or 1", what, (long long)i);
         for (const c3r_hap_allele_t *al : {&e.a, &e.b}) {
             const char which = al == &e.a ? 'A' : 'B';
@@ -1323,6 +1325,52 @@ int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, 
         a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.pool = (const uint8_t *)ctx->d_hapool.p;
         return (int)C3R_OK;
     });
+}
+
+int c3r_phase_allele_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *links) {
+    if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !links)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
+    if (int rc = check_hap_sites(ctx, "candidate site", sites, n, ins_pool, pool_bases, nullptr, true)) return rc;
+    if (n == 0) return C3R_OK;
+    const size_t words = (size_t)n * C3R_PHASE_LINKS * 2;
+    if (ctx->n_reads == 0) { memset(links, 0, words * 4); return C3R_OK; }               // (no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->d_pasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_papool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
+    AlleleLinkArgs a = read_args<AlleleLinkArgs>(ctx, ctx->n_reads);
+    a.sites = (const c3r_hap_site_t *)ctx->d_pasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_papool.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    return counter_table(ctx, ctx->d_links, words, links, [&](uint32_t *t) { a.links = t; launch_per_read(ctx, "k_phase_allele_links", k_phase_allele_links, a); });
+}
+
+int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *ulinks,
+                                int64_t cap_units, int64_t *n_units) {
+    if (!ctx || n < 0 || pool_bases < 0 || cap_units < 0 || (n && (!sites || !h1)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
+    if (int rc = check_hap_sites(ctx, "unit site", sites, n, ins_pool, pool_bases, h1, true)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (sites[i].ps != -1 && sites[i].ps < 1) return fail(ctx, C3R_EINVAL, "unit site %lld: ps %d is neither -1 (no block) nor a 1-based position", (long long)i, sites[i].ps);
+    std::vector<int32_t> unit_ps, unit_of;
+    {
+        std::vector<c3r_phase_site_t> pseudo((size_t)n);            // phase_units reads ps only
+        for (int64_t i = 0; i < n; ++i) { memset(&pseudo[(size_t)i], 0, sizeof pseudo[0]); pseudo[(size_t)i].pos = sites[i].pos; pseudo[(size_t)i].ps = sites[i].ps; }
+        phase_units(pseudo.data(), n, unit_ps, unit_of);
+    }
+    const int64_t U = (int64_t)unit_ps.size();
+    if (n_units) *n_units = U;
+    if (!ulinks) return C3R_OK;                                     // (the caller asks for the count)
+    if (cap_units < U) return fail(ctx, C3R_EOVERFLOW, "the links of %lld units do not fit %lld slots", (long long)U, (long long)cap_units);
+    const size_t words = (size_t)U * C3R_PHASE_LINKS * 2;
+    if (U < 2 || ctx->n_reads == 0) { if (words) memset(ulinks, 0, words * 4); return C3R_OK; }      // (nothing to link, or no voters: nothing to launch)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<c3r_hap_site_t> t(sites, sites + n);                // the device's table: h1 rides in reserved[0], as in c3r_set_phase_alleles
+    for (int64_t i = 0; i < n; ++i) { memset(t[(size_t)i].reserved, 0, sizeof t[(size_t)i].reserved); t[(size_t)i].reserved[0] = h1[i]; }
+    int rc;
+    if ((rc = upload(ctx, ctx->d_pasites, t.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_papool, ins_pool, (size_t)((pool_bases + 1) / 2))) ||
+        (rc = upload(ctx, ctx->d_unitof, unit_of.data(), (size_t)n))) return rc;
+    AlleleUnitLinkArgs a = read_args<AlleleUnitLinkArgs>(ctx, ctx->n_reads);
+    a.sites = (const c3r_hap_site_t *)ctx->d_pasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_papool.p;
+    a.unit_of = (const int32_t *)ctx->d_unitof.p; a.n_units = (int32_t)U;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    return counter_table(ctx, ctx->d_links, words, ulinks, [&](uint32_t *t2) { a.ulinks = t2; launch_per_read(ctx, "k_phase_allele_unit_links", k_phase_allele_unit_links, a); });   // (t and unit_of live until it returns)
 }
 
 int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts, const c3r_phase_params_t *p, c3r_phase_site_t *out,

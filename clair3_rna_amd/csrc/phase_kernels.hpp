@@ -1,6 +1,7 @@
 // phase_kernels.hpp — k_phase_links: pairwise linkage counts between the contig's heterozygous SNVs from the loaded reads (c3r_phase_links),
 // the device half of the project's own phasing; and k_phase_unit_links, the same between the blocks the chain left (c3r_phase_unit_links,
-// the block-merge stage; at the end of the file).  Included by c3r_lib.hip only.
+// the block-merge stage; at the end of the file); k_phase_allele_links and k_phase_allele_unit_links: the two over a table that also holds
+// insertions, deletions and two-ALT sites (c3r_phase_allele_links, c3r_phase_allele_unit_links).  Included by c3r_lib.hip only.
 //
 // What it replaces: the read pass of `whatshap phase` / `longphase phase` between the two passes of the reference flow
 // (run_clair3_rna:729-767).  The rule — a greedy linkage chain, not wMEC — is stated in include/c3r.h and restated, independently of this
@@ -35,7 +36,11 @@ struct LinkArgs : ReadArgs {
     uint32_t *links;                          // [n_sites][PHASE_K][2] cis / trans, zero on entry
 };
 
-__global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) {
+// The body of k_phase_links and k_phase_allele_links: the window loop above with column(site, R, the read's bases, walk_sites' arguments)
+// -> the allele index the read shows, 0 or 1, or 2 for nothing (the slab byte is the index + 1).  compat_plain: ReadInfo::compat of a read of the plain walk.  Every thread of the
+// workgroup comes here and reaches every barrier.
+template <class Args, class Column>
+__device__ __forceinline__ void phase_links_read(const Args &a, bool compat_plain, Column &&column) {
     __shared__ uint4 s_obs4[PREP_READS][PHASE_WIN / 16];
     __shared__ int s_nwin;
     const GroupAt g;
@@ -55,6 +60,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) 
             nwin = m < 2 ? 0 : m <= PHASE_WIN ? 1 : 1 + (m - PHASE_WIN + PHASE_STEP - 1) / PHASE_STEP;
             R = ReadInfo(d, i, a.cigars, 0);
             serial = a.serial[i] != 0;
+            if (compat_plain && !serial) R.compat = 1;
         }
     }
     const int lo = r.lo, hi = r.hi;
@@ -68,8 +74,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) 
         if (mine) s_obs4[slot][gl] = make_uint4(0, 0, 0, 0);
         __syncthreads();
         if (mine) {
-            walk_sites(R, gl, serial, a.sites, ws, we, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
-                const uint32_t al = snv_column(e, hap_nibble(rseq, q));
+            walk_sites(R, gl, serial, a.sites, ws, we, [&](int s, const auto &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+                const uint32_t al = column(e, R, rseq, q, last, iq, cx);
                 if (al != 2u) obs[s - ws] = (uint8_t)(al + 1u);
             });
         }
@@ -89,6 +95,30 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) 
         }
         __syncthreads();                                                       // (the next window clears the slab)
     }
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) {
+    phase_links_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+        return snv_column(e, hap_nibble(rseq, q));
+    });
+}
+
+// ---- k_phase_allele_links: the same link table over a table whose sites may be SNVs, insertions, deletions and two-ALT sites
+// (c3r_phase_allele_links; the rule is in include/c3r.h, restated by tests/phaseindelref.py).  k_phase_links' body with hap_observe
+// (haplotag_kernels.hpp) in the place of the nibble compare: columns 0 / 1 are the slab bytes 1 / 2, column 2 and no observation are 0.
+// As in k_haplotag_alleles the reads of the plain walk get ReadInfo::compat = 1 so that OpCtx::n2op is filled (an I with a D behind it).
+struct AlleleLinkArgs : ReadArgs {
+    const c3r_hap_site_t *sites; int32_t n_sites;         // candidate sites (ps and reserved are not read)
+    const uint8_t *pool;                      // the alleles' inserted bases, 4-bit packed like seq (never read when no allele is an insertion)
+    int32_t min_mq, excl_flags;               // the voters: read_kept
+    uint32_t *links;                          // [n_sites][PHASE_K][2] cis / trans, zero on entry
+};
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_links(const AlleleLinkArgs a) {
+    phase_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+        return al < 2u ? al : 2u;                                       // (another allele and no observation are both nothing here)
+    });
 }
 
 // ---- k_phase_unit_links: the link table of the block-merge stage (c3r_phase_unit_links; the rule is in include/c3r.h, restated by
@@ -127,25 +157,30 @@ struct UnitTally {
     }
 };
 
-// One walk over the sites [lo, hi) that the read's M ops cover; singleton sites are skipped before anything else.  All lanes of the group
-// come here together.
-__device__ __forceinline__ UnitTally unit_walk(const ReadInfo &R, int gl, bool serial, const UnitLinkArgs &a, int lo, int hi, int32_t cur) {
+// One walk over the sites [lo, hi) that the read's M ops cover; singleton sites are skipped before anything else.  column(site, R, the
+// read's bases, walk_sites' arguments) -> the allele index the read shows, 0 or 1, or 2 for nothing; h1_of(site) -> the index that lies on
+// haplotype 1.  All lanes of the group come here together.
+template <class Args, class Column, class H1Of>
+__device__ __forceinline__ UnitTally unit_walk(const ReadInfo &R, int gl, bool serial, const Args &a, int lo, int hi, int32_t cur, Column &&column, H1Of &&h1_of) {
     UnitTally t;
     t.c1 = 0; t.c2 = 0; t.u_min = UNIT_NONE; t.u_max = -1;
     const uint8_t *rseq = a.seq + R.seq_off;
-    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const auto &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         const int32_t u = a.unit_of[s];
         if (u < 0 || u < cur) return;
-        const uint32_t al = snv_column(e, hap_nibble(rseq, q));
+        const uint32_t al = column(e, R, rseq, q, last, iq, cx);
         if (al == 2u) return;
         if (u > cur) { t.u_min = min(t.u_min, u); t.u_max = max(t.u_max, u); return; }
-        if (al == e.h1) t.c1 += 1; else t.c2 += 1;                     // (u == cur)
+        if (al == h1_of(e)) t.c1 += 1; else t.c2 += 1;                 // (u == cur)
     });
     t.reduce();
     return t;
 }
 
-__global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLinkArgs a) {
+// The body of k_phase_unit_links and k_phase_allele_unit_links.  compat_plain: ReadInfo::compat of a read of the plain walk.  All lanes of
+// a group take the same way through it (whole groups leave: the shuffles stay inside a group).
+template <class Args, class Column, class H1Of>
+__device__ __forceinline__ void phase_unit_links_read(const Args &a, bool compat_plain, Column &&column, H1Of &&h1_of) {
     const GroupAt g;
     const int gl = g.gl, i = g.i;
     if (i >= a.n_reads) return;                                        // (whole groups leave: the shuffles below stay inside a group)
@@ -154,14 +189,15 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLin
     const SiteRange r = read_sites(a.sites, a.n_sites, d, gl);
     const int lo = r.lo, hi = r.hi;
     if (hi - lo < 2) return;                                           // (two units take two sites)
-    const ReadInfo R(d, i, a.cigars, 0);
+    ReadInfo R(d, i, a.cigars, 0);
     const bool serial = a.serial[i] != 0;
-    const UnitTally all = unit_walk(R, gl, serial, a, lo, hi, -1);
+    if (compat_plain && !serial) R.compat = 1;
+    const UnitTally all = unit_walk(R, gl, serial, a, lo, hi, -1, column, h1_of);
     if (all.u_min >= all.u_max) return;                                // no unit observed (UNIT_NONE, -1) or one
     uint32_t seen = 0, hap2 = 0;                                       // bit k: unit `last` - k was observed / with haplotype 2
     int32_t last = all.u_min;
     for (int32_t u = all.u_min; u != UNIT_NONE;) {
-        const UnitTally t = unit_walk(R, gl, serial, a, lo, hi, u);
+        const UnitTally t = unit_walk(R, gl, serial, a, lo, hi, u, column, h1_of);
         const int32_t dist = u - last;
         seen = dist < 32 ? seen << dist : 0u;                          // now bit k: unit u - k
         hap2 = dist < 32 ? hap2 << dist : 0u;
@@ -176,6 +212,31 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLin
         }
         u = t.u_min;
     }
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLinkArgs a) {
+    phase_unit_links_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+        return snv_column(e, hap_nibble(rseq, q));
+    }, [](const c3r_phase_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.h1; });
+}
+
+// ---- k_phase_allele_unit_links: the unit link table over the allele table (c3r_phase_allele_unit_links) -- k_phase_unit_links' body with
+// hap_observe in the place of the nibble compare.  The device's copy of the table holds h1 in reserved[0] of every site, as the copy of
+// c3r_set_phase_alleles does, so that a site is one 32-byte load.
+struct AlleleUnitLinkArgs : ReadArgs {
+    const c3r_hap_site_t *sites; int32_t n_sites;         // the chain's table: reserved[0] holds h1; ps is not read
+    const uint8_t *pool;                      // the alleles' inserted bases, 4-bit packed like seq
+    const int32_t *unit_of;                   // [n_sites] unit of every site, -1: singleton
+    int32_t n_units;
+    int32_t min_mq, excl_flags;               // the voters: read_kept
+    uint32_t *ulinks;                         // [n_units][PHASE_K][2] same / different haplotype, zero on entry
+};
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_unit_links(const AlleleUnitLinkArgs a) {
+    phase_unit_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+        return al < 2u ? al : 2u;
+    }, [](const c3r_hap_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.reserved[0]; });
 }
 
 }  // namespace c3r

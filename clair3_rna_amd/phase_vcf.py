@@ -9,6 +9,12 @@ consume (phasedvcf.contig_file).  A contig without candidates writes no file.  O
 c3r_phase_merge): blocks that reads bridge across a run of unlinked sites — RNA-editing sites called 0/1 — become one.  The [INFO] line
 then also says how many units joined in how many levels.
 
+--indels (default off, as `whatshap phase --indels` is): the candidates are every heterozygous row whose alleles are SNVs, insertions or
+deletions — `0/1` with one ALT, `1/2` with two (phasing.allele_candidates_from_vcf) —, phased by Engine.phase_allele_sites (include/c3r.h:
+c3r_phase_allele_links) and written as `0|1` / `1|0` / `1|2` / `2|1` + PS.  The alleles are read off the CIGAR position: no realignment,
+no left-alignment of the reads' indels, no base qualities; homozygous rows and rows with three or more ALTs are not candidates.  The
+second pass reads such a directory with `--haplotag_indels`.
+
 The rule (include/c3r.h: c3r_phase_links / c3r_phase_resolve) is a greedy linkage chain, not whatshap's wMEC: agreement with whatshap has
 not been measured.
 
@@ -33,6 +39,8 @@ def build_parser():
     a("--min_agree_pct", type=int, default=75, help="fewest per cent of them that agree on the orientation")
     a("--merge_levels", type=int, default=0,
       help="levels of the block-merge stage after the chain: joins the blocks that reads bridge across a run of unlinked sites (0: off)")
+    a("--indels", action="store_true",
+      help="also phase heterozygous insertions, deletions and 1/2 rows (alleles read off the CIGAR position; default: SNVs only)")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 
@@ -48,7 +56,9 @@ def Run(args, log=None):
     merge_levels = getattr(args, "merge_levels", 0)
     if merge_levels < 0:
         sys.exit("[ERROR] --merge_levels must be >= 0")
-    per = phasing.candidates_from_vcf(args.vcf_fn, None)
+    indels = bool(getattr(args, "indels", False))
+    per = phasing.allele_candidates_from_vcf(args.vcf_fn, None) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
+    what = "heterozygous SNV / indel / two-ALT" if indels else "heterozygous SNV"
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
     os.makedirs(args.output_dir, exist_ok=True)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
@@ -56,25 +66,31 @@ def Run(args, log=None):
     written = []
     try:
         for ctg in contigs:
-            sites, skipped = per.get(ctg, (None, None))
+            sites, *rest = per.get(ctg, (None, None))
+            skipped = rest[-1]
             if sites is None or not len(sites):
                 stale = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
                 if os.path.isfile(stale):                    # (an earlier run's: the second pass would read it)
                     os.remove(stale)
-                log("[INFO] %s: no heterozygous SNV candidates, nothing written" % ctg)
+                log("[INFO] %s: no %s candidates, nothing written" % (ctg, what))
                 continue
             if eng is None:
                 eng = capi.Engine(gpu_id)
                 eng.set_params(min_mq=args.min_mq)
             rs = io.load_reads(args.bam_fn, ctg)
             eng.load_reads(rs)
-            out, st = eng.phase_sites(sites, args.min_reads, args.min_agree_pct, merge_levels)
             fn = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
-            phasing.write_phased_vcf(args.vcf_fn, ctg, out, fn)
+            if indels:
+                pool, strings = rest[0], rest[1]
+                ps, h1, st = eng.phase_allele_sites(sites, pool, args.min_reads, args.min_agree_pct, merge_levels)
+                phasing.write_allele_phased_vcf(args.vcf_fn, ctg, sites, strings, ps, h1, fn)
+            else:
+                out, st = eng.phase_sites(sites, args.min_reads, args.min_agree_pct, merge_levels)
+                phasing.write_phased_vcf(args.vcf_fn, ctg, out, fn)
             written.append(fn)
             merged = ", block merge: %d units joined in %d levels" % (st["merge_units_joined"], st["merge_levels_run"]) if merge_levels else ""
-            log("[INFO] %s: %d reads, %d candidate sites (%s), %d phased in %d blocks, largest block %d sites%s -> %s"
-                % (ctg, len(rs), st["n_sites"], ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
+            log("[INFO] %s: %d reads, %d candidate sites%s (%s), %d phased in %d blocks, largest block %d sites%s -> %s"
+                % (ctg, len(rs), st["n_sites"], " with indels and two-ALT rows" if indels else "", ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
                    st["n_phased"], st["n_blocks"], st["max_block"], merged, fn))
     finally:
         if eng is not None:

@@ -10,7 +10,8 @@ several rows on one position the first is kept; everything else is counted by re
 
 allele_candidates_from_vcf / allele_phased_row are the same two steps for the FINAL VCF of a phased run under `hap_vcf --indels`
 (include/c3r.h: c3r_hap_allele_counts states the rule): heterozygous rows whose alleles are SNVs, insertions or deletions, GT `0/1` / `1/0`
-with one ALT or `1/2` / `2/1` with two.  The phasing between the two passes (phase_vcf) stays SNV-only."""
+with one ALT or `1/2` / `2/1` with two.  The phasing between the two passes (phase_vcf) reads and writes them too under `phase_vcf
+--indels` (write_allele_phased_vcf; include/c3r.h: c3r_phase_allele_links); without that flag it stays SNV-only."""
 import gzip
 
 import numpy as np
@@ -286,6 +287,27 @@ def write_phased_vcf(in_vcf, contig, sites_out, out_fn):
             if f_[0] != contig:
                 continue
             text, done = phased_row(line, f_, phased)
+            out.write(text)
+            n += int(done)
+    return n
+
+
+def write_allele_phased_vcf(in_vcf, contig, sites, strings, ps, h1, out_fn):
+    """write_phased_vcf for `phase_vcf --indels`: `sites` and `strings` as allele_candidates_from_vcf gives them for `contig`, `ps` / `h1`
+    per site as Engine.phase_allele_sites leaves them (ps < 0: the site stays unphased).  The rows of the phased sites are rewritten by
+    allele_phased_row (`0|1` / `1|0` / `1|2` / `2|1` + PS), every other row is written byte for byte.  Returns the number of rows rewritten."""
+    phased = {int(sites["pos"][j]): (strings[j][0], strings[j][1], int(ps[j]), int(h1[j])) for j in range(len(sites)) if int(ps[j]) >= 0}
+    n, has_ps = 0, False
+    with _open_text(in_vcf) as f, gzip.open(out_fn, "wt") as out:
+        for line in f:
+            if line.startswith("#"):
+                text, has_ps = header_row(line, has_ps)
+                out.write(text)
+                continue
+            f_ = line.rstrip("\r\n").split("\t")
+            if f_[0] != contig:
+                continue
+            text, done = allele_phased_row(line, f_, phased)
             out.write(text)
             n += int(done)
     return n

@@ -79,7 +79,7 @@ int c3r_set_params(c3r_ctx *ctx, const c3r_params_t *p);
  *     ends beyond 2^31".
  *   BED intervals (c3r_set_bed): 0-based half-open int32 pairs, 0 <= start < end <= INT32_MAX; they are only compared with row positions.
  *   genotyping sites (c3r_set_sites): 1-based int32, 1 .. INT32_MAX; only compared.
- *   phase sites and query sites (c3r_set_phase_sites, c3r_set_phase_alleles, c3r_hap_counts, c3r_hap_allele_counts, c3r_phase_links, c3r_phase_unit_links): 1-based
+ *   phase sites and query sites (c3r_set_phase_sites, c3r_set_phase_alleles, c3r_hap_counts, c3r_hap_allele_counts, c3r_phase_links, c3r_phase_unit_links, c3r_phase_allele_links, c3r_phase_allele_unit_links): 1-based
  *     int32 pos, 1 .. INT32_MAX, compared with read positions in 64-bit arithmetic; ps is a name (a position by convention), -1 or 0 .. INT32_MAX.
  * GRCh38 chr1 is 248,956,422 bp; BAI indexing ends at 2^29.  tests/test_gpu_coords.py runs the kernels at chr1 scale, at 2^28 and on the last
  * accepted and first refused values above. */
@@ -295,6 +295,34 @@ int c3r_phase_resolve(const c3r_phase_site_t *in, int64_t n, const uint32_t *lin
 int c3r_phase_unit_links(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint32_t *ulinks, int64_t cap_units, int64_t *n_units);
 int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulinks, int64_t n_units, const c3r_phase_params_t *p,
                     c3r_phase_site_t *out, c3r_phase_stats_t *stats, int64_t *n_joined);
+/* The phasing above over a table that also holds heterozygous insertions, deletions and two-ALT sites (`0/1` rows with an indel ALT, `1/2`
+ * rows).  Opt-in (phase_vcf --indels), like `whatshap phase --indels`.  It is the join of two contracts that are already here, and nothing
+ * else:
+ *  Table: as c3r_hap_allele_counts — sites sorted by strictly increasing pos; alleles A and B, base_matters, event_matters and the pool
+ *   exactly as there.
+ *  Voters: c3r_phase_links' — the loaded reads that pass read_kept under the current c3r_params, without the depth cap.
+ *  Observation: the column of c3r_hap_allele_counts at the site (normalised CIGAR, the event behind the anchor as defined there): column 0
+ *   is allele index 0 (A), column 1 is allele index 1 (B); column 2 (another allele) and no observation are nothing.
+ *  Links and resolution: those of c3r_phase_links / c3r_phase_resolve, and of c3r_phase_unit_links / c3r_phase_merge, unchanged.
+ *   c3r_phase_resolve and c3r_phase_merge read pos, ps and h1 only: the caller hands them a pseudo-table (pos, ref = 1, alt = 2, ps, h1),
+ *   as c3r_phase_merge itself does for the units.  h1 = 0: allele A lies on haplotype 1 (GT 0|1, 1|2); h1 = 1: allele B (GT 1|0, 2|1).
+ * On a table whose sites are all REF-and-one-SNV both calls give the words of c3r_phase_links / c3r_phase_unit_links.
+ * Limits, as for both parents: the alleles are read off the CIGAR position — no realignment, no left-alignment of the reads' indels, no
+ * base qualities; the chain is greedy, not wMEC; agreement with `whatshap phase --indels` is not measured.
+ *
+ * c3r_phase_allele_links: links [n][K][2] cis / trans.  ps is IGNORED (a negative one is accepted); every other validation is
+ * c3r_hap_allele_counts' (one checker), C3R_EINVAL naming the first bad index.  It needs no phase table.  n = 0: nothing is launched; no
+ * reads loaded: every count is 0.  It runs k_phase_allele_links (csrc/phase_kernels.hpp).
+ * c3r_phase_allele_unit_links: c3r_phase_unit_links over the allele table.  sites[j].ps is -1 or >= 1 as the chain leaves it, h1[j] is 0
+ * or 1 (refused otherwise, naming the index).  Units, the tie rule, ulinks = NULL (only *n_units), C3R_EOVERFLOW for cap_units < U, and
+ * U < 2 / n = 0 / no reads loaded (nothing is launched, the U rows are 0) are c3r_phase_unit_links'.  It runs k_phase_allele_unit_links on
+ * a copy of the table with h1 folded into the site records.
+ * Both keep device buffers of their own for the sites and the pool, allocated at the first call and kept: they change neither a table
+ * set by c3r_set_phase_sites / c3r_set_phase_alleles, nor the reads' haplotags and phase sets, nor anything a scan or
+ * c3r_hap_allele_counts reads.  The caller's arrays may go once a call returns. */
+int c3r_phase_allele_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *links);
+int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases,
+                                uint32_t *ulinks, int64_t cap_units, int64_t *n_units);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped
