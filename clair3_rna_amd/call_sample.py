@@ -20,6 +20,12 @@ The host stages overlap on threads (the GIL is released inside libc3r / libc3r_i
              for its kernels the others prepare or decode
     merge    per-record rules + order, in calling order as the contigs come out (libc3r_io.so)
 
+In this file: `_plan` checks the flags — all of their rules, before anything is created — and lists the steps of the run (the pass or passes, and
+phase_vcf / hap_vcf / haplotag_bam around them); `Run` executes them.  A pass (`_run_pass`) is four stages: set-up (`_set_up` -> one `_Pass` object:
+ranks and host budget, paths, plan_chunks, BED split, CMD, the index link, this rank's contigs, the REDIportal table), the contexts' bring-up
+(`_Engines`), the per-contig pipeline (`_Pipeline`, with `_FetchJoin`, `_device_stage` and `_decode_stage`; a contig goes from stage to stage as one
+`ContigResult`), and rank 0's assembly and finalisation (`_assemble`, `_finish`).  Which phase table a contig gets is phasedvcf.PhaseSource's business.
+
 Not covered (use the reference's own orchestration around call_var_bam for these): gVCF.  `--enable_phasing_model` runs the 30-channel pass only — the second half of
 run_clair3_rna:729-852 — either on an already haplotagged BAM (HP tags), or, with `--phased_vcf_fn`, on the ORIGINAL BAM plus
 the phased VCF(s) the phasing step wrote: the reads are then haplotagged on the GPU while they are prepared (c3r_set_phase_sites),
@@ -49,6 +55,8 @@ contig, with the HP / PS tags the GPU computed from the phase table the second p
         --enable_phasing_model --phasing builtin --output_dir out
 """
 import argparse
+import collections
+import importlib
 import os
 import sys
 import threading
@@ -335,817 +343,866 @@ def _empty_reads():
     return out
 
 
+def _index_link(bam_fn, out_dir):
+    """None when `bam_fn` needs no index of ours (not a BAM, or one with an index of its own), else the path of the link in tmp/ that gets
+    one beside it (asked of the BAM itself, not guessed from a link that an earlier run in this directory may have left to another file)."""
+    if not bam_fn.endswith(".bam"):
+        return None
+    from . import bamio
+    with bamio.BamFile(bam_fn) as probe:
+        if probe.has_index:
+            return None
+    return os.path.join(out_dir, "tmp", "input.bam")
+
+
 def _indexed_bam(args):
-    """The BAM the steps around the passes read: this run's, or — when IT has no index — the link with an index beside it that a pass left in
-    tmp/ (asked of the BAM again, not guessed from the link: an earlier run in this directory may have left one to another file)."""
-    bam_fn = args.bam_fn
-    if bam_fn.endswith(".bam"):
-        from . import bamio
-        with bamio.BamFile(bam_fn) as probe:
-            indexed = probe.has_index
-        link = os.path.join(args.output_dir, "tmp", "input.bam")
-        if not indexed and os.path.exists(link + ".bai") and os.path.realpath(link) == os.path.realpath(bam_fn):
-            bam_fn = link
-    return bam_fn
+    """The BAM the steps around the passes read: this run's, or — when IT has no index — the link with an index beside it that a pass left in tmp/."""
+    link = _index_link(args.bam_fn, args.output_dir)
+    if link and os.path.exists(link + ".bai") and os.path.realpath(link) == os.path.realpath(args.bam_fn):
+        return link
+    return args.bam_fn
 
 
-def Run(args, log=None):
-    """The passes (_run_flow), and with `--phase_output` / `--haplotagged_bam` one further step each behind them: hap_vcf on the phased pass's
-    VCF, haplotag_bam on the BAM — nothing inside a pass changes."""
-    phase_output, tagged_bam = getattr(args, "phase_output", False), getattr(args, "haplotagged_bam", False)
-    if not phase_output and getattr(args, "phase_indels", False):
+_Step = collections.namedtuple("_Step", "name handed needs")
+
+
+def _plan(args):
+    """Every rule about the phasing flags, in one place, before anything is created: exits with the [ERROR] line of the first rule that is
+    broken, else -> the steps of the run, in order, as _Step(name, handed, needs):
+        pass                                  handed: the args of that pass (_run_pass)
+        clear                                 handed: (directory, which names are an earlier run's files): they are removed, the directory is made
+        phase_vcf | hap_vcf | haplotag_bam    handed: that module's argv; --bam_fn is added when the step runs (_indexed_bam)
+    `needs` is the file without which Run skips the step (None: never skipped).
+    One pass; with `--phasing builtin` the unphased pass, phase_vcf on the file it wrote, and the 30-channel pass with --phased_vcf_fn on
+    phase_vcf's directory (--phasing_indels: phase_vcf --indels, and that pass reads the directory as under --haplotag_indels); with
+    `--phase_output` / `--haplotagged_bam` one further step each behind them.  Nothing inside a pass changes."""
+    import copy
+    builtin, phased = args.phasing is not None, args.enable_phasing_model
+
+    def one_process(what, instead):
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("[ERROR] %s runs in one process: under torch.distributed.run (WORLD_SIZE > 1) %s" % (what, instead))
+    if args.phase_indels and not args.phase_output:
         sys.exit("[ERROR] --phase_indels belongs to --phase_output (it phases the indels of the final VCF): it needs --phase_output")
-    tag_indels = getattr(args, "haplotag_indels", False)
-    if tag_indels and getattr(args, "phasing", None) is not None:
+    if args.haplotag_indels and builtin:
         sys.exit("[ERROR] --haplotag_indels changes nothing under --phasing builtin: the phasing between the passes is SNV-only, so the table the "
                  "reads are haplotagged from holds no indel.  The two-step way: 1. run with --phase_output --phase_indels; 2. rerun with "
                  "--phased_vcf_fn <prefix>_enable_phasing_phased.vcf.gz --haplotag_indels.  In one command, without --haplotag_indels: "
                  "--phasing builtin --phasing_indels phases the indels between the passes and tags the reads from them")
-    if tag_indels and not getattr(args, "phased_vcf_fn", None):
+    if args.haplotag_indels and not args.phased_vcf_fn:
         sys.exit("[ERROR] --haplotag_indels needs --phased_vcf_fn (it widens the table the reads are haplotagged from)")
-    if getattr(args, "phasing_indels", False):
-        if getattr(args, "phasing", None) is None:
-            sys.exit("[ERROR] --phasing_indels belongs to the built-in phasing (it phases indels and 1/2 rows between the passes): it needs --phasing builtin")
-        tag_indels = True                                     # (the steps behind the passes read phase_vcf --indels' directory with the allele table)
-    if not phase_output and not tagged_bam:
-        return _run_flow(args, log)
-    builtin = getattr(args, "phasing", None) is not None
-    if phase_output:
-        if not args.enable_phasing_model:
-            sys.exit("[ERROR] --phase_output needs --enable_phasing_model (it phases the 30-channel pass's VCF)")
-        if not builtin and not getattr(args, "phased_vcf_fn", None):
-            sys.exit("[ERROR] --phase_output needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            sys.exit("[ERROR] --phase_output runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the pass without it and then "
-                     "`python -m clair3_rna_amd.hap_vcf --bam_fn ... --vcf_fn <prefix>_enable_phasing.vcf.gz --phased_vcf_fn ... --output_fn ...`")
-    if tagged_bam:
-        if not args.enable_phasing_model:
-            sys.exit("[ERROR] --haplotagged_bam needs --enable_phasing_model (it writes the tags the 30-channel pass called with)")
-        if not builtin and not getattr(args, "phased_vcf_fn", None):
-            sys.exit("[ERROR] --haplotagged_bam needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            sys.exit("[ERROR] --haplotagged_bam runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the pass without it and then "
-                     "`python -m clair3_rna_amd.haplotag_bam --bam_fn ... --phased_vcf_fn ... --output_dir <output_dir>/tmp/phased_output/phased_bam`")
-    rc = _run_flow(args, log)
-    if rc:
-        return rc
+    if args.phasing_indels and not builtin:
+        sys.exit("[ERROR] --phasing_indels belongs to the built-in phasing (it phases indels and 1/2 rows between the passes): it needs --phasing builtin")
+    for flag, on, why, instead in (
+            ("--phase_output", args.phase_output, "it phases the 30-channel pass's VCF",
+             "run the pass without it and then `python -m clair3_rna_amd.hap_vcf --bam_fn ... --vcf_fn <prefix>_enable_phasing.vcf.gz "
+             "--phased_vcf_fn ... --output_fn ...`"),
+            ("--haplotagged_bam", args.haplotagged_bam, "it writes the tags the 30-channel pass called with",
+             "run the pass without it and then `python -m clair3_rna_amd.haplotag_bam --bam_fn ... --phased_vcf_fn ... --output_dir "
+             "<output_dir>/tmp/phased_output/phased_bam`")):
+        if on:
+            if not phased:
+                sys.exit("[ERROR] %s needs --enable_phasing_model (%s)" % (flag, why))
+            if not builtin and not args.phased_vcf_fn:
+                sys.exit("[ERROR] %s needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin" % flag)
+            one_process(flag, instead)
     ext = ".vcf" if args.no_compress else ".vcf.gz"
-    stem = os.path.join(args.output_dir, args.output_prefix + "_enable_phasing")
-    if not os.path.isfile(stem + ext):                        # (no contig found: the pass wrote nothing)
-        return rc
-    source = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf") if builtin else args.phased_vcf_fn
-    gpu = ["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else []
-    if phase_output:
-        from . import hap_vcf
-        hap_vcf.Run(hap_vcf.build_parser().parse_args(
-            ["--bam_fn", _indexed_bam(args), "--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext,
-             "--hap_counts_fn", stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if getattr(args, "phase_indels", False) else [])
-            + (["--haplotag_indels"] if tag_indels else []) + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + gpu), log)
-    if tagged_bam:
-        # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed
-        from . import haplotag_bam
-        contigs, _ = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn),
-                                 args.chunk_size, args.chunk_num)
-        bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
-        if os.path.isdir(bam_dir):                            # (files of an earlier run in this directory, for contigs this run did not process)
-            for name in os.listdir(bam_dir):
-                if name.endswith(".bam") or name.endswith(".bam.bai"):
-                    os.remove(os.path.join(bam_dir, name))
-        haplotag_bam.Run(haplotag_bam.build_parser().parse_args(
-            ["--bam_fn", _indexed_bam(args), "--phased_vcf_fn", source, "--output_dir", bam_dir,
-             "--ctg_name", ",".join(contigs)] + (["--haplotag_indels"] if tag_indels else []) + gpu), log)
-    return rc
-
-
-def _run_flow(args, log=None):
-    """One pass (_run_pass), or with `--phasing builtin` the three steps of the phased flow one after the other: the unphased pass, phase_vcf
-    on the file it wrote, the 30-channel pass with --phased_vcf_fn on phase_vcf's directory — nothing inside a pass changes.
-    --phasing_indels: phase_vcf --indels, and the second pass reads its directory as under --haplotag_indels."""
-    if getattr(args, "phasing", None) is None:
-        if getattr(args, "phase_merge_levels", 0):
-            sys.exit("[ERROR] --phase_merge_levels belongs to the built-in phasing: it needs --phasing builtin")
-        return _run_pass(args, log)
-    import copy
-    from . import phase_vcf
-    log = log or (lambda m: print(m, file=sys.stderr))
-    if not args.enable_phasing_model:
-        sys.exit("[ERROR] --phasing builtin needs --enable_phasing_model (it prepares the 30-channel pass)")
-    merge_levels = getattr(args, "phase_merge_levels", 0)
-    if merge_levels < 0:
-        sys.exit("[ERROR] --phase_merge_levels must be >= 0")
-    if getattr(args, "phased_vcf_fn", None):
-        sys.exit("[ERROR] --phasing builtin and --phased_vcf_fn exclude each other: the built-in phasing writes the phased VCFs itself")
-    if not args.phased_pileup_model_path:
-        sys.exit("[ERROR] --phased_pileup_model_path is required with --enable_phasing_model")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("[ERROR] --phasing builtin runs in one process: under torch.distributed.run (WORLD_SIZE > 1) run the unphased pass, "
-                 "`python -m clair3_rna_amd.phase_vcf`, and the pass with --phased_vcf_fn as three commands")
-    first = copy.copy(args)
-    first.phasing, first.enable_phasing_model = None, False
-    rc = _run_pass(first, log)
-    if rc:
-        return rc
-    vcf_fn = os.path.join(args.output_dir, args.output_prefix + (".vcf" if args.no_compress else ".vcf.gz"))
     phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
-    bam_fn = _indexed_bam(args)
-    # phased_<ctg>.vcf.gz of an earlier run in this directory: a contig without a row in this run's VCF would keep its file, and the second
-    # pass would haplotag from it
-    if os.path.isdir(phased_dir):
-        for name in os.listdir(phased_dir):
-            if name.startswith("phased_") and name.endswith(".vcf.gz"):
-                os.remove(os.path.join(phased_dir, name))
-    if os.path.isfile(vcf_fn):                                # (no contig found: the first pass wrote nothing, and neither will the second)
-        phase_vcf.Run(phase_vcf.build_parser().parse_args(
-            ["--bam_fn", bam_fn, "--vcf_fn", vcf_fn, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(merge_levels)]
-            + (["--indels"] if getattr(args, "phasing_indels", False) else [])
-            + (["--ctg_name", args.ctg_name] if args.ctg_name else []) + (["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else [])), log)
+    ctg = ["--ctg_name", args.ctg_name] if args.ctg_name else []
+    gpu = ["--gpu_id", str(args.gpu_id)] if args.gpu_id is not None else []
+    if not builtin:
+        if args.phase_merge_levels:
+            sys.exit("[ERROR] --phase_merge_levels belongs to the built-in phasing: it needs --phasing builtin")
+        if args.phased_vcf_fn and not phased:
+            sys.exit("[ERROR] --phased_vcf_fn needs --enable_phasing_model (haplotags only enter the 30-channel tensors)")
+        if args.phased_vcf_fn and not os.path.exists(args.phased_vcf_fn):
+            sys.exit("[ERROR] file %s not found" % args.phased_vcf_fn)
+        if phased and args.phased_pileup_model_path is None:
+            sys.exit("[ERROR] --phased_pileup_model_path is required with --enable_phasing_model")
+        steps = [_Step("pass", args, None)]
     else:
-        os.makedirs(phased_dir, exist_ok=True)
-    second = copy.copy(args)
-    second.phasing, second.phased_vcf_fn = None, phased_dir
-    if getattr(args, "phasing_indels", False):
-        second.haplotag_indels = True                         # (the table of c3r_set_phase_alleles, as --phased_vcf_fn DIR --haplotag_indels)
-    return _run_pass(second, log)
+        if not phased:
+            sys.exit("[ERROR] --phasing builtin needs --enable_phasing_model (it prepares the 30-channel pass)")
+        if args.phase_merge_levels < 0:
+            sys.exit("[ERROR] --phase_merge_levels must be >= 0")
+        if args.phased_vcf_fn:
+            sys.exit("[ERROR] --phasing builtin and --phased_vcf_fn exclude each other: the built-in phasing writes the phased VCFs itself")
+        if not args.phased_pileup_model_path:
+            sys.exit("[ERROR] --phased_pileup_model_path is required with --enable_phasing_model")
+        one_process("--phasing builtin", "run the unphased pass, `python -m clair3_rna_amd.phase_vcf`, and the pass with --phased_vcf_fn as three commands")
+        first, second = copy.copy(args), copy.copy(args)
+        first.phasing, first.enable_phasing_model = None, False
+        second.phasing, second.phased_vcf_fn = None, phased_dir
+        if args.phasing_indels:
+            second.haplotag_indels = True                     # (the table of c3r_set_phase_alleles, as --phased_vcf_fn DIR --haplotag_indels)
+        unphased = os.path.join(args.output_dir, args.output_prefix + ext)
+        # phased_<ctg>.vcf.gz of an earlier run in this directory: a contig without a row in this run's VCF would keep its file, and the
+        # second pass would haplotag from it
+        steps = [_Step("pass", first, None),
+                 _Step("clear", (phased_dir, lambda name: name.startswith("phased_") and name.endswith(".vcf.gz")), None),
+                 _Step("phase_vcf", ["--vcf_fn", unphased, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(args.phase_merge_levels)]
+                       + (["--indels"] if args.phasing_indels else []) + ctg + gpu, unphased),
+                 _Step("pass", second, None)]
+    stem = os.path.join(args.output_dir, args.output_prefix + "_enable_phasing")
+    source = phased_dir if builtin else args.phased_vcf_fn
+    # (--phasing_indels: the steps behind the passes read phase_vcf --indels' directory with the allele table)
+    tag_indels = ["--haplotag_indels"] if args.haplotag_indels or args.phasing_indels else []
+    if args.phase_output:
+        steps.append(_Step("hap_vcf", ["--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext, "--hap_counts_fn",
+                                       stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if args.phase_indels else []) + tag_indels + ctg + gpu,
+                           stem + ext))
+    if args.haplotagged_bam:
+        # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed (--ctg_name: added when the step runs); an
+        # earlier run's files in this directory, for contigs this run did not process, go first
+        bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
+        steps += [_Step("clear", (bam_dir, lambda name: name.endswith(".bam") or name.endswith(".bam.bai")), stem + ext),
+                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + gpu, stem + ext)]
+    return steps
 
 
-def _run_pass(args, log=None):
-    from . import capi
-    log = log or (lambda m: print(m, file=sys.stderr))
-    t_all = time()
+def Run(args, log=None):
+    """The steps of _plan, one after the other.  A step whose file is missing is skipped: no contig was found, and the pass wrote nothing."""
+    for step in _plan(args):
+        if step.needs is not None and not os.path.isfile(step.needs):
+            continue
+        if step.name == "pass":
+            rc = _run_pass(step.handed, log)
+            if rc:
+                return rc
+        elif step.name == "clear":
+            io.remove_stale(*step.handed)
+            os.makedirs(step.handed[0], exist_ok=True)
+        else:
+            argv = ["--bam_fn", _indexed_bam(args)] + step.handed
+            if step.name == "haplotag_bam":
+                contigs, _ = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn),
+                                         args.chunk_size, args.chunk_num)
+                argv += ["--ctg_name", ",".join(contigs)]
+            module = importlib.import_module("." + step.name, __package__)
+            module.Run(module.build_parser().parse_args(argv), log)
+    return 0
+
+
+# ---- one pass.  Stage 1: set-up
+class _Pass(object):
+    """What set-up (_set_up) leaves for the other stages of a pass, as plain attributes; nothing is added to it afterwards:
+        the run        args, log, t_all, timeline, compat (which samtools' column text), channels, qual_rows, qual_merge, weights
+        the ranks      rank, world, dist (torch.distributed or None), n_thr (the threads this process may count on)
+        the paths      out_dir, out_fn, out_nt_fn, parts_dir, split_dir, cmd_fn, bed_fn, vcf_fn (genotyping mode), bam_fn (the one fetched from)
+        the plan       all_contigs and chunk_nums (plan_chunks), contigs (this rank's, in calling order), fai ({contig: length})
+        the objects    table (REDIportal, or None), edits (its per-contig lists), merger (rank 0's SampleMerger, else None), fetcher,
+                       phase_source (phasedvcf.PhaseSource of --phased_vcf_fn, or None)"""
+
+    def mark(self, ctg, what, t0):
+        """A C3R_TIMING timeline line (tools/timeline_view.py reads them)."""
+        if self.timeline:
+            self.log("[timeline] %-6s %-8s %7.3f -> %7.3f s" % (ctg, what, t0 - self.t_all, time() - self.t_all))
+
+
+def _host_budget(args, world):
+    """-> the threads this process may count on.  One process per GPU shares the node's cores with its peers: this rank's slice of them (its
+    GPU's NUMA node when the topology says which), and thread counts cut to match — decode (C3R_THREADS), fetch, compression.  The same for
+    one process on the host slice a rank of an N-GPU run would get (C3R_HOST_SLICE, tools/host_slice.py)."""
+    if world == 1 and not os.environ.get("C3R_HOST_SLICE"):
+        return os.cpu_count() or 8
+    from . import shard
+    n_thr, _cpus = shard.host_budget(apply=True)
+    args.fetch_threads = max(1, min(args.fetch_threads, n_thr // 2 or 1))
+    os.environ.setdefault("C3R_FETCH_INFLATE", str(max(1, n_thr // args.fetch_threads)))    # inflate threads per fetch handle
+    return n_thr
+
+
+def _set_up(args, log, t_all):
+    """Ranks and host budget, paths, the plan of contigs and chunks, the split BED, CMD, the BAM index, this rank's contigs, the REDIportal
+    table, the weights, the merger and the fetcher -> _Pass, or None when no contig was found."""
+    p = _Pass()
+    p.args, p.log, p.t_all, p.timeline = args, log, t_all, os.environ.get("C3R_TIMING") is not None
     # which samtools the column text follows: asked in a child process before anything touches the GPU (rank 0's line is the one printed)
-    compat = mpileup_compat.resolve(getattr(args, "mpileup_compat", "auto"), getattr(args, "samtools", "samtools"),
-                                    log if int(os.environ.get("RANK", "0")) == 0 else (lambda m: None))
+    p.compat = mpileup_compat.resolve(args.mpileup_compat, args.samtools, log if int(os.environ.get("RANK", "0")) == 0 else (lambda m: None))
     # one process per GPU (`python -m torch.distributed.run --nproc-per-node N -m clair3_rna_amd.call_sample ...`): contigs are
     # dealt to the ranks largest-first, every rank leaves the merged records of its contigs under tmp/parts/, rank 0 puts the
     # file together.  No data-path collective (SURVEY.md 8e): torch.distributed (gloo) is the barrier, nothing else.
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    dist = None
-    if world > 1:
+    p.rank, p.world, p.dist = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), None
+    if p.world > 1:
         import torch.distributed as dist
+        p.dist = dist
         if not dist.is_initialized():
             dist.init_process_group("gloo")
         if args.gpu_id is None:
-            args.gpu_id = int(os.environ.get("LOCAL_RANK", str(rank)))
-        # one process per GPU shares the node's cores with its peers: this rank's slice of them (its GPU's NUMA node when the
-        # topology says which), and thread counts cut to match — decode (C3R_THREADS), fetch, compression
-        from . import shard
-        n_thr, _cpus = shard.host_budget(apply=True)
-        args.fetch_threads = max(1, min(args.fetch_threads, n_thr // 2 or 1))
-        os.environ.setdefault("C3R_FETCH_INFLATE", str(max(1, n_thr // args.fetch_threads)))    # inflate threads per fetch handle
-    elif os.environ.get("C3R_HOST_SLICE"):
-        # one process on the host slice a rank of an N-GPU run would get (tools/host_slice.py)
-        from . import shard
-        n_thr, _cpus = shard.host_budget(apply=True)
-        args.fetch_threads = max(1, min(args.fetch_threads, n_thr // 2 or 1))
-        os.environ.setdefault("C3R_FETCH_INFLATE", str(max(1, n_thr // args.fetch_threads)))
+            args.gpu_id = int(os.environ.get("LOCAL_RANK", str(p.rank)))
+    p.n_thr = _host_budget(args, p.world)
     if args.gpu_id is None:
         args.gpu_id = int(os.environ.get("C3R_DEVICE", "0"))
     for need in (args.bam_fn, args.ref_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
-    bed_fn, vcf_fn = existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn)
-    phased_vcf_fn = getattr(args, "phased_vcf_fn", None)
-    if phased_vcf_fn and not args.enable_phasing_model:
-        sys.exit("[ERROR] --phased_vcf_fn needs --enable_phasing_model (haplotags only enter the 30-channel tensors)")
-    if phased_vcf_fn and not os.path.exists(phased_vcf_fn):
-        sys.exit("[ERROR] file %s not found" % phased_vcf_fn)
-    channels = 30 if args.enable_phasing_model else 18
-    model = args.phased_pileup_model_path if args.enable_phasing_model else args.pileup_model_path
-    if model is None:
-        sys.exit("[ERROR] --phased_pileup_model_path is required with --enable_phasing_model")
-    out_dir = args.output_dir
+    p.bed_fn, p.vcf_fn = existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn)
+    p.channels = 30 if args.enable_phasing_model else 18
+    p.out_dir = out_dir = args.output_dir
     os.makedirs(os.path.join(out_dir, "tmp"), exist_ok=True)
     suffix = "_enable_phasing" if args.enable_phasing_model else ""
-    out_fn = os.path.join(out_dir, args.output_prefix + suffix + ".vcf")
-    out_nt_fn = os.path.join(out_dir, args.output_prefix + "_no_tagging" + suffix + ".vcf")
+    p.out_fn = os.path.join(out_dir, args.output_prefix + suffix + ".vcf")
+    p.out_nt_fn = os.path.join(out_dir, args.output_prefix + "_no_tagging" + suffix + ".vcf")
+    p.parts_dir = os.path.join(out_dir, "tmp", "parts")
 
-    contigs, chunk_nums = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, bed_fn, vcf_fn, args.chunk_size, args.chunk_num)
-    if not contigs:
+    p.all_contigs, p.chunk_nums = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, p.bed_fn, p.vcf_fn, args.chunk_size, args.chunk_num)
+    if not p.all_contigs:
         log("[WARNING] Exit calling because no contig was found in BAM!")
-        return 0
-    fai = {n: L for n, L, _o, _b, _w in io.read_fai(args.ref_fn)}
-    priv = os.path.join(out_dir, "tmp") if rank == 0 else os.path.join(out_dir, "tmp", "rank%d" % rank)
+        return None
+    p.fai = {n: L for n, L, _o, _b, _w in io.read_fai(args.ref_fn)}
+    priv = os.path.join(out_dir, "tmp") if p.rank == 0 else os.path.join(out_dir, "tmp", "rank%d" % p.rank)
     os.makedirs(priv, exist_ok=True)
-    split_dir = os.path.join(priv, "split_beds")
-    if bed_fn:
-        split_extend_bed(bed_fn, split_dir, set(contigs))
-    cmd_fn = os.path.join(out_dir, "tmp", "CMD")                        # run_clair3_rna:613-667: stamped into the VCF header
-    if rank == 0 and not os.path.exists(cmd_fn):
-        with open(cmd_fn, "w") as f:
+    p.split_dir = os.path.join(priv, "split_beds")
+    if p.bed_fn:
+        split_extend_bed(p.bed_fn, p.split_dir, set(p.all_contigs))
+    p.cmd_fn = os.path.join(out_dir, "tmp", "CMD")                      # run_clair3_rna:613-667: stamped into the VCF header
+    if p.rank == 0 and not os.path.exists(p.cmd_fn):
+        with open(p.cmd_fn, "w") as f:
             f.write(" ".join(sys.argv) + "\n")
-    bam_fn = args.bam_fn
-    if bam_fn.endswith(".bam"):
-        from . import bamio
-        with bamio.BamFile(bam_fn) as probe:
-            indexed = probe.has_index
-        if not indexed:
-            # without an index every contig would cost a pass over the whole file: build one next to a link in tmp/
-            # (run_clair3_rna insists on an existing index, :469-477; samtools is not a dependency here).  Rank 0 alone builds it,
-            # under temporary names that are renamed into place, and the other ranks open the BAM only after the barrier: nobody
-            # ever sees a missing link or a half-written .bai
-            link = os.path.join(out_dir, "tmp", "input.bam")
-            build_err = None
-            if rank == 0:
-                try:
-                    tmp_link, tmp_bai = link + ".tmp%d" % os.getpid(), link + ".bai.tmp%d" % os.getpid()
-                    if os.path.lexists(tmp_link):
-                        os.remove(tmp_link)
-                    os.symlink(os.path.abspath(bam_fn), tmp_link)
-                    log("[INFO] %s has no .bai: building %s.bai" % (bam_fn, link))
-                    try:
-                        bamio.index_build(tmp_link, tmp_bai)
-                        os.replace(tmp_bai, link + ".bai")
-                        os.replace(tmp_link, link)
-                    finally:
-                        for t_ in (tmp_link, tmp_bai):
-                            if os.path.lexists(t_):
-                                os.remove(t_)
-                except Exception as e:           # the other ranks are waiting at the barrier: reach it, then fail together
-                    build_err = e
-            _all_ranks_ok(dist, world, build_err, "building the BAM index")
-            bam_fn = link
-    all_contigs = contigs
-    parts_dir = os.path.join(out_dir, "tmp", "parts")
-    if world > 1:
-        from . import shard
-        os.makedirs(parts_dir, exist_ok=True)
-        dist.barrier()                                                  # CMD is in place before anybody builds the header
-        # contigs are dealt by the WORK they hold (SURVEY.md 8e: "by read count ... from the read index"): the mapped reads the BAM
-        # index reports per contig (pseudo-bin 37450), else the compressed bytes its records span, else its length.  RNA coverage is
-        # nowhere near proportional to length (chr19 against chr13), so a deal by length balances the wrong thing.
-        costs, basis = shard.contig_costs(bam_fn, all_contigs, fai)
-        plan = shard.lpt_assign(costs, world)
-        mine = plan[rank]
-        if rank == 0:
-            log("[INFO] %d contigs dealt to %d ranks by %s: load imbalance %.3f" % (len(all_contigs), world, basis, shard.imbalance(costs, plan)))
-        contigs = [all_contigs[i] for i in mine]
-
-    table = None
-    if args.tag_variant_using_readiportal:
-        src = args.readiportal_source_fn
-        if src is None or src.upper() == "NONE" or not os.path.exists(src):
-            log("[WARNING] Enabled tagging variant using readiportal, but --readiportal_source_fn %s file not found, skip tagging!" % src)
-            table = {}
-        else:
-            tags = set(args.readiportal_database_filter_tag.split(":")) if args.readiportal_database_filter_tag is not None else None
-            table = sort_vcf.load_rediportal(src, contigs, tags)
-
-    weights = io.load_weights(model, channels)
-    n_ctx = max(1, args.contexts)
-    engines = [None] * n_ctx
-    engine_ready = [threading.Event() for _ in range(n_ctx)]
-    engine_errs = []
-    engine_threads = []
-
-    def make_engines():
-        """The GPU contexts: created, given the weights and the arithmetic once the first fetches are under way (0.1-0.2 s that used to come
-        before the first BAM byte was read).  Each context on a thread of its own: context 0 takes the first contig the moment IT is ready
-        — HIP start-up and its own weights, 0.2 s in a fresh process — while the others' weights are still being packed (they are not needed
-        before the second contig has been fetched).  Returns at once; context_worker waits for its engine."""
-        def bring_up(k):
-            try:
-                if k > 0:
-                    # (the process' first c3r_create starts HIP, and two contexts that pack and calibrate their weights at once take twice as long
-                    # each: context 0 first — it is the one the first contig waits for —, the others are ready long before their contig is fetched)
-                    engine_ready[0].wait()
-                t0_ = time()
-                e = capi.Engine(args.gpu_id)
-                engines[k] = e
-                mark("ctx%d" % k, "create", t0_)
-                t0_ = time()
-                e.load_weights(weights, channels)             # (packing the weights into the kernels' layouts is host work: side by side)
-                mark("ctx%d" % k, "weights", t0_)
-                t0_ = time()
-                e.set_precision(args.gpu_precision)
-                mark("ctx%d" % k, "precision", t0_)
-                if k == 0 and args.gpu_precision != "f16x3":
-                    log("[INFO] network arithmetic: %s -> %s (calibration max |dP| %s)" % ((args.gpu_precision,) + tuple(e.precision())))
-            except BaseException as ex:
-                engine_errs.append(ex)
-            finally:
-                engine_ready[k].set()
-        for k in range(n_ctx):
-            t_ = threading.Thread(target=bring_up, args=(k,), name="c3r-bringup%d" % k, daemon=True)
-            engine_threads.append(t_)
-            t_.start()
-
-    def engine_of(k):
-        """Context k's engine, once it is up (raises what its bring-up raised)."""
-        engine_ready[k].wait()
-        if engine_errs:
-            raise engine_errs[0]
-        return engines[k]
-    qual_rows = args.qual if args.qual is not None else 2              # call_variants.py:1827 (STEP 1 never passes --qual)
-    qual_merge = args.qual if args.qual is not None else 2             # sort_vcf's own default
-    header = vcf.header(args.ref_fn, cmd_fn, args.sample_name) + "\n"
+    p.bam_fn = _ensure_index(p)
+    p.contigs = _deal_contigs(p)
+    p.table = _rediportal_table(args, p.contigs, log)
+    model = args.phased_pileup_model_path if args.enable_phasing_model else args.pileup_model_path
+    p.weights = io.load_weights(model, p.channels)
+    p.qual_rows = args.qual if args.qual is not None else 2            # call_variants.py:1827 (STEP 1 never passes --qual)
+    p.qual_merge = args.qual if args.qual is not None else 2           # sort_vcf's own default
+    header = vcf.header(args.ref_fn, p.cmd_fn, args.sample_name) + "\n"
     # (compressed output is written as it is produced — bgzip blocks and the tabix index grow contig by contig — so that no
     # compression pass is left after the last contig)
-    merger = sort_vcf.SampleMerger(out_fn, header, qual_merge, args.print_ref_calls, table, out_nt_fn, stream_gz=not args.no_compress) if rank == 0 else None
-
-    def device_stage(eng, ctg, rs, ref, phase=None):
-        """-> number of candidates left resident in `eng` (rows are produced by decode_stage).  phase: the contig's phase sites
-        (--phased_vcf_fn; None without the flag)."""
-        extend_bed = existing(os.path.join(split_dir, ctg)) if bed_fn else None
-        regions, site_sets, ext_iv = [], [], []
-        for k in range(1, chunk_nums[ctg] + 1):
-            a, b, sites, ext_iv = resolve_region(fai[ctg], ctg, k, chunk_nums[ctg], None, None, bed_fn, extend_bed, vcf_fn)
-            if sites is not None and not sites:
-                continue
-            regions.append((a, b))
-            site_sets.append(sites)
-        if not regions:
-            return 0
-        eng.params = capi.default_params()
-        eng.set_bed(0, ext_iv if extend_bed else None)
-        eng.set_bed(1, io.read_bed(bed_fn, ctg)[0] if bed_fn else None)
-        eng.set_params(channels=channels, min_mq=args.min_mq, min_coverage=args.min_coverage, snp_min_af=args.snp_min_af,
-                       indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
-                       splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(vcf_fn is not None),
-                       mpileup_compat=compat)
-        if phase is not None:                        # (--phased_vcf_fn; without it a context never holds a table)
-            eng.load_reads(_empty_reads())           # (the previous contig's reads are done with: a new table would tag them again first)
-            if isinstance(phase, tuple):             # (--haplotag_indels: phasedvcf.contig_alleles' table)
-                eng.set_phase_alleles(*phase[:4])
-                log("[INFO] %s: %d phased sites in the table of --haplotag_indels, %d with an insertion or deletion, %d with two ALTs"
-                    % (ctg, len(phase[0]), phase[4].kept["indel"], phase[4].kept["two_alt"]))
-                phase = phase[0]
-            else:
-                eng.set_phase_sites(phase)           # before the reads: they are tagged while they are prepared
-            if not len(phase):
-                rs.reads["hp"] = 0                   # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
-        t = [time()]
-        eng.load_reads(rs); t.append(time())
-        eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str))); t.append(time())      # (the fetcher's array: upper-cased, used in place)
-        if vcf_fn is None:
-            eng.begin_batch()
-            n = eng.scan_regions(regions)
-            eng.end_batch()
-            n = eng.n_candidates
-            t.append(time())
-            if n:
-                # (launched as soon as the tensors exist, side by side with the other context's pass: making the contexts take
-                # turns for the network — one copies while the other computes — measured 3.1-3.3 s against 2.7-2.8 s)
-                eng.infer(fetch=False)
-            t.append(time())
-            if os.environ.get("C3R_TIMING"):
-                log("[device_stage %s] load_reads %.0f ms, set_reference %.0f ms, scan %.0f ms, infer launch %.0f ms (%d reads, %d sites)"
-                    % (ctg, 1e3 * (t[1] - t[0]), 1e3 * (t[2] - t[1]), 1e3 * (t[3] - t[2]), 1e3 * (t[4] - t[3]), len(rs.reads), n))
-            return n
-        return [(r, s) for r, s in zip(regions, site_sets)]            # genotyping mode: one scan per chunk (its own site list)
-
-    def decode_stage(eng, ctg, todo):
-        if isinstance(todo, list):
-            rows = b""
-            for (a, b), sites in todo:
-                eng.set_sites(sites)
-                if eng.scan(a, b):
-                    eng.infer(fetch=False)
-                    rows += eng.call_rows_text(ctg, qual=qual_rows, show_ref=args.print_ref_calls)[0]
-            return rows
-        rows = eng.call_rows_text(ctg, qual=qual_rows, show_ref=args.print_ref_calls)[0] if todo else b""
-        dump = getattr(args, "debug_dump", None)
-        if dump is not None and todo:                                  # tests / debugging: what the rows were made from
-            dump[ctg] = dict(sites=eng.sites(), tokens=eng.tokens(), probs=eng.fetch_probs(todo), tensors=eng.tensors(), rows=rows)
-        return rows
-
-    part_counts = {}
-    edits_cache, edits_lock = [], threading.Lock()
-
-    def edits_by_contig():
-        """The REDIportal table as per-contig entry lists, built once for all the per-contig mergers of this rank."""
-        with edits_lock:
-            if not edits_cache:
-                d = {}
-                for (c, pos), hit in (table or {}).items():
-                    d.setdefault(c, []).append((pos, hit[0], hit[1]))
-                edits_cache.append(d)
-        return edits_cache[0]
-
-    def merge_contig(ctg, rows):
-        if world == 1:
-            merger.add_contig(ctg, rows)
-        else:                                 # this contig's records on their own; rank 0 concatenates in calling order
-            k = all_contigs.index(ctg)
-            m = sort_vcf.SampleMerger(os.path.join(parts_dir, "%05d.vcf" % k), "", qual_merge, args.print_ref_calls, table,
-                                      os.path.join(parts_dir, "%05d_nt.vcf" % k))
-            if table:
-                m._edits = edits_by_contig()
-            m.add_contig(ctg, rows)
-            m.out.close()
-            if m.out_nt:
-                m.out_nt.close()
-            part_counts[k] = (m.n_read, m.n_kept, m.n_tagged)
-
-    fetcher = _Fetcher(bam_fn, args.ref_fn)
-    phase_all, phase_lock = [], threading.Lock()
-
-    def phase_sites_of(ctg):
-        """--phased_vcf_fn: the contig's site table, read on a fetch thread.  One VCF for the whole sample is parsed once, by the
-        first thread that asks; a directory is read file by file."""
+    p.edits = sort_vcf.ContigEdits(p.table)                            # (one for all the per-contig mergers of this rank)
+    p.merger = sort_vcf.SampleMerger(p.out_fn, header, p.qual_merge, args.print_ref_calls, p.table, p.out_nt_fn, stream_gz=not args.no_compress,
+                                     edits=p.edits) if p.rank == 0 else None
+    p.fetcher = _Fetcher(p.bam_fn, args.ref_fn)
+    p.phase_source = None                                              # --phased_vcf_fn: every contig's table is read on a fetch thread
+    if args.phased_vcf_fn:
         from . import phasedvcf
-        tag_indels = getattr(args, "haplotag_indels", False)
-        if os.path.isdir(phased_vcf_fn):
-            return phasedvcf.contig_alleles(phased_vcf_fn, ctg) if tag_indels else phasedvcf.contig_sites(phased_vcf_fn, ctg)
-        with phase_lock:
-            if not phase_all:
-                phase_all.append(phasedvcf.read_all_phase_alleles(phased_vcf_fn) if tag_indels else phasedvcf.read_all_phase_sites(phased_vcf_fn))
-        hit = phase_all[0].get(ctg)
-        if tag_indels:
-            return hit or phasedvcf.empty_alleles()
-        return hit[0] if hit else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
-    t_setup = time() - t_all
-    # contigs fetched (or being fetched) but not yet through their context: every context busy + every fetch thread running ahead.
-    # (n_ctx + 2 starved the contexts: a fetch takes ~100 ms, a context needs a new contig every ~35 ms)
-    slots = threading.BoundedSemaphore(n_ctx + max(2, args.fetch_threads))
-    stats = dict(fetch=0.0, dev=0.0, sites=0)
-    lock = threading.Lock()
-
-    timeline = os.environ.get("C3R_TIMING") is not None
-    def mark(ctg, what, t0):
-        if timeline:
-            log("[timeline] %-6s %-8s %7.3f -> %7.3f s" % (ctg, what, t0 - t_all, time() - t_all))
+        p.phase_source = phasedvcf.PhaseSource(args.phased_vcf_fn, args.haplotag_indels)
+    return p
 
 
-    def submit_fetch(pool, ctg):
-        """A contig's fetch as tasks of the fetch pool — one per position range (_Fetcher.plan) and one for the reference — joined
-        by whichever finishes last.  -> Future of (ReadSet, reference, seconds)."""
-        from concurrent.futures import Future
-        t0 = time()
-        ranges = fetcher.plan(fai[ctg], max(1, args.fetch_threads))
-        out = Future()
-        state = dict(left=len(ranges) + 1 + int(bool(phased_vcf_fn)), parts=[None] * len(ranges), ref=b"", err=None, phase=None)
-        lk = threading.Lock()
-
-        def done_one():
-            with lk:
-                state["left"] -= 1
-                last = state["left"] == 0
-            if not last:
-                return
-            try:
-                if state["err"] is not None:
-                    raise state["err"]
-                rs = fetcher.join(state["parts"])
-                mark(ctg, "fetch", t0)
-                if timeline:
-                    log("[timeline-fetch %s] %d range(s): %d reads, %d CIGAR ops, %.0f MB of bases, %.0f Mb of reference" % (ctg, len(ranges), len(rs.reads), len(rs.cigar), len(rs.seq) / 1e6, len(state["ref"]) / 1e6))
-                rs.phase_sites = state["phase"]
-                out.set_result((rs, state["ref"] if len(rs.reads) else b"", time() - t0))
-            except BaseException as e:
-                out.set_exception(e)
-
-        def part_task(k, beg, end):
-            try:
-                state["parts"][k] = fetcher.part(ctg, beg, end)
-            except BaseException as e:
-                state["err"] = e
-            done_one()
-
-        def ref_task():
-            try:
-                state["ref"] = fetcher.reference(ctg, fai[ctg])
-            except BaseException as e:
-                state["err"] = e
-            done_one()
-
-        def phase_task():
-            try:
-                state["phase"] = phase_sites_of(ctg)
-            except BaseException as e:
-                state["err"] = e
-            done_one()
-
-        for k, (beg, end) in enumerate(ranges):
-            pool.submit(part_task, k, beg, end)
-        pool.submit(ref_task)
-        if phased_vcf_fn:
-            pool.submit(phase_task)
-        return out
-
-    def context_task(eng, ctg, fut):
-        """One contig on the context whose thread took it from the queue (contigs are taken in calling order by whichever context
-        is free): host preparation + uploads, tensor build, network, snapshot.  Contexts work side by side — while one waits for
-        its kernels another queues its uploads and scans."""
+def _ensure_index(p):
+    """-> the BAM the pass fetches from: the run's own, or the link in tmp/ with the index built here beside it."""
+    link = _index_link(p.args.bam_fn, p.out_dir)
+    if link is None:
+        return p.args.bam_fn
+    # without an index every contig would cost a pass over the whole file: build one next to a link in tmp/
+    # (run_clair3_rna insists on an existing index, :469-477; samtools is not a dependency here).  Rank 0 alone builds it,
+    # under temporary names that are renamed into place, and the other ranks open the BAM only after the barrier: nobody
+    # ever sees a missing link or a half-written .bai
+    build_err = None
+    if p.rank == 0:
+        from . import bamio
         try:
-            rs, ref, dt = fut.result()
+            tmp_link, tmp_bai = link + ".tmp%d" % os.getpid(), link + ".bai.tmp%d" % os.getpid()
+            if os.path.lexists(tmp_link):
+                os.remove(tmp_link)
+            os.symlink(os.path.abspath(p.args.bam_fn), tmp_link)
+            p.log("[INFO] %s has no .bai: building %s.bai" % (p.args.bam_fn, link))
+            try:
+                bamio.index_build(tmp_link, tmp_bai)
+                os.replace(tmp_bai, link + ".bai")
+                os.replace(tmp_link, link)
+            finally:
+                for t_ in (tmp_link, tmp_bai):
+                    if os.path.lexists(t_):
+                        os.remove(t_)
+        except Exception as e:           # the other ranks are waiting at the barrier: reach it, then fail together
+            build_err = e
+    _all_ranks_ok(p.dist, p.world, build_err, "building the BAM index")
+    return link
+
+
+def _deal_contigs(p):
+    """-> this rank's contigs, in calling order: all of them in one process."""
+    if p.world == 1:
+        return p.all_contigs
+    from . import shard
+    os.makedirs(p.parts_dir, exist_ok=True)
+    p.dist.barrier()                                                    # CMD is in place before anybody builds the header
+    # contigs are dealt by the WORK they hold (SURVEY.md 8e: "by read count ... from the read index"): the mapped reads the BAM
+    # index reports per contig (pseudo-bin 37450), else the compressed bytes its records span, else its length.  RNA coverage is
+    # nowhere near proportional to length (chr19 against chr13), so a deal by length balances the wrong thing.
+    costs, basis = shard.contig_costs(p.bam_fn, p.all_contigs, p.fai)
+    plan = shard.lpt_assign(costs, p.world)
+    if p.rank == 0:
+        p.log("[INFO] %d contigs dealt to %d ranks by %s: load imbalance %.3f" % (len(p.all_contigs), p.world, basis, shard.imbalance(costs, plan)))
+    return [p.all_contigs[i] for i in plan[p.rank]]
+
+
+def _rediportal_table(args, contigs, log):
+    """-> {(contig, pos): hit} of --readiportal_source_fn for `contigs`; {} when the file is missing; None without the flag."""
+    if not args.tag_variant_using_readiportal:
+        return None
+    src = args.readiportal_source_fn
+    if src is None or src.upper() == "NONE" or not os.path.exists(src):
+        log("[WARNING] Enabled tagging variant using readiportal, but --readiportal_source_fn %s file not found, skip tagging!" % src)
+        return {}
+    tags = set(args.readiportal_database_filter_tag.split(":")) if args.readiportal_database_filter_tag is not None else None
+    return sort_vcf.load_rediportal(src, contigs, tags)
+
+
+# ---- stage 2: the GPU contexts
+class _Engines(object):
+    """The GPU contexts: created, given the weights and the arithmetic once the first fetches are under way (0.1-0.2 s that used to come
+    before the first BAM byte was read).  Each context on a thread of its own: context 0 takes the first contig the moment IT is ready
+    — HIP start-up and its own weights, 0.2 s in a fresh process — while the others' weights are still being packed (they are not needed
+    before the second contig has been fetched)."""
+
+    def __init__(self, p, n_ctx):
+        self.p = p
+        self.engines = [None] * n_ctx
+        self.ready = [threading.Event() for _ in range(n_ctx)]
+        self.errs, self.threads = [], []
+
+    def start(self):
+        """Returns at once; `get` waits for its engine."""
+        for k in range(len(self.engines)):
+            t_ = threading.Thread(target=self._bring_up, args=(k,), name="c3r-bringup%d" % k, daemon=True)
+            self.threads.append(t_)
+            t_.start()
+
+    def _bring_up(self, k):
+        from . import capi           # (capi.Engine is looked up here, when a context is made: tests put a stand-in there)
+        p, args = self.p, self.p.args
+        try:
+            if k > 0:
+                # (the process' first c3r_create starts HIP, and two contexts that pack and calibrate their weights at once take twice as long
+                # each: context 0 first — it is the one the first contig waits for —, the others are ready long before their contig is fetched)
+                self.ready[0].wait()
+            t0 = time()
+            e = capi.Engine(args.gpu_id)
+            self.engines[k] = e
+            p.mark("ctx%d" % k, "create", t0)
+            t0 = time()
+            e.load_weights(p.weights, p.channels)             # (packing the weights into the kernels' layouts is host work: side by side)
+            p.mark("ctx%d" % k, "weights", t0)
+            t0 = time()
+            e.set_precision(args.gpu_precision)
+            p.mark("ctx%d" % k, "precision", t0)
+            if k == 0 and args.gpu_precision != "f16x3":
+                p.log("[INFO] network arithmetic: %s -> %s (calibration max |dP| %s)" % ((args.gpu_precision,) + tuple(e.precision())))
+        except BaseException as ex:
+            self.errs.append(ex)
+        finally:
+            self.ready[k].set()
+
+    def get(self, k):
+        """Context k's engine, once it is up (raises what its bring-up raised)."""
+        self.ready[k].wait()
+        if self.errs:
+            raise self.errs[0]
+        return self.engines[k]
+
+    def close(self):
+        """After the pipeline has stopped: no thread is inside libc3r any more."""
+        for t_ in self.threads:
+            t_.join()
+        for e in self.engines:
+            if e is not None:
+                e.close()
+
+
+# ---- stage 3: the per-contig pipeline
+class ContigResult(object):
+    """What has become of a contig, as the stages hand it on — `kind` says which case holds, `value` is that case's payload:
+        NO_READS   nothing mapped there: no payload
+        RESIDENT   tensors built and the network launched: the number of candidates left resident in the context
+        CHUNKS     genotyping mode, still to run chunk by chunk (each has its own site list): [((start, end), sites), ...]
+        ROWS       the contig's rows as bytes, still to merge
+        DECODING   decode (and merge) detached to a worker: a Future of a MERGED result
+        MERGED     merged on the worker: SampleMerger.merge_only's result, for the ordered write — None when the worker wrote this
+                   rank's part files itself (several ranks)"""
+    NO_READS, RESIDENT, CHUNKS, ROWS, DECODING, MERGED = "no_reads", "resident", "chunks", "rows", "decoding", "merged"
+
+    def __init__(self, kind, value=None):
+        self.kind, self.value = kind, value
+
+
+class _FetchJoin(object):
+    """A contig's fetch as tasks of the fetch pool — one per position range (_Fetcher.plan), one for the reference and, with
+    --phased_vcf_fn, one for the phase table — joined by whichever finishes last.  `future`: (ReadSet, reference, seconds, phase table or None)."""
+
+    def __init__(self, p, pool, ctg):
+        from concurrent.futures import Future
+        self.p, self.ctg, self.t0, self.future = p, ctg, time(), Future()
+        self.ranges = p.fetcher.plan(p.fai[ctg], max(1, p.args.fetch_threads))
+        self.parts, self.ref, self.phase, self.err = [None] * len(self.ranges), b"", None, None
+        self.left, self.lock = len(self.ranges) + 1 + int(p.phase_source is not None), threading.Lock()
+        for k, (beg, end) in enumerate(self.ranges):
+            pool.submit(self._task, self._part, k, beg, end)
+        pool.submit(self._task, self._reference)
+        if p.phase_source is not None:
+            pool.submit(self._task, self._phase)
+
+    def _part(self, k, beg, end):
+        self.parts[k] = self.p.fetcher.part(self.ctg, beg, end)
+
+    def _reference(self):
+        self.ref = self.p.fetcher.reference(self.ctg, self.p.fai[self.ctg])
+
+    def _phase(self):
+        self.phase = self.p.phase_source.table(self.ctg)
+
+    def _task(self, work, *a):
+        try:
+            work(*a)
+        except BaseException as e:
+            self.err = e
+        with self.lock:
+            self.left -= 1
+            last = self.left == 0
+        if not last:
+            return
+        p = self.p
+        try:
+            if self.err is not None:
+                raise self.err
+            rs = p.fetcher.join(self.parts)
+            p.mark(self.ctg, "fetch", self.t0)
+            if p.timeline:
+                p.log("[timeline-fetch %s] %d range(s): %d reads, %d CIGAR ops, %.0f MB of bases, %.0f Mb of reference" % (self.ctg, len(self.ranges), len(rs.reads), len(rs.cigar), len(rs.seq) / 1e6, len(self.ref) / 1e6))
+            self.future.set_result((rs, self.ref if len(rs.reads) else b"", time() - self.t0, self.phase))
+        except BaseException as e:
+            self.future.set_exception(e)
+
+
+def _device_stage(p, eng, ctg, rs, ref, phase):
+    """Reads, reference, tensor build and the network's launch on one context -> ContigResult RESIDENT, or CHUNKS in genotyping mode.
+    phase: the contig's phase table (--phased_vcf_fn; None without the flag)."""
+    from . import capi
+    args = p.args
+    extend_bed = existing(os.path.join(p.split_dir, ctg)) if p.bed_fn else None
+    regions, site_sets, ext_iv = [], [], []
+    for k in range(1, p.chunk_nums[ctg] + 1):
+        a, b, sites, ext_iv = resolve_region(p.fai[ctg], ctg, k, p.chunk_nums[ctg], None, None, p.bed_fn, extend_bed, p.vcf_fn)
+        if sites is not None and not sites:
+            continue
+        regions.append((a, b))
+        site_sets.append(sites)
+    if not regions:
+        return ContigResult(ContigResult.RESIDENT, 0)
+    eng.params = capi.default_params()
+    eng.set_bed(0, ext_iv if extend_bed else None)
+    eng.set_bed(1, io.read_bed(p.bed_fn, ctg)[0] if p.bed_fn else None)
+    eng.set_params(channels=p.channels, min_mq=args.min_mq, min_coverage=args.min_coverage, snp_min_af=args.snp_min_af,
+                   indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
+                   splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(p.vcf_fn is not None),
+                   mpileup_compat=p.compat)
+    if phase is not None:                            # (--phased_vcf_fn; without it a context never holds a table)
+        eng.load_reads(_empty_reads())               # (the previous contig's reads are done with: a new table would tag them again first)
+        p.phase_source.apply(eng, phase)             # before the reads: they are tagged while they are prepared
+        note = p.phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
+        if note:
+            p.log(note)
+        if not len(phase):
+            rs.reads["hp"] = 0                       # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
+    t = [time()]
+    eng.load_reads(rs); t.append(time())
+    eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str))); t.append(time())      # (the fetcher's array: upper-cased, used in place)
+    if p.vcf_fn is not None:
+        return ContigResult(ContigResult.CHUNKS, list(zip(regions, site_sets)))                   # genotyping mode: one scan per chunk (its own site list)
+    eng.begin_batch()
+    eng.scan_regions(regions)
+    eng.end_batch()
+    n = eng.n_candidates
+    t.append(time())
+    if n:
+        # (launched as soon as the tensors exist, side by side with the other context's pass: making the contexts take
+        # turns for the network — one copies while the other computes — measured 3.1-3.3 s against 2.7-2.8 s)
+        eng.infer(fetch=False)
+    t.append(time())
+    if os.environ.get("C3R_TIMING"):
+        p.log("[device_stage %s] load_reads %.0f ms, set_reference %.0f ms, scan %.0f ms, infer launch %.0f ms (%d reads, %d sites)"
+              % (ctg, 1e3 * (t[1] - t[0]), 1e3 * (t[2] - t[1]), 1e3 * (t[3] - t[2]), 1e3 * (t[4] - t[3]), len(rs.reads), n))
+    return ContigResult(ContigResult.RESIDENT, n)
+
+
+def _decode_stage(p, eng, ctg, todo):
+    """The rows of a RESIDENT or CHUNKS contig, decoded on the context's own thread -> ContigResult ROWS."""
+    show_ref = p.args.print_ref_calls
+    rows = b""
+    if todo.kind == ContigResult.CHUNKS:
+        for (a, b), sites in todo.value:
+            eng.set_sites(sites)
+            if eng.scan(a, b):
+                eng.infer(fetch=False)
+                rows += eng.call_rows_text(ctg, qual=p.qual_rows, show_ref=show_ref)[0]
+    elif todo.value:
+        rows = eng.call_rows_text(ctg, qual=p.qual_rows, show_ref=show_ref)[0]
+    return ContigResult(ContigResult.ROWS, rows)
+
+
+class _Pipeline(object):
+    """Fetch threads -> look-ahead slots -> context threads -> decode workers -> the ordered write.  Everything the threads share is made
+    here, before any of them starts."""
+
+    def __init__(self, p):
+        import queue
+        self.p, args = p, p.args
+        self.n_ctx = n_ctx = max(1, args.contexts)
+        self.engines = _Engines(p, n_ctx)
+        # contigs fetched (or being fetched) but not yet through their context: every context busy + every fetch thread running ahead.
+        # (n_ctx + 2 starved the contexts: a fetch takes ~100 ms, a context needs a new contig every ~35 ms)
+        self.slots = threading.BoundedSemaphore(n_ctx + max(2, args.fetch_threads))
+        self.stats, self.lock = dict(fetch=0.0, dev=0.0, sites=0), threading.Lock()
+        # candidates per kb of contig: ~3 on the synthetic GRCh38-sized samples, so a contig past ~50 Mb fills a whole network slice
+        self.reserve_sites = min(262144, int(max(p.fai[c] for c in p.contigs) * 0.005)) if p.contigs else 0
+        self.ctx_queue = queue.Queue()                                       # (contig, fetch future, result future) in calling order; None ends a worker
+        self.ctx_threads = [threading.Thread(target=self.context_worker, args=(k,), name="c3r-ctx%d" % k, daemon=True) for k in range(n_ctx)]
+        # snapshots -> rows (-> merged records), beside the contexts.  A large contig's merge is 0.2-0.7 s on one thread when every
+        # candidate is a record: with n_ctx + 1 workers the snapshots queued up behind three merges (full-length GRCh38 timeline)
+        self.n_dec = int(os.environ.get("C3R_DECODE_WORKERS", "0")) or max(2, min(8, (p.n_thr if p.world > 1 else (os.cpu_count() or 8)) // 4))
+        self.decode_pool = ThreadPoolExecutor(self.n_dec)
+        self.snap_slots = threading.Semaphore(self.n_dec + 2)                # snapshots taken but not decoded yet
+        self.eng_decodes = [[] for _ in range(n_ctx)]                        # decode futures per context (its worker waits for them before it closes the engine)
+        self.stop = threading.Event()
+        self.tasks = [None] * len(p.contigs)                                 # per contig: the Future of its ContigResult, once submitted
+        self.submitted = [threading.Event() for _ in p.contigs]
+        self.feeder_err = []
+        self.part_counts = {}                                                # several ranks: {index in all_contigs: (read, kept, tagged)}
+        self.t_merge, self.called = 0.0, []
+
+    def merge_contig(self, ctg, rows):
+        p = self.p
+        if p.world == 1:
+            p.merger.add_contig(ctg, rows)
+        else:                                 # this contig's records on their own; rank 0 concatenates in calling order
+            k = p.all_contigs.index(ctg)
+            m = sort_vcf.SampleMerger(os.path.join(p.parts_dir, "%05d.vcf" % k), "", p.qual_merge, p.args.print_ref_calls, p.table,
+                                      os.path.join(p.parts_dir, "%05d_nt.vcf" % k), edits=p.edits)
+            m.add_contig(ctg, rows)
+            # (close: an empty part — nothing was written to it — is made anew as the empty file it was, and the warning about it is rank 0's to
+            # give for the whole output, not a part's)
+            self.part_counts[k] = m.close(log=lambda _m: None)
+
+    def context_task(self, k, eng, ctg, fut):
+        """One contig on context k, whose thread took it from the queue (contigs are taken in calling order by whichever context
+        is free): host preparation + uploads, tensor build, network, snapshot.  Contexts work side by side — while one waits for
+        its kernels another queues its uploads and scans.  -> ContigResult NO_READS, ROWS or DECODING."""
+        p = self.p
+        try:
+            rs, ref, dt, phase = fut.result()
             if not len(rs.reads):
-                return None
+                return ContigResult(ContigResult.NO_READS)
             # (A context sizes its device buffers on its first contig.  Round 2 made first uses take turns, each on a quiet GPU,
             # because a multi-GB hipMalloc under another context's kernels took 0.3-0.5 s; with the network's buffers reserved
             # ahead (c3r_reserve) what is left is cheaper than the wait: 1.38-1.47 s against 1.58-1.60 s on 22 half-length contigs.)
             t0 = time()
-            todo = device_stage(eng, ctg, rs, ref, getattr(rs, "phase_sites", None))
+            todo = _device_stage(p, eng, ctg, rs, ref, phase)
             t1 = time()
-            mark(ctg, "device", t0)
-            with lock:
-                stats["fetch"] += dt
-                stats["dev"] += t1 - t0
-                stats["sites"] += todo if isinstance(todo, int) else 0
-            detach = isinstance(todo, int) and todo and hasattr(eng, "rows_begin") and getattr(args, "debug_dump", None) is None
-            if detach:
+            p.mark(ctg, "device", t0)
+            with self.lock:
+                self.stats["fetch"] += dt
+                self.stats["dev"] += t1 - t0
+                self.stats["sites"] += todo.value if todo.kind == ContigResult.RESIDENT else 0
+            if todo.kind == ContigResult.RESIDENT and todo.value and hasattr(eng, "rows_begin"):
                 # the decode inputs leave the context as a host snapshot (c3r_rows_begin): this thread goes on to the next contig
                 # while a decode worker turns the snapshot into rows and — single process — merges them (c3r_vcf_merge)
                 # (snapshots hold ~0.3 GB of staging and their contig's reference: the contexts may not run further ahead of the decode
                 # pool than it has workers + 2)
-                snap_slots.acquire()
+                self.snap_slots.acquire()
                 try:
                     # (without --print_ref_calls the sites the decoder's early RefCall exit would drop anyway stay on the device; the decoder
                     # reads inserted bases from the fetched arrays in place — the snapshot keeps them alive)
-                    snap = eng.rows_begin(drop_ref_calls=not args.print_ref_calls)
+                    snap = eng.rows_begin(drop_ref_calls=not p.args.print_ref_calls)
                 except BaseException:
-                    snap_slots.release()
+                    self.snap_slots.release()
                     raise
-                mark(ctg, "snapshot", t1)
-                fut_d = decode_pool.submit(decode_task, snap, ctg)     # (the look-ahead slot is free: the fetched arrays are done with)
-                eng_decodes[engines.index(eng)].append(fut_d)
-                return fut_d
-            rows = decode_stage(eng, ctg, todo)
-            mark(ctg, "decode", t1)
-            return rows
+                p.mark(ctg, "snapshot", t1)
+                fut_d = self.decode_pool.submit(self.decode_task, snap, ctg)     # (the look-ahead slot is free: the fetched arrays are done with)
+                self.eng_decodes[k].append(fut_d)
+                return ContigResult(ContigResult.DECODING, fut_d)
+            res = _decode_stage(p, eng, ctg, todo)
+            p.mark(ctg, "decode", t1)
+            return res
         finally:
-            slots.release()
+            self.slots.release()
 
-    def decode_task(snap, ctg):
+    def decode_task(self, snap, ctg):
+        """On a decode worker: a snapshot -> rows -> merged records (one process) or this rank's part files -> ContigResult MERGED."""
+        p = self.p
         try:
             t0 = time()
             # (rows stay a uint8 array from here to the compressed piece: no 100-MB bytes objects built under the GIL)
-            rows = snap.decode(ctg, qual=qual_rows, show_ref=args.print_ref_calls, as_array=True)[0]
-            mark(ctg, "decode", t0)
+            rows = snap.decode(ctg, qual=p.qual_rows, show_ref=p.args.print_ref_calls, as_array=True)[0]
+            p.mark(ctg, "decode", t0)
             t1 = time()
-            if world == 1:
-                res = ("merged", merger.merge_only(ctg, rows))
+            if p.world == 1:
+                res = ContigResult(ContigResult.MERGED, p.merger.merge_only(ctg, rows))
             else:
-                merge_contig(ctg, rows)                    # this rank's part files of the contig, written here on the worker
-                res = ("merged", None)
-            mark(ctg, "merge", t1)
+                self.merge_contig(ctg, rows)               # this rank's part files of the contig, written here on the worker
+                res = ContigResult(ContigResult.MERGED)
+            p.mark(ctg, "merge", t1)
             return res
         finally:
-            snap_slots.release()
+            self.snap_slots.release()
 
-    def context_worker(k):
+    def context_worker(self, k):
         """Thread of context k: contigs from the shared queue until the end marker, then — once the decodes that still read this
         context's snapshots are through — the context is released: device and page-locked memory go back while the last contigs
         are still being decoded and written."""
+        p = self.p
         try:
-            eng = engine_of(k)
+            eng = self.engines.get(k)
         except BaseException as e:           # the bring-up failed: every contig this worker takes fails with that
             while True:
-                item = ctx_queue.get()
+                item = self.ctx_queue.get()
                 if item is None:
                     return
                 if item[2].set_running_or_notify_cancel():
                     item[2].set_exception(e)
-        if reserve_sites and hasattr(eng, "reserve"):
+        if self.reserve_sites and hasattr(eng, "reserve"):
             # the network's buffers (8.9 GB for a full slice: 0.25-0.4 s of a first hipMalloc) while the first fetch is under way
             t0 = time()
             try:
-                eng.reserve(reserve_sites)
+                eng.reserve(self.reserve_sites)
             except Exception:
                 pass                      # (the first infer() sizes them, and reports whatever is wrong)
-            mark("ctx%d" % k, "reserve", t0)
+            p.mark("ctx%d" % k, "reserve", t0)
         while True:
-            item = ctx_queue.get()
+            item = self.ctx_queue.get()
             if item is None:
                 break
             ctg, fut, out = item
             if not out.set_running_or_notify_cancel():          # (cancelled by the failure path, which released its slot)
                 continue
             try:
-                out.set_result(context_task(eng, ctg, fut))
+                out.set_result(self.context_task(k, eng, ctg, fut))
             except BaseException as e:
                 out.set_exception(e)
         t0 = time()
-        for f in list(eng_decodes[k]):
+        for f in list(self.eng_decodes[k]):
             try:
                 f.result()
             except BaseException:
                 pass                      # (reported by the main loop, which holds the same future)
-        if not stop.is_set():
+        if not self.stop.is_set():
             eng.close()
-            mark("ctx%d" % k, "close", t0)
+            p.mark("ctx%d" % k, "close", t0)
 
-    work_err = None
-    t_merge = 0.0
-    results = []
-    n_sites = t_fetch = t_dev = 0
-    called = []
-    import queue
-    from concurrent.futures import Future
-    # candidates per kb of contig: ~3 on the synthetic GRCh38-sized samples, so a contig past ~50 Mb fills a whole network slice
-    reserve_sites = min(262144, int(max(fai[c] for c in contigs) * 0.005)) if contigs else 0
-    ctx_queue = queue.Queue()                                            # (contig, fetch future, result future) in calling order; None ends a worker
-    ctx_threads = [threading.Thread(target=context_worker, args=(k,), name="c3r-ctx%d" % k, daemon=True) for k in range(n_ctx)]
-    # snapshots -> rows (-> merged records), beside the contexts.  A large contig's merge is 0.2-0.7 s on one thread when every
-    # candidate is a record: with n_ctx + 1 workers the snapshots queued up behind three merges (full-length GRCh38 timeline)
-    n_dec = int(os.environ.get("C3R_DECODE_WORKERS", "0")) or max(2, min(8, (n_thr if world > 1 else (os.cpu_count() or 8)) // 4))
-    decode_pool = ThreadPoolExecutor(n_dec)
-    snap_slots = threading.Semaphore(n_dec + 2)                                # snapshots taken but not decoded yet
-    eng_decodes = [[] for _ in range(n_ctx)]                                  # decode futures per context (its finish task waits for them)
-    stop = threading.Event()
-
-    def stop_workers():
+    def stop_workers(self):
         """Failure path: nothing may still be inside a c3r_* call (or queued to make one) when the engines are destroyed.  Queued
         contigs are cancelled, the running ones finish, and the feeder — possibly parked on a look-ahead slot that a cancelled task
-        will never release — is told to stop and woken."""
-        stop.set()
+        will never release — is told to stop and woken.  Idempotent."""
+        import queue
+        self.stop.set()
         while True:                       # contigs no context has taken yet are cancelled; the running ones finish
             try:
-                item = ctx_queue.get_nowait()
+                item = self.ctx_queue.get_nowait()
             except queue.Empty:
                 break
             if item is not None:
                 item[2].cancel()
                 try:
-                    slots.release()
+                    self.slots.release()
                 except ValueError:
                     pass
-        for _ in range(n_dec + n_ctx + 4):   # (a context parked on a snapshot slot whose decode will be cancelled below)
-            snap_slots.release()
-        for _t in ctx_threads:
-            ctx_queue.put(None)
-        for t_ in ctx_threads:
+        for _ in range(self.n_dec + self.n_ctx + 4):   # (a context parked on a snapshot slot whose decode will be cancelled below)
+            self.snap_slots.release()
+        for _t in self.ctx_threads:
+            self.ctx_queue.put(None)
+        for t_ in self.ctx_threads:
             if t_.is_alive():
                 t_.join()
-        decode_pool.shutdown(wait=True, cancel_futures=True)
-        for _ in range(len(contigs) + n_ctx + args.fetch_threads + 2):
+        self.decode_pool.shutdown(wait=True, cancel_futures=True)
+        for _ in range(len(self.p.contigs) + self.n_ctx + self.p.args.fetch_threads + 2):
             try:
-                slots.release()
+                self.slots.release()
             except ValueError:           # (bounded semaphore: every slot is free again)
                 break
 
-    try:
-        with ThreadPoolExecutor(max(1, args.fetch_threads)) as fetch_pool:
-            # A feeder takes the look-ahead slot BEFORE it submits a contig's fetch, strictly in calling order.  (Taken inside the
-            # fetch workers, a later contig could grab the last slot while the one its context needs next was still waiting for
-            # one — every context consumes its contigs in order, so nothing would ever have released a slot again.)
-            tasks = [None] * len(contigs)
-            submitted = [threading.Event() for _ in contigs]
-            feeder_err = []
+    def feeder(self, fetch_pool):
+        """Takes the look-ahead slot BEFORE it submits a contig's fetch, strictly in calling order.  (Taken inside the fetch workers, a
+        later contig could grab the last slot while the one its context needs next was still waiting for one — every context consumes
+        its contigs in order, so nothing would ever have released a slot again.)"""
+        from concurrent.futures import Future
+        try:
+            for i, c in enumerate(self.p.contigs):
+                self.slots.acquire()
+                if self.stop.is_set():
+                    break
+                fut = _FetchJoin(self.p, fetch_pool, c).future
+                self.tasks[i] = Future()
+                self.ctx_queue.put((c, fut, self.tasks[i]))
+                self.submitted[i].set()
+            for _k in range(self.n_ctx):
+                self.ctx_queue.put(None)
+        except BaseException as e:          # (e.g. the pools were shut down by a failure below)
+            self.feeder_err.append(e)
+        finally:
+            for ev in self.submitted:
+                ev.set()
 
-            def feeder():
-                try:
-                    for i, c in enumerate(contigs):
-                        slots.acquire()
-                        if stop.is_set():
-                            break
-                        fut = submit_fetch(fetch_pool, c)
-                        tasks[i] = Future()
-                        ctx_queue.put((c, fut, tasks[i]))
-                        submitted[i].set()
-                    for _k in range(n_ctx):
-                        ctx_queue.put(None)
-                except BaseException as e:          # (e.g. the pools were shut down by a failure below)
-                    feeder_err.append(e)
-                finally:
-                    for ev in submitted:
-                        ev.set()
+    def close_fetcher(self, feed, fetch_pool):
+        """The BAM handles (the mapped file, the record buffers of the largest contig each thread fetched) go as soon as
+        the last fetch is through, beside the contexts' last contigs."""
+        feed.join()
+        fetch_pool.shutdown(wait=True)          # (every fetch has been submitted; the with-block's own shutdown is then a no-op)
+        t0 = time()
+        self.p.fetcher.close()
+        self.p.mark("all", "bam_close", t0)
 
-            feed = threading.Thread(target=feeder, name="c3r-feeder", daemon=True)
+    def collect(self, i, ctg):
+        """The main thread's step per contig, in calling order: its result, merged (if a worker has not done that) and written."""
+        p = self.p
+        self.submitted[i].wait()
+        if self.tasks[i] is None:
+            raise RuntimeError("contig %s was never submitted: %r" % (ctg, self.feeder_err[:1]))
+        res = self.tasks[i].result()
+        self.tasks[i] = None
+        if res.kind == ContigResult.NO_READS:
+            p.log("[WARNING] Contig name %s provided but no mapped reads found in BAM, skip!" % ctg)
+            return
+        if res.kind == ContigResult.DECODING:
+            res = res.value.result()
+        t0 = time()
+        if res.kind == ContigResult.MERGED:
+            if res.value is not None:
+                p.merger.write_merged(res.value)               # merged on the worker: only the ordered write is left
+        else:
+            self.merge_contig(ctg, res.value)
+        self.t_merge += time() - t0
+        p.mark(ctg, "write" if res.kind == ContigResult.MERGED else "merge", t0)
+        self.called.append(ctg)
+
+    def run(self):
+        """All contigs of this rank through the pipeline.  On any failure the workers are stopped first (stop_workers) and the error
+        goes on to the caller."""
+        p = self.p
+        with ThreadPoolExecutor(max(1, p.args.fetch_threads)) as fetch_pool:
+            feed = threading.Thread(target=self.feeder, args=(fetch_pool,), name="c3r-feeder", daemon=True)
             feed.start()
-
-            def close_fetcher():
-                """The BAM handles (the mapped file, the record buffers of the largest contig each thread fetched) go as soon as
-                the last fetch is through, beside the contexts' last contigs."""
-                feed.join()
-                fetch_pool.shutdown(wait=True)          # (every fetch has been submitted; the with-block's own shutdown is then a no-op)
-                t0_ = time()
-                fetcher.close()
-                mark("all", "bam_close", t0_)
-            closer = threading.Thread(target=close_fetcher, name="c3r-closer", daemon=True)
+            closer = threading.Thread(target=self.close_fetcher, args=(feed, fetch_pool), name="c3r-closer", daemon=True)
             closer.start()
             try:
                 t0 = time()
-                make_engines()                                             # (the first fetches are running)
-                mark("all", "engines", t0)
-                for t_ in ctx_threads:
+                self.engines.start()                                       # (the first fetches are running)
+                p.mark("all", "engines", t0)
+                for t_ in self.ctx_threads:
                     t_.start()
-                for i, ctg in enumerate(contigs):                          # merge in calling order as the contigs come out
-                    submitted[i].wait()
-                    if tasks[i] is None:
-                        raise RuntimeError("contig %s was never submitted: %r" % (ctg, feeder_err[:1]))
-                    rows = tasks[i].result()
-                    tasks[i] = None
-                    if rows is None:
-                        log("[WARNING] Contig name %s provided but no mapped reads found in BAM, skip!" % ctg)
-                        continue
-                    if hasattr(rows, "result"):                        # decode (and merge) detached to a worker
-                        rows = rows.result()
-                    t0 = time()
-                    if isinstance(rows, tuple) and rows[0] == "merged":
-                        if rows[1] is not None:
-                            merger.write_merged(rows[1])               # merged on the worker: only the ordered write is left
-                    else:
-                        merge_contig(ctg, rows)
-                    t_merge += time() - t0
-                    mark(ctg, "write" if isinstance(rows, tuple) else "merge", t0)
-                    results.append((ctg, None))
+                for i, ctg in enumerate(p.contigs):                        # merge in calling order as the contigs come out
+                    self.collect(i, ctg)
             except BaseException:
-                stop_workers()           # before the fetch pool's own shutdown waits for fetches nobody will consume
+                self.stop_workers()      # before the fetch pool's own shutdown waits for fetches nobody will consume
                 raise
         t0 = time()
-        for t_ in ctx_threads:
+        for t_ in self.ctx_threads:
             t_.join()
-        decode_pool.shutdown()
-        n_sites, t_fetch, t_dev = stats["sites"], stats["fetch"], stats["dev"]
+        self.decode_pool.shutdown()
         closer.join()
-        mark("all", "shutdown", t0)
-        called = [c for c, _f in results]
+        p.mark("all", "shutdown", t0)
+
+
+# ---- stage 4: rank assembly and finalisation
+def _load_part(merger, fns):
+    """One contig's merged records as the ranks left them -> what SampleMerger.append_part takes: with compressed output a piece
+    compressed and indexed here, on a pool thread (the ordered step is then a file append), else the text."""
+    out = []
+    for fn_, want in ((fns[0], True), (fns[1], merger.out_nt_fn is not None)):
+        if not want or not os.path.exists(fn_):
+            out.append(None)
+        elif merger.stream_gz:
+            from . import bamio
+            data = np.fromfile(fn_, dtype=np.uint8)
+            out.append(bamio.VcfPiece(data) if data.size else None)
+        else:
+            out.append(open(fn_).read())
+    return out
+
+
+def _assemble(p):
+    """Rank 0 under several ranks: the parts of all ranks, in calling order, into the output -> (contigs called, candidate sites)."""
+    import json
+    called_set, n_sites, counts = set(), 0, {}
+    for r in range(p.world):
+        j = json.load(open(os.path.join(p.parts_dir, "rank%d.json" % r)))
+        called_set.update(j["called"])
+        n_sites += j["n_sites"]
+        counts.update((int(k), tuple(v)) for k, v in j["counts"].items())
+    todo = []
+    for k, c in enumerate(p.all_contigs):
+        fn = os.path.join(p.parts_dir, "%05d.vcf" % k)
+        if c in called_set and os.path.exists(fn) and os.path.getsize(fn):
+            todo.append((k, (fn, os.path.join(p.parts_dir, "%05d_nt.vcf" % k))))
+    with ThreadPoolExecutor(max(1, min(8, p.n_thr // 4 or 1))) as part_pool:
+        for (k, _fns), (main_part, nt_part) in zip(todo, part_pool.map(lambda job: _load_part(p.merger, job[1]), todo)):
+            p.merger.append_part(main_part, nt_part, counts.pop(k, (0, 0, 0)))
+    for c in counts.values():                                          # (contigs that left no record still count as read)
+        p.merger.append_part(None, None, c)
+    return [c for c in p.all_contigs if c in called_set], n_sites
+
+
+def _finish(p, called, n_sites, t_setup, t_fetch, t_dev, t_merge):
+    """The output closed (and compressed, unless it was streamed), tmp/CONTIGS and tmp/CHUNK_LIST, the summary lines."""
+    args, log = p.args, p.log
+    t0 = time()
+    n_read, n_kept, n_tag = p.merger.close(log)
+    p.mark("all", "close_out", t0)
+    # tmp/CONTIGS and tmp/CHUNK_LIST as run_clair3_rna leaves them (:436-449): contigs without reads are dropped by its
+    # `samtools idxstats` check (:184-210) before they are written; here that is known once the contig has been fetched
+    with open(os.path.join(p.out_dir, "tmp", "CONTIGS"), "w") as f:
+        f.write("\n".join(called))
+    with open(os.path.join(p.out_dir, "tmp", "CHUNK_LIST"), "w") as f:
+        for c in called:
+            for k in range(1, p.chunk_nums[c] + 1):
+                f.write("%s %d %d\n" % (c, k, p.chunk_nums[c]))
+    t0 = time()
+    if not args.no_compress and not getattr(p.merger, "streamed", False):      # (streamed: <out>.vcf.gz + .tbi are complete already)
+        sort_vcf.compress_vcf(p.out_fn)
+        if p.table is not None and n_kept:
+            sort_vcf.compress_vcf(p.out_nt_fn)
+    if p.table is not None:
+        log("[INFO] Dataset size:%d, total variants tagged by REDIportal dataset: %d" % (len(p.table), n_tag))
+    log("[INFO] %d contigs, %d candidate sites, %d records written to %s%s" % (len(called), n_sites, n_kept, p.out_fn, "" if args.no_compress else ".gz"))
+    t_gz = time() - t0
+    log("[INFO] set-up %.2f s, fetch %.2f s (overlapped), device stage %.2f s, merge %.2f s, bgzip+tabix %.2f s, total %.2f s"
+        % (t_setup, t_fetch, t_dev, t_merge, t_gz, time() - p.t_all))
+
+
+def _run_pass(args, log=None):
+    """One pass over the sample: set-up (_set_up), the contexts' bring-up and the per-contig pipeline (_Pipeline), then — on rank 0 —
+    assembly and finalisation (_assemble, _finish).  With several ranks every rank reaches each of the three rendezvous, whatever failed."""
+    log = log or (lambda m: print(m, file=sys.stderr))
+    t_all = time()
+    p = _set_up(args, log, t_all)
+    if p is None:
+        return 0
+    t_setup = time() - t_all
+    pipe = _Pipeline(p)
+    work_err = None
+    try:
+        pipe.run()
     except Exception as e:               # with several ranks: reach the rendezvous first, then every rank fails
         work_err = e
-        stop_workers()                   # (idempotent) no thread is inside libc3r any more
-        if merger is not None:
-            merger.discard()             # no truncated output.vcf.gz (without EOF block) beside a stale .tbi
-        if world == 1:
-            for t_ in engine_threads:
-                t_.join()
-            for e_ in engines:
-                if e_ is not None:
-                    e_.close()
+        pipe.stop_workers()              # (idempotent) no thread is inside libc3r any more
+        if p.merger is not None:
+            p.merger.discard()           # no truncated output.vcf.gz (without EOF block) beside a stale .tbi
+        if p.world == 1:
+            pipe.engines.close()
             raise
-    for t_ in engine_threads:
-        t_.join()
-    for e in engines:
-        if e is not None:
-            e.close()
-    if world > 1:
+    pipe.engines.close()
+    called, n_sites = pipe.called, pipe.stats["sites"]
+    if p.world > 1:
         import json
-        with open(os.path.join(parts_dir, "rank%d.json" % rank), "w") as f:
-            json.dump(dict(counts={str(k): v for k, v in part_counts.items()}, called=called, n_sites=n_sites), f)
-        _all_ranks_ok(dist, world, work_err, "calling its contigs")
-        if rank != 0:
-            _all_ranks_ok(dist, world, None, "assembling the output")  # leave only when rank 0 has written the result
+        with open(os.path.join(p.parts_dir, "rank%d.json" % p.rank), "w") as f:
+            json.dump(dict(counts={str(k): v for k, v in pipe.part_counts.items()}, called=called, n_sites=n_sites), f)
+        _all_ranks_ok(p.dist, p.world, work_err, "calling its contigs")
+        if p.rank != 0:
+            _all_ranks_ok(p.dist, p.world, None, "assembling the output")  # leave only when rank 0 has written the result
             return 0
     fin_err = None
     try:
-        if world > 1:
-            called_set, n_sites = set(), 0
-            for r in range(world):
-                j = json.load(open(os.path.join(parts_dir, "rank%d.json" % r)))
-                called_set.update(j["called"])
-                n_sites += j["n_sites"]
-                for k, (a, b, c) in j["counts"].items():
-                    merger.n_read += a; merger.n_kept += b; merger.n_tagged += c
-            called = [c for c in all_contigs if c in called_set]
-            todo = []
-            for k, c in enumerate(all_contigs):
-                fn = os.path.join(parts_dir, "%05d.vcf" % k)
-                if c in called_set and os.path.exists(fn) and os.path.getsize(fn):
-                    todo.append((fn, os.path.join(parts_dir, "%05d_nt.vcf" % k)))
-
-            def load_part(fns):
-                """One contig's merged records as the ranks left them -> what the writer takes: with compressed output a piece
-                compressed and indexed here, on a pool thread (the ordered step is then a file append), else the text."""
-                out = []
-                for fn_, want in ((fns[0], True), (fns[1], merger.out_nt is not None)):
-                    if not want or not os.path.exists(fn_):
-                        out.append(None)
-                    elif merger.stream_gz:
-                        from . import bamio as _b
-                        data = np.fromfile(fn_, dtype=np.uint8)
-                        out.append(_b.VcfPiece(data) if data.size else None)
-                    else:
-                        out.append(open(fn_).read())
-                return out
-            with ThreadPoolExecutor(max(1, min(8, n_thr // 4 or 1))) as part_pool:
-                for main_part, nt_part in part_pool.map(load_part, todo):
-                    merger._header()
-                    for out_, m_ in ((merger.out, main_part), (merger.out_nt, nt_part)):
-                        if out_ is None or m_ is None:
-                            continue
-                        if hasattr(m_, "free"):
-                            out_.append(m_)
-                        else:
-                            out_.write(m_)
-        t0 = time()
-        n_read, n_kept, n_tag = merger.close(log)
-        mark("all", "close_out", t0)
-        # tmp/CONTIGS and tmp/CHUNK_LIST as run_clair3_rna leaves them (:436-449): contigs without reads are dropped by its
-        # `samtools idxstats` check (:184-210) before they are written; here that is known once the contig has been fetched
-        with open(os.path.join(out_dir, "tmp", "CONTIGS"), "w") as f:
-            f.write("\n".join(called))
-        with open(os.path.join(out_dir, "tmp", "CHUNK_LIST"), "w") as f:
-            for c in called:
-                for k in range(1, chunk_nums[c] + 1):
-                    f.write("%s %d %d\n" % (c, k, chunk_nums[c]))
-        t0 = time()
-        if not args.no_compress and not getattr(merger, "streamed", False):      # (streamed: <out>.vcf.gz + .tbi are complete already)
-            sort_vcf.compress_vcf(out_fn)
-            if table is not None and n_kept:
-                sort_vcf.compress_vcf(out_nt_fn)
-        if table is not None:
-            log("[INFO] Dataset size:%d, total variants tagged by REDIportal dataset: %d" % (len(table), n_tag))
-        log("[INFO] %d contigs, %d candidate sites, %d records written to %s%s" % (len(called), n_sites, n_kept, out_fn, "" if args.no_compress else ".gz"))
-        t_gz = time() - t0
-        log("[INFO] set-up %.2f s, fetch %.2f s (overlapped), device stage %.2f s, merge %.2f s, bgzip+tabix %.2f s, total %.2f s"
-            % (t_setup, t_fetch, t_dev, t_merge, t_gz, time() - t_all))
+        if p.world > 1:
+            called, n_sites = _assemble(p)
+        _finish(p, called, n_sites, t_setup, pipe.stats["fetch"], pipe.stats["dev"], pipe.t_merge)
     except Exception as e:               # rank 0 still meets the others at the last rendezvous, and all of them fail
         fin_err = e
-        if merger is not None:
-            merger.discard()
-        if world == 1:
+        if p.merger is not None:
+            p.merger.discard()
+        if p.world == 1:
             raise
-    if world > 1:
-        _all_ranks_ok(dist, world, fin_err, "assembling the output")
+    if p.world > 1:
+        _all_ranks_ok(p.dist, p.world, fin_err, "assembling the output")
     return 0
 
 

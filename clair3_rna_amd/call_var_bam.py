@@ -201,28 +201,26 @@ def Run(args, engine=None):
     if sites is not None:
         eng.set_sites(sites)
     # the phase sites of the WHOLE contig, before the reads: a read's tag must not depend on the chunk it is loaded for
-    phase_sites = None
+    phase = phase_source = None
     if phased_vcf_fn:
         from . import phasedvcf
-        if haplotag_indels:
-            phase_sites, phase_h1, phase_pool, phase_pool_bases, phase_skipped = phasedvcf.contig_alleles(phased_vcf_fn, ctg)
-            print("[INFO] %s: %d phased sites in the table of --haplotag_indels, %d with an insertion or deletion, %d with two ALTs"
-                  % (ctg, len(phase_sites), phase_skipped.kept["indel"], phase_skipped.kept["two_alt"]), file=sys.stderr)
-        else:
-            phase_sites = phasedvcf.contig_sites(phased_vcf_fn, ctg)
+        phase_source = phasedvcf.PhaseSource(phased_vcf_fn, haplotag_indels, only=ctg)
+        phase = phase_source.table(ctg)
+        note = phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
+        if note:
+            print(note, file=sys.stderr)
         if engine is not None:
             from .reads import ReadSet
             engine.load_reads(ReadSet.from_records([]))      # (a caller's engine may still hold a chunk's reads: a new table would tag them again first)
-    if haplotag_indels:
-        eng.set_phase_alleles(phase_sites, phase_h1, phase_pool, phase_pool_bases)
+        phase_source.apply(eng, phase)
     else:
-        eng.set_phase_sites(phase_sites)
+        eng.set_phase_sites(None)                            # (a caller's engine may hold the table of an earlier chunk)
     eng.set_params(channels=channels, min_mq=args.minMQ, min_coverage=args.minCoverage, snp_min_af=args.snp_min_af,
                    indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
                    splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(sites is not None),
                    mpileup_compat=compat)
     rs = io.load_reads(args.bam_fn, ctg, extend_start - 1, extend_end)      # mpileup -r ctg:extend_start-extend_end
-    if phased_vcf_fn and not len(phase_sites):
+    if phase is not None and not len(phase):
         rs.reads["hp"] = 0                  # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
     eng.load_reads(rs)
     eng.set_reference(ref_start, ref_seq)

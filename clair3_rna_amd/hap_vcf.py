@@ -142,33 +142,22 @@ def Run(args, log=None):
     for need in (args.bam_fn, args.vcf_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
-    if not os.path.exists(args.phased_vcf_fn):
-        sys.exit("[ERROR] file %s not found" % args.phased_vcf_fn)
+    source = phasedvcf.PhaseSource(args.phased_vcf_fn, getattr(args, "haplotag_indels", False))
     if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
         sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
     indels = bool(getattr(args, "indels", False))
     per = phasing.allele_candidates_from_vcf(args.vcf_fn, None) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
-    tag_indels = bool(getattr(args, "haplotag_indels", False))
-    if os.path.isdir(args.phased_vcf_fn):
-        tables = None
-    else:
-        tables = phasedvcf.read_all_phase_alleles(args.phased_vcf_fn) if tag_indels else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
     eng = None
     assigned, strings, lines = {}, {}, ["\t".join(ALLELE_COLUMNS if indels else COLUMNS) + "\n"]
     try:
         for ctg in contigs:
             cands, skipped = (per[ctg][0], per[ctg][-1]) if ctg in per else (None, None)
-            if tag_indels:                                   # (the table's pos / ps serve nearest_sets and the log as the SNV table's do)
-                full = phasedvcf.contig_alleles(args.phased_vcf_fn, ctg) if tables is None else tables.get(ctg) or phasedvcf.empty_alleles()
-                table = full[0]
-                log("[INFO] %s: --haplotag_indels: %d phased sites in the table, %d with an insertion or deletion, %d with two ALTs"
-                    % (ctg, len(table), full[4].kept["indel"], full[4].kept["two_alt"]))
-            elif tables is None:
-                table = phasedvcf.contig_sites(args.phased_vcf_fn, ctg)
-            else:
-                table = tables[ctg][0] if ctg in tables else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
+            table = source.table(ctg)                         # (its pos / ps serve nearest_sets and the log, whatever its kind)
+            note = source.indel_note(table, "[INFO] %s: --haplotag_indels: %d phased sites in the table, " % (ctg, len(table)))
+            if note:
+                log(note)
             if cands is None or not len(cands) or not len(table):
                 log("[INFO] %s: %d phased sites in the table, %d heterozygous %s candidates: rows copied unchanged"
                     % (ctg, len(table), 0 if cands is None else len(cands), "SNV / indel / two-ALT" if indels else "SNV"))
@@ -176,12 +165,9 @@ def Run(args, log=None):
             if eng is None:
                 eng = capi.Engine(gpu_id)
                 eng.set_params(min_mq=args.min_mq)
-            query = nearest_sets(cands, table)
+            query = nearest_sets(cands, table.sites)
             rs = io.load_reads(args.bam_fn, ctg)
-            if tag_indels:
-                eng.set_phase_alleles(*full[:4])
-            else:
-                eng.set_phase_sites(table)
+            source.apply(eng, table)
             eng.load_reads(rs)
             if indels:
                 counts = eng.hap_allele_counts(query, per[ctg][1])
@@ -194,7 +180,7 @@ def Run(args, log=None):
                 lines += counts_lines(ctg, query, out, counts)
             assigned[ctg] = out
             log("[INFO] %s: %d reads, %d phased sites in %d sets, %d candidate sites (%s), %d phased, %d with too few tagged reads, %d without agreement -> %s"
-                % (ctg, len(rs), len(table), len(set(table["ps"].tolist())), st["n_sites"],
+                % (ctg, len(rs), len(table), len(set(table.ps.tolist())), st["n_sites"],
                    ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
                    st["n_phased"], st["n_few_reads"], st["n_disagree"], args.output_fn))
     finally:

@@ -83,16 +83,10 @@ def Run(args, log=None):
     log = log or (lambda m: print(m, file=sys.stderr))
     if not os.path.isfile(args.bam_fn):
         sys.exit("[ERROR] file %s not found" % args.bam_fn)
-    if not os.path.exists(args.phased_vcf_fn):
-        sys.exit("[ERROR] file %s not found" % args.phased_vcf_fn)
+    source = phasedvcf.PhaseSource(args.phased_vcf_fn, getattr(args, "haplotag_indels", False))
     threads = int(getattr(args, "threads", 0) or 0)
     command = getattr(args, "command", None) or " ".join(sys.argv)
     os.makedirs(args.output_dir, exist_ok=True)
-    tag_indels = bool(getattr(args, "haplotag_indels", False))
-    if os.path.isdir(args.phased_vcf_fn):
-        tables = None
-    else:
-        tables = phasedvcf.read_all_phase_alleles(args.phased_vcf_fn) if tag_indels else phasedvcf.read_all_phase_sites(args.phased_vcf_fn)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
     done, eng = {}, None
     with bamio.BamFile(args.bam_fn, threads=threads) as bf:
@@ -103,14 +97,7 @@ def Run(args, log=None):
                 if ctg not in in_bam:
                     log("[INFO] %s: not in the header of %s: no file" % (ctg, args.bam_fn))
                     continue
-                full = None
-                if tag_indels:
-                    full = phasedvcf.contig_alleles(args.phased_vcf_fn, ctg) if tables is None else tables.get(ctg) or phasedvcf.empty_alleles()
-                    table = full[0]
-                elif tables is None:
-                    table = phasedvcf.contig_sites(args.phased_vcf_fn, ctg)
-                else:
-                    table = tables[ctg][0] if ctg in tables else np.zeros(0, dtype=capi.PHASE_SITE_DTYPE)
+                table = source.table(ctg)
                 rs = hp = ps = None
                 if len(table):
                     rs = bf.fetch(ctg)                             # io.load_reads(bam, ctg) on the handle that is open already (--threads)
@@ -118,10 +105,7 @@ def Run(args, log=None):
                     if eng is None:
                         eng = capi.Engine(gpu_id)
                         eng.set_params()
-                    if tag_indels:
-                        eng.set_phase_alleles(*full[:4])
-                    else:
-                        eng.set_phase_sites(table)
+                    source.apply(eng, table)
                     eng.load_reads(rs)
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()
                 elif rs is not None:                               # (no read record: nothing to launch; the contig's other records still go out)
@@ -146,7 +130,7 @@ def Run(args, log=None):
                 done[ctg] = st
                 log("[INFO] %s: %d records, %d HP1, %d HP2, %d untagged, %d unpaired (not read records: copied, never tagged), %d phased sites%s -> %s"
                     % (ctg, st["records"], st["hp1"], st["hp2"], st["records"] - st["tagged"] - st["unpaired"], st["unpaired"], len(table),
-                       (" (--haplotag_indels: %d with an insertion or deletion, %d with two ALTs)" % (full[4].kept["indel"], full[4].kept["two_alt"]) if tag_indels else "")
+                       source.indel_note(table, " (--haplotag_indels: ", ")")
                        + ("" if len(table) else " (nothing phased on this contig: every read untagged)"), out))
         finally:
             if eng is not None:

@@ -152,3 +152,11 @@ def load_weights(chkpnt_fn, channels):
         return tfckpt.weights_from_bundle(chkpnt_fn, channels)
     raise FileNotFoundError("no weights found for --chkpnt_fn %s (expected %s.c3rw.npy or the checkpoint bundle %s.index)"
                             % (chkpnt_fn, chkpnt_fn, chkpnt_fn))
+
+
+def remove_stale(directory, is_stale):
+    """Files of an earlier run in `directory` (which need not exist): every one whose name is_stale() accepts is removed."""
+    if os.path.isdir(directory):
+        for name in os.listdir(directory):
+            if is_stale(name):
+                os.remove(os.path.join(directory, name))

@@ -69,9 +69,7 @@ def Run(args, log=None):
             sites, *rest = per.get(ctg, (None, None))
             skipped = rest[-1]
             if sites is None or not len(sites):
-                stale = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
-                if os.path.isfile(stale):                    # (an earlier run's: the second pass would read it)
-                    os.remove(stale)
+                io.remove_stale(args.output_dir, lambda name: name == "phased_%s.vcf.gz" % ctg)     # (an earlier run's: the second pass would read it)
                 log("[INFO] %s: no %s candidates, nothing written" % (ctg, what))
                 continue
             if eng is None:

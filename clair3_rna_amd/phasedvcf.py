@@ -159,3 +159,60 @@ def contig_alleles(path, contig):
     was phased there."""
     fn = contig_file(path, contig)
     return read_phase_alleles(fn, contig) if fn else empty_alleles()
+
+
+class PhaseTable(object):
+    """One contig's table, of either kind: `sites` (sorted by pos; the fields pos and ps exist in both dtypes), `skipped` ({reason: rows
+    skipped}) and `kept` (dict(indel, two_alt): both 0 in the table of biallelic SNVs).  len() is the number of sites."""
+
+    def __init__(self, sites, skipped, rest=()):
+        self.sites, self.skipped, self._rest = sites, skipped, rest             # _rest: (h1, pool, pool_bases) of an allele table
+        self.kept = getattr(skipped, "kept", dict(indel=0, two_alt=0))
+        self.pos, self.ps = sites["pos"], sites["ps"]
+
+    def __len__(self):
+        return len(self.sites)
+
+
+class PhaseSource(object):
+    """What `--phased_vcf_fn PATH [--haplotag_indels]` means, for every driver: which table a contig gets (`table`), and which engine call
+    takes it (`apply`).  PATH is a directory of phased_<ctg>.vcf.gz, read file by file, or one VCF for all contigs, parsed once by
+    whichever thread asks first (call_sample asks from its fetch threads) — or, with `only`, for that one contig alone (the per-chunk
+    driver never asks for another).  A contig without a file or without a row gets the empty table of the source's kind."""
+
+    def __init__(self, path, tag_indels=False, only=None):
+        import os
+        import sys
+        import threading
+        if not os.path.exists(path):
+            sys.exit("[ERROR] file %s not found" % path)
+        self.path, self.tag_indels, self.only = path, bool(tag_indels), only
+        self.per_contig = os.path.isdir(path) or only is not None
+        self.all, self.lock = None, threading.Lock()
+
+    def table(self, contig):
+        if self.per_contig:
+            fn = contig_file(self.path, contig)
+            hit = (read_phase_alleles if self.tag_indels else read_phase_sites)(fn, contig) if fn else None
+        else:
+            with self.lock:
+                if self.all is None:
+                    self.all = (read_all_phase_alleles if self.tag_indels else read_all_phase_sites)(self.path)
+            hit = self.all.get(contig)
+        if self.tag_indels:
+            sites, h1, pool, pool_bases, skipped = hit or empty_alleles()
+            return PhaseTable(sites, skipped, (h1, pool, pool_bases))
+        return PhaseTable(*(hit or (np.zeros(0, dtype=PHASE_SITE_DTYPE), dict.fromkeys(SKIP_REASONS, 0))))
+
+    def apply(self, engine, table):
+        """Before the contig's reads: they are tagged while they are prepared."""
+        if self.tag_indels:
+            engine.set_phase_alleles(table.sites, *table._rest)
+        else:
+            engine.set_phase_sites(table.sites)
+
+    def indel_note(self, table, head, tail=""):
+        """A driver's words about the table of --haplotag_indels — `head`, the two counts, `tail` — and "" without the flag."""
+        if not self.tag_indels:
+            return ""
+        return "%s%d with an insertion or deletion, %d with two ALTs%s" % (head, table.kept["indel"], table.kept["two_alt"], tail)

@@ -138,19 +138,36 @@ def merge_chunk_vcfs(input_dir, output_fn, contigs, prefix="pileup", suffix=".vc
     return n_read, n_kept, n_tagged
 
 
+class ContigEdits(object):
+    """The REDIportal table as the per-contig entry lists c3r_vcf_merge takes: one pass over the table, made by whichever thread asks first."""
+
+    def __init__(self, rediportal):
+        import threading
+        self.rediportal, self.per, self.lock = rediportal, None, threading.Lock()
+
+    def of(self, contig):
+        if not self.rediportal:
+            return None
+        with self.lock:
+            if self.per is None:
+                self.per = {}
+                for (c, pos), hit in self.rediportal.items():
+                    self.per.setdefault(c, []).append((pos, hit[0], hit[1]))
+        return self.per.get(contig)
+
+
 class SampleMerger(object):
     """In-process form of the same merge for the whole-sample driver (call_sample.py): contigs are added in output order,
     each as the newline-terminated rows its chunks produced (any order, duplicates at chunk seams allowed); the files written
     are byte-identical to merge_chunk_vcfs over the per-chunk files."""
 
     def __init__(self, output_fn, header_text, qual=2, show_ref=False, rediportal=None, output_no_tagging_fn=None, native=True,
-                 stream_gz=False):
+                 stream_gz=False, edits=None):
         """stream_gz: write <output_fn>.gz + .tbi directly, block by block as the contigs arrive (bamio.VcfGzWriter: the bytes
-        compress_vcf would make of the finished file), instead of the plain file that compress_vcf turns into them afterwards."""
+        compress_vcf would make of the finished file), instead of the plain file that compress_vcf turns into them afterwards.
+        edits: the ContigEdits of `rediportal` that several mergers share (call_sample's per-contig mergers); default: this merger's own."""
         self.output_fn, self.header = output_fn, header_text
-        self.native, self._edits = native, None
-        import threading
-        self._edits_lock = threading.Lock()
+        self.native, self._edits = native, edits or ContigEdits(rediportal)
         self.qual, self.show_ref, self.rediportal = qual, show_ref, rediportal
         self.stream_gz = bool(stream_gz) and native is not False
         self.out_nt_fn = output_no_tagging_fn if rediportal is not None else None
@@ -193,14 +210,7 @@ class SampleMerger(object):
         blob = rows.encode() if isinstance(rows, str) else (rows if hasattr(rows, "ctypes") else bytes(rows))     # (uint8 array: by pointer)
         if not len(blob):
             return
-        edits = None
-        if self.rediportal:
-            if self._edits is None:                       # one pass over the table: per-contig entry lists
-                self._edits = {}
-                for (c, pos), hit in self.rediportal.items():
-                    self._edits.setdefault(c, []).append((pos, hit[0], hit[1]))
-            edits = self._edits.get(contig)
-        self.write_merged(bamio.vcf_merge(blob, self.qual, self.show_ref, edits, self.out_nt is not None))
+        self.write_merged(bamio.vcf_merge(blob, self.qual, self.show_ref, self._edits.of(contig), self.out_nt is not None))
 
     def merge_only(self, contig, rows):
         """The per-contig work of add_contig without touching the output (c3r_vcf_merge releases the GIL): callable from worker
@@ -211,15 +221,7 @@ class SampleMerger(object):
         blob = rows.encode() if isinstance(rows, str) else (rows if hasattr(rows, "ctypes") else bytes(rows))     # (uint8 array: by pointer)
         if not len(blob):
             return None
-        edits = None
-        if self.rediportal:
-            with self._edits_lock:
-                if self._edits is None:
-                    self._edits = {}
-                    for (c, pos), hit in self.rediportal.items():
-                        self._edits.setdefault(c, []).append((pos, hit[0], hit[1]))
-            edits = self._edits.get(contig)
-        merged, merged_nt, counts = bamio.vcf_merge(blob, self.qual, self.show_ref, edits, self.out_nt is not None)
+        merged, merged_nt, counts = bamio.vcf_merge(blob, self.qual, self.show_ref, self._edits.of(contig), self.out_nt is not None)
         if self.stream_gz:
             # compressed and indexed here, on the worker (bamio.VcfPiece): write_merged only appends the finished blocks
             merged = bamio.VcfPiece(merged) if merged is not None and len(merged) else None
@@ -227,9 +229,13 @@ class SampleMerger(object):
         return merged, merged_nt, counts
 
     def write_merged(self, res):
-        if res is None:
-            return
-        merged, merged_nt, (n_read, n_kept, n_tag) = res
+        if res is not None:
+            self.append_part(*res)
+
+    def append_part(self, merged, merged_nt, counts):
+        """One contig's merged records — arrays or text, or compressed pieces (bamio.VcfPiece) — behind what is written already, and its
+        (read, kept, tagged) counts: merge_only's result, or a part another rank left (call_sample under several ranks)."""
+        n_read, n_kept, n_tag = counts
         self._header()
         self.n_read += n_read
         self.n_kept += n_kept
@@ -240,7 +246,7 @@ class SampleMerger(object):
             if hasattr(m, "free"):
                 out.append(m)
             elif len(m):
-                out.write(m if self.stream_gz else (m.tobytes() if hasattr(m, "tobytes") else m).decode())
+                out.write(m if self.stream_gz or isinstance(m, str) else (m.tobytes() if hasattr(m, "tobytes") else m).decode())
 
     def _header(self):
         if not self.header_done:

@@ -30,13 +30,41 @@ class FakeEngine(object):
     def set_sites(self, sites): self.sites = list(sites)
     def set_reference(self, start, seq, upper_view=False):
         self.ref = seq if isinstance(seq, bytes) else (seq.encode() if isinstance(seq, str) else bytes(seq))
+        self._phase_log()
         if os.environ.get("C3R_FAKE_FAIL_LEN") == str(len(self.ref)):       # test hook: this contig's device stage fails
             raise RuntimeError("stand-in engine: injected failure on the contig of length %d" % len(self.ref))
 
     def load_reads(self, rs):
+        self._loads = getattr(self, "_loads", []) + [(len(rs.reads), int((rs.reads["hp"] != 0).sum()))]
         self.pos = rs.reads["pos"].astype(np.int64)
         self.cov = np.zeros(len(self.ref) + 2 if hasattr(self, "ref") else 1, dtype=bool)
         self.rs = rs
+
+    # test hook: the phase tables the driver hands over (the stand-in ignores the tags).  $C3R_FAKE_PHASE_LOG receives one JSON line per
+    # contig, written when its reference arrives: (contig length, [(kind, sites, reads the context held when the table was set — those of its
+    # last load_reads, whichever contig's —, the loads between the previous contig and the table)] of the tables set since the previous contig,
+    # [(reads, reads with hp != 0)] of the loads since the last table)
+    def set_phase_sites(self, sites): self._table("sites", sites)
+    def set_phase_alleles(self, sites, h1, pool, pool_bases): self._table("alleles", sites, h1, pool_bases)
+
+    def _table(self, kind, sites, *rest):
+        if kind == "alleles":
+            assert len(rest[0]) == len(sites) and int(rest[1]) >= 0
+        held = len(self.rs.reads) if hasattr(self, "rs") else 0              # (self.rs outlives _phase_log: the previous contig's, unless emptied)
+        self._tables = getattr(self, "_tables", []) + [(kind, -1 if sites is None else len(sites), held, getattr(self, "_loads", []))]
+        self._loads = []
+
+    def _phase_log(self):
+        fn = os.environ.get("C3R_FAKE_PHASE_LOG")
+        if fn:
+            import json
+            line = json.dumps([len(self.ref), getattr(self, "_tables", []), getattr(self, "_loads", [])]) + "\n"
+            fd = os.open(fn, os.O_WRONLY | os.O_APPEND | os.O_CREAT, 0o644)       # (one write per line: several contexts append)
+            try:
+                os.write(fd, line.encode())
+            finally:
+                os.close(fd)
+        self._tables, self._loads = [], []
 
     def _covered(self):
         cov = np.zeros(len(self.ref) + 2, dtype=bool)

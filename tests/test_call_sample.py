@@ -91,8 +91,8 @@ def test_plan_include_all_ctg_name_bed_and_vcf(ref_fa, tmp_path):
         call_sample.split_extend_bed(bad, d, None)
 
 
-def _fake_sample(tmp):
-    """FASTA + BAM (+ .bai) + weights for the stand-in engine runs."""
+def _fake_sample(tmp, hp_contig=None):
+    """FASTA + BAM (+ .bai) + weights for the stand-in engine runs.  hp_contig: that contig's reads carry HP:1 tags."""
     import numpy as np
     from clair3_rna_amd import bam, bamio, synth
     spec = [("chr1", 40000, 3), ("chr2", 26000, 5), ("chr3", 30000, 6), ("chrX", 22000, 7), ("chr9", 9000, 11)]
@@ -100,6 +100,8 @@ def _fake_sample(tmp):
     for name, L, seed in spec:
         ref, rs, _ = synth.small_case(seed=seed, ref_len=L, n_genes=max(3, L // 5000), depth=8)
         contigs.append((name, ref))
+        if name == hp_contig:
+            rs.reads["hp"][:] = 1
         if name != "chr9":
             reads[name] = rs
     fa, bm, wfn = os.path.join(tmp, "ref.fa"), os.path.join(tmp, "in.bam"), os.path.join(tmp, "model")
@@ -110,7 +112,7 @@ def _fake_sample(tmp):
     return fa, bm, wfn
 
 
-def _launch(tmp, out, fa, bm, wfn, extra, world=1, env_extra=None, expect_fail=False, compress=False):
+def _launch(tmp, out, fa, bm, wfn, extra, world=1, env_extra=None, expect_fail=False, compress=False, result="output"):
     import socket
     import subprocess
     import sys
@@ -135,10 +137,10 @@ def _launch(tmp, out, fa, bm, wfn, extra, world=1, env_extra=None, expect_fail=F
         return [p.returncode for p in procs], outs
     assert all(p.returncode == 0 for p in procs), ([p.returncode for p in procs], outs)
     if compress:
-        assert os.path.exists(os.path.join(out, "output.vcf.gz.tbi")) and not os.path.exists(os.path.join(out, "output.vcf"))
-        text = gzip.open(os.path.join(out, "output.vcf.gz"), "rt").read()
+        assert os.path.exists(os.path.join(out, result + ".vcf.gz.tbi")) and not os.path.exists(os.path.join(out, result + ".vcf"))
+        text = gzip.open(os.path.join(out, result + ".vcf.gz"), "rt").read()
     else:
-        text = open(os.path.join(out, "output.vcf")).read()
+        text = open(os.path.join(out, result + ".vcf")).read()
     return [r for r in text.split("\n") if not r.startswith("##cmdline=")]
 
 
@@ -285,3 +287,141 @@ def test_a_failing_fetch_ends_the_run_with_an_error_not_a_hang(tmp_path):
     # beside it)
     left = sorted(f for f in os.listdir(os.path.join(tmp, "bad")) if f.startswith("output"))
     assert left == [], left
+
+
+FLAG_MATRIX = os.path.join(HERE, "golden", "call_sample_flag_matrix.json")
+MATRIX_FLAGS = ["--enable_phasing_model", "--phased_pileup_model_path", "--phased_vcf_fn", "--phasing", "--phase_output", "--phasing_indels",
+                "--haplotag_indels", "--phase_indels", "--haplotagged_bam"]
+
+
+class _PlanReached(Exception):
+    pass
+
+
+def _flag_matrix(tmp, monkeypatch):
+    """-> ({"world=W levels=L": [outcome per bit mask of MATRIX_FLAGS]}, [masks whose refusal left the output directory behind]).
+    An outcome is the SystemExit text with `tmp` replaced, or "validated" when anything else came out (the planning sentinel)."""
+    import shutil
+    import torch.distributed
+    from clair3_rna_amd import capi, shard
+
+    def no_engine(*a, **k):
+        raise RuntimeError("no engine in this test")
+
+    def planned(*a, **k):
+        raise _PlanReached()
+    bam, ref, phased, out = (os.path.join(tmp, n) for n in ("in.bam", "ref.fa", "phased.vcf", "out"))
+    for fn in (bam, ref, phased):
+        open(fn, "w").close()
+    monkeypatch.setattr(capi, "Engine", no_engine)
+    monkeypatch.setattr(call_sample, "plan_chunks", planned)
+    # a rank of a two-rank run HAS a process group and a host share: without them the pass would stop at the rendezvous set-up, before
+    # its own rules, for a reason no run under torch.distributed.run has
+    monkeypatch.setattr(torch.distributed, "is_initialized", lambda: True)
+    monkeypatch.setattr(shard, "host_budget", lambda *a, **k: (8, None))
+    monkeypatch.setenv("C3R_FETCH_INFLATE", os.environ.get("C3R_FETCH_INFLATE", "8"))      # (the host budget sets it with setdefault: restored after the test)
+    for name in ("RANK", "LOCAL_RANK", "C3R_HOST_SLICE"):
+        monkeypatch.delenv(name, raising=False)
+    values = {"--phased_pileup_model_path": [os.path.join(tmp, "model30")], "--phased_vcf_fn": [phased], "--phasing": ["builtin"]}
+    base = ["--bam_fn", bam, "--ref_fn", ref, "--output_dir", out, "--pileup_model_path", os.path.join(tmp, "model"), "--mpileup_compat", "1"]
+    table, left = {}, []
+    for world in (1, 2):
+        monkeypatch.setenv("WORLD_SIZE", str(world))
+        for levels in (None, 2, -1):
+            row = table["world=%d levels=%s" % (world, "absent" if levels is None else levels)] = []
+            for mask in range(1 << len(MATRIX_FLAGS)):
+                argv = list(base) + ([] if levels is None else ["--phase_merge_levels", str(levels)])
+                for k, flag in enumerate(MATRIX_FLAGS):
+                    if mask >> k & 1:
+                        argv += [flag] + values.get(flag, [])
+                try:
+                    call_sample.Run(call_sample.build_parser().parse_args(argv), log=lambda m: None)
+                    row.append("validated")
+                except SystemExit as e:
+                    row.append(str(e.code).replace(tmp, "<tmp>"))
+                    if os.path.exists(out):
+                        left.append((world, levels, mask))
+                except BaseException:
+                    row.append("validated")
+                shutil.rmtree(out, ignore_errors=True)
+    return table, left
+
+
+def test_flag_matrix_equals_the_recorded_table(tmp_path, monkeypatch):
+    """Every combination of the nine phasing flags x --phase_merge_levels absent / 2 / -1 x WORLD_SIZE 1 / 2 (3,072 runs of Run with the
+    planning step replaced by a sentinel): the refusal — its text, character for character — or "validated" equals the table recorded
+    before the flag rules were folded into one function, and no refusal leaves the output directory behind."""
+    rec = json.load(open(FLAG_MATRIX))
+    assert rec["flags"] == MATRIX_FLAGS
+    table, left = _flag_matrix(str(tmp_path), monkeypatch)
+    assert left == []
+    assert sorted(table) == sorted(rec["table"])
+    for key, row in table.items():
+        want = [rec["outcomes"][int(ch, 36)] for ch in rec["table"][key]]
+        assert len(row) == len(want) == 1 << len(MATRIX_FLAGS)
+        diff = [(m, row[m], want[m]) for m in range(len(row)) if row[m] != want[m]]
+        assert not diff, (key, len(diff), diff[:3])
+    assert sum(o == "validated" for o in table["world=1 levels=absent"] + table["world=1 levels=2"] + table["world=1 levels=-1"]) == 39
+
+
+PHASED_ROWS = {          # chr3 has reads and no phased row, chr9 neither; chr1 has the rows only the table of --haplotag_indels keeps
+    "chr1": [(1200, "A", "G", "0|1:1200"), (2500, "C", "T", "1|0:1200"), (2600, "G", "GAC", "0|1:1200"), (2700, "TCA", "T", "1|0:1200"),
+             (3100, "A", "C,G", "1|2:1200"), (9000, "T", "C", "0/1:."), (20500, "G", "A", "1|0:20500")],
+    "chr2": [(700, "C", "A", "0|1:700"), (15000, "G", "T", "0|1:15000")],
+    "chrX": [(21000, "T", "G", "1|0:21000")],
+}
+
+
+def _phased_inputs(tmp):
+    """-> (one phased VCF for all contigs, a directory of phased_<ctg>.vcf.gz) with PHASED_ROWS."""
+    head = "##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE\n"
+    text = {c: "".join("%s\t%d\t.\t%s\t%s\t30\tPASS\t.\tGT:PS\t%s\n" % (c, p, r, a, g) for p, r, a, g in rows) for c, rows in PHASED_ROWS.items()}
+    one, per = os.path.join(tmp, "phased_all.vcf"), os.path.join(tmp, "phased_dir")
+    with open(one, "w") as f:
+        f.write(head + "".join(text.values()))
+    os.makedirs(per)
+    for c, rows in text.items():
+        with gzip.open(os.path.join(per, "phased_%s.vcf.gz" % c), "wt") as f:
+            f.write(head + rows)
+    return one, per
+
+
+def test_phased_orchestration_hands_every_contig_its_table(tmp_path):
+    """--enable_phasing_model --phased_vcf_fn on the stand-in engine, which records the tables it is handed: from a directory, from one
+    VCF, and from that VCF with --haplotag_indels, with the default threads and with three contexts on one fetch thread.  Every contig
+    with reads gets exactly one table — of the kind and size phasedvcf reads for it — set while the context holds no read (after an
+    empty load_reads) and before the contig's own reads; a contig without a phased row gets the empty table and its reads arrive with
+    hp == 0 whatever the BAM says; the VCF is the one of the run without --phased_vcf_fn (the stand-in ignores tags)."""
+    import numpy as np
+    from clair3_rna_amd import phasedvcf
+    tmp = str(tmp_path)
+    fa, bm, wfn = _fake_sample(tmp, hp_contig="chr3")
+    np.save(wfn + "30.c3rw.npy", np.ones(8, dtype=np.float32))
+    one, per = _phased_inputs(tmp)
+    lengths = {40000: "chr1", 26000: "chr2", 30000: "chr3", 22000: "chrX"}
+    n_reads = {c: len(io.load_reads(bm, c).reads) for c in lengths.values()}
+    phased = ["--print_ref_calls", "--enable_phasing_model", "--phased_pileup_model_path", wfn + "30"]
+
+    def launch_phased(name, extra, threads):
+        log, out = os.path.join(tmp, name + ".log"), os.path.join(tmp, name)
+        rows = _launch(tmp, out, fa, bm, wfn, phased + extra + threads, env_extra={"C3R_FAKE_PHASE_LOG": log}, result="output_enable_phasing")
+        return rows, [json.loads(l) for l in open(log)]
+
+    plain, seen = launch_phased("plain", [], [])
+    assert sorted(lengths[e[0]] for e in seen) == sorted(lengths.values()) and all(e[1] == [] for e in seen)      # no table without the flag
+    assert any(r.startswith("chr3\t") for r in plain)
+    for threads in ([], ["--contexts", "3", "--fetch_threads", "1"]):
+        for name, source, tag in (("dir", per, False), ("one", one, False), ("one_indels", one, True)):
+            rows, seen = launch_phased(name + str(len(threads)), ["--phased_vcf_fn", source] + (["--haplotag_indels"] if tag else []), threads)
+            assert rows == plain
+            assert sorted(lengths[e[0]] for e in seen) == sorted(lengths.values())          # every contig with reads, once
+            for length, tables, loads in seen:
+                ctg = lengths[length]
+                want = len(phasedvcf.contig_alleles(source, ctg)[0]) if tag else len(phasedvcf.contig_sites(source, ctg))
+                # one table; the context held no read when it came, because the driver had just loaded the empty read set
+                assert tables == [["alleles" if tag else "sites", want, 0, [[0, 0]]]], (name, ctg, tables)
+                assert len(loads) == 1 and loads[0][0] == n_reads[ctg] > 0, (name, ctg, loads)
+                if ctg == "chr3":
+                    assert want == 0 and loads[0][1] == 0                                   # the BAM's HP:1 tags do not count
+            by = {lengths[e[0]]: e[1][0][1] for e in seen}
+            assert by["chr1"] == (6 if tag else 3) and by["chr2"] == 2 and by["chrX"] == 1
