@@ -44,6 +44,9 @@ hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
 `--phase_indels` (with --phase_output) hands hap_vcf --indels: heterozygous insertions, deletions and rows with two ALT alleles are phased too,
 by CIGAR-position alleles (no realignment, no left-alignment, no base qualities); without it both files are what they were.
+`--left_align_indels` (with one of --phase_indels, --haplotag_indels, --phasing_indels) lifts "no left-alignment" for every step that reads indels: the flag and
+--ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h: c3r_set_hap_left_align).  A shift stops at a read's M run's
+start, at an N or another indel; there is still no realignment and there are no base qualities; agreement with whatshap is not measured.
 `--haplotagged_bam` (same conditions as --phase_output, and combinable with it) adds the step the reference's "Haplotag the BAM" commands stand
 for: haplotag_bam writes <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai for the contigs the run processed — every record of the
 contig, with the HP / PS tags the GPU computed from the phase table the second pass read; without the flag nothing changes.
@@ -188,9 +191,14 @@ def build_parser():
            "from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows that --phase_output --phase_indels and `whatshap "
            "phase --indels` write.  Not with --phasing builtin (the phasing between the passes is SNV-only): run with --phase_output "
            "--phase_indels first, then rerun with --phased_vcf_fn <prefix>_enable_phasing_phased.vcf.gz --haplotag_indels")
+    a("--left_align_indels", action="store_true",
+      help="with --phase_indels, --haplotag_indels or --phasing_indels: left-align the indels those steps read — the tables' against --ref_fn, "
+           "every read's inside its own M run, on the device (include/c3r.h: c3r_set_hap_left_align) — so that a read whose aligner placed an "
+           "indel elsewhere in a homopolymer or short tandem repeat shows the allele and not the reference; the flag is handed to every such "
+           "step.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities")
     a("--phase_indels", action="store_true",
       help="with --phase_output: handed to hap_vcf as --indels — heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2) are "
-           "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels, no base qualities), and the counts "
+           "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels unless --left_align_indels is given, no base qualities), and the counts "
            "file gets the column ALLELES")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
@@ -406,6 +414,10 @@ def _plan(args):
             if not builtin and not args.phased_vcf_fn:
                 sys.exit("[ERROR] %s needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin" % flag)
             one_process(flag, instead)
+    left_align = bool(getattr(args, "left_align_indels", False))
+    if left_align and not (args.phase_indels or args.haplotag_indels or args.phasing_indels):
+        sys.exit("[ERROR] --left_align_indels needs one of --phase_indels, --haplotag_indels, --phasing_indels (it left-aligns the indels those steps read)")
+    la = ["--left_align_indels", "--ref_fn", args.ref_fn] if left_align else []
     ext = ".vcf" if args.no_compress else ".vcf.gz"
     phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
     ctg = ["--ctg_name", args.ctg_name] if args.ctg_name else []
@@ -441,22 +453,24 @@ def _plan(args):
         steps = [_Step("pass", first, None),
                  _Step("clear", (phased_dir, lambda name: name.startswith("phased_") and name.endswith(".vcf.gz")), None),
                  _Step("phase_vcf", ["--vcf_fn", unphased, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(args.phase_merge_levels)]
-                       + (["--indels"] if args.phasing_indels else []) + ctg + gpu, unphased),
+                       + (["--indels"] + la if args.phasing_indels else []) + ctg + gpu, unphased),
                  _Step("pass", second, None)]
     stem = os.path.join(args.output_dir, args.output_prefix + "_enable_phasing")
     source = phased_dir if builtin else args.phased_vcf_fn
     # (--phasing_indels: the steps behind the passes read phase_vcf --indels' directory with the allele table)
     tag_indels = ["--haplotag_indels"] if args.haplotag_indels or args.phasing_indels else []
+    # (--left_align_indels goes to every step that reads indels: its candidates, its tags, or both)
     if args.phase_output:
         steps.append(_Step("hap_vcf", ["--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext, "--hap_counts_fn",
-                                       stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if args.phase_indels else []) + tag_indels + ctg + gpu,
+                                       stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if args.phase_indels else []) + tag_indels
+                           + (la if args.phase_indels or tag_indels else []) + ctg + gpu,
                            stem + ext))
     if args.haplotagged_bam:
         # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed (--ctg_name: added when the step runs); an
         # earlier run's files in this directory, for contigs this run did not process, go first
         bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
         steps += [_Step("clear", (bam_dir, lambda name: name.endswith(".bam") or name.endswith(".bam.bai")), stem + ext),
-                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + gpu, stem + ext)]
+                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + gpu, stem + ext)]
     return steps
 
 
@@ -576,7 +590,10 @@ def _set_up(args, log, t_all):
     p.phase_source = None                                              # --phased_vcf_fn: every contig's table is read on a fetch thread
     if args.phased_vcf_fn:
         from . import phasedvcf
-        p.phase_source = phasedvcf.PhaseSource(args.phased_vcf_fn, args.haplotag_indels)
+        ref_of = None
+        if getattr(args, "left_align_indels", False) and args.haplotag_indels:         # (asked from the fetch threads: nothing shared)
+            ref_of = lambda c: (1, io.fetch_reference(args.ref_fn, c, 1, 2 ** 31, raw=True))
+        p.phase_source = phasedvcf.PhaseSource(args.phased_vcf_fn, args.haplotag_indels, *(() if ref_of is None else (None, ref_of)))
     return p
 
 
@@ -790,6 +807,8 @@ def _device_stage(p, eng, ctg, rs, ref, phase):
                    mpileup_compat=p.compat)
     if phase is not None:                            # (--phased_vcf_fn; without it a context never holds a table)
         eng.load_reads(_empty_reads())               # (the previous contig's reads are done with: a new table would tag them again first)
+        if p.phase_source.left_align is not None:    # (--left_align_indels: the tagging reads the whole contig's reference, set below again for the scan)
+            eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str)))
         p.phase_source.apply(eng, phase)             # before the reads: they are tagged while they are prepared
         note = p.phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
         if note:

@@ -118,7 +118,11 @@ def build_parser():
     a('--haplotag_indels', action='store_true',
       help="with --phased_vcf_fn: the reads are haplotagged from the phased insertions, deletions and two-ALT rows (`1|2`) of the phased VCF "
            "too, not from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows `--phase_output --phase_indels` and "
-           "`whatshap phase --indels` write.  Alleles are read off the CIGAR position: no realignment, no left-alignment, no base qualities")
+           "`whatshap phase --indels` write.  Alleles are read off the CIGAR position: no realignment, no left-alignment (--left_align_indels lifts it), no base qualities")
+    a('--left_align_indels', action='store_true',
+      help="with --haplotag_indels: left-align the table's indels against the reference and every read's indel inside its own M run, on the "
+           "device (include/c3r.h: c3r_set_hap_left_align), which lifts \"no left-alignment\"; the reference is then fetched for the whole "
+           "contig.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities")
     a('--minCoverage', type=int, default=4)
     a('--minMQ', type=int, default=5)
     a('--minBQ', type=int, default=0)
@@ -170,6 +174,9 @@ def Run(args, engine=None):
     haplotag_indels = getattr(args, "haplotag_indels", False)
     if haplotag_indels and not phased_vcf_fn:
         sys.exit("[ERROR] --haplotag_indels needs --phased_vcf_fn (it widens the table the reads are haplotagged from)")
+    left_align = bool(getattr(args, "left_align_indels", False))
+    if left_align and not haplotag_indels:
+        sys.exit("[ERROR] --left_align_indels needs --haplotag_indels (it left-aligns the indels the reads are haplotagged from)")
     for need in (args.bam_fn, args.ref_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
@@ -184,8 +191,9 @@ def Run(args, engine=None):
     if sites is not None and not sites:
         return 0
     extend_start, extend_end = max(1, ctg_start - 33), ctg_end + 33
-    ref_start = max(1, ctg_start - 1000)
-    ref_seq = io.fetch_reference(args.ref_fn, ctg, ref_start, ctg_end + 1000)
+    # (--left_align_indels: the whole contig — the table is the whole contig's, and the slice must cover every loaded read)
+    ref_start = 1 if left_align else max(1, ctg_start - 1000)
+    ref_seq = io.fetch_reference(args.ref_fn, ctg, ref_start, 2 ** 31 if left_align else ctg_end + 1000)
     if not ref_seq:
         sys.exit("[ERROR] Failed to load reference sequence from file (%s)." % args.ref_fn)
 
@@ -204,7 +212,7 @@ def Run(args, engine=None):
     phase = phase_source = None
     if phased_vcf_fn:
         from . import phasedvcf
-        phase_source = phasedvcf.PhaseSource(phased_vcf_fn, haplotag_indels, only=ctg)
+        phase_source = phasedvcf.PhaseSource(phased_vcf_fn, haplotag_indels, only=ctg, **(dict(left_align=lambda c: (ref_start, ref_seq)) if left_align else {}))
         phase = phase_source.table(ctg)
         note = phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
         if note:
@@ -212,6 +220,8 @@ def Run(args, engine=None):
         if engine is not None:
             from .reads import ReadSet
             engine.load_reads(ReadSet.from_records([]))      # (a caller's engine may still hold a chunk's reads: a new table would tag them again first)
+        if left_align:
+            eng.set_reference(ref_start, ref_seq)            # (before the reads: they are tagged against it while they are prepared)
         phase_source.apply(eng, phase)
     else:
         eng.set_phase_sites(None)                            # (a caller's engine may hold the table of an earlier chunk)

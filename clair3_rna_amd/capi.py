@@ -55,6 +55,10 @@ class HapAssignStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_sites", "n_phased", "n_few_reads", "n_disagree")]
 
 
+class LeftAlignStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_in", "n_out", "n_moved", "n_not_left_alignable", "n_same_pos_after_left_align")]
+
+
 class C3RError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, "libc3r: %s (%s)" % (msg, C3R_ERRORS.get(code, code)))
@@ -67,7 +71,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
            "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
-           "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links"]
+           "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links",
+           "c3r_set_hap_left_align", "c3r_hap_left_align_sites"]
 
 _lib = None
 
@@ -118,6 +123,8 @@ def load_library():
     L.c3r_phase_allele_unit_links.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
     L.c3r_hap_assign.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(HapAssignStats)]
+    L.c3r_set_hap_left_align.argtypes = [vp, i32]
+    L.c3r_hap_left_align_sites.argtypes = [vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(LeftAlignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.c3r_batch_begin.argtypes = [vp]
@@ -314,6 +321,18 @@ class Engine(object):
         if nb < 0 or (nb + 1) // 2 > len(pl):
             raise ValueError("pool_bases = %d does not fit a pool of %d bytes" % (nb, len(pl)))
         self._chk(self.L.c3r_set_phase_alleles(self.h, _ptr(a), _ptr(h) if len(h) else None, len(a), _ptr(pl) if nb else None, nb))
+
+    def set_hap_left_align(self, on):
+        """The opt-in switch of --left_align_indels (c3r_set_hap_left_align, default off): while on, hap_allele_counts, phase_allele_links,
+        phase_allele_unit_links and the tagging of set_phase_alleles / load_reads bring each read's insertion or deletion to its left-most
+        place inside its M run before they compare it with the table — which the caller normalises with hap_left_align_sites — and need a
+        reference (set_reference) that covers the loaded reads.  With an allele table set and reads loaded the reads are tagged again."""
+        self._chk(self.L.c3r_set_hap_left_align(self.h, 1 if on else 0))
+
+    @staticmethod
+    def hap_left_align_sites(sites, pool, ref_start, ref, pool_bases=None):
+        """capi.hap_left_align_sites (host only: no device is touched)."""
+        return hap_left_align_sites(sites, pool, ref_start, ref, pool_bases)
 
     def haplotags(self):
         """(uint8[n] tags of the loaded reads in load order, dict(n_reads, n_hp1, n_hp2, n_no_vote, n_tie, n_votes)); an error while no
@@ -675,6 +694,26 @@ def _phase_site_array(sites):
     if a.dtype != PHASE_SITE_DTYPE:
         raise TypeError("sites must be a capi.PHASE_SITE_DTYPE array, got %r" % (a.dtype,))
     return np.ascontiguousarray(a)
+
+
+def hap_left_align_sites(sites, pool, ref_start, ref, pool_bases=None):
+    """The table half of the left-alignment rule of include/c3r.h on the host (c3r_hap_left_align_sites; no GPU, no engine): a
+    HAP_SITE_DTYPE array (any order), its packed pool and a reference slice (`ref`: str / bytes / uint8 array whose first letter is 1-based
+    `ref_start`) -> (the sites that stay, left-aligned and sorted by pos; their packed pool; its number of bases; int64 input index of
+    every output site; dict(n_in, n_out, n_moved, n_not_left_alignable, n_same_pos_after_left_align))."""
+    L = load_library()
+    a = _hap_site_array(sites)
+    pl, nb = _pool_args(pool, pool_bases)
+    r = np.frombuffer(ref.encode() if isinstance(ref, str) else bytes(ref), dtype=np.uint8) if not isinstance(ref, np.ndarray) else np.ascontiguousarray(ref, dtype=np.uint8)
+    cap = int(a["a_len"][a["a_kind"] == HAP_EV_INS].sum()) + int(a["b_len"][a["b_kind"] == HAP_EV_INS].sum())
+    out, out_pool, src = np.zeros(len(a), dtype=HAP_SITE_DTYPE), np.zeros((cap + 1) // 2, dtype=np.uint8), np.zeros(len(a), dtype=np.int64)
+    m, ob, st = C.c_int64(0), C.c_int64(0), LeftAlignStats()
+    rc = L.c3r_hap_left_align_sites(_ptr(a), len(a), _ptr(pl) if nb else None, nb, int(ref_start), _ptr(r) if len(r) else None, len(r),
+                                    _ptr(out), _ptr(out_pool) if cap else None, cap, C.byref(ob), _ptr(src), C.byref(m), C.byref(st))
+    if rc != 0:
+        raise C3RError(rc, "c3r_hap_left_align_sites: pos >= 1, flags 0 / 1, kinds 0 .. 2, an indel has a length and every insertion lies inside the pool")
+    return (np.ascontiguousarray(out[:m.value]), np.ascontiguousarray(out_pool[:(ob.value + 1) // 2]), int(ob.value), np.ascontiguousarray(src[:m.value]),
+            {k: int(getattr(st, k)) for k, _ in LeftAlignStats._fields_})
 
 
 def phase_resolve(sites, links, min_reads=2, min_agree_pct=75):

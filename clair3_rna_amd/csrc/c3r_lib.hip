@@ -164,6 +164,7 @@ struct c3r_ctx {
     // the sites of whichever is set, phase_alleles says which; d_phasea holds c3r_hap_site_t with h1 in reserved[0], d_phasepool the inserted bases.
     int64_t n_phase = 0;
     bool phase_alleles = false;
+    bool hap_la = false;                      // c3r_set_hap_left_align: the four allele kernels run their _la instantiation against d_ref
     DevBuf d_phase, d_hptag, d_hpps, d_phasea, d_phasepool;
     // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
     DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
@@ -431,6 +432,16 @@ Args read_args(const c3r_ctx *ctx, int n) {
     a.seq = (const uint8_t *)ctx->d_seq.p;
     return a;
 }
+// The reference slice as the left-aligned observation reads it (c3r_set_hap_left_align), and the refusal of its four calls without one.
+HapRef hap_ref(const c3r_ctx *ctx) {
+    HapRef r;
+    r.ref = (const uint8_t *)ctx->d_ref.p; r.beg0 = (int32_t)(ctx->ref_start1 - 1); r.len = (int32_t)ctx->ref_len;
+    return r;
+}
+int hap_la_needs_ref(c3r_ctx *ctx, const char *call) {
+    if (ctx->hap_la && ctx->ref_len == 0) return fail(ctx, C3R_EINVAL, "%s: c3r_set_hap_left_align is on and no reference is set (c3r_set_reference)", call);
+    return C3R_OK;
+}
 // One launch of such a kernel: a group of PREP_GRP lanes per read.
 template <class Args>
 void launch_per_read(c3r_ctx *ctx, const char *label, void (*kernel)(Args), const Args &a) {
@@ -631,9 +642,11 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
             h.sites = (const c3r_phase_site_t *)ctx->d_phase.p;
             launch_per_read(ctx, "k_haplotag", k_haplotag, h);
         } else {
-            HapAlleleTagArgs h = tag_args(read_args<HapAlleleTagArgs>(ctx, n));
+            if ((rc = hap_la_needs_ref(ctx, "c3r_load_reads"))) return rc;
+            HapAlleleTagLaArgs h = tag_args(read_args<HapAlleleTagLaArgs>(ctx, n));
             h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.pool = (const uint8_t *)ctx->d_phasepool.p;
-            launch_per_read(ctx, "k_haplotag_alleles", k_haplotag_alleles, h);
+            if (ctx->hap_la) { h.ref = hap_ref(ctx); launch_per_read(ctx, "k_haplotag_alleles_la", k_haplotag_alleles_la, h); }
+            else launch_per_read<HapAlleleTagArgs>(ctx, "k_haplotag_alleles", k_haplotag_alleles, h);
         }
     }
     // ---- second pass (nothing below waits for the device): every record into its bin
@@ -891,6 +904,7 @@ int c3r_load_reads(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const
     if (!ctx || n_reads < 0 || n_cigar_ops < 0 || n_seq_bytes < 0 || (n_reads && (!reads || !cigars || !seq4))) return C3R_EINVAL;
     if (n_reads >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many reads");
     if (n_cigar_ops >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many CIGAR ops");
+    if (ctx->phase_alleles) if (int rc0 = hap_la_needs_ref(ctx, "c3r_load_reads")) return rc0;       // (before anything of the previous load is given up)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool timing = getenv("C3R_TIMING") != nullptr;
     // whatever happens below, the previous contig's tables are gone
@@ -1301,6 +1315,7 @@ static int check_hap_sites(c3r_ctx *ctx, const char *what, const c3r_hap_site_t 
 int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !h1)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "phase allele site", sites, n, ins_pool, pool_bases, h1)) return rc;
+    if (n) if (int rc = hap_la_needs_ref(ctx, "c3r_set_phase_alleles")) return rc;
     if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (n) {
@@ -1319,33 +1334,43 @@ int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8
 int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !counts)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "query site", sites, n, ins_pool, pool_bases, nullptr)) return rc;
-    return hap_count_table(ctx, "k_hap_allele_counts", k_hap_allele_counts, n, counts, [&](HapAlleleArgs &a) {
+    if (int rc = hap_la_needs_ref(ctx, "c3r_hap_allele_counts")) return rc;
+    auto upload_sites = [&](HapAlleleArgs &a) {
         int rc;
         if ((rc = upload(ctx, ctx->d_hasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_hapool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
         a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.pool = (const uint8_t *)ctx->d_hapool.p;
         return (int)C3R_OK;
-    });
+    };
+    if (ctx->hap_la) return hap_count_table(ctx, "k_hap_allele_counts_la", k_hap_allele_counts_la, n, counts, [&](HapAlleleLaArgs &a) { a.ref = hap_ref(ctx); return upload_sites(a); });
+    return hap_count_table(ctx, "k_hap_allele_counts", k_hap_allele_counts, n, counts, upload_sites);
 }
 
 int c3r_phase_allele_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *links) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !links)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "candidate site", sites, n, ins_pool, pool_bases, nullptr, true)) return rc;
+    if (int rc = hap_la_needs_ref(ctx, "c3r_phase_allele_links")) return rc;
     if (n == 0) return C3R_OK;
     const size_t words = (size_t)n * C3R_PHASE_LINKS * 2;
     if (ctx->n_reads == 0) { memset(links, 0, words * 4); return C3R_OK; }               // (no voters: nothing to launch)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = upload(ctx, ctx->d_pasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_papool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
-    AlleleLinkArgs a = read_args<AlleleLinkArgs>(ctx, ctx->n_reads);
+    AlleleLinkLaArgs a = read_args<AlleleLinkLaArgs>(ctx, ctx->n_reads);
     a.sites = (const c3r_hap_site_t *)ctx->d_pasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_papool.p;
     a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
-    return counter_table(ctx, ctx->d_links, words, links, [&](uint32_t *t) { a.links = t; launch_per_read(ctx, "k_phase_allele_links", k_phase_allele_links, a); });
+    if (ctx->hap_la) a.ref = hap_ref(ctx);
+    return counter_table(ctx, ctx->d_links, words, links, [&](uint32_t *t) {
+        a.links = t;
+        if (ctx->hap_la) launch_per_read(ctx, "k_phase_allele_links_la", k_phase_allele_links_la, a);
+        else launch_per_read<AlleleLinkArgs>(ctx, "k_phase_allele_links", k_phase_allele_links, a);
+    });
 }
 
 int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *ulinks,
                                 int64_t cap_units, int64_t *n_units) {
     if (!ctx || n < 0 || pool_bases < 0 || cap_units < 0 || (n && (!sites || !h1)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "unit site", sites, n, ins_pool, pool_bases, h1, true)) return rc;
+    if (int rc = hap_la_needs_ref(ctx, "c3r_phase_allele_unit_links")) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (sites[i].ps != -1 && sites[i].ps < 1) return fail(ctx, C3R_EINVAL, "unit site %lld: ps %d is neither -1 (no block) nor a 1-based position", (long long)i, sites[i].ps);
     std::vector<int32_t> unit_ps, unit_of;
@@ -1366,11 +1391,122 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
     int rc;
     if ((rc = upload(ctx, ctx->d_pasites, t.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_papool, ins_pool, (size_t)((pool_bases + 1) / 2))) ||
         (rc = upload(ctx, ctx->d_unitof, unit_of.data(), (size_t)n))) return rc;
-    AlleleUnitLinkArgs a = read_args<AlleleUnitLinkArgs>(ctx, ctx->n_reads);
+    AlleleUnitLinkLaArgs a = read_args<AlleleUnitLinkLaArgs>(ctx, ctx->n_reads);
     a.sites = (const c3r_hap_site_t *)ctx->d_pasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_papool.p;
     a.unit_of = (const int32_t *)ctx->d_unitof.p; a.n_units = (int32_t)U;
     a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
-    return counter_table(ctx, ctx->d_links, words, ulinks, [&](uint32_t *t2) { a.ulinks = t2; launch_per_read(ctx, "k_phase_allele_unit_links", k_phase_allele_unit_links, a); });   // (t and unit_of live until it returns)
+    if (ctx->hap_la) a.ref = hap_ref(ctx);
+    return counter_table(ctx, ctx->d_links, words, ulinks, [&](uint32_t *t2) {                                  // (t and unit_of live until it returns)
+        a.ulinks = t2;
+        if (ctx->hap_la) launch_per_read(ctx, "k_phase_allele_unit_links_la", k_phase_allele_unit_links_la, a);
+        else launch_per_read<AlleleUnitLinkArgs>(ctx, "k_phase_allele_unit_links", k_phase_allele_unit_links, a);
+    });
+}
+
+int c3r_set_hap_left_align(c3r_ctx *ctx, int on) {
+    if (!ctx) return C3R_EINVAL;
+    const bool want = on != 0;
+    if (want == ctx->hap_la) return C3R_OK;
+    const bool retag = ctx->phase_alleles && ctx->n_reads > 0;    // the tags on the device are those of the other observation
+    if (retag && want && ctx->ref_len == 0)
+        return fail(ctx, C3R_EINVAL, "c3r_set_hap_left_align: an allele table is set and reads are loaded, and no reference is set (c3r_set_reference)");
+    ctx->hap_la = want;
+    if (!retag) return C3R_OK;
+    ctx->last_scan_pruned = false;
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
+// The rule `left_align` of include/c3r.h on the host, for the table: base codes 1, 2, 4, 8 of the slice (0: outside, or not A, C, G, T).
+namespace {
+struct LaRef {
+    const char *ref; int64_t beg0, len;
+    uint8_t code(int64_t p) const {
+        const int64_t o = p - beg0;
+        if (o < 0 || o >= len) return 0;
+        switch (ref[o]) { case 'A': case 'a': return 1; case 'C': case 'c': return 2; case 'G': case 'g': return 4; case 'T': case 't': return 8; default: return 0; }
+    }
+};
+// k and, for an insertion, the rotated bases in s (n codes, in place)
+int64_t la_shift(const LaRef &R, int64_t a, bool ins, int64_t n, std::vector<uint8_t> &s) {
+    int64_t k = 0;
+    for (;; ++k) {
+        const uint8_t r = R.code(a - k);
+        if (!r || !R.code(a - k - 1)) break;
+        const uint8_t t = ins ? s[(size_t)n - 1] : R.code(a - k + n);
+        if (r != t) break;
+        if (ins) { s.pop_back(); s.insert(s.begin(), r); }
+    }
+    return k;
+}
+}  // namespace
+
+int c3r_hap_left_align_sites(const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, int64_t ref_start, const char *ref,
+                             int64_t ref_len, c3r_hap_site_t *out_sites, uint8_t *out_pool, int64_t out_pool_cap, int64_t *out_pool_bases,
+                             int64_t *src_index, int64_t *n_out, c3r_left_align_stats_t *stats) {
+    if (n < 0 || pool_bases < 0 || ref_len < 0 || ref_start < 1 || out_pool_cap < 0 || (n && (!sites || !out_sites || !src_index)) || (pool_bases && !ins_pool) ||
+        (ref_len && !ref) || (out_pool_cap && !out_pool) || !n_out)
+        return C3R_EINVAL;
+    const LaRef R{ref, ref_start - 1, ref_len};
+    auto pool_at = [&](uint64_t q) { const uint8_t byte = ins_pool[q >> 1]; return (uint8_t)((q & 1) ? (byte & 15) : (byte >> 4)); };
+    c3r_left_align_stats_t st;
+    memset(&st, 0, sizeof st);
+    st.n_in = n;
+    struct Moved { c3r_hap_site_t e; int64_t src; std::vector<uint8_t> ins[2]; };
+    std::vector<Moved> kept;
+    kept.reserve((size_t)n);
+    int64_t need = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        Moved m;
+        m.e = sites[i]; m.src = i;
+        if (m.e.pos < 1 || m.e.base_matters > 1 || m.e.event_matters > 1) return C3R_EINVAL;
+        c3r_hap_allele_t *al[2] = {&m.e.a, &m.e.b};
+        int64_t k = -1;
+        bool ok = true;
+        for (int w = 0; w < 2; ++w) {
+            const c3r_hap_allele_t &x = *al[w];
+            if (x.kind > C3R_HAP_EV_DEL || (x.kind == C3R_HAP_EV_NONE ? x.len != 0 : x.len == 0)) return C3R_EINVAL;
+            if (x.kind == C3R_HAP_EV_NONE) continue;
+            if (x.kind == C3R_HAP_EV_INS) {
+                if ((int64_t)x.ins_off + x.len > pool_bases) return C3R_EINVAL;
+                for (uint32_t j = 0; j < x.len; ++j) m.ins[w].push_back(pool_at((uint64_t)x.ins_off + j));
+                need += x.len;
+            }
+            const int64_t kw = la_shift(R, (int64_t)m.e.pos - 1, x.kind == C3R_HAP_EV_INS, x.len, m.ins[w]);
+            if (k >= 0 && kw != k) ok = false;
+            k = kw;
+        }
+        if (k < 0) k = 0;                                              // (no event allele: nothing to shift)
+        if (!ok || (k > 0 && m.e.base_matters)) { st.n_not_left_alignable += 1; continue; }
+        if (k > 0) {
+            m.e.pos = (int32_t)(m.e.pos - k);
+            m.e.a.base = m.e.b.base = R.code((int64_t)m.e.pos - 1);
+            st.n_moved += 1;
+        }
+        kept.push_back(std::move(m));
+    }
+    if (need > out_pool_cap) return C3R_EOVERFLOW;
+    std::stable_sort(kept.begin(), kept.end(), [](const Moved &x, const Moved &y) { return x.e.pos != y.e.pos ? x.e.pos < y.e.pos : x.src < y.src; });
+    if (out_pool_cap) memset(out_pool, 0, (size_t)((out_pool_cap + 1) / 2));
+    int64_t m_out = 0, nb = 0;
+    for (size_t i = 0; i < kept.size(); ++i) {
+        Moved &m = kept[i];
+        if (m_out > 0 && out_sites[m_out - 1].pos == m.e.pos) { st.n_same_pos_after_left_align += 1; continue; }
+        c3r_hap_allele_t *al[2] = {&m.e.a, &m.e.b};
+        for (int w = 0; w < 2; ++w) {
+            if (al[w]->kind != C3R_HAP_EV_INS) continue;
+            al[w]->ins_off = (uint32_t)nb;
+            for (uint8_t c : m.ins[w]) { out_pool[nb >> 1] |= (uint8_t)((nb & 1) ? c : c << 4); ++nb; }
+        }
+        out_sites[m_out] = m.e;
+        src_index[m_out] = m.src;
+        ++m_out;
+    }
+    st.n_out = m_out;
+    *n_out = m_out;
+    if (out_pool_bases) *out_pool_bases = nb;
+    if (stats) *stats = st;
+    return C3R_OK;
 }
 
 int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts, const c3r_phase_params_t *p, c3r_phase_site_t *out,

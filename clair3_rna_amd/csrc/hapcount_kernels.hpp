@@ -32,7 +32,7 @@ struct HapTableArgs : ReadArgs {
 // The body of k_hap_counts and k_hap_allele_counts: one walk of the group's read, one add per site where
 // column(site, R, the read's bases, walk_sites' arguments) gives 0, 1 or 2 (more: nothing).  compat_plain: ReadInfo::compat of a read of
 // the plain walk.  All lanes of a group take the same way through it (whole groups leave: the ballots of the searches stay inside a group).
-template <class Args, class Column>
+template <bool LA = false, class Args, class Column>
 __device__ __forceinline__ void hap_count_read(const Args &a, bool compat_plain, Column &&column) {
     const GroupAt g;
     const int gl = g.gl, i = g.i;
@@ -41,13 +41,13 @@ __device__ __forceinline__ void hap_count_read(const Args &a, bool compat_plain,
     if (!read_kept(d.flag, d.mapq, a.min_mq, a.excl_flags)) return;
     const SiteRange r = read_sites(a.sites, a.n_sites, d, gl);
     if (r.lo >= r.hi) return;
-    const bool serial = a.serial[i] != 0;
+    const bool serial = a.serial[i] != 0 || (LA && cigar_has_m_neighbours(ReadInfo(d, i, a.cigars, 0), gl));
     const ReadInfo R(d, i, a.cigars, compat_plain && !serial ? 1 : 0);
     const uint8_t *rseq = a.seq + R.seq_off;
     const uint32_t tag = a.tags[i] & 3u;
     const int32_t set = tag ? a.read_ps[i] : -1;
-    walk_sites(R, gl, serial, a.sites, r.lo, r.hi, [&](int s, const auto &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
-        const uint32_t al = column(e, R, rseq, q, last, iq, cx);
+    walk_sites(R, gl, serial, a.sites, r.lo, r.hi, [&](int s, const auto &e, unsigned long long q, bool first, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = column(e, R, rseq, q, first, last, iq, cx);
         if (al > 2u) return;
         const uint32_t row = e.ps == set ? tag : 0u;                   // (set = -1 equals no query ps: they are >= 0)
         __hip_atomic_fetch_add(&a.counts[(size_t)s * 9 + row * 3 + al], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -59,7 +59,7 @@ struct HapCountArgs : HapTableArgs {
 };
 
 __global__ __launch_bounds__(PREP_THREADS) void k_hap_counts(const HapCountArgs a) {
-    hap_count_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+    hap_count_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
         const uint32_t b = hap_nibble(rseq, q);
         return hap_is_acgt(b) ? snv_column(e, b) : HAP_NOTHING;
     });
@@ -75,8 +75,17 @@ struct HapAlleleArgs : HapTableArgs {
 };
 
 __global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts(const HapAlleleArgs a) {
-    hap_count_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+    hap_count_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         return hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+    });
+}
+
+// The same with the left-aligned observation (c3r_set_hap_left_align): hap_observe_la against the reference slice.
+struct HapAlleleLaArgs : HapAlleleArgs { HapRef ref; };
+
+__global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts_la(const HapAlleleLaArgs a) {
+    hap_count_read<true>(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_observe_la(e, rseq, R.l_seq, a.pool, a.ref, q, first, iq, cx);
     });
 }
 

@@ -22,7 +22,7 @@
 // the sites of that set.
 //
 // The pieces that every kernel which holds reads against a sorted site table shares are here as well (hapcount_kernels.hpp and
-// phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe.
+// phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe, hap_observe_la.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -89,8 +89,8 @@ __device__ __forceinline__ uint32_t hap_nibble(const uint8_t *p, unsigned long l
 }
 
 // One walk of a read over the sites [lo, hi) (k_phase_links: a window of them) that its M ops cover: every M op searches its own stretch once.
-// on_site(site index, site, query offset of the read's base there, is it the op's last base, query offset behind the op — where an
-// insertion's bases start —, the op's neighbours) runs in the lane that holds the op.  Every kernel's walk; all lanes of the group come here together.
+// on_site(site index, site, query offset of the read's base there, is it the op's first base, is it the op's last base, query offset behind
+// the op — where an insertion's bases start —, the op's neighbours) runs in the lane that holds the op.  Every kernel's walk; all lanes of the group come here together.
 template <class Site, class OnSite>
 __device__ __forceinline__ void walk_sites(const ReadInfo &R, int gl, bool serial, const Site *sites, int lo, int hi, OnSite &&on_site) {
     auto on_op = [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) __attribute__((always_inline)) {
@@ -101,7 +101,7 @@ __device__ __forceinline__ void walk_sites(const ReadInfo &R, int gl, bool seria
             if (dd >= (long long)len) break;
             const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
             if (q >= R.l_seq) break;                                   // (the later sites of this op lie further out still)
-            on_site(s, e, q, dd == (long long)len - 1, (unsigned long long)y + len, cx);
+            on_site(s, e, q, dd == 0, dd == (long long)len - 1, (unsigned long long)y + len, cx);
         }
     };
     if (!serial) walk_plain_ops(R, gl, on_op);
@@ -148,6 +148,81 @@ __device__ __forceinline__ uint32_t hap_observe(const c3r_hap_site_t &e, const u
     return shows(e.a) ? 0u : shows(e.b) ? 1u : 2u;
 }
 
+// ---- the left-aligned observation (c3r_set_hap_left_align; the rule `left_align` of include/c3r.h, restated by tests/leftalignref.py) ----------
+// The reference slice of c3r_set_reference as the four allele kernels read it: upper-case ASCII, 0-based position p at ref[p - beg0].
+struct HapRef {
+    const uint8_t *ref; int32_t beg0, len;
+    // base code 1, 2, 4, 8 of position p; 0: outside the slice, or not A, C, G, T (either stops a shift)
+    __device__ __forceinline__ uint32_t code(long long p) const {
+        const long long o = p - beg0;
+        if (o < 0 || o >= (long long)len) return 0u;
+        const uint32_t c = ref[o];
+        return c == 'A' ? 1u : c == 'C' ? 2u : c == 'G' ? 4u : c == 'T' ? 8u : 0u;
+    }
+};
+
+// Does the read's CIGAR hold two M-like ops in a row (`3M2=`)?  The plain walk hands them out as two ops, and the left-aligned observation
+// needs the whole run — its first base and its distance to the event —, so with the switch on such a read takes the serial walk, which
+// hands out the normalised form.  By the 16 lanes together; all return the group's answer.
+__device__ __forceinline__ bool cigar_has_m_neighbours(const ReadInfo &R, int gl) {
+    int o = 0;
+    for (uint32_t k0 = 0; k0 < R.n_cig; k0 += PREP_GRP) {
+        const uint32_t k = k0 + (uint32_t)gl;
+        if (k > 0 && k < R.n_cig && fold_op(R.cig[k]) == C3R_CIG_M && fold_op(R.cig[k - 1]) == C3R_CIG_M) o = 1;
+    }
+#pragma unroll
+    for (int off = PREP_GRP / 2; off > 0; off >>= 1) o |= __shfl_xor(o, off, PREP_GRP);
+    return o != 0;
+}
+// hap_observe with the read's event brought to its left-most form inside its M run.  The op at hand is the whole run (see above): the site
+// lies `tail` = iq - 1 - q bases before its last base, whose reference position is a = pos - 1 + tail, and the event E behind the run shows
+// at this site when left_align shifts it by exactly `tail` — or by more, when this is the run's first base (the cap).  Every other site of the
+// run sees no event.  Not shifted, and seen on the run's last base only: an I with a D at once behind it (OTHER) and an insertion that SEQ
+// cuts off (no observation).  A run whose last base lies past SEQ carries no event.  The loop ends at the first step that fails: a read
+// pays the length of the repeat it sits in, not of its run.  The shifted insertion s' is ref[pos .. pos + k) followed by the first n - k
+// inserted bases of the read.
+__device__ __forceinline__ uint32_t hap_observe_la(const c3r_hap_site_t &e, const uint8_t *rseq, uint32_t l_seq, const uint8_t *pool, const HapRef &ref, unsigned long long q,
+                                                   bool first, unsigned long long iq, const OpCtx &cx) {
+    const uint32_t b = hap_nibble(rseq, q);
+    if (e.base_matters && !hap_is_acgt(b)) return HAP_NOTHING;
+    uint32_t ek = C3R_HAP_EV_NONE, en = 0, k = 0;
+    if (e.event_matters && iq - 1 < l_seq) {
+        const unsigned long long tail = iq - 1 - q;
+        if (cx.nop == C3R_CIG_I && (cx.n2op == C3R_CIG_D || iq + cx.nlen > l_seq)) {
+            if (tail == 0) {
+                if (cx.n2op != C3R_CIG_D) return HAP_NOTHING;
+                ek = HAP_EV_OTHER;
+            }
+        } else if (cx.nop == C3R_CIG_I || cx.nop == C3R_CIG_D) {
+            const bool ins = cx.nop == C3R_CIG_I;
+            const uint32_t n = cx.nlen;
+            const long long a = (long long)e.pos - 1 + (long long)tail;
+            // step j: the anchor moves from a - j to a - j - 1 (an A, C, G, T of the slice too) when ref[a - j] equals the event's last base
+            auto step = [&](unsigned long long j) __attribute__((always_inline)) {
+                const uint32_t r = ref.code(a - (long long)j);
+                if (r == 0u || ref.code(a - (long long)j - 1) == 0u) return false;
+                const uint32_t t = (ins && j < n) ? hap_nibble(rseq, iq + n - 1 - j) : ref.code(a - (long long)j + n);
+                return r == t;
+            };
+            unsigned long long j = 0;
+            while (j < tail && step(j)) ++j;
+            if (j == tail && (first || !step(tail))) { ek = ins ? C3R_HAP_EV_INS : C3R_HAP_EV_DEL; en = n; k = (uint32_t)min(tail, (unsigned long long)n); }
+        }
+    }
+    auto shows = [&](const c3r_hap_allele_t &al) __attribute__((always_inline)) {
+        if (e.base_matters && b != al.base) return false;
+        if (!e.event_matters) return true;
+        if (ek != al.kind || en != al.len) return false;               // (NONE: both lengths are 0)
+        if (ek != C3R_HAP_EV_INS) return true;
+        for (uint32_t j = 0; j < en; ++j) {
+            const uint32_t s = j < k ? ref.code((long long)e.pos + j) : hap_nibble(rseq, iq + j - k);
+            if (s != hap_nibble(pool, (unsigned long long)al.ins_off + j)) return false;
+        }
+        return true;
+    };
+    return shows(e.a) ? 0u : shows(e.b) ? 1u : 2u;
+}
+
 // ---- the tags ---------------------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t HAP_NONE = 0xffffffffu;    // no phase set (ps is an int32 >= 0)
 
@@ -188,9 +263,9 @@ struct HapTagArgs : ReadArgs {
 };
 
 // The tag of the group's read from walk(R, gl, serial, lo, hi, cur) -> HapTally, the reduced votes of one walk (steps 1 to 3 above), and
-// lane 0's three stores.  compat_plain: ReadInfo::compat of a read of the plain walk.  The body of k_haplotag and k_haplotag_alleles; all
+// lane 0's three stores.  compat_plain: ReadInfo::compat of a read of the plain walk.  LA: the left-aligned observation (cigar_has_m_neighbours).  The body of k_haplotag and k_haplotag_alleles; all
 // lanes of a group take the same way through it (whole groups leave: the shuffles stay inside a group).
-template <class Args, class Walk>
+template <bool LA = false, class Args, class Walk>
 __device__ __forceinline__ void hap_tag_read(const Args &a, bool compat_plain, Walk &&walk) {
     const GroupAt g;
     const int gl = g.gl, i = g.i;
@@ -199,7 +274,7 @@ __device__ __forceinline__ void hap_tag_read(const Args &a, bool compat_plain, W
     const SiteRange r = read_sites(a.sites, a.n_sites, d, gl);
     uint32_t tag = 0, votes = 0, set = HAP_NONE;
     if (r.lo < r.hi) {
-        const bool serial = a.serial[i] != 0;
+        const bool serial = a.serial[i] != 0 || (LA && cigar_has_m_neighbours(ReadInfo(d, i, a.cigars, 0), gl));
         const ReadInfo R(d, i, a.cigars, compat_plain && !serial ? 1 : 0);
         HapTally t = walk(R, gl, serial, r.lo, r.hi, HAP_NONE);
         votes = t.c1 + t.c2;
@@ -233,7 +308,7 @@ __device__ __forceinline__ HapTally hap_walk(const ReadInfo &R, int gl, bool ser
     HapTally t;
     t.clear();
     const uint8_t *rseq = a.seq + R.seq_off;
-    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
         const uint32_t al = snv_column(e, hap_nibble(rseq, q));
         if (al != 2u) t.vote(cur, (uint32_t)e.ps, al == e.h1, s);
     });
@@ -257,13 +332,13 @@ struct HapAlleleTagArgs : HapTagArgs {
     const uint8_t *pool;                      // the alleles' inserted bases, 4-bit packed like seq (never read when no allele is an insertion)
 };
 
-// hap_walk for the allele table
-__device__ __forceinline__ HapTally hap_walk_alleles(const ReadInfo &R, int gl, bool serial, const HapAlleleTagArgs &a, int lo, int hi, uint32_t cur) {
+// hap_walk for the allele table; observe(site, walk_sites' arguments) -> hap_observe's column
+template <class Observe>
+__device__ __forceinline__ HapTally hap_walk_alleles(const ReadInfo &R, int gl, bool serial, const HapAlleleTagArgs &a, int lo, int hi, uint32_t cur, Observe &&observe) {
     HapTally t;
     t.clear();
-    const uint8_t *rseq = a.seq + R.seq_off;
-    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_hap_site_t &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
-        const uint32_t al = hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_hap_site_t &e, unsigned long long q, bool first, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = observe(e, q, first, last, iq, cx);
         if (al < 2u) t.vote(cur, (uint32_t)e.ps, al == e.reserved[0], s);
     });
     t.reduce();
@@ -271,7 +346,24 @@ __device__ __forceinline__ HapTally hap_walk_alleles(const ReadInfo &R, int gl, 
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles(const HapAlleleTagArgs a) {
-    hap_tag_read(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) { return hap_walk_alleles(R, gl, serial, a, lo, hi, cur); });
+    hap_tag_read(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+        const uint8_t *rseq = a.seq + R.seq_off;
+        return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+            return hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+        });
+    });
+}
+
+// The same with the left-aligned observation (c3r_set_hap_left_align): hap_observe_la against the reference slice.
+struct HapAlleleTagLaArgs : HapAlleleTagArgs { HapRef ref; };
+
+__global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles_la(const HapAlleleTagLaArgs a) {
+    hap_tag_read<true>(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+        const uint8_t *rseq = a.seq + R.seq_off;
+        return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+            return hap_observe_la(e, rseq, R.l_seq, a.pool, a.ref, q, first, iq, cx);
+        });
+    });
 }
 
 }  // namespace c3r

@@ -39,7 +39,7 @@ struct LinkArgs : ReadArgs {
 // The body of k_phase_links and k_phase_allele_links: the window loop above with column(site, R, the read's bases, walk_sites' arguments)
 // -> the allele index the read shows, 0 or 1, or 2 for nothing (the slab byte is the index + 1).  compat_plain: ReadInfo::compat of a read of the plain walk.  Every thread of the
 // workgroup comes here and reaches every barrier.
-template <class Args, class Column>
+template <bool LA = false, class Args, class Column>
 __device__ __forceinline__ void phase_links_read(const Args &a, bool compat_plain, Column &&column) {
     __shared__ uint4 s_obs4[PREP_READS][PHASE_WIN / 16];
     __shared__ int s_nwin;
@@ -59,7 +59,7 @@ __device__ __forceinline__ void phase_links_read(const Args &a, bool compat_plai
             const int m = r.hi - r.lo;
             nwin = m < 2 ? 0 : m <= PHASE_WIN ? 1 : 1 + (m - PHASE_WIN + PHASE_STEP - 1) / PHASE_STEP;
             R = ReadInfo(d, i, a.cigars, 0);
-            serial = a.serial[i] != 0;
+            serial = a.serial[i] != 0 || (LA && cigar_has_m_neighbours(R, gl));
             if (compat_plain && !serial) R.compat = 1;
         }
     }
@@ -74,8 +74,8 @@ __device__ __forceinline__ void phase_links_read(const Args &a, bool compat_plai
         if (mine) s_obs4[slot][gl] = make_uint4(0, 0, 0, 0);
         __syncthreads();
         if (mine) {
-            walk_sites(R, gl, serial, a.sites, ws, we, [&](int s, const auto &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
-                const uint32_t al = column(e, R, rseq, q, last, iq, cx);
+            walk_sites(R, gl, serial, a.sites, ws, we, [&](int s, const auto &e, unsigned long long q, bool first, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+                const uint32_t al = column(e, R, rseq, q, first, last, iq, cx);
                 if (al != 2u) obs[s - ws] = (uint8_t)(al + 1u);
             });
         }
@@ -98,7 +98,7 @@ __device__ __forceinline__ void phase_links_read(const Args &a, bool compat_plai
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_links(const LinkArgs a) {
-    phase_links_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+    phase_links_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
         return snv_column(e, hap_nibble(rseq, q));
     });
 }
@@ -115,9 +115,19 @@ struct AlleleLinkArgs : ReadArgs {
 };
 
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_links(const AlleleLinkArgs a) {
-    phase_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+    phase_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         const uint32_t al = hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
         return al < 2u ? al : 2u;                                       // (another allele and no observation are both nothing here)
+    });
+}
+
+// The same with the left-aligned observation (c3r_set_hap_left_align): hap_observe_la against the reference slice.
+struct AlleleLinkLaArgs : AlleleLinkArgs { HapRef ref; };
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_links_la(const AlleleLinkLaArgs a) {
+    phase_links_read<true>(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe_la(e, rseq, R.l_seq, a.pool, a.ref, q, first, iq, cx);
+        return al < 2u ? al : 2u;
     });
 }
 
@@ -165,10 +175,10 @@ __device__ __forceinline__ UnitTally unit_walk(const ReadInfo &R, int gl, bool s
     UnitTally t;
     t.c1 = 0; t.c2 = 0; t.u_min = UNIT_NONE; t.u_max = -1;
     const uint8_t *rseq = a.seq + R.seq_off;
-    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const auto &e, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+    walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const auto &e, unsigned long long q, bool first, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         const int32_t u = a.unit_of[s];
         if (u < 0 || u < cur) return;
-        const uint32_t al = column(e, R, rseq, q, last, iq, cx);
+        const uint32_t al = column(e, R, rseq, q, first, last, iq, cx);
         if (al == 2u) return;
         if (u > cur) { t.u_min = min(t.u_min, u); t.u_max = max(t.u_max, u); return; }
         if (al == h1_of(e)) t.c1 += 1; else t.c2 += 1;                 // (u == cur)
@@ -179,7 +189,7 @@ __device__ __forceinline__ UnitTally unit_walk(const ReadInfo &R, int gl, bool s
 
 // The body of k_phase_unit_links and k_phase_allele_unit_links.  compat_plain: ReadInfo::compat of a read of the plain walk.  All lanes of
 // a group take the same way through it (whole groups leave: the shuffles stay inside a group).
-template <class Args, class Column, class H1Of>
+template <bool LA = false, class Args, class Column, class H1Of>
 __device__ __forceinline__ void phase_unit_links_read(const Args &a, bool compat_plain, Column &&column, H1Of &&h1_of) {
     const GroupAt g;
     const int gl = g.gl, i = g.i;
@@ -190,7 +200,7 @@ __device__ __forceinline__ void phase_unit_links_read(const Args &a, bool compat
     const int lo = r.lo, hi = r.hi;
     if (hi - lo < 2) return;                                           // (two units take two sites)
     ReadInfo R(d, i, a.cigars, 0);
-    const bool serial = a.serial[i] != 0;
+    const bool serial = a.serial[i] != 0 || (LA && cigar_has_m_neighbours(R, gl));
     if (compat_plain && !serial) R.compat = 1;
     const UnitTally all = unit_walk(R, gl, serial, a, lo, hi, -1, column, h1_of);
     if (all.u_min >= all.u_max) return;                                // no unit observed (UNIT_NONE, -1) or one
@@ -215,7 +225,7 @@ __device__ __forceinline__ void phase_unit_links_read(const Args &a, bool compat
 }
 
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_unit_links(const UnitLinkArgs a) {
-    phase_unit_links_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
+    phase_unit_links_read(a, false, [&](const c3r_phase_site_t &e, const ReadInfo &, const uint8_t *rseq, unsigned long long q, bool, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
         return snv_column(e, hap_nibble(rseq, q));
     }, [](const c3r_phase_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.h1; });
 }
@@ -233,8 +243,18 @@ struct AlleleUnitLinkArgs : ReadArgs {
 };
 
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_unit_links(const AlleleUnitLinkArgs a) {
-    phase_unit_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+    phase_unit_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         const uint32_t al = hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
+        return al < 2u ? al : 2u;
+    }, [](const c3r_hap_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.reserved[0]; });
+}
+
+// The same with the left-aligned observation (c3r_set_hap_left_align): hap_observe_la against the reference slice.
+struct AlleleUnitLinkLaArgs : AlleleUnitLinkArgs { HapRef ref; };
+
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_unit_links_la(const AlleleUnitLinkLaArgs a) {
+    phase_unit_links_read<true>(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe_la(e, rseq, R.l_seq, a.pool, a.ref, q, first, iq, cx);
         return al < 2u ? al : 2u;
     }, [](const c3r_hap_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.reserved[0]; });
 }

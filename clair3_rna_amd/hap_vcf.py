@@ -24,6 +24,12 @@ allele B, and one more column ALLELES says which they are: `0,1` or `1,2`.  The 
 left-alignment of the reads' indels, no base qualities; a homozygous row or one with three or more ALTs stays as it is.  Agreement with
 `whatshap --indels` has not been measured.  Without --indels both files are what they were.
 
+--left_align_indels (off by default; needs --indels and --ref_fn) lifts "no left-alignment", as in phase_vcf: the candidates' indels are
+left-aligned against the reference, each read's indel inside its own M run on the device (include/c3r.h: c3r_set_hap_left_align); with
+--haplotag_indels the phase table is left-aligned too and the reads are tagged by the same observation.  Rows keep their POS, REF and ALT
+in both files.  A shift stops at the M run's start, at an N or another indel and at the contig's ends; no realignment, no base qualities;
+agreement with whatshap is not measured.
+
     python -m clair3_rna_amd.hap_vcf --bam_fn x.bam --vcf_fn out/output_enable_phasing.vcf.gz \\
         --phased_vcf_fn out/tmp/phased_output/phased_vcf --output_fn out/phased.vcf.gz --hap_counts_fn out/hap_counts.tsv
 """
@@ -71,10 +77,11 @@ def allele_counts_lines(contig, cands, strings, assigned, counts):
     """counts_lines under --indels: candidates of phasing.allele_candidates_from_vcf (query sites and their rows' (REF, ALT) strings),
     hap_assign's output, (n, 3, 3) counts."""
     lines = []
-    for c, (ref, alt), o, t in zip(cands, strings, assigned, counts):
+    for j, (c, o, t) in enumerate(zip(cands, assigned, counts)):
+        ref, alt = strings[j][0], strings[j][1]
         a, b = ("1", "2") if "," in alt else ("0", "1")
         gt = (b + "|" + a if int(o["h1"]) else a + "|" + b) if int(o["ps"]) >= 0 else a + "/" + b
-        lines.append("\t".join([contig, str(int(c["pos"])), ref, alt, str(int(c["ps"])), gt]
+        lines.append("\t".join([contig, str(phasing.row_pos(cands, strings, j)), ref, alt, str(int(c["ps"])), gt]
                                + [str(int(t[r][k])) for r in (1, 2, 0) for k in (0, 1, 2)] + [a + "," + b]) + "\n")
     return lines
 
@@ -88,7 +95,8 @@ def write_vcf(in_vcf, assigned_by_contig, out_fn, strings_by_contig=None):
         phased = {c: {int(s["pos"]): s for s in a if int(s["ps"]) >= 0} for c, a in assigned_by_contig.items()}
         rewrite = phasing.phased_row
     else:
-        phased = {c: {int(s["pos"]): (ref, alt, int(s["ps"]), int(s["h1"])) for s, (ref, alt) in zip(a, strings_by_contig[c]) if int(s["ps"]) >= 0}
+        phased = {c: {phasing.row_pos(a, strings_by_contig[c], j): (strings_by_contig[c][j][0], strings_by_contig[c][j][1], int(s["ps"]), int(s["h1"]))
+                      for j, s in enumerate(a) if int(s["ps"]) >= 0}
                   for c, a in assigned_by_contig.items()}
         rewrite = phasing.allele_phased_row
     plain = out_fn[:-3] if out_fn.endswith(".gz") else out_fn
@@ -128,10 +136,14 @@ def build_parser():
     a("--min_agree_pct", type=int, default=75, help="fewest per cent of them that agree on the orientation")
     a("--indels", action="store_true",
       help="also phase heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2), by CIGAR-position alleles: no realignment, no "
-           "left-alignment, no base qualities; the counts file gets the column ALLELES.  Off: SNVs only, both files as they were")
+           "left-alignment (--left_align_indels lifts it), no base qualities; the counts file gets the column ALLELES.  Off: SNVs only, both files as they were")
     a("--haplotag_indels", action="store_true",
       help="tag the reads from the phased insertions, deletions and two-ALT rows of --phased_vcf_fn too, not from its biallelic SNVs alone "
            "(what the 30-channel pass did when it ran with this flag; include/c3r.h: c3r_set_phase_alleles)")
+    a("--left_align_indels", action="store_true",
+      help="with --indels: left-align the candidates' indels (and, with --haplotag_indels, the phase table's) against --ref_fn and every read's "
+           "indel inside its M run, on the device (default: the alleles are read off the CIGAR position as they stand)")
+    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 
@@ -142,11 +154,14 @@ def Run(args, log=None):
     for need in (args.bam_fn, args.vcf_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
-    source = phasedvcf.PhaseSource(args.phased_vcf_fn, getattr(args, "haplotag_indels", False))
+    from .phase_vcf import left_align_reference
+    indels = bool(getattr(args, "indels", False))
+    tag_indels = bool(getattr(args, "haplotag_indels", False))
+    ref_of = left_align_reference(args, "--indels", indels or tag_indels)     # (or --haplotag_indels alone: then only the tags' table is left-aligned)
+    source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None or not tag_indels else (None, ref_of)))
     if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
         sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
-    indels = bool(getattr(args, "indels", False))
-    per = phasing.allele_candidates_from_vcf(args.vcf_fn, None) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
+    per = phasing.allele_candidates_from_vcf(args.vcf_fn, None, *(() if ref_of is None else (ref_of,))) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
     gpu_id = args.gpu_id if args.gpu_id is not None else int(os.environ.get("C3R_DEVICE", "0"))
     eng = None
@@ -167,6 +182,9 @@ def Run(args, log=None):
                 eng.set_params(min_mq=args.min_mq)
             query = nearest_sets(cands, table.sites)
             rs = io.load_reads(args.bam_fn, ctg)
+            if ref_of is not None:                            # (the whole contig: it covers every read)
+                eng.set_reference(*ref_of(ctg))
+                eng.set_hap_left_align(True)
             source.apply(eng, table)
             eng.load_reads(rs)
             if indels:
@@ -179,8 +197,8 @@ def Run(args, log=None):
                 out, st = capi.hap_assign(query, counts, args.min_reads, args.min_agree_pct)
                 lines += counts_lines(ctg, query, out, counts)
             assigned[ctg] = out
-            log("[INFO] %s: %d reads, %d phased sites in %d sets, %d candidate sites (%s), %d phased, %d with too few tagged reads, %d without agreement -> %s"
-                % (ctg, len(rs), len(table), len(set(table.ps.tolist())), st["n_sites"],
+            log("[INFO] %s: %d reads, %d phased sites in %d sets, %d candidate sites%s (%s), %d phased, %d with too few tagged reads, %d without agreement -> %s"
+                % (ctg, len(rs), len(table), len(set(table.ps.tolist())), st["n_sites"], phasing.left_align_note(skipped),
                    ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
                    st["n_phased"], st["n_few_reads"], st["n_disagree"], args.output_fn))
     finally:

@@ -19,7 +19,9 @@ supplementary alignments and MAPQ 0 included); every phased heterozygous SNV a r
 whose allele the read shows at the CIGAR position; the read's set is the one with the most votes.  No realignment, no base qualities, no
 indels, no tagging of a supplementary alignment after its primary.  Agreement with `whatshap haplotag` / `longphase haplotag` has not been
 measured.  --haplotag_indels: the phased insertions, deletions and two-ALT rows of the phased VCF vote too (c3r_set_phase_alleles:
-phasedvcf.contig_alleles -> Engine.set_phase_alleles), still as CIGAR-position alleles without left-alignment.
+phasedvcf.contig_alleles -> Engine.set_phase_alleles), still as CIGAR-position alleles without left-alignment — unless --left_align_indels (with
+--ref_fn) is given: then the table's indels are left-aligned against the reference and every read's indel inside its own M run, on the device
+(include/c3r.h: c3r_set_hap_left_align); a shift stops at the run's start, at an N or another indel; still no realignment, no base qualities.
 
     python -m clair3_rna_amd.haplotag_bam --bam_fn x.bam --phased_vcf_fn out/tmp/phased_output/phased_vcf \\
         --output_dir out/tmp/phased_output/phased_bam
@@ -67,6 +69,11 @@ def build_parser():
     a("--haplotag_indels", action="store_true",
       help="tag the reads from the phased insertions, deletions and two-ALT rows of --phased_vcf_fn too, not from its biallelic SNVs alone "
            "(include/c3r.h: c3r_set_phase_alleles): the tags of a 30-channel pass that ran with this flag")
+    a("--left_align_indels", action="store_true",
+      help="with --haplotag_indels: left-align the table's indels against --ref_fn and every read's indel inside its own M run, on the device "
+           "(include/c3r.h: c3r_set_hap_left_align): the tags of a 30-channel pass that ran with this flag.  A shift stops at the M run's "
+           "start, at an N or another indel; no realignment, no base qualities; agreement with whatshap is not measured")
+    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     a("--threads", type=int, default=0, help="BGZF inflate / deflate threads; default: the CPUs this process may run on, 32 at the most")
     return p
@@ -83,7 +90,10 @@ def Run(args, log=None):
     log = log or (lambda m: print(m, file=sys.stderr))
     if not os.path.isfile(args.bam_fn):
         sys.exit("[ERROR] file %s not found" % args.bam_fn)
-    source = phasedvcf.PhaseSource(args.phased_vcf_fn, getattr(args, "haplotag_indels", False))
+    from .phase_vcf import left_align_reference
+    tag_indels = bool(getattr(args, "haplotag_indels", False))
+    ref_of = left_align_reference(args, "--haplotag_indels", tag_indels)
+    source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None else (None, ref_of)))
     threads = int(getattr(args, "threads", 0) or 0)
     command = getattr(args, "command", None) or " ".join(sys.argv)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -105,6 +115,8 @@ def Run(args, log=None):
                     if eng is None:
                         eng = capi.Engine(gpu_id)
                         eng.set_params()
+                    if ref_of is not None:                         # (the whole contig: it covers every read)
+                        eng.set_reference(*ref_of(ctg))
                     source.apply(eng, table)
                     eng.load_reads(rs)
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()

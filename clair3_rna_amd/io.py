@@ -57,6 +57,18 @@ def fetch_reference(ref_fn, ctg, start1, end1, raw=False):
     raise KeyError("contig %s not in %s.fai" % (ctg, ref_fn))
 
 
+def contig_reference(ref_fn):
+    """A function contig -> (1, the contig's bases as they stand in the file): the reference slice of --left_align_indels, which covers
+    every read of the contig whatever its span.  The contig asked for last is kept."""
+    last = {}
+
+    def of(ctg):
+        if last.get("ctg") != ctg:
+            last.update(ctg=ctg, seq=fetch_reference(ref_fn, ctg, 1, 2 ** 31, raw=True))
+        return 1, last["seq"]
+    return of
+
+
 def write_fasta(path, contigs, width=60):
     """contigs: list of (name, sequence).  Also writes the .fai."""
     fai = []

@@ -15,6 +15,14 @@ c3r_phase_allele_links) and written as `0|1` / `1|0` / `1|2` / `2|1` + PS.  The 
 no left-alignment of the reads' indels, no base qualities; homozygous rows and rows with three or more ALTs are not candidates.  The
 second pass reads such a directory with `--haplotag_indels`.
 
+--left_align_indels (default off; needs --indels and --ref_fn) lifts "no left-alignment": the candidates' indels are brought to their
+left-most form against the reference (phasing.left_align_table) and each read's indel to its left-most place inside its own M run, on the
+device (include/c3r.h: c3r_set_hap_left_align), so that a read whose aligner placed the indel elsewhere in a homopolymer or a short tandem
+repeat shows the allele and not the reference.  A row whose alleles cannot move together is no candidate (`not_left_alignable`), nor is the
+later of two that land on one position (`same_pos_after_left_align`).  Written rows keep their POS, REF and ALT.  What remains: a shift
+stops at the M run's start, at an N or another indel, and at the contig's ends; no realignment, no base qualities; agreement with whatshap
+is not measured.
+
 The rule (include/c3r.h: c3r_phase_links / c3r_phase_resolve) is a greedy linkage chain, not whatshap's wMEC: agreement with whatshap has
 not been measured.
 
@@ -40,9 +48,29 @@ def build_parser():
     a("--merge_levels", type=int, default=0,
       help="levels of the block-merge stage after the chain: joins the blocks that reads bridge across a run of unlinked sites (0: off)")
     a("--indels", action="store_true",
-      help="also phase heterozygous insertions, deletions and 1/2 rows (alleles read off the CIGAR position; default: SNVs only)")
+      help="also phase heterozygous insertions, deletions and 1/2 rows (alleles read off the CIGAR position, no left-alignment unless "
+           "--left_align_indels is given; default: SNVs only)")
+    a("--left_align_indels", action="store_true",
+      help="with --indels: left-align the candidates' indels against --ref_fn and every read's indel inside its M run, on the device "
+           "(default: the alleles are read off the CIGAR position as they stand)")
+    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
+
+
+def left_align_reference(args, needs, has):
+    """The contig -> reference slice function of --left_align_indels, or None without the flag; refuses the flag without its
+    prerequisite (`needs`: the flag's name, `has`: is it given) or without --ref_fn."""
+    if not getattr(args, "left_align_indels", False):
+        return None
+    if not has:
+        sys.exit("[ERROR] --left_align_indels needs %s" % needs)
+    ref_fn = getattr(args, "ref_fn", None)
+    if not ref_fn:
+        sys.exit("[ERROR] --left_align_indels needs --ref_fn")
+    if not os.path.isfile(ref_fn):
+        sys.exit("[ERROR] file %s not found" % ref_fn)
+    return io.contig_reference(ref_fn)
 
 
 def Run(args, log=None):
@@ -57,7 +85,8 @@ def Run(args, log=None):
     if merge_levels < 0:
         sys.exit("[ERROR] --merge_levels must be >= 0")
     indels = bool(getattr(args, "indels", False))
-    per = phasing.allele_candidates_from_vcf(args.vcf_fn, None) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
+    ref_of = left_align_reference(args, "--indels", indels)
+    per = phasing.allele_candidates_from_vcf(args.vcf_fn, None, *(() if ref_of is None else (ref_of,))) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
     what = "heterozygous SNV / indel / two-ALT" if indels else "heterozygous SNV"
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -76,6 +105,9 @@ def Run(args, log=None):
                 eng = capi.Engine(gpu_id)
                 eng.set_params(min_mq=args.min_mq)
             rs = io.load_reads(args.bam_fn, ctg)
+            if ref_of is not None:                            # (the whole contig: it covers every read)
+                eng.set_reference(*ref_of(ctg))
+                eng.set_hap_left_align(True)
             eng.load_reads(rs)
             fn = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
             if indels:
@@ -87,8 +119,8 @@ def Run(args, log=None):
                 phasing.write_phased_vcf(args.vcf_fn, ctg, out, fn)
             written.append(fn)
             merged = ", block merge: %d units joined in %d levels" % (st["merge_units_joined"], st["merge_levels_run"]) if merge_levels else ""
-            log("[INFO] %s: %d reads, %d candidate sites%s (%s), %d phased in %d blocks, largest block %d sites%s -> %s"
-                % (ctg, len(rs), st["n_sites"], " with indels and two-ALT rows" if indels else "", ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
+            log("[INFO] %s: %d reads, %d candidate sites%s%s (%s), %d phased in %d blocks, largest block %d sites%s -> %s"
+                % (ctg, len(rs), st["n_sites"], " with indels and two-ALT rows" if indels else "", phasing.left_align_note(skipped), ", ".join("%s %d" % (k, v) for k, v in sorted(skipped.items()) if v and k != "other_contig") or "none skipped",
                    st["n_phased"], st["n_blocks"], st["max_block"], merged, fn))
     finally:
         if eng is not None:

@@ -112,24 +112,32 @@ def read_all_phase_sites(vcf_fn):
 
 
 # ---- the table of Engine.set_phase_alleles: SNVs, insertions, deletions and two-ALT rows
-def _allele_table(rows, skipped):
-    """read_phase_alleles' tuple from the rows of phasing._parse_alleles(phased=True): (pos, allele A, allele B, REF, ALT, ps, h1)."""
+def _allele_table(rows, skipped, ref=None):
+    """read_phase_alleles' tuple from the rows of phasing._parse_alleles(phased=True): (pos, allele A, allele B, REF, ALT, ps, h1).
+    ref (--left_align_indels; None: off): (1-based start, reference slice) — the table goes through phasing.left_align_table."""
     from . import phasing                                    # (phasing imports this module: not at import time)
     keep = phasing._first_rows(rows, skipped)
     sites, pool = phasing._allele_sites(keep)                 # (flags and pool: as for hap_vcf --indels)
     sites["ps"] = [r[5] for r in keep]
     h1 = np.array([r[6] for r in keep], dtype=np.uint8)
+    moved = None
+    if ref is not None:
+        sites, pool, _, src, st = phasing.left_align_table(sites, pool, ref)
+        keep, h1 = [keep[j] for j in src], np.ascontiguousarray(h1[src])
+        skipped, moved = dict(skipped, **{k: st["n_" + k] for k in phasing.LEFT_ALIGN_REASONS}), st["n_moved"]
     pool_bases = int(sum(int(sites[n + "_len"][sites[n + "_kind"] == HAP_EV_INS].sum()) for n in "ab"))
-    return sites, h1, pool, pool_bases, Skipped(skipped, indel=int((sites["event_matters"] != 0).sum()), two_alt=sum("," in r[4] for r in keep))
+    return sites, h1, pool, pool_bases, Skipped(skipped, indel=int((sites["event_matters"] != 0).sum()), two_alt=sum("," in r[4] for r in keep), moved=moved)
 
 
 class Skipped(dict):
     """{reason: rows skipped} of an allele table, with `kept`: dict(indel = the sites kept with an insertion or deletion among their two
-    alleles, two_alt = the sites kept from rows with two ALTs) — what the drivers' [INFO] lines count.  Compares like the plain dict."""
+    alleles, two_alt = the sites kept from rows with two ALTs) — what the drivers' [INFO] lines count — and, under --left_align_indels,
+    `moved`: the sites whose anchor moved (None without the flag).  Compares like the plain dict."""
 
-    def __init__(self, skipped, indel=0, two_alt=0):
+    def __init__(self, skipped, indel=0, two_alt=0, moved=None):
         dict.__init__(self, skipped)
         self.kept = dict(indel=indel, two_alt=two_alt)
+        self.moved = moved
 
 
 def empty_alleles():
@@ -137,21 +145,22 @@ def empty_alleles():
     return np.zeros(0, dtype=HAP_SITE_DTYPE), np.zeros(0, np.uint8), np.zeros(0, np.uint8), 0, Skipped(dict.fromkeys(ALLELE_SKIP_REASONS, 0))
 
 
-def read_phase_alleles(vcf_fn, contig):
+def read_phase_alleles(vcf_fn, contig, left_align=None):
     """(HAP_SITE_DTYPE array sorted by pos, uint8 h1 per site, packed pool of the insertions' bases, number of bases in the pool, {reason: rows
-    skipped}) for `contig` of a plain or gzipped VCF: the arguments of Engine.set_phase_alleles."""
+    skipped}) for `contig` of a plain or gzipped VCF: the arguments of Engine.set_phase_alleles.  left_align (--left_align_indels; None:
+    off): a function contig -> (1-based start, reference slice); the table is then left-aligned against it (_allele_table)."""
     from . import phasing
     with _open_text(vcf_fn) as f:
         rows, skipped = phasing._parse_alleles(f, contig, phased=True)[contig]
-    return _allele_table(rows, skipped)
+    return _allele_table(rows, skipped, left_align(contig) if left_align else None)
 
 
-def read_all_phase_alleles(vcf_fn):
+def read_all_phase_alleles(vcf_fn, left_align=None):
     """{contig: read_phase_alleles' tuple} for every contig of the file, in one pass."""
     from . import phasing
     with _open_text(vcf_fn) as f:
         per = phasing._parse_alleles(f, None, phased=True)
-    return {c: _allele_table(*v) for c, v in per.items()}
+    return {c: _allele_table(*v, left_align(c) if left_align else None) for c, v in per.items()}
 
 
 def contig_alleles(path, contig):
@@ -180,24 +189,30 @@ class PhaseSource(object):
     whichever thread asks first (call_sample asks from its fetch threads) — or, with `only`, for that one contig alone (the per-chunk
     driver never asks for another).  A contig without a file or without a row gets the empty table of the source's kind."""
 
-    def __init__(self, path, tag_indels=False, only=None):
+    def __init__(self, path, tag_indels=False, only=None, left_align=None):
+        """left_align (--left_align_indels, with tag_indels only; None: off): a function contig -> (1-based start, reference slice).  The
+        allele table is left-aligned against it where it is read, and `apply` switches the engine's observation to match."""
         import os
         import sys
         import threading
         if not os.path.exists(path):
             sys.exit("[ERROR] file %s not found" % path)
-        self.path, self.tag_indels, self.only = path, bool(tag_indels), only
+        if left_align is not None and not tag_indels:
+            sys.exit("[ERROR] --left_align_indels needs --haplotag_indels")
+        self.path, self.tag_indels, self.only, self.left_align = path, bool(tag_indels), only, left_align
         self.per_contig = os.path.isdir(path) or only is not None
         self.all, self.lock = None, threading.Lock()
 
     def table(self, contig):
         if self.per_contig:
             fn = contig_file(self.path, contig)
-            hit = (read_phase_alleles if self.tag_indels else read_phase_sites)(fn, contig) if fn else None
+            extra = () if self.left_align is None else (self.left_align,)
+            hit = (read_phase_alleles(fn, contig, *extra) if self.tag_indels else read_phase_sites(fn, contig)) if fn else None
         else:
             with self.lock:
                 if self.all is None:
-                    self.all = (read_all_phase_alleles if self.tag_indels else read_all_phase_sites)(self.path)
+                    extra = () if self.left_align is None else (self.left_align,)
+                    self.all = read_all_phase_alleles(self.path, *extra) if self.tag_indels else read_all_phase_sites(self.path)
             hit = self.all.get(contig)
         if self.tag_indels:
             sites, h1, pool, pool_bases, skipped = hit or empty_alleles()
@@ -205,8 +220,11 @@ class PhaseSource(object):
         return PhaseTable(*(hit or (np.zeros(0, dtype=PHASE_SITE_DTYPE), dict.fromkeys(SKIP_REASONS, 0))))
 
     def apply(self, engine, table):
-        """Before the contig's reads: they are tagged while they are prepared."""
+        """Before the contig's reads: they are tagged while they are prepared.  Under --left_align_indels the caller has set a reference
+        slice that covers the contig's reads before this."""
         if self.tag_indels:
+            if self.left_align is not None:
+                engine.set_hap_left_align(True)
             engine.set_phase_alleles(table.sites, *table._rest)
         else:
             engine.set_phase_sites(table.sites)
@@ -215,4 +233,7 @@ class PhaseSource(object):
         """A driver's words about the table of --haplotag_indels — `head`, the two counts, `tail` — and "" without the flag."""
         if not self.tag_indels:
             return ""
-        return "%s%d with an insertion or deletion, %d with two ALTs%s" % (head, table.kept["indel"], table.kept["two_alt"], tail)
+        moved = getattr(table.skipped, "moved", None)
+        la = "" if moved is None else ", --left_align_indels: %d left-aligned, %d not_left_alignable, %d same_pos_after_left_align" % (
+            moved, table.skipped.get("not_left_alignable", 0), table.skipped.get("same_pos_after_left_align", 0))
+        return "%s%d with an insertion or deletion, %d with two ALTs%s%s" % (head, table.kept["indel"], table.kept["two_alt"], la, tail)

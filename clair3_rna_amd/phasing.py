@@ -201,17 +201,61 @@ def _allele_sites(keep):
     return sites, pack_nibbles(pool)
 
 
-def allele_candidates_from_vcf(vcf_fn, contig):
+LEFT_ALIGN_REASONS = ("not_left_alignable", "same_pos_after_left_align")
+
+
+class LeftAligned(dict):
+    """{reason: rows skipped} of a table that left_align_table has been through — the reasons of the parse and LEFT_ALIGN_REASONS — with
+    `moved`: the sites whose anchor moved.  Compares like the plain dict."""
+
+    def __init__(self, skipped, stats):
+        dict.__init__(self, skipped)
+        self.update({k: stats["n_" + k] for k in LEFT_ALIGN_REASONS})
+        self.moved = stats["n_moved"]
+
+
+def left_align_table(sites, pool, ref, pool_bases=None):
+    """The one place where a driver's table meets --left_align_indels (include/c3r.h: c3r_hap_left_align_sites, host code): a
+    HAP_SITE_DTYPE array and its pool, and `ref` = (1-based position of the slice's first base, the slice: str / bytes / uint8 array) ->
+    (the sites that stay, left-aligned and sorted by pos; their pool; the bases in it; the input index of every output site; the
+    statistics).  A site whose alleles cannot move together is dropped (`not_left_alignable`), and so is the later of two that land on one
+    position (`same_pos_after_left_align`)."""
+    from .capi import hap_left_align_sites
+    return hap_left_align_sites(sites, pool, ref[0], ref[1], pool_bases)
+
+
+def left_align_note(skipped):
+    """A driver's words about what --left_align_indels did to a table, and "" without the flag (`skipped` is then a plain dict)."""
+    return ", %d left-aligned" % skipped.moved if isinstance(skipped, LeftAligned) else ""
+
+
+def _left_aligned_candidates(table, ref):
+    """_allele_table's tuple after left_align_table; a row's strings get a third element, the row's own POS (the site may have moved)."""
+    sites, pool, strings, skipped = table
+    out, opool, _, src, st = left_align_table(sites, pool, ref)
+    return out, opool, [(strings[j][0], strings[j][1], int(sites["pos"][j])) for j in src], LeftAligned(skipped, st)
+
+
+def row_pos(sites, strings, j):
+    """The POS of the VCF row that site j of a candidate table came from: the site's own unless --left_align_indels moved it."""
+    return strings[j][2] if len(strings[j]) > 2 else int(sites["pos"][j])
+
+
+def allele_candidates_from_vcf(vcf_fn, contig, left_align=None):
     """(HAP_SITE_DTYPE array sorted by pos — ps is 0 —, the packed pool of the insertions' bases (capi.pack_nibbles), [(REF string, ALT
     string)] of the rows as the file spells them, {reason: rows skipped}) for `contig` of a plain or gzipped VCF; contig None: {contig: that
     tuple} for every contig of the file, in one pass.  A row is kept when FILTER is PASS, its GT is `0/1` / `1/0` with one ALT (A = REF,
     B = the ALT) or `1/2` / `2/1` with two ALTs (A = the first, B = the second), every ALT reduces to an SNV, an insertion or a deletion
-    anchored on POS (reduce_allele) and the two alleles differ; of several such rows on one position the first is kept."""
+    anchored on POS (reduce_allele) and the two alleles differ; of several such rows on one position the first is kept.
+    left_align (--left_align_indels; None: off): a function contig -> (1-based start, reference slice).  The table then goes through
+    left_align_table: sites may move to the left and some are dropped, the dict is a LeftAligned, and a row's strings are (REF, ALT, the
+    row's POS)."""
     with _open_text(vcf_fn) as f:
         per = _parse_alleles(f, contig)
-    if contig is None:
-        return {c: _allele_table(rows, skipped) for c, (rows, skipped) in per.items()}
-    return _allele_table(*per[contig])
+    done = {c: _allele_table(rows, skipped) for c, (rows, skipped) in per.items()}
+    if left_align is not None:
+        done = {c: _left_aligned_candidates(t, left_align(c)) for c, t in done.items()}
+    return done if contig is None else done[contig]
 
 
 def phased_only(sites_out):
@@ -296,7 +340,7 @@ def write_allele_phased_vcf(in_vcf, contig, sites, strings, ps, h1, out_fn):
     """write_phased_vcf for `phase_vcf --indels`: `sites` and `strings` as allele_candidates_from_vcf gives them for `contig`, `ps` / `h1`
     per site as Engine.phase_allele_sites leaves them (ps < 0: the site stays unphased).  The rows of the phased sites are rewritten by
     allele_phased_row (`0|1` / `1|0` / `1|2` / `2|1` + PS), every other row is written byte for byte.  Returns the number of rows rewritten."""
-    phased = {int(sites["pos"][j]): (strings[j][0], strings[j][1], int(ps[j]), int(h1[j])) for j in range(len(sites)) if int(ps[j]) >= 0}
+    phased = {row_pos(sites, strings, j): (strings[j][0], strings[j][1], int(ps[j]), int(h1[j])) for j in range(len(sites)) if int(ps[j]) >= 0}
     n, has_ps = 0, False
     with _open_text(in_vcf) as f, gzip.open(out_fn, "wt") as out:
         for line in f:

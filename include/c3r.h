@@ -323,6 +323,58 @@ int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulink
 int c3r_phase_allele_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *links);
 int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases,
                                 uint32_t *ulinks, int64_t cap_units, int64_t *n_units);
+/* Left-alignment of indels for the four calls that hold reads against an allele table (c3r_hap_allele_counts, c3r_phase_allele_links,
+ * c3r_phase_allele_unit_links and the tagging of c3r_set_phase_alleles / c3r_load_reads).  Opt-in (--left_align_indels); switched off,
+ * every path, launch and output byte is what the contracts above say.  It lifts their "no left-alignment of the reads' indels": in a
+ * homopolymer or a short tandem repeat the aligner may place a read's indel one or more repeat units away from the VCF's anchor, and such
+ * a read then shows (base, NONE) there — a vote for REF.  Switched on, the table's alleles are brought to their left-most form against the
+ * reference (host: c3r_hap_left_align_sites), each read's event is brought to its left-most form inside its own M run (device), and the two
+ * are compared as above.  This is where the rule is stated; csrc/haplotag_kernels.hpp (hap_observe_la), c3r_hap_left_align_sites and
+ * tests/leftalignref.py restate it.
+ *
+ * left_align(ref, a, kind, n, s) -> (k, s'), for an event behind the 0-based anchor a: shift by one while the reference base on the anchor
+ * equals the event's last base and both are one of A, C, G, T.  Step j = 0, 1, ...: for DEL(n) the condition is ref[a - j] == ref[a - j + n];
+ * for INS(s) it is ref[a - j] == last(s_j), with s_0 = s and s_{j+1} = ref[a - j] + s_j[:-1].  `ref` is the slice given (c3r_set_reference;
+ * the arguments of c3r_hap_left_align_sites), compared in upper case: a position outside it stops the shift — a - j, a - j + n, and the
+ * anchor the step would move to, a - j - 1 — and so does any code other than A, C, G, T on one of the three.  k is the number of shifts, s' = s_k the rotated
+ * insertion (= (ref[a - k + 1 .. a] + s)[:n]).
+ *
+ * Table (c3r_hap_left_align_sites, host code: no context, no device).  Input: n sites as c3r_hap_allele_counts takes them (pos need not be
+ * sorted; ps is copied), their pool, and a reference slice (ref_start 1-based, any letter case).  Per site, k_A / k_B = left_align's count
+ * for each allele that is an insertion or a deletion, with a = pos - 1.  The site moves to pos - k when every such allele of the site
+ * shifts by the same k, and k == 0 or base_matters == 0.  A moved site (k > 0) takes the reference base at the new anchor as both alleles'
+ * base (an A, C, G or T by the rule; base_matters is 0, so it is never compared) and the rotated bases s' in the pool.  A site that meets neither condition is dropped (`not_left_alignable`).  The table is then sorted by pos again (stable);
+ * of two sites on one position the first in input order stays, the other is dropped (`same_pos_after_left_align`).  Output: the m sites
+ * that stay in out_sites (cap n), their pool in out_pool (rebuilt: insertion k of the output starts where insertion k - 1 ended;
+ * out_pool_cap bases must hold the inserted bases of all input alleles, C3R_EOVERFLOW if not), *out_pool_bases, src_index[j] = the input
+ * index of output site j (the caller's map to its VCF rows and its h1), and the statistics.  *n_out = m.  C3R_EINVAL for pos < 1, a flag
+ * other than 0 / 1, an unknown kind, an indel of length 0 (or a length on kind NONE) or an insertion that runs past the pool.
+ *
+ * Read (device), on the read's NORMALISED CIGAR, where adjacent M-like ops are one run (`3M2=` before a D is a run of 5).  Take an event
+ * E — the I or D op directly behind an M run that covers the reference positions [x, x + len), as in c3r_hap_allele_counts — and k =
+ * min(left_align's count with a = x + len - 1, len - 1): the anchor stays inside the run.  At the site whose anchor is x + len - 1 - k the
+ * read shows E, an insertion with s' (the rotation takes reference bases, whatever the read shows there).  At every other site of the run —
+ * the run's last base included when k > 0 — the event is NONE.  Not shifted, and seen on the run's last base only, as before: an I with a
+ * D at once behind it (OTHER), and an insertion that l_seq cuts off (no observation).  A run whose last base lies at or past l_seq carries
+ * no event.  The read's base on a site is the one the CIGAR puts there, and everything else of the observation is unchanged.  The result
+ * does not depend on the walk a read takes: a read whose CIGAR holds two M-like ops in a row takes the serial walk while the switch is on
+ * (the plain walk hands them out one by one; aligners that write = / X pay one lane per read there).
+ * What remains: a shift stops at the M run's start, at an N or another indel, and at the slice's edge; there is no realignment and there
+ * are no base qualities; agreement with whatshap is not measured.
+ *
+ * c3r_set_hap_left_align(ctx, on): default 0.  While on, the four calls above run k_*_la (the same launches, one kernel each, with
+ * hap_observe_la in hap_observe's place) against the slice of c3r_set_reference that is current when they run, and return C3R_EINVAL with a
+ * message when no reference is set (c3r_set_phase_alleles with n = 0 still clears).  The caller hands them a table that
+ * c3r_hap_left_align_sites has normalised against the same reference; the slice must cover every loaded read's [pos, end) for the
+ * results to be those of the rule on the whole reference.  Toggling the switch with an allele table set and reads loaded tags the reads
+ * again, as setting a table does (C3R_EINVAL, and the switch stays, when that needs a reference and none is set).  A later
+ * c3r_set_reference does NOT tag again: the tags are those of the slice that was set when they were made.  The table of
+ * c3r_set_phase_sites and the four SNV kernels never look at the switch. */
+typedef struct { int64_t n_in, n_out, n_moved, n_not_left_alignable, n_same_pos_after_left_align; } c3r_left_align_stats_t;
+int c3r_set_hap_left_align(c3r_ctx *ctx, int on);
+int c3r_hap_left_align_sites(const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, int64_t ref_start, const char *ref,
+                             int64_t ref_len, c3r_hap_site_t *out_sites, uint8_t *out_pool, int64_t out_pool_cap, int64_t *out_pool_bases,
+                             int64_t *src_index, int64_t *n_out, c3r_left_align_stats_t *stats);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped
