@@ -2,7 +2,7 @@
 
 Replaces the input side of `samtools mpileup <bam> -r ctg:...` (src/create_tensor_pileup.py:446-451): core.pos,
 flag, MAPQ, CIGAR (incl. the CG:B,I long-CIGAR convention), 4-bit SEQ and the HP aux tag are all the tensor
-builder needs (base qualities are not used: --min-BQ 0).  Sequential scan of the file, no .bai needed; records of
+builder needs (it does not use base qualities: --min-BQ 0; read_contig(..., want_quals=True) carries them for --hap_min_bq).  Sequential scan of the file, no .bai needed; records of
 other contigs are skipped.  The writer exists so that tests and the demo can produce real BAM files.
 """
 import struct
@@ -80,8 +80,9 @@ def read_header(path):
     return buf, gen
 
 
-def read_contig(path, contig):
-    """All alignments of `contig`, in file order -> ReadSet."""
+def read_contig(path, contig, want_quals=False):
+    """All alignments of `contig`, in file order -> ReadSet.  want_quals: the set also carries the QUAL column (ReadSet.qual, the layout of
+    include/c3r_io.h) — opt-in, as in bamio.BamFile.fetch: a set with qualities uploads them with every Engine.load_reads."""
     blocks = list(_bgzf_blocks(path))
     buf = b"".join(blocks)
     if buf[:4] != b"BAM\x01":
@@ -98,7 +99,7 @@ def read_contig(path, contig):
     if contig not in names:
         return ReadSet(np.zeros(0, READ_DTYPE), np.zeros(0, np.uint32), np.zeros(0, np.uint8))
     tid = names.index(contig)
-    recs, cigs, seqs = [], [], []
+    recs, cigs, seqs, quals = [], [], [], []
     coff = soff = 0
     n = len(buf)
     while p + 4 <= n:
@@ -118,12 +119,17 @@ def read_contig(path, contig):
             recs.append((pos, coff, len(cigar), l_seq, soff, flag, mapq, hp, 0))
             cigs.append(cigar)
             seqs.append(seq)
+            if want_quals:
+                qual = np.full(2 * nb, 0xff, np.uint8)
+                qual[:l_seq] = np.frombuffer(buf, dtype=np.uint8, count=l_seq, offset=s0 + nb)
+                quals.append(qual)
             coff += len(cigar)
             soff += nb
         p = end
     reads = np.array(recs, dtype=READ_DTYPE) if recs else np.zeros(0, READ_DTYPE)
     return ReadSet(reads, np.concatenate(cigs) if cigs else np.zeros(0, np.uint32),
-                   np.concatenate(seqs) if seqs else np.zeros(0, np.uint8))
+                   np.concatenate(seqs) if seqs else np.zeros(0, np.uint8),
+                   (np.concatenate(quals) if quals else np.zeros(0, np.uint8)) if want_quals else None)
 
 
 def _bgzf_write(f, payload):
@@ -154,11 +160,12 @@ def write_bam(path, contigs, contig_reads, sample="SAMPLE"):
             cig = rs.cigar[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["n_cigar"])]
             nb = (int(r["l_seq"]) + 1) // 2
             seq = rs.seq[int(r["seq_off"]):int(r["seq_off"]) + nb].tobytes()
+            qual = b"\xff" * int(r["l_seq"]) if rs.qual is None else rs.qual[2 * int(r["seq_off"]):2 * int(r["seq_off"]) + int(r["l_seq"])].tobytes()
             aux = b""
             if r["hp"]:
                 aux = b"HPC" + struct.pack("<B", int(r["hp"]))
             body = struct.pack("<iiBBHHHiiii", tid, int(r["pos"]), len(qname), int(r["mapq"]), 4680, len(cig), int(r["flag"]),
-                               int(r["l_seq"]), -1, -1, 0) + qname + cig.astype("<u4").tobytes() + seq + b"\xff" * int(r["l_seq"]) + aux
+                               int(r["l_seq"]), -1, -1, 0) + qname + cig.astype("<u4").tobytes() + seq + qual + aux
             out += struct.pack("<i", len(body)) + body
     with open(path, "wb") as f:
         _bgzf_write(f, bytes(out))

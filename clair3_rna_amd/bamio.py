@@ -10,7 +10,7 @@ import numpy as np
 from .reads import READ_DTYPE, ReadSet
 
 EXPORTS = ["c3r_bam_open", "c3r_bam_close", "c3r_bam_last_error", "c3r_bam_n_contigs", "c3r_bam_contig", "c3r_bam_has_index", "c3r_bam_contig_weight",
-           "c3r_bam_fetch", "c3r_bam_copy", "c3r_bam_index_build", "c3r_bam_header_text", "c3r_bam_write_haplotagged", "c3r_vcf_merge", "c3r_vcf_compress", "c3r_vcfz_open", "c3r_vcfz_write",
+           "c3r_bam_fetch", "c3r_bam_copy", "c3r_bam_want_quals", "c3r_bam_copy_quals", "c3r_bam_index_build", "c3r_bam_header_text", "c3r_bam_write_haplotagged", "c3r_vcf_merge", "c3r_vcf_compress", "c3r_vcfz_open", "c3r_vcfz_write",
            "c3r_vcfz_close", "c3r_vcfz_piece_make", "c3r_vcfz_append", "c3r_vcfz_piece_free", "c3r_fasta_fetch", "c3r_io_alloc", "c3r_io_free"]
 _LIB = None
 
@@ -33,6 +33,8 @@ def load_library():
         L.c3r_bam_contig_weight.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.c3r_bam_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64] + [C.POINTER(C.c_int64)] * 3
         L.c3r_bam_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.c3r_bam_want_quals.argtypes = [C.c_void_p, C.c_int]
+        L.c3r_bam_copy_quals.argtypes = [C.c_void_p, C.c_void_p]
         L.c3r_bam_index_build.argtypes = [C.c_char_p, C.c_char_p]
         L.c3r_bam_header_text.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64)]
         L.c3r_bam_write_haplotagged.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int,
@@ -110,7 +112,9 @@ class BamFile:
             out[name] = (nm.value, fb.value)
         return out
 
-    def fetch(self, contig, beg0=0, end0=None):
+    def fetch(self, contig, beg0=0, end0=None, want_quals=False):
+        """want_quals: the ReadSet also carries the QUAL column (c3r_bam_want_quals / c3r_bam_copy_quals)."""
+        self.L.c3r_bam_want_quals(self.h, int(bool(want_quals)))
         n, nc, ns = C.c_int64(), C.c_int64(), C.c_int64()
         rc = self.L.c3r_bam_fetch(self.h, contig.encode(), int(beg0), int(end0) if end0 else 0, C.byref(n), C.byref(nc), C.byref(ns))
         if rc != 0:
@@ -119,7 +123,12 @@ class BamFile:
         cigar = huge_empty(nc.value, np.uint32)
         seq = huge_empty(ns.value, np.uint8)
         self.L.c3r_bam_copy(self.h, reads.ctypes.data, cigar.ctypes.data, seq.ctypes.data)
-        return ReadSet(reads, cigar, seq)
+        qual = None
+        if want_quals:
+            qual = huge_empty(2 * ns.value, np.uint8)
+            if self.L.c3r_bam_copy_quals(self.h, qual.ctypes.data) != 0:
+                raise IOError("c3r_bam_copy_quals: %s" % self.L.c3r_bam_last_error(self.h).decode())
+        return ReadSet(reads, cigar, seq, qual)
 
     def header_text(self):
         """The header text as bytes (what a new @PG line is chained to)."""

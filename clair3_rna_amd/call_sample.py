@@ -43,10 +43,10 @@ only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line
 hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU into
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
 `--phase_indels` (with --phase_output) hands hap_vcf --indels: heterozygous insertions, deletions and rows with two ALT alleles are phased too,
-by CIGAR-position alleles (no realignment, no left-alignment, no base qualities); without it both files are what they were.
+by CIGAR-position alleles (no realignment, no left-alignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)); without it both files are what they were.
 `--left_align_indels` (with one of --phase_indels, --haplotag_indels, --phasing_indels) lifts "no left-alignment" for every step that reads indels: the flag and
 --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h: c3r_set_hap_left_align).  A shift stops at a read's M run's
-start, at an N or another indel; there is still no realignment and there are no base qualities; agreement with whatshap is not measured.
+start, at an N or another indel; there is still no realignment and there are no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap is not measured.
 `--haplotagged_bam` (same conditions as --phase_output, and combinable with it) adds the step the reference's "Haplotag the BAM" commands stand
 for: haplotag_bam writes <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai for the contigs the run processed — every record of the
 contig, with the HP / PS tags the GPU computed from the phase table the second pass read; without the flag nothing changes.
@@ -195,10 +195,17 @@ def build_parser():
       help="with --phase_indels, --haplotag_indels or --phasing_indels: left-align the indels those steps read — the tables' against --ref_fn, "
            "every read's inside its own M run, on the device (include/c3r.h: c3r_set_hap_left_align) — so that a read whose aligner placed an "
            "indel elsewhere in a homopolymer or short tandem repeat shows the allele and not the reference; the flag is handed to every such "
-           "step.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities")
+           "step.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)")
+    a("--hap_min_bq", type=int, default=0, metavar="N",
+      help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: a base whose quality is below N does not vote — every step that "
+           "holds reads against a site table (phase_vcf between the passes, the 30-channel pass's haplotagging, hap_vcf, haplotag_bam) gets the flag, "
+           "fetches the qualities and reads such a base as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  The tensor build and "
+           "the unphased pass never look at it.  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads "
+           "without qualities are never masked; agreement with whatshap is not measured")
     a("--phase_indels", action="store_true",
       help="with --phase_output: handed to hap_vcf as --indels — heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2) are "
-           "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels unless --left_align_indels is given, no base qualities), and the counts "
+           "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels unless --left_align_indels is given, no base qualities "
+           "(`--hap_min_bq` lifts it: a threshold, not weights)), and the counts "
            "file gets the column ALLELES")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
@@ -257,8 +264,9 @@ class _Fetcher(object):
 
     PART_BP = 24_000_000                 # shortest range worth a fetch of its own
 
-    def __init__(self, bam_fn, ref_fn):
+    def __init__(self, bam_fn, ref_fn, want_quals=False):
         self.bam_fn, self.ref_fn, self.tls = bam_fn, ref_fn, threading.local()
+        self.want_quals = bool(want_quals)   # --hap_min_bq: the parts carry the base qualities, two bytes per sequence byte
         self.handles, self.fai = [], None
         self.lock = threading.Lock()
 
@@ -285,8 +293,8 @@ class _Fetcher(object):
         """The alignments that START in [beg0, end0) (a fetch returns everything that overlaps the range: what started before it
         belongs to the range before) -> ReadSet views, offsets relative to this part."""
         if self.bam_fn.endswith(".npz"):
-            return io.load_reads(self.bam_fn, ctg)
-        rs = self._handle().fetch(ctg, beg0, end0)
+            return io.load_reads(self.bam_fn, ctg, **(dict(want_quals=True) if self.want_quals else {}))
+        rs = self._handle().fetch(ctg, beg0, end0, **(dict(want_quals=True) if self.want_quals else {}))
         if beg0 > 0 and len(rs.reads):
             i0 = int(np.searchsorted(rs.reads["pos"], beg0, side="left"))
             if i0:
@@ -295,6 +303,8 @@ class _Fetcher(object):
                 c0, s0 = int(rs.reads["cigar_off"][i0]), int(rs.reads["seq_off"][i0])
                 out = ReadSet.__new__(ReadSet)
                 out.reads, out.cigar, out.seq = rs.reads[i0:], rs.cigar[c0:], rs.seq[s0:]
+                if rs.qual is not None:
+                    out.qual = rs.qual[2 * s0:]
                 out.base = (c0, s0)
                 return out
         return rs
@@ -321,6 +331,8 @@ class _Fetcher(object):
         out.reads = bamio.huge_empty(sum(len(p_.reads) for p_ in parts), READ_DTYPE)
         out.cigar = bamio.huge_empty(sum(len(p_.cigar) for p_ in parts), np.uint32)
         out.seq = bamio.huge_empty(sum(len(p_.seq) for p_ in parts), np.uint8)
+        if parts[0].qual is not None:
+            out.qual = bamio.huge_empty(2 * len(out.seq), np.uint8)
         r0 = c0 = s0 = 0
         for p_ in parts:
             nr, nc, ns = len(p_.reads), len(p_.cigar), len(p_.seq)
@@ -330,6 +342,8 @@ class _Fetcher(object):
             out.reads["seq_off"][r0:r0 + nr] += np.uint64((s0 - bs) & 0xffffffffffffffff)
             out.cigar[c0:c0 + nc] = p_.cigar
             out.seq[s0:s0 + ns] = p_.seq
+            if out.qual is not None:
+                out.qual[2 * s0:2 * (s0 + ns)] = p_.qual
             r0 += nr; c0 += nc; s0 += ns
         return out
 
@@ -418,6 +432,10 @@ def _plan(args):
     if left_align and not (args.phase_indels or args.haplotag_indels or args.phasing_indels):
         sys.exit("[ERROR] --left_align_indels needs one of --phase_indels, --haplotag_indels, --phasing_indels (it left-aligns the indels those steps read)")
     la = ["--left_align_indels", "--ref_fn", args.ref_fn] if left_align else []
+    from . import phasing
+    min_bq = phasing.hap_min_bq_arg(args, bool(phased and (builtin or args.phased_vcf_fn)),
+                                    "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step holds the reads against one")
+    bq = ["--hap_min_bq", str(min_bq)] if min_bq else []
     ext = ".vcf" if args.no_compress else ".vcf.gz"
     phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
     ctg = ["--ctg_name", args.ctg_name] if args.ctg_name else []
@@ -444,6 +462,7 @@ def _plan(args):
         one_process("--phasing builtin", "run the unphased pass, `python -m clair3_rna_amd.phase_vcf`, and the pass with --phased_vcf_fn as three commands")
         first, second = copy.copy(args), copy.copy(args)
         first.phasing, first.enable_phasing_model = None, False
+        first.hap_min_bq = 0                                  # (the unphased pass holds its reads against no site table: phase_vcf loads them itself)
         second.phasing, second.phased_vcf_fn = None, phased_dir
         if args.phasing_indels:
             second.haplotag_indels = True                     # (the table of c3r_set_phase_alleles, as --phased_vcf_fn DIR --haplotag_indels)
@@ -453,7 +472,7 @@ def _plan(args):
         steps = [_Step("pass", first, None),
                  _Step("clear", (phased_dir, lambda name: name.startswith("phased_") and name.endswith(".vcf.gz")), None),
                  _Step("phase_vcf", ["--vcf_fn", unphased, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(args.phase_merge_levels)]
-                       + (["--indels"] + la if args.phasing_indels else []) + ctg + gpu, unphased),
+                       + (["--indels"] + la if args.phasing_indels else []) + bq + ctg + gpu, unphased),
                  _Step("pass", second, None)]
     stem = os.path.join(args.output_dir, args.output_prefix + "_enable_phasing")
     source = phased_dir if builtin else args.phased_vcf_fn
@@ -463,14 +482,14 @@ def _plan(args):
     if args.phase_output:
         steps.append(_Step("hap_vcf", ["--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext, "--hap_counts_fn",
                                        stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if args.phase_indels else []) + tag_indels
-                           + (la if args.phase_indels or tag_indels else []) + ctg + gpu,
+                           + (la if args.phase_indels or tag_indels else []) + bq + ctg + gpu,
                            stem + ext))
     if args.haplotagged_bam:
         # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed (--ctg_name: added when the step runs); an
         # earlier run's files in this directory, for contigs this run did not process, go first
         bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
         steps += [_Step("clear", (bam_dir, lambda name: name.endswith(".bam") or name.endswith(".bam.bai")), stem + ext),
-                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + gpu, stem + ext)]
+                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + gpu, stem + ext)]
     return steps
 
 
@@ -500,7 +519,8 @@ def Run(args, log=None):
 # ---- one pass.  Stage 1: set-up
 class _Pass(object):
     """What set-up (_set_up) leaves for the other stages of a pass, as plain attributes; nothing is added to it afterwards:
-        the run        args, log, t_all, timeline, compat (which samtools' column text), channels, qual_rows, qual_merge, weights
+        the run        args, log, t_all, timeline, compat (which samtools' column text), channels, qual_rows, qual_merge, weights,
+                       hap_min_bq (--hap_min_bq of a pass with a phase table, else 0)
         the ranks      rank, world, dist (torch.distributed or None), n_thr (the threads this process may count on)
         the paths      out_dir, out_fn, out_nt_fn, parts_dir, split_dir, cmd_fn, bed_fn, vcf_fn (genotyping mode), bam_fn (the one fetched from)
         the plan       all_contigs and chunk_nums (plan_chunks), contigs (this rank's, in calling order), fai ({contig: length})
@@ -586,7 +606,8 @@ def _set_up(args, log, t_all):
     p.edits = sort_vcf.ContigEdits(p.table)                            # (one for all the per-contig mergers of this rank)
     p.merger = sort_vcf.SampleMerger(p.out_fn, header, p.qual_merge, args.print_ref_calls, p.table, p.out_nt_fn, stream_gz=not args.no_compress,
                                      edits=p.edits) if p.rank == 0 else None
-    p.fetcher = _Fetcher(p.bam_fn, args.ref_fn)
+    p.hap_min_bq = int(getattr(args, "hap_min_bq", 0) or 0) if args.phased_vcf_fn else 0       # (only a pass with a phase table tags reads)
+    p.fetcher = _Fetcher(p.bam_fn, args.ref_fn, want_quals=bool(p.hap_min_bq))
     p.phase_source = None                                              # --phased_vcf_fn: every contig's table is read on a fetch thread
     if args.phased_vcf_fn:
         from . import phasedvcf
@@ -816,7 +837,8 @@ def _device_stage(p, eng, ctg, rs, ref, phase):
         if not len(phase):
             rs.reads["hp"] = 0                       # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
     t = [time()]
-    eng.load_reads(rs); t.append(time())
+    from . import phasing
+    phasing.load_reads_min_bq(eng, rs, p.hap_min_bq if phase is not None else 0, ctg, p.log); t.append(time())
     eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str))); t.append(time())      # (the fetcher's array: upper-cased, used in place)
     if p.vcf_fn is not None:
         return ContigResult(ContigResult.CHUNKS, list(zip(regions, site_sets)))                   # genotyping mode: one scan per chunk (its own site list)

@@ -72,7 +72,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
            "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
            "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links",
-           "c3r_set_hap_left_align", "c3r_hap_left_align_sites"]
+           "c3r_set_hap_left_align", "c3r_hap_left_align_sites",
+           "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq"]
 
 _lib = None
 
@@ -102,6 +103,10 @@ def load_library():
     L.c3r_default_params.restype = None
     L.c3r_set_params.argtypes = [vp, C.POINTER(Params)]
     L.c3r_load_reads.argtypes = [vp, vp, i64, vp, i64, vp, i64]
+    L.c3r_load_reads_q.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.c3r_set_hap_min_bq.argtypes = [vp, i32]
+    L.c3r_get_hap_min_bq.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    L.c3r_get_hap_seq.argtypes = [vp, vp, i64]
     L.c3r_host_alloc.argtypes = [C.c_size_t]
     L.c3r_host_alloc.restype = vp
     L.c3r_host_free.argtypes = [vp]
@@ -201,9 +206,11 @@ def pinned_copy(a):
 
 
 def pinned_readset(rs):
-    """ReadSet with its three arrays in page-locked memory."""
+    """ReadSet with its arrays — the qualities too, when it carries them — in page-locked memory."""
     out = ReadSet.__new__(ReadSet)
     out.reads, out.cigar, out.seq = pinned_copy(rs.reads), pinned_copy(rs.cigar), pinned_copy(rs.seq)
+    if getattr(rs, "qual", None) is not None:
+        out.qual = pinned_copy(rs.qual)
     return out
 
 
@@ -260,6 +267,10 @@ class Engine(object):
     def load_reads(self, rs):
         assert isinstance(rs, ReadSet)
         self.readset = rs
+        if getattr(rs, "qual", None) is not None:        # (the base qualities go along: c3r_load_reads_q, for set_hap_min_bq)
+            self._chk(self.L.c3r_load_reads_q(self.h, _ptr(rs.reads), len(rs.reads), _ptr(rs.cigar), len(rs.cigar), _ptr(rs.seq), len(rs.seq),
+                                              _ptr(rs.qual), len(rs.qual)))
+            return
         self._chk(self.L.c3r_load_reads(self.h, _ptr(rs.reads), len(rs.reads), _ptr(rs.cigar), len(rs.cigar), _ptr(rs.seq), len(rs.seq)))
 
     def set_reference(self, ref_start, seq, upper_view=False):
@@ -328,6 +339,28 @@ class Engine(object):
         place inside its M run before they compare it with the table — which the caller normalises with hap_left_align_sites — and need a
         reference (set_reference) that covers the loaded reads.  With an allele table set and reads loaded the reads are tagged again."""
         self._chk(self.L.c3r_set_hap_left_align(self.h, 1 if on else 0))
+
+    def set_hap_min_bq(self, q):
+        """The opt-in threshold of --hap_min_bq (c3r_set_hap_min_bq, 0 .. 93, default 0 = off): while above 0, every call that holds the
+        loaded reads against a site table — the tagging of set_phase_sites / set_phase_alleles / load_reads, hap_counts, hap_allele_counts,
+        phase_links, phase_unit_links and their allele forms — reads a base whose quality is below q as N (a base without a quality, 0xff,
+        never).  Needs reads loaded with qualities (a ReadSet with `qual`); valid before or after load_reads with the same result; with a
+        phase table set and reads loaded the reads are tagged again.  A threshold, not quality weights."""
+        self._chk(self.L.c3r_set_hap_min_bq(self.h, int(q)))
+
+    def hap_min_bq(self):
+        """(q, n_masked): the threshold and the number of bases of the loaded reads that it masks (c3r_get_hap_min_bq)."""
+        q, n = C.c_int(), C.c_int64()
+        self._chk(self.L.c3r_get_hap_min_bq(self.h, C.byref(q), C.byref(n)))
+        return int(q.value), int(n.value)
+
+    def hap_seq(self):
+        """uint8[n_seq_bytes]: the packed bases that the site-table kernels read — the masked copy, or with q = 0 the loaded sequence
+        (c3r_get_hap_seq)."""
+        n = len(self.readset.seq) if getattr(self, "readset", None) is not None else 0
+        out = np.zeros(n, np.uint8)
+        self._chk(self.L.c3r_get_hap_seq(self.h, _ptr(out) if n else None, n))
+        return out
 
     @staticmethod
     def hap_left_align_sites(sites, pool, ref_start, ref, pool_bases=None):

@@ -205,7 +205,7 @@ struct HugeAlloc {
 template <class T> using hvec = std::vector<T, HugeAlloc<T>>;
 
 // a worker's share of a batch parsed on threads (kept with the handle: its capacity is reused batch after batch)
-struct RecPart { hvec<c3r_read_t> reads; hvec<uint32_t> cigar; hvec<uint8_t> seq; };
+struct RecPart { hvec<c3r_read_t> reads; hvec<uint32_t> cigar; hvec<uint8_t> seq, qual; };
 
 struct c3r_bam {
     Mapped file;
@@ -223,6 +223,10 @@ struct c3r_bam {
     hvec<c3r_read_t> reads;
     hvec<uint32_t> cigar;
     hvec<uint8_t> seq;
+    // base qualities (c3r_bam_want_quals): byte 2 * seq_off + j is the QUAL of base j; 2 * seq.size() bytes, the byte behind a read of
+    // odd length is 0xff.  Empty, and never touched, while want_quals is off.
+    bool want_quals = false, have_quals = false;
+    hvec<uint8_t> qual;
     std::vector<RecPart> parts;
     double t_inflate = 0, t_visit = 0, t_parse = 0;      // seconds of the current fetch (reported under C3R_TIMING)
 };
@@ -239,6 +243,7 @@ int failb(c3r_bam *b, int code, const char *fmt, ...) {
 // Where take_record puts what it keeps: the handle's own arrays, or a worker's part of a batch parsed on threads.
 struct RecSink {
     hvec<c3r_read_t> *reads; hvec<uint32_t> *cigar; hvec<uint8_t> *seq;
+    hvec<uint8_t> *qual = nullptr;      // nullptr: qualities are not collected
     bool malformed = false; int32_t bad_pos = 0; const char *bad_what = nullptr;
 };
 
@@ -342,11 +347,16 @@ int take_record_into(RecSink &o, const uint8_t *r, size_t block_size, int tid, i
     o.cigar->resize(cb + v.n_cig);
     for (uint32_t k = 0; k < v.n_cig; ++k) (*o.cigar)[cb + k] = le32(v.cig + 4 * k);
     o.seq->insert(o.seq->end(), r + v.s0, r + v.s0 + v.nb);
+    if (o.qual) {
+        o.qual->insert(o.qual->end(), r + v.s0 + v.nb, r + v.s0 + v.nb + v.l_seq);
+        if (v.l_seq & 1) o.qual->push_back(0xff);
+    }
     return 1;
 }
 
 int take_record(c3r_bam *b, const uint8_t *r, size_t block_size, int tid, int64_t beg, int64_t end) {
     RecSink o{&b->reads, &b->cigar, &b->seq};
+    if (b->want_quals) o.qual = &b->qual;
     const int rc = take_record_into(o, r, block_size, tid, beg, end);
     if (o.malformed) return malformed_record(b, o.bad_pos, o.bad_what);
     return rc;
@@ -369,8 +379,9 @@ bool take_records(c3r_bam *b, const std::vector<RecRef> &recs, int tid, int64_t 
     std::vector<RecSink> sinks(T);
     auto work = [&](size_t t) {
         RecPart &q = b->parts[t];
-        q.reads.clear(); q.cigar.clear(); q.seq.clear();
+        q.reads.clear(); q.cigar.clear(); q.seq.clear(); q.qual.clear();
         sinks[t] = RecSink{&q.reads, &q.cigar, &q.seq};
+        if (b->want_quals) sinks[t].qual = &q.qual;
         for (size_t i = n * t / T; i < n * (t + 1) / T; ++i)
             if (take_record_into(sinks[t], recs[i].p, recs[i].bs, tid, beg, end) == 2 && sinks[t].malformed) break;
     };
@@ -384,6 +395,7 @@ bool take_records(c3r_bam *b, const std::vector<RecRef> &recs, int tid, int64_t 
     if (nr > b->reads.capacity()) b->reads.reserve(std::max(nr, 2 * b->reads.capacity()));
     if (nc > b->cigar.capacity()) b->cigar.reserve(std::max(nc, 2 * b->cigar.capacity()));
     if (ns > b->seq.capacity()) b->seq.reserve(std::max(ns, 2 * b->seq.capacity()));
+    if (b->want_quals && 2 * ns > b->qual.capacity()) b->qual.reserve(std::max(2 * ns, 2 * b->qual.capacity()));
     for (size_t t = 0; t < T; ++t) {
         RecPart &q = b->parts[t];
         const uint32_t base_c = (uint32_t)b->cigar.size();
@@ -392,6 +404,7 @@ bool take_records(c3r_bam *b, const std::vector<RecRef> &recs, int tid, int64_t 
         b->reads.insert(b->reads.end(), q.reads.begin(), q.reads.end());
         b->cigar.insert(b->cigar.end(), q.cigar.begin(), q.cigar.end());
         b->seq.insert(b->seq.end(), q.seq.begin(), q.seq.end());
+        b->qual.insert(b->qual.end(), q.qual.begin(), q.qual.end());
         if (sinks[t].malformed) { malformed_record(b, sinks[t].bad_pos, sinks[t].bad_what); return false; }   // (what follows it is dropped, as in a serial pass)
     }
     return true;
@@ -650,6 +663,7 @@ int fetch_indexed(c3r_bam *b, int tid, int64_t beg, int64_t end) {
                 if (rc) return rc;
                 if (truncated && lim < b->file.n) {        // start over with more blocks (rare: a record longer than the margin)
                     b->reads.resize(n_reads0); b->cigar.resize(n_cig0); b->seq.resize(n_seq0);
+                    if (b->want_quals) b->qual.resize(2 * n_seq0);
                     continue;
                 }
                 done = true;
@@ -723,7 +737,8 @@ int c3r_bam_contig(c3r_bam *b, int i, const char **name, int64_t *length) {
 
 int c3r_bam_fetch(c3r_bam *b, const char *contig, int64_t beg0, int64_t end0, int64_t *n_reads, int64_t *n_cigar, int64_t *n_seq_bytes) {
     if (!b || !contig) return C3R_EINVAL;
-    b->reads.clear(); b->cigar.clear(); b->seq.clear();
+    b->reads.clear(); b->cigar.clear(); b->seq.clear(); b->qual.clear();
+    b->have_quals = b->want_quals;
     b->malformed = false;
     b->t_inflate = b->t_visit = b->t_parse = 0;
     const auto t_fetch0 = std::chrono::steady_clock::now();
@@ -739,7 +754,7 @@ int c3r_bam_fetch(c3r_bam *b, const char *contig, int64_t beg0, int64_t end0, in
             rc = scan_all(b, [&](const uint8_t *r, size_t bs, uint64_t, uint64_t) { return take_record(b, r, bs, tid, beg0, end0) != 2; });
         }
     }
-    if (rc == C3R_OK && b->malformed) { rc = C3R_EINVAL; b->reads.clear(); b->cigar.clear(); b->seq.clear(); }
+    if (rc == C3R_OK && b->malformed) { rc = C3R_EINVAL; b->reads.clear(); b->cigar.clear(); b->seq.clear(); b->qual.clear(); }
     if (getenv("C3R_TIMING") && b->reads.size() > 10000)
         fprintf(stderr, "[c3r_bam_fetch %s] %zu reads in %.0f ms: inflate %.0f ms, record walk %.0f ms, parse %.0f ms\n", contig, b->reads.size(),
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_fetch0).count(), 1e3 * b->t_inflate, 1e3 * b->t_visit, 1e3 * b->t_parse);
@@ -754,6 +769,19 @@ int c3r_bam_copy(c3r_bam *b, c3r_read_t *reads, uint32_t *cigar, uint8_t *seq) {
     if (reads && !b->reads.empty()) memcpy(reads, b->reads.data(), b->reads.size() * sizeof(c3r_read_t));
     if (cigar && !b->cigar.empty()) memcpy(cigar, b->cigar.data(), b->cigar.size() * 4);
     if (seq && !b->seq.empty()) memcpy(seq, b->seq.data(), b->seq.size());
+    return C3R_OK;
+}
+
+int c3r_bam_want_quals(c3r_bam *b, int on) {
+    if (!b) return C3R_EINVAL;
+    b->want_quals = on != 0;
+    return C3R_OK;
+}
+
+int c3r_bam_copy_quals(c3r_bam *b, uint8_t *qual) {
+    if (!b) return C3R_EINVAL;
+    if (!b->have_quals) return failb(b, C3R_EINVAL, "c3r_bam_copy_quals: the last fetch did not collect qualities (c3r_bam_want_quals was off)");
+    if (qual && !b->qual.empty()) memcpy(qual, b->qual.data(), b->qual.size());
     return C3R_OK;
 }
 

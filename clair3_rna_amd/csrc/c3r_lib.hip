@@ -28,6 +28,7 @@
 #include "haplotag_kernels.hpp"
 #include "phase_kernels.hpp"
 #include "hapcount_kernels.hpp"
+#include "qual_kernels.hpp"
 #include <sched.h>
 
 using namespace c3r;
@@ -166,6 +167,12 @@ struct c3r_ctx {
     bool phase_alleles = false;
     bool hap_la = false;                      // c3r_set_hap_left_align: the four allele kernels run their _la instantiation against d_ref
     DevBuf d_phase, d_hptag, d_hpps, d_phasea, d_phasepool;
+    // c3r_set_hap_min_bq: the threshold; whether the loaded reads came with qualities (c3r_load_reads_q); the qualities (2 n_seq_bytes, then
+    // 32 bytes of 0xff), the masked copy of d_seq that read_args hands out while the threshold is above 0 (n_seq_bytes, then 16 zeroed bytes,
+    // like d_seq) and the count of masked bases (k_mask_low_bq).  Nothing of it is allocated without qualities.
+    int hap_min_bq = 0;
+    bool has_qual = false;
+    DevBuf d_qual, d_hapseq, d_nmasked;
     // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
     DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
@@ -429,8 +436,29 @@ Args read_args(const c3r_ctx *ctx, int n) {
     Args a;
     memset(&a, 0, sizeof a);
     a.reads = (const DevRead *)ctx->d_reads.p; a.n_reads = n; a.serial = (const uint8_t *)ctx->d_serial.p; a.cigars = (const uint32_t *)ctx->d_rawcig.p;
-    a.seq = (const uint8_t *)ctx->d_seq.p;
+    a.seq = (const uint8_t *)(ctx->hap_min_bq > 0 && ctx->has_qual ? ctx->d_hapseq.p : ctx->d_seq.p);      // (c3r_set_hap_min_bq: the masked copy)
     return a;
+}
+// c3r_set_hap_min_bq above 0 and qualities on the device: the masked copy of d_seq, on the context's stream (nothing waits).  Flat over the
+// packed sequence, so it depends on neither the filters nor the read tables.
+int mask_low_bq(c3r_ctx *ctx) {
+    if (ctx->hap_min_bq <= 0 || !ctx->has_qual) return C3R_OK;
+    const long long nsb = ctx->n_seq_bytes, n_chunks = (nsb + 7) / 8;
+    if (int rc = ensure(ctx, ctx->d_hapseq, (size_t)nsb + 16)) return rc;
+    constexpr size_t count_bytes = (size_t)MASKBQ_SLOTS * MASKBQ_SLOT_WORDS * 8;
+    if (int rc = ensure(ctx, ctx->d_nmasked, count_bytes)) return rc;
+    HIPCHK(ctx, hipMemsetAsync((char *)ctx->d_hapseq.p + nsb, 0, 16, ctx->stream));         // (the walks read the packed bases 16 bytes at a time)
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_nmasked.p, 0, count_bytes, ctx->stream));
+    if (n_chunks == 0) return C3R_OK;
+    {
+        Launch L(ctx, "k_mask_low_bq");
+        const long long blocks = std::min<long long>((n_chunks + MASKBQ_THREADS - 1) / MASKBQ_THREADS, MASKBQ_MAX_BLOCKS);      // (the kernel strides over the rest)
+        hipLaunchKernelGGL(k_mask_low_bq, dim3((unsigned)blocks), dim3(MASKBQ_THREADS), 0, ctx->stream,
+                           (const uint8_t *)ctx->d_qual.p, (const uint8_t *)ctx->d_seq.p, (uint8_t *)ctx->d_hapseq.p, nsb, n_chunks, ctx->hap_min_bq,
+                           (unsigned long long *)ctx->d_nmasked.p);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return C3R_OK;
 }
 // The reference slice as the left-aligned observation reads it (c3r_set_hap_left_align), and the refusal of its four calls without one.
 HapRef hap_ref(const c3r_ctx *ctx) {
@@ -840,7 +868,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -901,7 +929,17 @@ int c3r_set_params(c3r_ctx *ctx, const c3r_params_t *p) {
 
 int c3r_load_reads(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const uint32_t *cigars, int64_t n_cigar_ops,
                    const uint8_t *seq4, int64_t n_seq_bytes) {
+    return c3r_load_reads_q(ctx, reads, n_reads, cigars, n_cigar_ops, seq4, n_seq_bytes, nullptr, 0);
+}
+
+int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const uint32_t *cigars, int64_t n_cigar_ops,
+                     const uint8_t *seq4, int64_t n_seq_bytes, const uint8_t *qual, int64_t n_qual_bytes) {
     if (!ctx || n_reads < 0 || n_cigar_ops < 0 || n_seq_bytes < 0 || (n_reads && (!reads || !cigars || !seq4))) return C3R_EINVAL;
+    if (qual && n_qual_bytes != 2 * n_seq_bytes)
+        return fail(ctx, C3R_EINVAL, "c3r_load_reads_q: %lld quality bytes for %lld sequence bytes (there are two per byte)", (long long)n_qual_bytes, (long long)n_seq_bytes);
+    if (!qual && n_qual_bytes != 0) return fail(ctx, C3R_EINVAL, "c3r_load_reads_q: %lld quality bytes and no array", (long long)n_qual_bytes);
+    if (!qual && n_reads > 0 && ctx->hap_min_bq > 0)               // (before anything of the previous load is given up)
+        return fail(ctx, C3R_EINVAL, "c3r_load_reads: c3r_set_hap_min_bq is %d and the reads come without qualities (c3r_load_reads_q)", ctx->hap_min_bq);
     if (n_reads >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many reads");
     if (n_cigar_ops >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many CIGAR ops");
     if (ctx->phase_alleles) if (int rc0 = hap_la_needs_ref(ctx, "c3r_load_reads")) return rc0;       // (before anything of the previous load is given up)
@@ -918,6 +956,8 @@ int c3r_load_reads(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const
     // c3r_host_alloc) and every table the tile kernels need is derived from them on the device
     if ((rc = ensure(ctx, ctx->d_rawreads, std::max<size_t>((size_t)n * sizeof(c3r_read_t), 16))) || (rc = ensure(ctx, ctx->d_rawcig, std::max<size_t>((size_t)n_cigar_ops * 4, 16))) ||
         (rc = ensure(ctx, ctx->d_seq, (size_t)n_seq_bytes + 16))) return rc;
+    ctx->has_qual = false;
+    if (qual && (rc = ensure(ctx, ctx->d_qual, 2 * (size_t)n_seq_bytes + 32))) return rc;
     upload_waiters(ctx->device).fetch_add(1);
     std::unique_lock<std::mutex> gate(upload_gate(ctx->device));
     upload_waiters(ctx->device).fetch_sub(1);
@@ -925,7 +965,9 @@ int c3r_load_reads(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const
         Launch l(ctx, "h2d_reads");           // (profiling: the three uploads as one entry of the kernel statistics — PCIe time, not a kernel)
         if ((rc = upload(ctx, ctx->d_rawreads, reads, (size_t)n)) || (rc = upload(ctx, ctx->d_rawcig, cigars, (size_t)n_cigar_ops))) return rc;
         if (n_seq_bytes && (rc = big_h2d(ctx, ctx->d_seq.p, seq4, (size_t)n_seq_bytes))) return rc;
+        if (qual && n_seq_bytes && (rc = big_h2d(ctx, ctx->d_qual.p, qual, 2 * (size_t)n_seq_bytes))) return rc;
     }
+    if (qual) HIPCHK(ctx, hipMemsetAsync((char *)ctx->d_qual.p + 2 * n_seq_bytes, 0xff, 32, ctx->stream));    // (k_mask_low_bq reads them 16 bytes at a time)
     HIPCHK(ctx, hipMemsetAsync((char *)ctx->d_seq.p + n_seq_bytes, 0, 16, ctx->stream));        // (the walk reads the packed bases 16 bytes at a time)
     if (upload_waiters(ctx->device).load() > 0) {
         // another context is waiting to upload: the link is handed over when THESE copies are through, not a first table pass later
@@ -935,6 +977,8 @@ int c3r_load_reads(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const
         gate.unlock();
     }
     ctx->n_seq_bytes = n_seq_bytes; ctx->n_cigar_ops = n_cigar_ops;
+    ctx->has_qual = qual != nullptr;
+    if ((rc = mask_low_bq(ctx))) return rc;                       // (before the haplotag launch of prepare_tables, on the same stream)
     if (n == 0) return C3R_OK;
     ctx->first_pos = std::max(reads[0].pos, 0);
     // the last read's position bounds the first guess of the bins (the records are sorted; an unsorted set fails in the first pass)
@@ -1415,6 +1459,50 @@ int c3r_set_hap_left_align(c3r_ctx *ctx, int on) {
     ctx->last_scan_pruned = false;
     ctx->host_cache.reset();
     return ::refilter(ctx);
+}
+
+int c3r_set_hap_min_bq(c3r_ctx *ctx, int min_bq) {
+    if (!ctx) return C3R_EINVAL;
+    if (min_bq < 0 || min_bq > 93) return fail(ctx, C3R_EINVAL, "c3r_set_hap_min_bq: %d is outside 0 .. 93", min_bq);
+    if (min_bq == ctx->hap_min_bq) return C3R_OK;
+    if (min_bq > 0 && ctx->n_reads > 0 && !ctx->has_qual)
+        return fail(ctx, C3R_EINVAL, "c3r_set_hap_min_bq: the loaded reads came without qualities (c3r_load_reads_q)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the copy first: while it cannot be made (its buffers are allocated before anything is written) the old threshold stays, and with it
+    // what read_args hands out
+    const int old_bq = ctx->hap_min_bq;
+    ctx->hap_min_bq = min_bq;
+    if (int rc = mask_low_bq(ctx)) { ctx->hap_min_bq = old_bq; return rc; }
+    if (!(ctx->n_phase > 0 && ctx->n_reads > 0 && ctx->has_qual)) return C3R_OK;
+    ctx->last_scan_pruned = false;                                 // the tags on the device are those of the other sequence
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
+int c3r_get_hap_min_bq(c3r_ctx *ctx, int *min_bq, int64_t *n_masked) {
+    if (!ctx) return C3R_EINVAL;
+    if (min_bq) *min_bq = ctx->hap_min_bq;
+    if (n_masked) {
+        unsigned long long m = 0;
+        if (ctx->hap_min_bq > 0 && ctx->has_qual && ctx->d_nmasked.p) {
+            std::vector<unsigned long long> slots((size_t)MASKBQ_SLOTS * MASKBQ_SLOT_WORDS);
+            HIPCHK(ctx, hipSetDevice(ctx->device));
+            HIPCHK(ctx, hipMemcpyAsync(slots.data(), ctx->d_nmasked.p, slots.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            for (int s = 0; s < MASKBQ_SLOTS; ++s) m += slots[(size_t)s * MASKBQ_SLOT_WORDS];
+        }
+        *n_masked = (int64_t)m;
+    }
+    return C3R_OK;
+}
+
+int c3r_get_hap_seq(c3r_ctx *ctx, uint8_t *seq4, int64_t cap) {
+    if (!ctx || cap < 0 || (cap && !seq4)) return C3R_EINVAL;
+    if (cap < ctx->n_seq_bytes) return fail(ctx, C3R_EOVERFLOW, "c3r_get_hap_seq: %lld bytes offered, %lld needed", (long long)cap, (long long)ctx->n_seq_bytes);
+    if (ctx->n_seq_bytes == 0) return C3R_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const void *src = ctx->hap_min_bq > 0 && ctx->has_qual ? ctx->d_hapseq.p : ctx->d_seq.p;
+    return big_d2h(ctx, seq4, src, (size_t)ctx->n_seq_bytes);
 }
 
 // The rule `left_align` of include/c3r.h on the host, for the table: base codes 1, 2, 4, 8 of the slice (0: outside, or not A, C, G, T).

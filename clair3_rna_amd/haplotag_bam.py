@@ -16,12 +16,13 @@ Contigs: --ctg_name, else every contig of the BAM header; a contig without a rec
 
 The tag rule is the one of include/c3r.h (c3r_set_phase_sites): ALL loaded reads are tagged, whatever excl_flags / min_mq say (secondary and
 supplementary alignments and MAPQ 0 included); every phased heterozygous SNV a read covers is one vote of unit weight for the haplotype
-whose allele the read shows at the CIGAR position; the read's set is the one with the most votes.  No realignment, no base qualities, no
+whose allele the read shows at the CIGAR position; the read's set is the one with the most votes.  No realignment, no base qualities
+(`--hap_min_bq` lifts it: a threshold, not weights), no
 indels, no tagging of a supplementary alignment after its primary.  Agreement with `whatshap haplotag` / `longphase haplotag` has not been
 measured.  --haplotag_indels: the phased insertions, deletions and two-ALT rows of the phased VCF vote too (c3r_set_phase_alleles:
 phasedvcf.contig_alleles -> Engine.set_phase_alleles), still as CIGAR-position alleles without left-alignment — unless --left_align_indels (with
 --ref_fn) is given: then the table's indels are left-aligned against the reference and every read's indel inside its own M run, on the device
-(include/c3r.h: c3r_set_hap_left_align); a shift stops at the run's start, at an N or another indel; still no realignment, no base qualities.
+(include/c3r.h: c3r_set_hap_left_align); a shift stops at the run's start, at an N or another indel; still no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights).
 
     python -m clair3_rna_amd.haplotag_bam --bam_fn x.bam --phased_vcf_fn out/tmp/phased_output/phased_vcf \\
         --output_dir out/tmp/phased_output/phased_bam
@@ -59,7 +60,7 @@ def build_parser():
     p = argparse.ArgumentParser(
         description="Write the haplotagged BAM of a phased run (one indexed <ctg>.bam per contig) with the HP / PS tags MI355X computes from the phased "
                     "VCF: all loaded reads are tagged whatever their flags or MAPQ, unit-weight votes of CIGAR-position alleles at phased "
-                    "heterozygous SNVs, no realignment, no base qualities.  Agreement with whatshap / longphase haplotag has not been measured")
+                    "heterozygous SNVs, no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights).  Agreement with whatshap / longphase haplotag has not been measured")
     a = p.add_argument
     a("-b", "--bam_fn", type=str, required=True, help="the BAM the phased VCF was made from (coordinate-sorted; an index beside it keeps every contig's pass short)")
     a("--phased_vcf_fn", type=str, required=True,
@@ -72,8 +73,10 @@ def build_parser():
     a("--left_align_indels", action="store_true",
       help="with --haplotag_indels: left-align the table's indels against --ref_fn and every read's indel inside its own M run, on the device "
            "(include/c3r.h: c3r_set_hap_left_align): the tags of a 30-channel pass that ran with this flag.  A shift stops at the M run's "
-           "start, at an N or another indel; no realignment, no base qualities; agreement with whatshap is not measured")
+           "start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap is not measured")
     a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
+    a("--hap_min_bq", type=int, default=0, metavar="N",
+      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     a("--threads", type=int, default=0, help="BGZF inflate / deflate threads; default: the CPUs this process may run on, 32 at the most")
     return p
@@ -86,7 +89,7 @@ def _version():
 
 def Run(args, log=None):
     """-> {contig: dict(records, tagged, stripped, unpaired, hp1, hp2, path)} of the files written."""
-    from . import bamio, capi, phasedvcf
+    from . import bamio, capi, phasedvcf, phasing
     log = log or (lambda m: print(m, file=sys.stderr))
     if not os.path.isfile(args.bam_fn):
         sys.exit("[ERROR] file %s not found" % args.bam_fn)
@@ -94,6 +97,7 @@ def Run(args, log=None):
     tag_indels = bool(getattr(args, "haplotag_indels", False))
     ref_of = left_align_reference(args, "--haplotag_indels", tag_indels)
     source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None else (None, ref_of)))
+    min_bq = phasing.hap_min_bq_arg(args, True, "")
     threads = int(getattr(args, "threads", 0) or 0)
     command = getattr(args, "command", None) or " ".join(sys.argv)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -110,7 +114,7 @@ def Run(args, log=None):
                 table = source.table(ctg)
                 rs = hp = ps = None
                 if len(table):
-                    rs = bf.fetch(ctg)                             # io.load_reads(bam, ctg) on the handle that is open already (--threads)
+                    rs = bf.fetch(ctg, **(dict(want_quals=True) if min_bq else {}))                             # io.load_reads(bam, ctg) on the handle that is open already (--threads)
                 if rs is not None and len(rs):
                     if eng is None:
                         eng = capi.Engine(gpu_id)
@@ -118,7 +122,7 @@ def Run(args, log=None):
                     if ref_of is not None:                         # (the whole contig: it covers every read)
                         eng.set_reference(*ref_of(ctg))
                     source.apply(eng, table)
-                    eng.load_reads(rs)
+                    phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()
                 elif rs is not None:                               # (no read record: nothing to launch; the contig's other records still go out)
                     hp, ps = np.zeros(0, np.uint8), np.zeros(0, np.int32)

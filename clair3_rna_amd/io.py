@@ -131,22 +131,28 @@ def save_reads(path, contig_reads):
         arrs["reads__" + name] = rs.reads
         arrs["cigar__" + name] = rs.cigar
         arrs["seq__" + name] = rs.seq
+        if rs.qual is not None:
+            arrs["qual__" + name] = rs.qual
     np.savez(path, **arrs)
 
 
-def load_reads(path, contig, beg0=None, end0=None):
+def load_reads(path, contig, beg0=None, end0=None, want_quals=False):
     """Read source of the per-chunk driver.  *.npz = flat read archive; *.bam = BGZF/BAM through libc3r_io.so
     (csrc/bamio.cpp): with a .bai only the BGZF blocks holding alignments that overlap the 0-based half-open region
-    [beg0, end0) are inflated — the `-r ctg:beg-end` of the reference's mpileup call (create_tensor_pileup.py:446-451)."""
+    [beg0, end0) are inflated — the `-r ctg:beg-end` of the reference's mpileup call (create_tensor_pileup.py:446-451).
+    want_quals: the ReadSet also carries the base qualities (--hap_min_bq); an archive written without them yields 0xff, "absent"."""
     if path.endswith(".npz"):
         z = np.load(path)
         key = "reads__" + contig
         if key not in z.files:
             return ReadSet(np.zeros(0, READ_DTYPE), np.zeros(0, np.uint32), np.zeros(0, np.uint8))
-        return ReadSet(z[key], z["cigar__" + contig], z["seq__" + contig])
+        qual = None
+        if want_quals:
+            qual = z["qual__" + contig] if "qual__" + contig in z.files else np.full(2 * len(z["seq__" + contig]), 0xff, np.uint8)
+        return ReadSet(z[key], z["cigar__" + contig], z["seq__" + contig], qual)
     from . import bamio
     with bamio.BamFile(path) as bf:
-        return bf.fetch(contig, beg0 or 0, end0)
+        return bf.fetch(contig, beg0 or 0, end0, want_quals=want_quals)
 
 
 # ----------------------------------------------------------------------------- weights

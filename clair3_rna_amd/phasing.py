@@ -229,6 +229,45 @@ def left_align_note(skipped):
     return ", %d left-aligned" % skipped.moved if isinstance(skipped, LeftAligned) else ""
 
 
+def hap_min_bq_arg(args, has_consumer, needs):
+    """A driver's --hap_min_bq (0: off, also when the parser has no such flag); refuses a value outside 0 .. 93 and the flag without a
+    step that holds reads against a site table (`has_consumer`; `needs`: what the message asks for)."""
+    import sys
+    q = int(getattr(args, "hap_min_bq", 0) or 0)
+    if q == 0:
+        return 0
+    if not 0 < q <= 93:
+        sys.exit("[ERROR] --hap_min_bq must lie between 0 and 93 (phred; 0: off)")
+    if not has_consumer:
+        sys.exit("[ERROR] --hap_min_bq needs %s (it masks low-quality bases for the steps that hold reads against a site table)" % needs)
+    return q
+
+
+def reads_without_quals(rs):
+    """How many reads of a ReadSet with qualities have bases and no quality (BAM: 0xff throughout; the first byte says it)."""
+    r = rs.reads[rs.reads["l_seq"] > 0]
+    return int((rs.qual[2 * r["seq_off"].astype(np.int64)] == 0xff).sum()) if len(r) else 0
+
+
+def load_reads_min_bq(eng, rs, q, ctg, log):
+    """The one place where a driver's engine meets --hap_min_bq (include/c3r.h: c3r_set_hap_min_bq): Engine.load_reads under the
+    threshold q.  q = 0: the plain load, nothing else.  Otherwise `rs` must carry qualities (io.load_reads(..., want_quals=True)); the
+    threshold is set before the load, one [INFO] line gives masked / total bases, and one [WARNING] line counts the reads without
+    qualities when there are any — they are not refused: none of their bases is masked."""
+    if not q:
+        eng.load_reads(rs)
+        return
+    if getattr(rs, "qual", None) is None:
+        raise ValueError("--hap_min_bq %d: the reads of %s were fetched without their qualities" % (q, ctg))
+    eng.set_hap_min_bq(q)
+    eng.load_reads(rs)
+    total = int(rs.reads["l_seq"].sum(dtype=np.int64)) if len(rs.reads) else 0
+    log("[INFO] %s: --hap_min_bq %d: %d of %d bases masked for haplotagging, counts and phasing votes" % (ctg, q, eng.hap_min_bq()[1], total))
+    without = reads_without_quals(rs)
+    if without:
+        log("[WARNING] %s: %d of %d reads carry no base qualities: --hap_min_bq masks none of their bases" % (ctg, without, len(rs.reads)))
+
+
 def _left_aligned_candidates(table, ref):
     """_allele_table's tuple after left_align_table; a row's strings get a third element, the row's own POS (the site may have moved)."""
     sites, pool, strings, skipped = table

@@ -124,7 +124,8 @@ int c3r_set_sites(c3r_ctx *ctx, const int32_t *sites, int64_t n);
  * the read's base there is the site's ref (allele 0) or alt (allele 1) — for haplotype 1 when allele == h1, else for haplotype 2; votes
  * are counted per phase set as (c1, c2); the read's phase set is the one with the most votes (equal: the one whose first voting site on
  * the read comes first); hp = 1 if c1 > c2, 2 if c2 > c1, else 0.  This is whatshap's per-phase-set majority with unit weights and the
- * allele read off the CIGAR position: no realignment, and no base-quality weights (the records carry no qualities).
+ * allele read off the CIGAR position: no realignment, and no base-quality weights (c3r_set_hap_min_bq, below, lifts it as far as a threshold does:
+ * a threshold, not weights).
  * n = 0 clears the table: nothing is launched then and the records' own hp count again.  C3R_EINVAL, naming the first bad index, for an
  * unsorted or repeated position, pos < 1, a base code other than 1, 2, 4, 8, ref == alt, h1 > 1 or ps < 0.  Valid before or after c3r_load_reads
  * with the same result: when reads are loaded their tables are rebuilt from the records the device holds (as c3r_set_params does for new
@@ -168,7 +169,7 @@ int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts
                    c3r_hap_assign_stats_t *stats);
 /* The same counts for a heterozygous call whose two alleles may be SNVs, insertions or deletions: `0/1` rows with an indel ALT and `1/2` rows
  * (`C  T,CGG`, `ACC  A,TCC`).  Opt-in (hap_vcf --indels), like `whatshap phase --indels`.  The alleles are read off the CIGAR position: no
- * realignment, no left-alignment of the reads' indels, no base qualities; agreement with `whatshap --indels` is not measured.  This is where
+ * realignment, no left-alignment of the reads' indels, no base qualities (c3r_set_hap_min_bq lifts it: a threshold, not weights); agreement with `whatshap --indels` is not measured.  This is where
  * the rule is stated; phasing.allele_candidates_from_vcf, csrc/hapcount_kernels.hpp and tests/hapalleleref.py restate it.
  *
  * Alleles of a VCF row: REF r and an ALT a, upper-cased, letters of ACGT only; the common SUFFIX is stripped while both are longer than one
@@ -360,7 +361,7 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
  * does not depend on the walk a read takes: a read whose CIGAR holds two M-like ops in a row takes the serial walk while the switch is on
  * (the plain walk hands them out one by one; aligners that write = / X pay one lane per read there).
  * What remains: a shift stops at the M run's start, at an N or another indel, and at the slice's edge; there is no realignment and there
- * are no base qualities; agreement with whatshap is not measured.
+ * are no base qualities (c3r_set_hap_min_bq lifts it: a threshold, not weights); agreement with whatshap is not measured.
  *
  * c3r_set_hap_left_align(ctx, on): default 0.  While on, the four calls above run k_*_la (the same launches, one kernel each, with
  * hap_observe_la in hap_observe's place) against the slice of c3r_set_reference that is current when they run, and return C3R_EINVAL with a
@@ -375,6 +376,48 @@ int c3r_set_hap_left_align(c3r_ctx *ctx, int on);
 int c3r_hap_left_align_sites(const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, int64_t ref_start, const char *ref,
                              int64_t ref_len, c3r_hap_site_t *out_sites, uint8_t *out_pool, int64_t out_pool_cap, int64_t *out_pool_bases,
                              int64_t *src_index, int64_t *n_out, c3r_left_align_stats_t *stats);
+/* A base-quality threshold for the twelve kernels that hold the loaded reads against a site table: k_haplotag, k_hap_counts, k_phase_links,
+ * k_phase_unit_links, k_haplotag_alleles, k_hap_allele_counts, k_phase_allele_links, k_phase_allele_unit_links and the four _la
+ * instantiations — the tagging of c3r_set_phase_sites / c3r_set_phase_alleles / c3r_load_reads, c3r_hap_counts, c3r_hap_allele_counts,
+ * c3r_phase_links, c3r_phase_unit_links, c3r_phase_allele_links and c3r_phase_allele_unit_links.  Opt-in (--hap_min_bq); switched off,
+ * every launch, upload and output byte is what the contracts above say.  It lifts their "no base qualities" as far as a threshold does: on
+ * ONT direct-RNA reads a wrong base on a phased site is a unit-weight vote for the wrong haplotype, and its quality is the only evidence
+ * the read carries against it.  This is where the rule is stated; csrc/qual_kernels.hpp and tests/qualref.py restate it.
+ *
+ * Qualities (c3r_load_reads_q): qual[2 * n_seq_bytes]; the quality of base j of read i is byte 2 * reads[i].seq_off + j — one byte where
+ * the sequence has a nibble, so c3r_read_t has no field for it.  Values are phred as BAM stores them; a record without qualities holds
+ * 0xff throughout; the padding byte behind a read of odd length is 0xff (c3r_bam_copy_quals, include/c3r_io.h, delivers this layout).
+ *
+ * Rule: Q = hap_min_bq, 0 <= Q <= 93, Q = 0 is off.  With Q > 0, base j of a read is MASKED iff its quality byte q satisfies
+ * q < Q && q != 0xff: a base without a quality is never masked.  The twelve kernels read the reads' bases from a masked copy of the packed
+ * sequence in which a masked base is code 15 (N), and nothing else changes for them.  The contracts above say what an N means: no
+ * observation at an SNV site and at an allele site with base_matters; a pure indel site is still observed by its event; an insertion that
+ * holds an N equals no allele (column 2 of the counts, no vote in tags and links); under c3r_set_hap_left_align a shift stops at an N
+ * (an N never equals a reference code).  Hence the results with (qualities, Q) equal, element for element,
+ * the results with Q = 0 on reads whose masked bases the caller replaced by N.  Everything else reads the sequence as it was loaded: the
+ * tensor build and its tokens, the ordered recompute, the decoder's copy of the bases, c3r_rows_begin_ex.
+ * What remains: it is a threshold, not whatshap's quality-weighted votes; an indel's own quality is not modelled (an indel carries none in
+ * BAM); agreement with whatshap is not measured; the default is 0.
+ *
+ * c3r_load_reads_q is c3r_load_reads plus the qualities (c3r_load_reads is this call with qual = NULL, n_qual_bytes = 0).
+ * n_qual_bytes != 2 * n_seq_bytes: C3R_EINVAL.  The qualities go up like the three other arrays and stay on the device (2 bytes per
+ * sequence byte) until the next load; their buffer exists only once qualities were handed over.  With Q > 0 the masked copy is made
+ * (k_mask_low_bq, on the context's stream, before the tags) inside the load.  A load of n_reads > 0 WITHOUT qualities while Q > 0 is
+ * C3R_EINVAL, before anything of the previous load is given up: a threshold that silently does not apply is refused.  n_reads = 0 is allowed.
+ * c3r_set_hap_min_bq: C3R_EINVAL for a value outside 0 .. 93 (a threshold above every legal quality would mask everything) and for Q > 0
+ * while reads are loaded that came without qualities; the context stays as it was, and so it does when the masked copy cannot be made
+ * (C3R_ENOMEM, C3R_EHIP: the old threshold stays in force; a failure of the tagging that follows loses the loaded reads' tables, as a
+ * failed c3r_set_params does).  Valid before or after the load with the same result:
+ * with reads loaded the copy is made again, and with a phase table set the reads are tagged again, as c3r_set_hap_left_align does.  The copy
+ * depends on neither min_mq nor excl_flags: c3r_set_params does not make it again.
+ * c3r_get_hap_min_bq: Q and the number of masked bases of the loaded reads (0 with Q = 0 or without qualities); either pointer may be NULL.
+ * c3r_get_hap_seq: the n_seq_bytes bytes that the twelve kernels read — the masked copy, or with Q = 0 the sequence itself — into
+ * seq4[cap]; C3R_EOVERFLOW when cap is smaller. */
+int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, const uint32_t *cigars, int64_t n_cigar_ops, const uint8_t *seq4,
+                     int64_t n_seq_bytes, const uint8_t *qual, int64_t n_qual_bytes);
+int c3r_set_hap_min_bq(c3r_ctx *ctx, int min_bq);
+int c3r_get_hap_min_bq(c3r_ctx *ctx, int *min_bq, int64_t *n_masked);
+int c3r_get_hap_seq(c3r_ctx *ctx, uint8_t *seq4, int64_t cap);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped

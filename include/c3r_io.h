@@ -48,6 +48,14 @@ int c3r_bam_fetch(c3r_bam *b, const char *contig, int64_t beg0, int64_t end0, in
 /* Copy the result of the last fetch: reads[n_reads] (cigar_off / seq_off index the other two arrays),
  * cigar[n_cigar] BAM-encoded (len<<4|op), seq[n_seq_bytes] 4-bit packed, (l_seq+1)/2 bytes per read. */
 int c3r_bam_copy(c3r_bam *b, c3r_read_t *reads, uint32_t *cigar, uint8_t *seq);
+/* Base qualities, for c3r_load_reads_q / c3r_set_hap_min_bq (include/c3r.h).  c3r_bam_want_quals(b, 1): every later fetch also collects
+ * the QUAL column of the records it keeps; off by default, and while off a fetch does and costs what it did without these calls.
+ * c3r_bam_copy_quals copies the qualities of the last fetch: qual[2 * n_seq_bytes], the quality of base j of read i is byte
+ * 2 * reads[i].seq_off + j — one byte where the sequence has a nibble, so the record needs no field for it — as the file stores it
+ * (phred, 0xff throughout for a record without qualities); the padding byte behind a read of odd length is 0xff.  C3R_EINVAL when the
+ * last fetch did not collect them. */
+int c3r_bam_want_quals(c3r_bam *b, int on);
+int c3r_bam_copy_quals(c3r_bam *b, uint8_t *qual);
 
 /* `samtools index` equivalent (samtools is not a dependency of this path): write a .bai for a
  * coordinate-sorted BAM. */

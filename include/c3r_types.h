@@ -3,9 +3,11 @@
  *
  * The read record is the flat, device-friendly form of one BAM alignment: exactly the fields
  * `samtools mpileup` consumes when the reference spawns it at src/create_tensor_pileup.py:436-451
- * (core.pos, flag, MAPQ, CIGAR, 4-bit SEQ, optional HP aux tag).  Base qualities are not carried:
+ * (core.pos, flag, MAPQ, CIGAR, 4-bit SEQ, optional HP aux tag).  Base qualities have no field here:
  * the reference always runs with --min-BQ 0 (shared/param_p.py:21, call_var_bam.py:205-228) and
- * never reads the QUAL column.
+ * never reads the QUAL column, and neither does the tensor build.  The opt-in threshold of
+ * c3r_set_hap_min_bq (include/c3r.h) takes them as an array of its own beside the packed sequence
+ * (c3r_load_reads_q): byte 2 * seq_off + j is the quality of base j — one byte where SEQ has a nibble.
  */
 #ifndef C3R_TYPES_H
 #define C3R_TYPES_H
