@@ -577,7 +577,7 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     const auto t_begin = std::chrono::steady_clock::now();
     // bins from the first read's position (the records are sorted) to a guess of the largest end: the last read's position plus 2 Mb —
     // when a read reaches further (the device knows after the first pass) the table grows and the pass runs again
-    int64_t want_end = std::max<int64_t>(last_pos, ctx->first_pos) + ((int64_t)1 << 21);
+    int64_t want_end = std::max<int64_t>(last_pos, ctx->first_pos) + BIN_END_GUESS;
     LoadStats hs;
     for (int attempt = 0;; ++attempt) {
         const int32_t base = ctx->first_pos >> BIN_SHIFT;

@@ -371,6 +371,9 @@ __host__ __device__ __forceinline__ uint32_t cnt_at(uint32_t b) {          // (_
 #endif
 constexpr int WG_TAB_PAIRS = C3R_WG_TAB_PAIRS, WG_TAB_WORDS = 2 * WG_TAB_PAIRS + 4;      // PrepArgs::wg_tab: a 4-KB slab per workgroup; a workgroup with more occupied slots
                                                                              // (long reads far apart) says so ([0] = ~0) and the second pass counts again
+// The host's first guess of the largest end (prepare_tables, c3r_lib.hip): the bin table reaches this far beyond the last read's start; a read
+// that ends further away makes the table grow and the first pass run again.
+constexpr int64_t BIN_END_GUESS = (int64_t)1 << 21;
 // slot of `bin`, or -1: not there (insert: and no free slot among its HB_PROBES places — such a bin goes to the global counter directly,
 // in every walk alike, because an occupied slot never becomes free)
 __device__ __forceinline__ int hb_find(BinHash &T, uint32_t bin, bool insert) {

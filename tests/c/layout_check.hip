@@ -24,6 +24,17 @@ ROUTE_CONST(c3r::GIANT_SLOTS == 256, "GIANT_SLOTS, the giant spans of a scan tha
 ROUTE_CONST(c3r::FUSE_IN == 224 && c3r::TILE == 256 && C3R_FLANK == 16, "FUSE_IN / TILE / C3R_FLANK, the positions of a span,");
 ROUTE_CONST(c3r::OP_CHOP == 30, "OP_CHOP, the positions of one record,");
 
+// The limits of c3r_load_reads that tests/test_gpu_load_edges.py and tests/test_load_edges_ref.py size their cases by (tests/helpers.py holds the same numbers)
+#define LOAD_CONST(expr, what) static_assert(expr, what " changed: update tests/helpers.py (the load-edge generators), tests/test_load_edges_ref.py and tests/test_gpu_load_edges.py")
+LOAD_CONST(c3r::HB == 1024 && c3r::HB_LOG == 10, "HB, the slots of k_prep's LDS hash,");
+LOAD_CONST(c3r::HB_PROBES == 16, "HB_PROBES, the places a bin may take in that hash,");
+LOAD_CONST(c3r::WG_TAB_PAIRS == 510 && c3r::WG_TAB_WORDS * 4 == 4096, "WG_TAB_PAIRS, the bins of a workgroup's slab (above it the second pass counts again),");
+LOAD_CONST(c3r::PREP_READS == 16 && c3r::PREP_THREADS == 256 && c3r::PREP_GRP == 16, "PREP_READS, the reads of a k_prep workgroup,");
+LOAD_CONST(c3r::PM_BLK == 1024, "PM_BLK, the reads of a k_prefmax_bins block,");
+LOAD_CONST(c3r::BS_BLK == 4096, "BS_BLK, the bins of a k_bin_scan block,");
+LOAD_CONST(c3r::BIN_END_GUESS == (1 << 21), "BIN_END_GUESS, how far beyond the last read's start the bin table is sized before the ends are known,");
+LOAD_CONST(c3r::BIN_SHIFT == 5 && c3r::CBIN_SHIFT == 3, "BIN_SHIFT / CBIN_SHIFT, the positions of a bin (32) and the bins of a coarse bin (8),");
+
 // The scans' control blocks (pileup_kernels.hpp: ScanCtl + ScanCtlLayout for c3r_ctx::d_lb, ColCtl for ::d_small).  The kernels take pointers to single
 // words and the host reads the blocks back by field: every field stays on the byte it had when the host addressed it by number.
 #define CTL_AT(S, field, off) static_assert(offsetof(c3r::S, field) == off, #S "::" #field " has moved")

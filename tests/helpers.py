@@ -883,3 +883,181 @@ def shallow_locus_beside_a_deep_one(n_deep, deep_len=60, n_shallow=12, fwd_every
     alt = "A" if ref[170] != "A" else "C"
     recs += [dict(pos=150, cigar="60M", seq=ref[150:170] + alt + ref[171:210], flag=16 * (i % 2)) for i in range(n_shallow)]
     return ref, ReadSet.from_records(recs)
+
+
+# ---- read sets sized for the limits of c3r_load_reads (reads_kernels.hpp: k_prep, k_prefmax_bins, k_bin_scan; c3r_lib.hip: prepare_tables).
+# tests/test_load_edges_ref.py holds each generator in its bracket against the oracle alone, tests/test_gpu_load_edges.py runs the engine.
+# The numbers below are the kernels' constants; tests/c/layout_check.hip ties each to its name.
+LOAD_BIN, LOAD_CBIN = 32, 256                  # positions of a bin (C3R_BIN_SHIFT = 5) and of a coarse bin (CBIN_SHIFT = 3)
+PREP_READS, HB, HB_PROBES, WG_TAB_PAIRS = 16, 1024, 16, 510          # reads of a k_prep workgroup; slots and probes of its LDS hash; pairs of its slab
+PM_BLK, BS_BLK = 1024, 4096                    # reads of a k_prefmax_bins block; bins of a k_bin_scan block
+BIN_END_GUESS = 1 << 21                        # prepare_tables sizes the bin table to the last read's start plus this
+OP_CHOP = 30                                   # positions of one record
+
+
+def random_reference(n, seed):
+    """n random bases as str, built with numpy."""
+    return np.frombuffer(b"ACGT", np.uint8)[np.random.RandomState(seed).randint(0, 4, n)].tobytes().decode()
+
+
+def _with_subs(ref, p0, n, sites):
+    """ref[p0:p0 + n] with a substitution on every reference position of `sites` that it covers (A, or C where the reference has A)."""
+    seq = list(ref[p0:p0 + n])
+    for p in sites:
+        if p0 <= p < p0 + n:
+            seq[p - p0] = "A" if ref[p] != "A" else "C"
+    return "".join(seq)
+
+
+def record_start_bins(recs):
+    """Per read, the set of 32-position bins that hold the start of one of its records — plain `<n>M` reads and the `aM0DbM` form that
+    the serial walk merges into one M: a record every OP_CHOP positions from the read's start."""
+    import re
+    out = []
+    for r in recs:
+        assert re.fullmatch(r"\d+M(0D\d+M)?", r["cigar"]), r["cigar"]
+        out.append(set((r["pos"] + q) // LOAD_BIN for q in range(0, cigar_ref_len(r["cigar"]), OP_CHOP)))
+    return out
+
+
+def workgroup_bins(recs):
+    """Per k_prep workgroup (16 consecutive reads): the distinct bins its records start in."""
+    b = record_start_bins(recs)
+    return [len(set().union(*b[i:i + PREP_READS])) for i in range(0, len(b), PREP_READS)]
+
+
+def workgroup_whole_bins(recs):
+    """Per k_prep workgroup: the bins that lie wholly inside one of its reads.  Records are cut every 30 positions, a bin has 32: every such
+    bin holds a record start, so this is a lower bound of workgroup_bins that needs no knowledge of where the cuts fall."""
+    out = []
+    for i in range(0, len(recs), PREP_READS):
+        bins = set()
+        for r in recs[i:i + PREP_READS]:
+            a, b = r["pos"], r["pos"] + cigar_ref_len(r["cigar"])
+            bins.update(range(-(-a // LOAD_BIN), b // LOAD_BIN))
+        out.append(len(bins))
+    return out
+
+
+def line_positions(lines):
+    return [int(l.split("\t")[1]) for l in lines]
+
+
+def reads_with_a_line(recs, lines):
+    """Per read: does some line's position (1-based) lie inside the read's alignment?"""
+    pos = np.array(sorted(set(line_positions(lines))), np.int64) - 1
+    return [bool(np.searchsorted(pos, r["pos"] + cigar_ref_len(r["cigar"])) > np.searchsorted(pos, r["pos"])) for r in recs]
+
+
+HASH_LOCI, HASH_PITCH, HASH_RLEN = 24, 8000, 5500
+
+
+def hash_exhaustion_case(seed=31):
+    """(ref, records): 24 loci 8000 positions apart, each two reads of 5500 M — the second 3 bases after the first, on the other strand and
+    with the other haplotype — with a substitution every 97 bases on the same reference positions in both; every third locus is written
+    `2750M0D2750M` (the serial walk).  Sixteen consecutive reads are eight loci that share no bin: 8 x 171 bins wholly inside a read, more
+    than the 1024 slots of k_prep's hash."""
+    L = 500 + HASH_LOCI * HASH_PITCH
+    ref = random_reference(L, seed)
+    recs = []
+    for i in range(HASH_LOCI):
+        p0 = 500 + i * HASH_PITCH
+        sites = range(p0 + 40, p0 + HASH_RLEN, 97)
+        cigar = "%dM0D%dM" % (HASH_RLEN // 2, HASH_RLEN // 2) if i % 3 == 0 else "%dM" % HASH_RLEN
+        for rep in range(2):
+            recs.append(dict(pos=p0 + 3 * rep, cigar=cigar, seq=_with_subs(ref, p0 + 3 * rep, HASH_RLEN, sites), flag=16 * rep, hp=1 + rep))
+    return ref, recs
+
+
+def hash_exhaustion_regions(L):
+    """Chunks of 20000 positions: their boundaries fall inside loci 2, 4, 7, ... (a locus covers 500 + 8000 i .. + 5503)."""
+    return [(a, min(a + 19999, L)) for a in range(1, L + 1, 20000)]
+
+
+def slab_overflow_case(seed=11):
+    """(ref, records) of tests/test_gpu_load.py's recount case: 12 loci of five reads, then 48 lone reads of 1300 M, one per 4 kb — sixteen
+    of them are a workgroup of 16 x 41 = 656 bins, above the slab's 510 pairs and below the hash's 1024 slots.  The lone reads carry a
+    substitution every 31 bases: with min_coverage = 1 every one is a candidate, and the 33-position windows of neighbouring candidates
+    overlap, so every position of a lone read — every record that a recounting workgroup places — lies inside a compared window."""
+    import random
+    rng = random.Random(seed)
+    pitch, rlen, n_loci, n_lone = 4000, 1300, 12, 48
+    L = (n_loci + n_lone) * pitch + 3000
+    ref = "".join(rng.choice("ACGT") for _ in range(L))
+    recs = []
+    for i in range(n_loci):                          # loci of five reads with the same mismatches
+        for rep in range(5):
+            p0 = 500 + i * pitch + rep * 3
+            seq = list(ref[p0:p0 + rlen])
+            for q in range(60 - rep * 3, rlen, 97):
+                seq[q] = "A" if ref[p0 + q] != "A" else "C"
+            recs.append(dict(pos=p0, cigar="%dM" % rlen, seq="".join(seq), flag=16 * (rep % 2)))
+    for i in range(n_lone):                          # ... and lone long reads, one per 4 kb
+        p0 = 500 + (n_loci + i) * pitch
+        recs.append(dict(pos=p0, cigar="%dM" % rlen, seq=_with_subs(ref, p0, rlen, range(p0 + 7, p0 + rlen, 31)), flag=16 * (i % 2)))
+    recs.sort(key=lambda r: r["pos"])
+    return ref, recs
+
+
+EDGE_REF_LEN, BRIDGE_CIGAR, BRIDGE_SKIP = 2300000, "60M2200000N60M", 2200000
+_edge_ref = []
+
+
+def edge_reference():
+    """The 2.3-Mb reference shared by the regrowth and the depth-cap-gate cases (built once)."""
+    if not _edge_ref:
+        _edge_ref.append(random_reference(EDGE_REF_LEN, 77))
+    return _edge_ref[0]
+
+
+def bridging_read(ref, pos, flag=0, mapq=60, hp=0, sites=None):
+    """`60M2200000N60M` at 0-based pos with substitutions on the reference positions `sites` (default: 20 and 45 bases into either segment)."""
+    far = pos + 60 + BRIDGE_SKIP
+    if sites is None:
+        sites = (pos + 20, pos + 45, far + 20, far + 45)
+    return dict(pos=pos, cigar=BRIDGE_CIGAR, seq=_with_subs(ref, pos, 60, sites) + _with_subs(ref, far, 60, sites), flag=flag, mapq=mapq, hp=hp)
+
+
+REGROW_BRIDGES, REGROW_SHORT, REGROW_SHORT0 = (1000, 1010, 1020, 1020), 3000, 2000
+
+
+def regrowth_case(bridge_mapq=7):
+    """(ref, records, near region, far region): four bridging reads that start at 1000, 1010 and 1020 (twice: mpileup's depth cap
+    can discard only a read that is not the first on its position) and end beyond 2.2 Mb, then 3000
+    reads of 50 M 20 positions apart (three blocks of k_prefmax_bins) with a substitution on every 37th reference position.  The last read
+    starts near 62 kb: the bridging reads' end lies beyond that plus 2 Mb, so the first pass of the load runs twice; the far region's
+    first read is found through prefix maxima that the bridging reads hold for all 3000 reads behind them."""
+    ref = edge_reference()
+    far = REGROW_BRIDGES[0] + 60 + BRIDGE_SKIP
+    sites = [q + o for q in (REGROW_BRIDGES[0], far) for o in (24, 33, 42, 51)]          # (positions that all four bridging reads cover)
+    recs = [bridging_read(ref, p, flag=16 * (k % 2), mapq=bridge_mapq, hp=1 + k % 2, sites=sites) for k, p in enumerate(REGROW_BRIDGES)]
+    for k in range(REGROW_SHORT):
+        p0 = REGROW_SHORT0 + 20 * k
+        recs.append(dict(pos=p0, cigar="50M", seq=_with_subs(ref, p0, 50, range(-(-p0 // 37) * 37, p0 + 50, 37)), flag=16 * (k % 2), hp=k % 3))
+    return ref, recs, (1, REGROW_SHORT0 + 20 * REGROW_SHORT + 100), (far - 250, far + 350)
+
+
+GATE_K, GATE_M = 30, 10
+GATE_FIRSTS, GATE_EDGES, GATE_DS = (1000, 1024), ("device", "host"), (-1, 0, 1)
+GATE_CAPS = (GATE_K + 2, GATE_K + GATE_M + 1, 0)
+
+
+def gate_edge(first, kind):
+    """The 0-based position on which a 256-position coarse bin begins, two bins behind the first read: the device counts its coarse bins from
+    the first read's 32-position bin (k_prep, k_bin_scan), the host's hot zones are absolute (depth_cap_mask)."""
+    return ((first >> 5) << 5) + 512 if kind == "device" else ((first >> 8) + 2) << 8
+
+
+def gate_case(first, kind, d, far=False):
+    """(ref, records, last position to scan): an anchor pair at `first`, K = 30 reads of 60 M whose exclusive end is edge + d, M = 10 reads of
+    60 M that start on the edge; every group with substitutions of its own.  far: one bridging read in front of the anchors, on the same
+    position — the bin table then spans more than 4096 coarse bins (k_bin_scan's coarse chain has more than one block)."""
+    ref = edge_reference()
+    edge = gate_edge(first, kind)
+    recs = [bridging_read(ref, first, mapq=60)] if far else []
+    recs += [dict(pos=first, cigar="60M", seq=_with_subs(ref, first, 60, (first + 30,)), flag=16 * k) for k in range(2)]
+    p0 = edge + d - 60
+    recs += [dict(pos=p0, cigar="60M", seq=_with_subs(ref, p0, 60, (p0 + 11, p0 + 50)), flag=16 * (k % 2), hp=k % 3) for k in range(GATE_K)]
+    recs += [dict(pos=edge, cigar="60M", seq=_with_subs(ref, edge, 60, (edge + 9, edge + 40)), flag=16 * (k % 2), hp=k % 3) for k in range(GATE_M)]
+    last = edge + 200
+    return (ref if far else ref[:last + 100]), recs, last
