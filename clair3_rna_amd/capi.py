@@ -68,7 +68,7 @@ class C3RError(RuntimeError):
 EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_error", "c3r_synchronize", "c3r_stream",
            "c3r_default_params", "c3r_set_params", "c3r_load_reads", "c3r_host_alloc", "c3r_host_free", "c3r_set_reference", "c3r_set_reference_view", "c3r_set_bed", "c3r_set_sites",
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
-           "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
+           "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_info", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
            "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
            "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links",
@@ -156,6 +156,7 @@ def load_library():
     L.c3r_rows_begin_ex.argtypes = [vp, i32, vp, vp, C.POINTER(vp)]
     L.c3r_rows_decode.argtypes = [vp, C.c_char_p, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     L.c3r_rows_get.argtypes = [vp, vp, i64]
+    L.c3r_rows_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.c3r_rows_free.argtypes = [vp]
     L.c3r_rows_free.restype = None
     L.c3r_decode_text.argtypes = [C.c_char_p, i64, vp, vp, i32, C.POINTER(C.c_char_p), vp, i32, i32, vp, i64, C.POINTER(i64)]
@@ -807,6 +808,14 @@ class RowSnapshot(object):
             return (buf[:n.value] if as_array else buf[:n.value].tobytes()), nr.value
         finally:
             self.free()
+
+    def info(self):
+        """-> (sites, token bytes, indel records) that the snapshot brought off the device (c3r_rows_info)."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = self.L.c3r_rows_info(self.h, C.byref(a), C.byref(b), C.byref(c))
+        if rc != 0:
+            raise C3RError(rc, "c3r_rows_info failed")
+        return a.value, b.value, c.value
 
     def free(self):
         if self.h:

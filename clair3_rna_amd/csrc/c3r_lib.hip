@@ -1649,18 +1649,11 @@ static int run_gather(c3r_ctx *ctx, int rescale, void *dst, bool with_sites, boo
 
 // exclusive scan of n ints in place on the context's stream, total to *d_total: one block for short inputs, three launches for long
 static int device_excl_scan(c3r_ctx *ctx, int32_t *d, int n, int32_t *d_total) {
-    if (n <= 4 * SCAN_BLK) {
-        Launch L(ctx, "k_excl_scan");
-        hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, ctx->stream, d, n, d_total);
-        return C3R_OK;
-    }
-    const int nb = (n + SCAN_BLK - 1) / SCAN_BLK;
-    int rc = ensure(ctx, ctx->d_scan_tops, (size_t)nb * 4 + 16);
-    if (rc) return rc;
+    const int nb = excl_scan_tops(n);                // (the routing and the launches: pileup_kernels.hpp, launch_excl_scan)
+    int rc;
+    if (nb && (rc = ensure(ctx, ctx->d_scan_tops, (size_t)nb * 4 + 16))) return rc;
     Launch L(ctx, "k_excl_scan");
-    hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(1024), 0, ctx->stream, d, n, (int32_t *)ctx->d_scan_tops.p);
-    hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, ctx->stream, (int32_t *)ctx->d_scan_tops.p, nb, d_total);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, ctx->stream, d, n, (const int32_t *)ctx->d_scan_tops.p);
+    launch_excl_scan(ctx->stream, d, n, d_total, (int32_t *)ctx->d_scan_tops.p);
     return C3R_OK;
 }
 
@@ -2741,6 +2734,7 @@ struct c3r_rows {
     TokRec *recs = nullptr; int64_t n_recs = 0;           // the tokens that carry an indel (k_pack_tokens), own allocation
     int ref_slot = -1; const char *ref = nullptr; size_t ref_len = 0; int64_t ref_start1 = 1;
     std::string rows; int64_t rows_count = 0;
+    int64_t info_sites = 0, info_tokb = 0, info_recs = 0; // c3r_rows_info: what left the device (kept when the inputs are released)
 };
 extern "C" {
 
@@ -2817,7 +2811,7 @@ int c3r_rows_begin_ex(c3r_ctx *ctx, int drop_ref_calls, const c3r_read_t *host_r
     const auto t0 = now();
     if (timing) (void)hipStreamSynchronize(ctx->stream);              // (separates the wait for the network from the copies in the report)
     const auto t1 = now();
-    // tokens leave the device packed (k_pack_tokens: a byte per token, 12-byte records for the tokens with an indel)
+    // tokens leave the device packed (k_pack_tokens: a byte per token, 16-byte records for the tokens with an indel)
     int rc = C3R_OK;
     if ((rc = ensure(ctx, ctx->d_tokb, (size_t)std::max<int64_t>(n_tok, 1))) || (rc = ensure(ctx, ctx->d_tokrec, (size_t)std::max<int64_t>(n_tok, 1) * sizeof(TokRec))) ||
         (rc = ensure(ctx, ctx->d_recoff, (size_t)n * 4 + 32)))
@@ -2856,6 +2850,7 @@ int c3r_rows_begin_ex(c3r_ctx *ctx, int drop_ref_calls, const c3r_read_t *host_r
     if ((rc = check_lstm_status(ctx, lstm_st))) return bail(rc);
     const auto t2 = now();
     r->n_recs = (int64_t)*(unsigned long long *)ctx->h_pack;
+    r->info_sites = n; r->info_tokb = n_tok; r->info_recs = r->n_recs;
     if (r->n_recs > 0) {
         r->recs = (TokRec *)huge_alloc((size_t)r->n_recs * sizeof(TokRec));
         if (!r->recs) return bail(fail(ctx, C3R_ENOMEM, "indel records of %lld tokens: allocation failed", (long long)r->n_recs));
@@ -2918,6 +2913,14 @@ int c3r_rows_decode(c3r_rows *r, const char *ctg, int qual, int show_ref, int64_
     for (unsigned t = 0; t < nt; ++t) { r->rows += part[t]; r->rows_count += cnt[t]; }
     *out_len = (int64_t)r->rows.size();
     if (n_rows) *n_rows = r->rows_count;
+    return C3R_OK;
+}
+
+int c3r_rows_info(const c3r_rows *r, int64_t *n_sites, int64_t *n_token_bytes, int64_t *n_indel_records) {
+    if (!r) return C3R_EINVAL;
+    if (n_sites) *n_sites = r->info_sites;
+    if (n_token_bytes) *n_token_bytes = r->info_tokb;
+    if (n_indel_records) *n_indel_records = r->info_recs;
     return C3R_OK;
 }
 

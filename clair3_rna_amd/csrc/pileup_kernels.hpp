@@ -1,5 +1,6 @@
 // pileup_kernels.hpp — gfx950 tensor-build kernels (K1): CIGAR walk -> per-position channel counts
-// in LDS -> candidate gates -> window gather.  Included by c3r_lib.hip only.
+// in LDS -> candidate gates -> window gather.  Included by c3r_lib.hip (and, for the row-export kernels at its end, by
+// tests/c/row_export_check.hip: the header compiles on its own).
 //
 // What it replaces (reference, /root/reference):
 //   samtools mpileup column semantics ........ src/create_tensor_pileup.py:436-451 (third-party htslib)
@@ -1568,6 +1569,20 @@ __global__ __launch_bounds__(1024) void k_scan_add(int32_t *data, int n, const i
 #pragma unroll
     for (int k = 0; k < SCAN_IT; ++k) if (i0 + k < n) data[i0 + k] += off;
 }
+// The routing between the two, for the library (device_excl_scan) and for tests/c/row_export_check.hip: exclusive scan of n ints in
+// place on `stream`, total to *d_total.  One block up to 4 * SCAN_BLK items; beyond that three launches, which need
+// excl_scan_tops(n) ints at d_tops (0: d_tops is not touched).
+inline int excl_scan_tops(int n) { return n <= 4 * SCAN_BLK ? 0 : (n + SCAN_BLK - 1) / SCAN_BLK; }
+inline void launch_excl_scan(hipStream_t stream, int32_t *d, int n, int32_t *d_total, int32_t *d_tops) {
+    const int nb = excl_scan_tops(n);
+    if (!nb) {
+        hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, stream, d, n, d_total);
+        return;
+    }
+    hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(1024), 0, stream, d, n, d_tops);
+    hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, stream, d_tops, nb, d_total);
+    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, stream, d, n, (const int32_t *)d_tops);
+}
 
 // tile_cand[tile] = {index of the tile's first candidate in cand_idx, number of candidates}: a wavefront's 64 x 4 positions are
 // exactly one tile (zeroed beforehand: blocks without aligned bases leave early)
@@ -2764,7 +2779,7 @@ __global__ __launch_bounds__(256) void k_export_tokens(const c3r_site_t *sites, 
 
 // ---- tokens for the row decoder, packed.  A token is 16 bytes (c3r_token_t) but the decoder reads the read index, the indel length
 // and the query offset only of the few tokens that carry an indel; of all others it needs the base code.  One wavefront per site
-// turns its tokens into one byte each (base code | 0x20 on the reverse strand | 0x80 when an indel record follows) and appends the indel records (12 bytes,
+// turns its tokens into one byte each (base code | 0x20 on the reverse strand | 0x80 when an indel record follows) and appends the indel records (TokRec, 16 bytes,
 // token order kept by a ballot prefix) to a contiguous range it draws from one counter: a 250-Mb contig copies out ~60 MB instead
 // of 760 MB.
 struct TokRec { uint32_t read_idx; int32_t indel; uint32_t qpos; uint32_t del_after; };

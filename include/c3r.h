@@ -523,6 +523,10 @@ int c3r_rows_begin(c3r_ctx *ctx, c3r_rows **out);
 int c3r_rows_begin_ex(c3r_ctx *ctx, int drop_ref_calls, const c3r_read_t *host_reads, const uint8_t *host_seq, c3r_rows **out);
 int c3r_rows_decode(c3r_rows *rows, const char *ctg, int qual, int show_ref, int64_t *out_len, int64_t *n_rows);
 int c3r_rows_get(c3r_rows *rows, char *out, int64_t cap);
+/* What the snapshot brought off the device (read-only, valid until c3r_rows_free, also after c3r_rows_decode): the sites it holds
+ * (drop_ref_calls: the kept ones), the bytes of its packed token stream (one per token of the kept sites; without drop_ref_calls the whole
+ * token slot space, which the sites' tok_off address) and its indel records (one per token with indel != 0).  Any pointer may be NULL. */
+int c3r_rows_info(const c3r_rows *rows, int64_t *n_sites, int64_t *n_token_bytes, int64_t *n_indel_records);
 void c3r_rows_free(c3r_rows *rows);
 /* The same decoder on caller-supplied text (no GPU, no context): n sites, alt_info strings "<depth>-<k v ...>".
  * Returns C3R_EOVERFLOW (with *out_len = bytes needed, excluding the NUL) when `out` is too small. */

@@ -1061,3 +1061,61 @@ def gate_case(first, kind, d, far=False):
     recs += [dict(pos=edge, cigar="60M", seq=_with_subs(ref, edge, 60, (edge + 9, edge + 40)), flag=16 * (k % 2), hp=k % 3) for k in range(GATE_M)]
     last = edge + 200
     return (ref if far else ref[:last + 100]), recs, last
+
+
+DEEP_TIE_TOKENS = (63, 64, 65, 128, 129, 200)
+
+
+def deep_tie_loci(seed=11, n_ref_reads=4):
+    """Hand-made reads for the row-export tests: one locus per entry of DEEP_TIE_TOKENS, 200 bp apart.  Every read of a locus spans 81 bp
+    around its column and shows there one of: two mismatching bases (equal read counts), two insertion alleles (equal counts), two deletion
+    lengths (equal counts); an odd total gets one read with a third base.  The carriers are interleaved in BAM order and alternate strands, so
+    the FIRST read of each kind decides every tie of the decoder's allele choice — which a token order other than BAM order changes.
+    n_ref_reads reads per locus show the reference.  Returns (ref, ReadSet, [1-based column of each locus])."""
+    import random
+    from clair3_rna_amd.reads import ReadSet
+    rng = random.Random(seed)
+    ref = "".join(rng.choice("ACGT") for _ in range(200 * len(DEEP_TIE_TOKENS) + 200))
+    recs, cols = [], []
+    for k, total in enumerate(DEEP_TIE_TOKENS):
+        c = 100 + 200 * k                      # 0-based column
+        s = c - 40
+        cols.append(c + 1)
+        others = [b for b in "ACGT" if b != ref[c]]
+        rng.shuffle(others)
+        pair = total // 2
+        n_ins = n_del = pair // 3
+        n_snv = pair - n_ins - n_del
+        left, right = ref[s:c], ref[c + 1:s + 81]
+        kinds = ([("X0", i) for i in range(n_snv)] + [("X1", i) for i in range(n_snv)] + [("I0", i) for i in range(n_ins)] + [("I1", i) for i in range(n_ins)] +
+                 [("D0", i) for i in range(n_del)] + [("D1", i) for i in range(n_del)] + [("X2", 0)] * (total & 1) + [("R", i) for i in range(n_ref_reads)])
+        kinds.sort(key=lambda t: (t[1], rng.random()))            # round-robin over the kinds, their order shuffled within a round
+        ins = ("TG", "CAT") if ref[c + 1] != "T" else ("GT", "CAG")
+        for j, (kind, _i) in enumerate(kinds):
+            flag = 16 if j % 2 else 0
+            if kind[0] == "X":
+                recs.append(dict(pos=s, cigar="81M", seq=left + others[int(kind[1])] + right, flag=flag))
+            elif kind[0] == "I":
+                a = ins[int(kind[1])]
+                recs.append(dict(pos=s, cigar="41M%dI40M" % len(a), seq=left + ref[c] + a + right, flag=flag))
+            elif kind[0] == "D":
+                d = (1, 3)[int(kind[1])]
+                recs.append(dict(pos=s, cigar="41M%dD40M" % d, seq=left + ref[c] + ref[c + 1 + d:c + 1 + d + 40], flag=flag))
+            else:
+                recs.append(dict(pos=s, cigar="81M", seq=left + ref[c] + right, flag=flag))
+    return ref, ReadSet.from_records(recs), cols
+
+
+def build_row_export_check(exe, timeout=None):
+    """tests/c/row_export_check.hip -> exe (hipcc cross-compiles for gfx950 without a GPU); None when there is no hipcc"""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        return None
+    cc = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wall", "-Wno-unused-function",
+                         os.path.join(root, "tests", "c", "row_export_check.hip"), "-o", exe], capture_output=True, text=True, timeout=timeout)
+    assert cc.returncode == 0 and "warning:" not in cc.stderr, cc.stderr[-3000:]
+    return exe
