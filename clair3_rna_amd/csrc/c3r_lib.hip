@@ -24,6 +24,7 @@
 #include "decode.hpp"
 #include "net_host.hpp"
 #include "pileup_kernels.hpp"
+#include "export_kernels.hpp"
 #include "reads_kernels.hpp"
 #include "haplotag_kernels.hpp"
 #include "phase_kernels.hpp"
@@ -95,7 +96,6 @@ struct c3r_ctx {
     bool legacy_wanted = false;           // a fused 30-channel scan of this context has met a column whose haplotype channels depend on the reads' order
     LoadStats *h_stats = nullptr;          // pinned
     int32_t *h_lstm = nullptr;             // pinned: this context's copy of the layer-2 time-out word (queue_lstm_status)
-    void *h_pack = nullptr;                // pinned: the indel-record count of k_pack_tokens
     // large copies from / to ORDINARY host memory go through two page-locked 8-MB buffers the context owns (big_h2d / big_d2h): the
     // runtime would pin the caller's pages for every copy and unpin them afterwards, which takes the process's memory-map lock — the
     // lock the BAM fetchers' page faults take as well (call_sample: 8-120 ms for a contig's records where the transfer is 3 ms)
@@ -103,13 +103,12 @@ struct c3r_ctx {
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     bool pin_busy[2] = {false, false};
     DevBuf d_tokb, d_tokrec, d_recoff;     // packed tokens of a row snapshot (c3r_rows_begin)
+    DevBuf d_rowctl; RowCtl *h_rowctl = nullptr;   // the control words of row export (export_kernels.hpp) and their page-locked host mirror (row_ctl)
     DevBuf d_keep, d_sites_c, d_probs_c;   // c3r_rows_begin_ex(drop_ref_calls): keep flags / row numbers, the kept sites' records and probabilities
     std::vector<DevRead> h_reads;          // lazily: ensure_host_reads
     std::vector<int32_t> h_prefmax;        // lazily: host copy of the prefix max of read ends (passing reads)
     std::vector<uint32_t> h_zone_sc, h_zone_ec;   // depth_cap_mask: reads per 256-position bin by start / by exclusive end
     bool host_reads_valid = false;
-    std::vector<uint8_t> h_seq;            // lazily: ensure_host_seq (decode reads inserted bases)
-    bool host_seq_valid = false;
     DevBuf d_reads, d_cigar, d_seq, d_prefmax;
     DevBuf d_wgtab;                        // k_prep's per-workgroup bin tables between its two passes
     // mpileup_compat = 1: the insertions of the loaded reads that hold pads (c3r_padins_t), on the device for ev_equal and on the host for
@@ -200,7 +199,6 @@ struct c3r_ctx {
     int64_t last_cand = 0, last_base = 0; // candidates of the most recent scan and their offset in the batch
     bool batching = false;
     DevBuf d_cand, d_tensors, d_raw, d_sites_out, d_tokcnt, d_tok;
-    bool tokens_ready = false;
 
     // ---- network
     NetState net;
@@ -208,8 +206,6 @@ struct c3r_ctx {
     double mx_calib_err = -1.0;            // max |dP| of precision 2 against precision 1 on the calibration windows (-1: not measured)
     double f16_calib_err = -1.0;           // max |dP| of split-f16 against the fp32 MFMA path on the same windows, measured at c3r_load_weights
     bool f16_fell_back = false;            // the guard sent a split-f16 request to the fp32 path
-
-    // ---- host decode (A8)
 };
 
 namespace {
@@ -222,6 +218,10 @@ static inline unsigned usable_cpus() {
     if (sched_getaffinity(0, sizeof set, &set) == 0) { const int n = CPU_COUNT(&set); if (n > 0) return (unsigned)n; }
     return std::max(1u, std::thread::hardware_concurrency());
 }
+
+typedef std::chrono::steady_clock::time_point TimePt;         // (the C3R_TIMING reports)
+inline TimePt now() { return std::chrono::steady_clock::now(); }
+inline double ms(TimePt a, TimePt b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
 int fail(c3r_ctx *ctx, int code, const char *fmt, ...) {
     char buf[512];
@@ -307,6 +307,31 @@ int ensure(c3r_ctx *ctx, DevBuf &b, size_t bytes) {
     if (poison_byte() >= 0) { HIPCHK(ctx, hipMemsetAsync(b.p, poison_byte(), want, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
     b.cap = want;
     return C3R_OK;
+}
+
+// The pool of staging blocks (c3r_ctx::stage_pool; snapshots are released from other threads).  take: a pooled block of at least `need` bytes, else —
+// when `grow` — a fresh one with a quarter to spare; null when there is none.  give: the pool keeps three blocks.
+void *stage_take(c3r_ctx *ctx, size_t need, bool grow, size_t *cap) {
+    {   std::lock_guard<std::mutex> g(ctx->pool_mu);
+        for (auto it = ctx->stage_pool.begin(); it != ctx->stage_pool.end(); ++it)
+            if (it->second >= need) { void *p = it->first; *cap = it->second; ctx->stage_pool.erase(it); return p; }
+    }
+    void *p = nullptr;
+    *cap = need * 5 / 4 + 4096;
+    if (grow && !stage_pinned()) p = huge_alloc(*cap);
+    else if (grow && hipHostMalloc(&p, *cap, hipHostMallocDefault) != hipSuccess) p = nullptr;
+    return p;
+}
+void stage_give(c3r_ctx *ctx, void *p, size_t cap) {
+    std::lock_guard<std::mutex> g(ctx->pool_mu);
+    if (ctx->stage_pool.size() < 3) ctx->stage_pool.push_back({p, cap}); else stage_free(p);
+}
+// The control block of row export on the device (whoever counts in it clears it first) and its page-locked mirror, made at first use.
+int row_ctl(c3r_ctx *ctx, RowCtl **d_ctl) {
+    if (!ctx->h_rowctl && hipHostMalloc((void **)&ctx->h_rowctl, sizeof(RowCtl), hipHostMallocDefault) != hipSuccess) return fail(ctx, C3R_ENOMEM, "hipHostMalloc(64) failed");
+    const int rc = ensure(ctx, ctx->d_rowctl, sizeof(RowCtl));
+    *d_ctl = (RowCtl *)ctx->d_rowctl.p;
+    return rc;
 }
 
 // grow a buffer but keep its first `used` bytes (batch mode appends scan after scan)
@@ -695,7 +720,6 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     // (under the profiler: how many workgroups of the second pass counted their records again — no kernel, `launches` is the count)
     if (ctx->profiling && hs.n_recount > 0) ctx->kstats["k_prep_recount_workgroups"].n += hs.n_recount;
     if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "[c3r_load_reads] %d reads, %d records in %d bins: first pass until the sync %.2f ms, second pass queued in %.2f ms\n", n, hs.n_rec, ctx->bins.nb,
                 ms(t_begin, t_sync), ms(t_sync, std::chrono::steady_clock::now()));
     }
@@ -732,8 +756,8 @@ int ensure_legacy_tables(c3r_ctx *ctx) {
     return C3R_OK;
 }
 
-// Host copies, fetched only by the paths that walk reads on the host: mpileup's depth cap (sequential by nature) and the decoder
-// (inserted bases of the alt alleles).
+// Host copies, fetched only by the path that walks reads on the host: mpileup's depth cap (sequential by nature).  (The decoder's copies — inserted
+// bases of the alt alleles — belong to the row snapshots: HostReads, rows_read_source.)
 int ensure_host_reads(c3r_ctx *ctx) {
     if (ctx->host_reads_valid) return C3R_OK;
     ctx->h_reads.resize((size_t)ctx->n_reads); ctx->h_prefmax.resize((size_t)ctx->n_reads);
@@ -743,14 +767,6 @@ int ensure_host_reads(c3r_ctx *ctx) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->host_reads_valid = true;
-    return C3R_OK;
-}
-int ensure_host_seq(c3r_ctx *ctx) {
-    if (ctx->host_seq_valid) return C3R_OK;
-    ctx->h_seq.resize((size_t)ctx->n_seq_bytes + 16);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_seq.data(), ctx->d_seq.p, ctx->h_seq.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->host_seq_valid = true;
     return C3R_OK;
 }
 
@@ -869,16 +885,16 @@ void c3r_destroy(c3r_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
                       &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
-                      &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
-    int n_dev = 0; size_t b_dev = 0, b_pin = 0;
+                      &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_rowctl, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
+    int n_dev = 0; size_t b_dev = 0, b_pin = 0, cap = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
     const auto t1 = std::chrono::steady_clock::now();
     net_free(ctx->net);
     const auto t2 = std::chrono::steady_clock::now();
     if (ctx->rows_snap) c3r_rows_free(ctx->rows_snap);
-    for (auto &sp : ctx->stage_pool) { stage_free(sp.first); b_pin += sp.second; }
+    while (void *p = stage_take(ctx, 0, false, &cap)) { stage_free(p); b_pin += cap; }
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
-    if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
+    if (ctx->h_rowctl) (void)hipHostFree(ctx->h_rowctl);
     for (int k = 0; k < 2; ++k) { if (ctx->pin_buf[k]) (void)hipHostFree(ctx->pin_buf[k]); if (ctx->pin_ev[k]) (void)hipEventDestroy(ctx->pin_ev[k]); }
     if (ctx->h_lstm) (void)hipHostFree(ctx->h_lstm);
     if (ctx->h_scan) (void)hipHostFree(ctx->h_scan);
@@ -895,7 +911,6 @@ void c3r_destroy(c3r_ctx *ctx) {
     if (ctx->ev_net) (void)hipEventDestroy(ctx->ev_net);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "[c3r_destroy %p] %d device buffers (%.0f MB) %.1f ms, network buffers %.1f ms, host blocks (%.0f MB) %.1f ms, events + stream %.1f ms\n",
                 (void *)ctx, n_dev, b_dev / 1e6, ms(t0, t1), ms(t1, t2), b_pin / 1e6, ms(t2, t3), ms(t3, std::chrono::steady_clock::now()));
     }
@@ -947,7 +962,7 @@ int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, con
     const bool timing = getenv("C3R_TIMING") != nullptr;
     // whatever happens below, the previous contig's tables are gone
     ctx->n_reads = 0; ctx->n_indel_ops = 0; ctx->n_seq_bytes = 0; ctx->n_cigar_ops = 0; ctx->max_cover = 0;
-    ctx->host_reads_valid = false; ctx->host_seq_valid = false; ctx->last_scan_pruned = false; ctx->legacy_valid = false;
+    ctx->host_reads_valid = false; ctx->last_scan_pruned = false; ctx->legacy_valid = false;
     ctx->host_cache.reset();              // (snapshots of the previous contig keep their copy alive)
     ctx->padins.reset();
     const int n = (int)n_reads;
@@ -1865,7 +1880,7 @@ static int scan_geometry(c3r_ctx *ctx, int32_t n_regions, const int64_t *ctg_sta
 // a scan that produces candidates starts here: outside a batch the resident totals start over
 static void scan_output_begin(c3r_ctx *ctx) {
     if (!ctx->batching) { ctx->n_cand = 0; ctx->n_tok = 0; ctx->n_rows = 0; ctx->n_tokspace = 0; }
-    ctx->last_cand = 0; ctx->last_base = ctx->n_cand; ctx->tokens_ready = false;
+    ctx->last_cand = 0; ctx->last_base = ctx->n_cand;
 }
 
 // C3R_SCAN_DBG: the phase clocks of the tile kernels (timing aid, off in production)
@@ -2028,7 +2043,6 @@ static int scan_column_store(c3r_ctx *ctx, const ScanKnobs &kn, int32_t n_region
     HIPCHK(ctx, hipMemcpyAsync(&h.tok_written, &ctl->tok_written, offsetof(ColCtl, unused) - offsetof(ColCtl, tok_written), hipMemcpyDeviceToHost, ctx->stream));   // tok_written, tok_lost
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (h.tok_lost) return fail(ctx, C3R_EOVERFLOW, "internal: %d tokens found no slot (the gates' bound of a site's tokens was too small)", h.tok_lost);
-    ctx->tokens_ready = true;
     ctx->n_cand = base_cand + n_cand;
     ctx->n_tok += h.tok_written;
     ctx->n_rows = base_row + n_cand; ctx->n_tokspace = base_tok + h.n_tok;
@@ -2279,7 +2293,6 @@ static int scan_fused(c3r_ctx *ctx, const ScanKnobs &kn, int32_t n_regions, cons
     ctx->last_cand = n_cand; ctx->last_shards = nsh; ctx->last_shard_rows = (int32_t)want_c;
     ctx->scan_counts[0] = h.ctl.n_listed; ctx->scan_counts[1] = h.ctl.n_deep; ctx->scan_counts[2] = h.ctl.n_giant; ctx->scan_counts[3] = h.ctl.n_help;
     if (n_candidates) *n_candidates = n_cand;
-    ctx->tokens_ready = true;
     ctx->n_cand = base_cand + n_cand;
     ctx->n_tok += n_tok;
     // (one allocator: dense output, the next scan of the batch appends; several: the scan's whole row / token space is taken)
@@ -2411,10 +2424,10 @@ int c3r_get_tokens(c3r_ctx *ctx, c3r_token_t *tokens, int64_t cap_tokens) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // site order (see c3r_get_sites): offsets = exclusive sums of the sites' token counts, then one wavefront per site copies its run
     const int n = (int)ctx->n_cand;
-    int rc;
-    if ((rc = ensure(ctx, ctx->d_tokoff, (size_t)(n + 2) * 4)) || (rc = ensure(ctx, ctx->d_tokexp, (size_t)ctx->n_tok * sizeof(c3r_token_t))) || (rc = ensure(ctx, ctx->d_small, sizeof(ColCtl)))) return rc;
+    int rc; RowCtl *ctl = nullptr;
+    if ((rc = ensure(ctx, ctx->d_tokoff, (size_t)(n + 2) * 4)) || (rc = ensure(ctx, ctx->d_tokexp, (size_t)ctx->n_tok * sizeof(c3r_token_t))) || (rc = row_ctl(ctx, &ctl))) return rc;
     hipLaunchKernelGGL(k_site_ntok, dim3((unsigned)(n / 256 + 1)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p, n, (int32_t *)ctx->d_tokoff.p);
-    if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_tokoff.p, n + 1, &((ColCtl *)ctx->d_small.p)->export_toks))) return rc;
+    if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_tokoff.p, n + 1, &ctl->export_toks))) return rc;
     hipLaunchKernelGGL(k_export_tokens, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 8192)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p,
                        (const int32_t *)ctx->d_tokoff.p, n, (const c3r_token_t *)ctx->d_tok.p, (c3r_token_t *)ctx->d_tokexp.p);
     HIPCHK(ctx, hipMemcpyAsync(tokens, ctx->d_tokexp.p, (size_t)ctx->n_tok * sizeof(c3r_token_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2723,9 +2736,9 @@ int c3r_decode_text(const char *ctg, int64_t n, const int32_t *pos, const char *
 }  // extern "C"
 struct c3r_rows {
     c3r_ctx *ctx = nullptr;
-    // one staging block: sites | token bytes | probabilities | indel-record offsets | read headers | packed bases
+    // one staging block (rows_stage): sites | token bytes | probabilities | indel-record offsets
     void *stage = nullptr; size_t stage_cap = 0;
-    int64_t n = 0, n_tok = 0;
+    int64_t n = 0;
     c3r_site_t *sites = nullptr; uint8_t *tokb = nullptr; float *probs = nullptr; uint32_t *rec_off = nullptr;
     std::shared_ptr<HostReads> hr;                        // the contig's read headers and packed bases (inserted bases of the alt alleles)
     std::shared_ptr<PadInsTab> padins;                    // mpileup_compat = 1: its insertions with pads (null / empty otherwise)
@@ -2736,6 +2749,91 @@ struct c3r_rows {
     std::string rows; int64_t rows_count = 0;
     int64_t info_sites = 0, info_tokb = 0, info_recs = 0; // c3r_rows_info: what left the device (kept when the inputs are released)
 };
+namespace {
+// device -> the snapshot's (ordinary) memory, in stream order; the large arrays through the context's page-locked buffers (big_d2h: complete on return)
+int rows_d2h(c3r_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    if (bytes >= PIN_MIN && pin_ring_on()) return big_d2h(ctx, dst, src, bytes);
+    if (bytes) HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return C3R_OK;
+}
+// drop_ref_calls: only the sites that can print a row without --show_ref leave the device.  k_row_keep flags them, an exclusive scan turns the flags into row
+// numbers (d_keep, read by k_pack_rows) and the host waits for their count.  (the keep decision reads the probabilities: the layer-2 time-out word is checked
+// with the same wait, before the count is acted on — a timed-out batch whose garbage looks like RefCalls must fail, not come back as an empty snapshot)
+int rows_keep_count(c3r_ctx *ctx, RowCtl *ctl, int64_t n_all, int64_t *n_keep) {
+    int rc; int32_t *lstm_st = nullptr;
+    if ((rc = ensure(ctx, ctx->d_keep, (size_t)(n_all + 2) * 4))) return rc;
+    hipLaunchKernelGGL(k_row_keep, dim3((unsigned)(n_all / 256 + 1)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p, (const float *)ctx->net.d_probs, (int)n_all,
+                       (int32_t *)ctx->d_keep.p);
+    if ((rc = device_excl_scan(ctx, (int32_t *)ctx->d_keep.p, (int)n_all + 1, &ctl->n_keep)) || (rc = queue_lstm_status(ctx, &lstm_st))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(&ctx->h_rowctl->n_keep, &ctl->n_keep, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *n_keep = ctx->h_rowctl->n_keep;
+    return check_lstm_status(ctx, lstm_st);
+}
+// the staging block for r->n sites and, at most, the token bytes of the whole slot space.  -> *need: its bytes
+int rows_stage(c3r_ctx *ctx, c3r_rows *r, size_t *need) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t n = (size_t)r->n, b_sites = up(n * sizeof(c3r_site_t)), b_tokb = up((size_t)std::max<int64_t>(ctx->n_tokspace, 1)), b_probs = up(n * C3R_NPROB * sizeof(float));
+    *need = b_sites + b_tokb + b_probs + up(n * 4);
+    r->stage = stage_take(ctx, *need, true, &r->stage_cap);
+    if (!r->stage) return fail(ctx, C3R_ENOMEM, "staging block of %zu bytes: allocation failed", r->stage_cap);
+    r->sites = (c3r_site_t *)r->stage; r->tokb = (uint8_t *)r->stage + b_sites;
+    r->probs = (float *)(r->tokb + b_tokb); r->rec_off = (uint32_t *)(r->tokb + b_tokb + b_probs);
+    return C3R_OK;
+}
+// where the decoder reads inserted bases: the caller's own arrays, else the context's host copy of the loaded contig.  -> that copy is new and still to be filled
+// (rows_copy_out; the context gets it when the snapshot is complete: a half-copied cache is no cache)
+bool rows_read_source(c3r_ctx *ctx, c3r_rows *r, const c3r_read_t *host_reads, const uint8_t *host_seq) {
+    r->padins = ctx->padins;
+    if (host_reads) { r->creads = host_reads; r->seq = host_seq; return false; }
+    r->hr = ctx->host_cache;
+    if (!r->hr) r->hr = std::make_shared<HostReads>(HostReads{std::vector<DevRead>((size_t)std::max(ctx->n_reads, 1)), std::vector<uint8_t>((size_t)ctx->n_seq_bytes + 16)});
+    r->reads = r->hr->reads.data(); r->seq = r->hr->seq.data();
+    return !ctx->host_cache;
+}
+// tokens leave the device packed (export_kernels.hpp: a byte per token, 16-byte records for the tokens with an indel): all n_all sites where they lie, or — `drop` —
+// the r->n kept ones back to back, their records and probabilities with them
+int rows_pack(c3r_ctx *ctx, const c3r_rows *r, RowCtl *ctl, bool drop, int64_t n_all) {
+    const size_t n_tok = (size_t)std::max<int64_t>(ctx->n_tokspace, 1);   // (token bytes are addressed through the sites' tok_off: the whole slot space)
+    int rc;
+    if ((rc = ensure(ctx, ctx->d_tokb, n_tok)) || (rc = ensure(ctx, ctx->d_tokrec, n_tok * sizeof(TokRec))) || (rc = ensure(ctx, ctx->d_recoff, (size_t)r->n * 4))) return rc;
+    if (drop && ((rc = ensure(ctx, ctx->d_sites_c, (size_t)r->n * sizeof(c3r_site_t))) || (rc = ensure(ctx, ctx->d_probs_c, (size_t)r->n * C3R_NPROB * sizeof(float))))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctl, 0, offsetof(RowCtl, n_keep), ctx->stream));         // n_recs, n_bytes
+    Launch L(ctx, "k_pack_tokens");
+    if (drop)
+        hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p, (const c3r_token_t *)ctx->d_tok.p,
+                           (const float *)ctx->net.d_probs, (const int32_t *)ctx->d_keep.p, n_all, (c3r_site_t *)ctx->d_sites_c.p, (float *)ctx->d_probs_c.p, (uint8_t *)ctx->d_tokb.p,
+                           (TokRec *)ctx->d_tokrec.p, (uint32_t *)ctx->d_recoff.p, &ctl->n_recs);
+    else
+        hipLaunchKernelGGL(k_pack_tokens, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p, (const c3r_token_t *)ctx->d_tok.p, n_all,
+                           (uint8_t *)ctx->d_tokb.p, (TokRec *)ctx->d_tokrec.p, (uint32_t *)ctx->d_recoff.p, &ctl->n_recs);
+    return C3R_OK;
+}
+// counters, sites, token bytes, record offsets, the read source when it is fresh, probabilities: one wait at the end, behind the time-out word (only the snapshot
+// without RefCalls sizes its token copy from the counters and waits for them); then (*t_main) the indel records, in an allocation of the snapshot's own
+int rows_copy_out(c3r_ctx *ctx, c3r_rows *r, const RowCtl *ctl, bool drop, bool fresh_reads, TimePt *t_main) {
+    const size_t n = (size_t)r->n;
+    int64_t n_tok = ctx->n_tokspace;
+    int rc; int32_t *lstm_st = nullptr;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_rowctl, ctl, offsetof(RowCtl, n_keep), hipMemcpyDeviceToHost, ctx->stream));
+    if (drop) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); n_tok = (int64_t)ctx->h_rowctl->n_bytes; }      // (the kept sites' token bytes lie back to back)
+    const void *d_sites = drop ? ctx->d_sites_c.p : ctx->d_sites_out.p, *d_probs = drop ? ctx->d_probs_c.p : (const void *)ctx->net.d_probs;
+    if ((rc = rows_d2h(ctx, r->sites, d_sites, n * sizeof(c3r_site_t))) || (rc = rows_d2h(ctx, r->tokb, ctx->d_tokb.p, (size_t)n_tok)) || (rc = rows_d2h(ctx, r->rec_off, ctx->d_recoff.p, n * 4)) ||
+        (fresh_reads && ((rc = rows_d2h(ctx, r->hr->reads.data(), ctx->d_reads.p, (size_t)ctx->n_reads * sizeof(DevRead))) || (rc = rows_d2h(ctx, r->hr->seq.data(), ctx->d_seq.p, (size_t)ctx->n_seq_bytes + 16)))) ||
+        (rc = queue_lstm_status(ctx, &lstm_st)) || (rc = rows_d2h(ctx, r->probs, d_probs, n * C3R_NPROB * sizeof(float))))
+        return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    r->n_recs = (int64_t)ctx->h_rowctl->n_recs;
+    r->info_sites = r->n; r->info_tokb = n_tok; r->info_recs = r->n_recs;
+    *t_main = now();
+    if ((rc = check_lstm_status(ctx, lstm_st)) || r->n_recs <= 0) return rc;
+    r->recs = (TokRec *)huge_alloc((size_t)r->n_recs * sizeof(TokRec));
+    if (!r->recs) return fail(ctx, C3R_ENOMEM, "indel records of %lld tokens: allocation failed", (long long)r->n_recs);
+    if ((rc = rows_d2h(ctx, r->recs, ctx->d_tokrec.p, (size_t)r->n_recs * sizeof(TokRec)))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return C3R_OK;
+}
+}  // namespace
 extern "C" {
 
 int c3r_rows_begin(c3r_ctx *ctx, c3r_rows **out) { return c3r_rows_begin_ex(ctx, 0, nullptr, nullptr, out); }
@@ -2743,126 +2841,30 @@ int c3r_rows_begin(c3r_ctx *ctx, c3r_rows **out) { return c3r_rows_begin_ex(ctx,
 int c3r_rows_begin_ex(c3r_ctx *ctx, int drop_ref_calls, const c3r_read_t *host_reads, const uint8_t *host_seq, c3r_rows **out) {
     if (!ctx || !out || ((host_reads == nullptr) != (host_seq == nullptr))) return C3R_EINVAL;
     *out = nullptr;
-    int64_t n = ctx->n_cand;
-    if (n > 0 && (!ctx->net.d_probs || n > ctx->net.cap_probs)) return fail(ctx, C3R_EINVAL, "c3r_infer must run before c3r_call_rows");
+    const int64_t n_all = ctx->n_cand;
+    if (n_all > 0 && (!ctx->net.d_probs || n_all > ctx->net.cap_probs)) return fail(ctx, C3R_EINVAL, "c3r_infer must run before c3r_call_rows");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    c3r_rows *r = new c3r_rows();
-    r->ctx = ctx; r->n = n; r->n_tok = ctx->n_tok;
-    if (n == 0) { *out = r; return C3R_OK; }
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    int64_t n_tok = ctx->n_tokspace;                 // (token bytes are addressed through the sites' tok_off: the whole slot space)
-    // ---- drop_ref_calls: only the sites that can print a row without --show_ref leave the device (k_row_keep / k_pack_rows)
-    const int64_t n_all = n;
-    const c3r_site_t *d_sites_src = (const c3r_site_t *)ctx->d_sites_out.p;
-    const float *d_probs_src = ctx->net.d_probs;
-    bool packed = false;
-    if (drop_ref_calls) {
-        int rc0;
-        if ((rc0 = ensure(ctx, ctx->d_keep, (size_t)(n_all + 2) * 4)) || (rc0 = ensure(ctx, ctx->d_small, sizeof(ColCtl)))) { delete r; return rc0; }
-        hipLaunchKernelGGL(k_row_keep, dim3((unsigned)(n_all / 256 + 1)), dim3(256), 0, ctx->stream, d_sites_src, d_probs_src, (int)n_all, (int32_t *)ctx->d_keep.p);
-        if ((rc0 = device_excl_scan(ctx, (int32_t *)ctx->d_keep.p, (int)n_all + 1, &((ColCtl *)ctx->d_small.p)->n_keep))) { delete r; return rc0; }
-        int32_t n_keep = 0;
-        // (the keep decision reads the probabilities: the layer-2 time-out word is checked with the same wait, before the count is acted on —
-        // a timed-out batch whose garbage looks like RefCalls must fail, not come back as an empty snapshot)
-        int32_t *lstm_st0 = nullptr;
-        if ((rc0 = queue_lstm_status(ctx, &lstm_st0))) { delete r; return rc0; }
-        if (hipMemcpyAsync(&n_keep, &((ColCtl *)ctx->d_small.p)->n_keep, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            delete r; return fail(ctx, C3R_EHIP, "reading the number of kept sites failed");
-        }
-        if ((rc0 = check_lstm_status(ctx, lstm_st0))) { delete r; return rc0; }
-        n = n_keep; r->n = n;
-        if (n == 0) { r->n_tok = 0; *out = r; return C3R_OK; }
-        if ((rc0 = ensure(ctx, ctx->d_sites_c, (size_t)n * sizeof(c3r_site_t))) || (rc0 = ensure(ctx, ctx->d_probs_c, (size_t)n * C3R_NPROB * sizeof(float)))) { delete r; return rc0; }
-        packed = true;
-    }
-    const size_t b_sites = up((size_t)n * sizeof(c3r_site_t)), b_tokb = up((size_t)std::max<int64_t>(n_tok, 1)), b_probs = up((size_t)n * C3R_NPROB * sizeof(float)),
-                 b_off = up((size_t)n * 4);
-    const size_t need = b_sites + b_tokb + b_probs + b_off;
-    {   // a block from the pool of released snapshots
-        std::lock_guard<std::mutex> g(ctx->pool_mu);
-        for (size_t k = 0; k < ctx->stage_pool.size(); ++k)
-            if (ctx->stage_pool[k].second >= need) { r->stage = ctx->stage_pool[k].first; r->stage_cap = ctx->stage_pool[k].second; ctx->stage_pool.erase(ctx->stage_pool.begin() + (long)k); break; }
-    }
-    if (!r->stage) {
-        const size_t cap = need * 5 / 4 + 4096;
-        if (stage_pinned()) { if (hipHostMalloc(&r->stage, cap, hipHostMallocDefault) != hipSuccess) r->stage = nullptr; }
-        else r->stage = huge_alloc(cap);
-        if (!r->stage) { delete r; return fail(ctx, C3R_ENOMEM, "staging block of %zu bytes: allocation failed", cap); }
-        r->stage_cap = cap;
-    }
-    char *sp = (char *)r->stage;
-    r->sites = (c3r_site_t *)sp; sp += b_sites;
-    r->tokb = (uint8_t *)sp; sp += b_tokb;
-    r->probs = (float *)sp; sp += b_probs;
-    r->rec_off = (uint32_t *)sp; sp += b_off;
-    const bool fresh_reads = !host_reads && !ctx->host_cache;
-    if (host_reads) { r->creads = host_reads; r->seq = host_seq; }
-    else if (fresh_reads) {
-        ctx->host_cache = std::make_shared<HostReads>();
-        ctx->host_cache->reads.resize((size_t)std::max(ctx->n_reads, 1));
-        ctx->host_cache->seq.resize((size_t)ctx->n_seq_bytes + 16);
-    }
-    if (!host_reads) { r->hr = ctx->host_cache; r->reads = r->hr->reads.data(); r->seq = r->hr->seq.data(); }
-    r->padins = ctx->padins;
-    auto bail = [&](int rc) { if (fresh_reads) ctx->host_cache.reset(); c3r_rows_free(r); return rc; };      // (a half-copied cache is no cache)
+    std::unique_ptr<c3r_rows, void (*)(c3r_rows *)> guard(new c3r_rows(), c3r_rows_free);        // (every exit but release() frees the snapshot)
+    c3r_rows *const r = guard.get();
+    r->ctx = ctx; r->n = n_all;
+    const bool drop = drop_ref_calls != 0;
+    int rc; size_t need = 0; RowCtl *ctl = nullptr;
+    if (n_all && ((rc = row_ctl(ctx, &ctl)) || (drop && (rc = rows_keep_count(ctx, ctl, n_all, &r->n))))) return rc;
+    if (r->n == 0) { *out = guard.release(); return C3R_OK; }       // (no candidates, or none kept)
+    if ((rc = rows_stage(ctx, r, &need))) return rc;
+    const bool fresh_reads = rows_read_source(ctx, r, host_reads, host_seq);
     const bool timing = getenv("C3R_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t0 = now();
     if (timing) (void)hipStreamSynchronize(ctx->stream);              // (separates the wait for the network from the copies in the report)
-    const auto t1 = now();
-    // tokens leave the device packed (k_pack_tokens: a byte per token, 16-byte records for the tokens with an indel)
-    int rc = C3R_OK;
-    if ((rc = ensure(ctx, ctx->d_tokb, (size_t)std::max<int64_t>(n_tok, 1))) || (rc = ensure(ctx, ctx->d_tokrec, (size_t)std::max<int64_t>(n_tok, 1) * sizeof(TokRec))) ||
-        (rc = ensure(ctx, ctx->d_recoff, (size_t)n * 4 + 32)))
-        return bail(rc);
-    if (!ctx->h_pack && hipHostMalloc((void **)&ctx->h_pack, 64, hipHostMallocDefault) != hipSuccess) return bail(fail(ctx, C3R_ENOMEM, "hipHostMalloc(64) failed"));
-    unsigned long long *d_counter = (unsigned long long *)((char *)ctx->d_recoff.p + (((size_t)n * 4 + 7) & ~(size_t)7));
-    if (hipMemsetAsync(d_counter, 0, 16, ctx->stream) != hipSuccess) return bail(fail(ctx, C3R_EHIP, "hipMemsetAsync failed"));
-    if (packed) {
-        Launch L(ctx, "k_pack_tokens");
-        hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, ctx->stream, d_sites_src, (const c3r_token_t *)ctx->d_tok.p, d_probs_src,
-                           (const int32_t *)ctx->d_keep.p, n_all, (c3r_site_t *)ctx->d_sites_c.p, (float *)ctx->d_probs_c.p, (uint8_t *)ctx->d_tokb.p, (TokRec *)ctx->d_tokrec.p,
-                           (uint32_t *)ctx->d_recoff.p, d_counter);
-        d_sites_src = (const c3r_site_t *)ctx->d_sites_c.p; d_probs_src = (const float *)ctx->d_probs_c.p;
-    } else {
-        Launch L(ctx, "k_pack_tokens");
-        hipLaunchKernelGGL(k_pack_tokens, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, (const c3r_site_t *)ctx->d_sites_out.p, (const c3r_token_t *)ctx->d_tok.p, n,
-                           (uint8_t *)ctx->d_tokb.p, (TokRec *)ctx->d_tokrec.p, (uint32_t *)ctx->d_recoff.p, d_counter);
-    }
-    // (the snapshot's block is ordinary memory: the large arrays come down through the context's page-locked buffers, big_d2h)
-    auto d2h = [&](void *dst, const void *src, size_t bytes) {
-        if (bytes >= PIN_MIN && pin_ring_on()) return big_d2h(ctx, dst, src, bytes) == C3R_OK;
-        return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    };
-    // (only the packed snapshot sizes its token copy from the counters: the plain one keeps the single wait at the end)
-    if (!d2h(ctx->h_pack, d_counter, 16) || (packed && hipStreamSynchronize(ctx->stream) != hipSuccess)) return bail(fail(ctx, C3R_EHIP, "copying the token counters to the host failed"));
-    if (packed) n_tok = (int64_t)((unsigned long long *)ctx->h_pack)[1];          // (the kept sites' token bytes lie back to back)
-    if (!d2h(r->sites, d_sites_src, (size_t)n * sizeof(c3r_site_t)) || !d2h(r->tokb, ctx->d_tokb.p, (size_t)n_tok) ||
-        !d2h(r->rec_off, ctx->d_recoff.p, (size_t)n * 4) ||
-        (fresh_reads && (!d2h(r->hr->reads.data(), ctx->d_reads.p, (size_t)ctx->n_reads * sizeof(DevRead)) || !d2h(r->hr->seq.data(), ctx->d_seq.p, (size_t)ctx->n_seq_bytes + 16))))
-        return bail(fail(ctx, C3R_EHIP, "copying sites / tokens / reads to the host failed"));
-    int32_t *lstm_st = nullptr;
-    rc = queue_lstm_status(ctx, &lstm_st);
-    if (rc) return bail(rc);
-    if (!d2h(r->probs, d_probs_src, (size_t)n * C3R_NPROB * sizeof(float)) || hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return bail(fail(ctx, C3R_EHIP, "copying probabilities to the host failed"));
-    if ((rc = check_lstm_status(ctx, lstm_st))) return bail(rc);
-    const auto t2 = now();
-    r->n_recs = (int64_t)*(unsigned long long *)ctx->h_pack;
-    r->info_sites = n; r->info_tokb = n_tok; r->info_recs = r->n_recs;
-    if (r->n_recs > 0) {
-        r->recs = (TokRec *)huge_alloc((size_t)r->n_recs * sizeof(TokRec));
-        if (!r->recs) return bail(fail(ctx, C3R_ENOMEM, "indel records of %lld tokens: allocation failed", (long long)r->n_recs));
-        if (!d2h(r->recs, ctx->d_tokrec.p, (size_t)r->n_recs * sizeof(TokRec)) || hipStreamSynchronize(ctx->stream) != hipSuccess)
-            return bail(fail(ctx, C3R_EHIP, "copying indel records to the host failed"));
-    }
+    auto t1 = now(), t2 = t1;
+    if ((rc = rows_pack(ctx, r, ctl, drop, n_all)) || (rc = rows_copy_out(ctx, r, ctl, drop, fresh_reads, &t2))) return rc;
     if (timing)
         fprintf(stderr, "[rows_begin %p] %lld sites, %lld tokens (%lld with an indel): wait %.1f ms, pack + copies (%.0f MB) %.1f ms, indel records (%.0f MB) %.1f ms\n", (void *)ctx,
-                (long long)n, (long long)n_tok, (long long)r->n_recs, ms(t0, t1), need / 1e6, ms(t1, t2), r->n_recs * sizeof(TokRec) / 1e6, ms(t2, now()));
+                (long long)r->n, (long long)r->info_tokb, (long long)r->n_recs, ms(t0, t1), need / 1e6, ms(t1, t2), r->n_recs * sizeof(TokRec) / 1e6, ms(t2, now()));
     r->ref_slot = ctx->ref_cur; r->ref = ctx->h_ref; r->ref_len = ctx->ref_len; r->ref_start1 = ctx->ref_start1;
     if (r->ref_slot >= 0) ctx->refbuf[r->ref_slot].users.fetch_add(1);
-    *out = r;
+    if (fresh_reads) ctx->host_cache = r->hr;
+    *out = guard.release();
     return C3R_OK;
 }
 
@@ -2935,12 +2937,8 @@ int c3r_rows_get(c3r_rows *r, char *out, int64_t cap) {
 static void rows_release_inputs(c3r_rows *r) {
     c3r_ctx *ctx = r->ctx;
     if (r->ref_slot >= 0) { ctx->refbuf[r->ref_slot].users.fetch_sub(1); r->ref_slot = -1; r->ref = nullptr; r->ref_len = 0; }
-    if (r->stage) {
-        std::lock_guard<std::mutex> g(ctx->pool_mu);
-        if (ctx->stage_pool.size() < 3) ctx->stage_pool.push_back({r->stage, r->stage_cap});
-        else stage_free(r->stage);
-        r->stage = nullptr; r->stage_cap = 0; r->sites = nullptr; r->tokb = nullptr; r->probs = nullptr; r->rec_off = nullptr; r->reads = nullptr; r->seq = nullptr; r->creads = nullptr;
-    }
+    if (r->stage) stage_give(ctx, r->stage, r->stage_cap);
+    r->stage = nullptr; r->stage_cap = 0; r->sites = nullptr; r->tokb = nullptr; r->probs = nullptr; r->rec_off = nullptr; r->reads = nullptr; r->seq = nullptr; r->creads = nullptr;
     if (r->recs) { free(r->recs); r->recs = nullptr; r->n_recs = 0; }
     r->n = 0;
 }
@@ -2963,10 +2961,8 @@ int c3r_call_rows(c3r_ctx *ctx, const char *ctg, int qual, int show_ref, int64_t
     const auto t1 = std::chrono::steady_clock::now();
     rc = c3r_rows_decode(ctx->rows_snap, ctg, qual, show_ref, out_len, n_rows);
     rows_release_inputs(ctx->rows_snap);          // (only the text is kept for c3r_get_rows: no reference buffer stays pinned by it)
-    if (timing) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[c3r_call_rows] snapshot (D2H of sites, tokens, probabilities, read bases) %.1f ms, decode %.1f ms\n", ms(t0, t1), ms(t1, std::chrono::steady_clock::now()));
-    }
+    if (timing)
+        fprintf(stderr, "[c3r_call_rows] snapshot (D2H of sites, tokens, probabilities, read bases) %.1f ms, decode %.1f ms\n", ms(t0, t1), ms(t1, now()));
     return rc;
 }
 

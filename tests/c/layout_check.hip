@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <vector>
 #include "../../clair3_rna_amd/csrc/reads_kernels.hpp"
+#include "../../clair3_rna_amd/csrc/export_kernels.hpp"
 
 // The thresholds that tests/test_gpu_deep_routes.py sizes its cases by: which kernel builds a span, and how its indel alleles are counted
 #define ROUTE_CONST(expr, what) static_assert(expr, what " changed: update tests/test_gpu_deep_routes.py (its brackets and case sizes)")
@@ -45,7 +46,10 @@ CTL_AT(ScanCtl, rows_out, 36);      CTL_AT(ScanCtl, ticket_order, 40);  CTL_AT(S
 CTL_AT(ScanCtl, n_giant, 52);       CTL_AT(ScanCtl, n_help, 56);        CTL_AT(ScanCtl, ticket_walk, 60);
 CTL_AT(ColCtl, ev_cursor, 0);       CTL_AT(ColCtl, ev_overflow, 8);     CTL_AT(ColCtl, n_cand, 12);        CTL_AT(ColCtl, n_tok, 16);
 CTL_AT(ColCtl, n_tile_list, 20);    CTL_AT(ColCtl, n_tile_list2, 24);   CTL_AT(ColCtl, tok_written, 28);   CTL_AT(ColCtl, tok_lost, 32);
-CTL_AT(ColCtl, unused, 36);         CTL_AT(ColCtl, export_toks, 48);    CTL_AT(ColCtl, n_keep, 52);
+CTL_AT(ColCtl, unused, 36);
+// Row export's control block (export_kernels.hpp: RowCtl for c3r_ctx::d_rowctl and its host mirror); the packers take &n_recs as counters[0], [1]
+static_assert(sizeof(c3r::RowCtl) == 64, "the row-export control block is 64 bytes");
+CTL_AT(RowCtl, n_recs, 0);          CTL_AT(RowCtl, n_bytes, 8);         CTL_AT(RowCtl, n_keep, 16);        CTL_AT(RowCtl, export_toks, 20);
 // (k_order_spans and k_tile_tokens write totals[0] and totals[1] through one pointer)
 static_assert(offsetof(c3r::ScanCtl, n_tok) == offsetof(c3r::ScanCtl, n_cand) + 4 && offsetof(c3r::ColCtl, tok_lost) == offsetof(c3r::ColCtl, tok_written) + 4, "totals[0], [1]");
 static_assert(c3r::EV_OVF_SCRATCH == 1 && c3r::EV_OVF_DEPTH16 == 2, "EvOverflow bits");

@@ -1,4 +1,4 @@
-// The row-export kernels (clair3_rna_amd/csrc/pileup_kernels.hpp) against plain serial host code, on hand-made arrays:
+// The row-export kernels (clair3_rna_amd/csrc/export_kernels.hpp; the scan: pileup_kernels.hpp) against plain serial host code, on hand-made arrays:
 //   A  k_row_keep                                  the two RefCall rules of the decoder, restated here in float32
 //   B  launch_excl_scan                            (k_excl_scan, or k_scan_local + k_excl_scan + k_scan_add) against an int64 sum
 //   C  k_pack_tokens, k_pack_rows, k_export_tokens a stable sort of every site's tokens by (read_idx, arrival index); k_gather_rows beside them
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../clair3_rna_amd/csrc/pileup_kernels.hpp"
+#include "../../clair3_rna_amd/csrc/export_kernels.hpp"
 #include "../../clair3_rna_amd/csrc/decode.hpp"
 
 using namespace c3r;

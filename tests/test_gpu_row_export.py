@@ -208,3 +208,26 @@ def test_kept_count_equals_the_rule(eng, which):
     # (site order = token order of eng.tokens(): the kept sites' tokens and indel records are countable from the same arrays)
     owner = np.repeat(np.arange(n), sites["n_tok"])
     assert k_bytes == int(sites["n_tok"][kept].sum()) and k_recs == int(((toks["indel"] != 0) & kept[owner]).sum())
+
+
+def test_tokens_and_both_snapshot_kinds_interleaved_on_one_context(eng):
+    """The token export's scan total, the kept count and the two pack counters are words of one control block.  tokens(), a snapshot that drops
+    RefCalls, tokens(), a full snapshot and another dropping one, in that order on one context: each call leaves the others' results as they were."""
+    n = _scan_small(eng)
+    eng.set_precision("f16x3")
+    eng.load_weights(_biased_weights("bias 4"), 18)
+    eng.infer(fetch=False)
+    toks_a = eng.tokens()
+    drop_a = eng.rows_begin(drop_ref_calls=True)
+    info_a = drop_a.info()
+    text_a = drop_a.decode("chr20", qual=2, show_ref=False)[0]
+    toks_b = eng.tokens()
+    full = eng.rows_begin(host_reads=False)
+    info_full = full.info()
+    text_full = full.decode("chr20", qual=2, show_ref=False)[0]
+    drop_b = eng.rows_begin(drop_ref_calls=True)
+    info_b = drop_b.info()
+    text_b = drop_b.decode("chr20", qual=2, show_ref=False)[0]
+    assert toks_a.tobytes() == toks_b.tobytes() and len(toks_a) > 0
+    assert info_a == info_b and 0 < info_a[0] < n == info_full[0]
+    assert text_a == text_b == text_full and text_a != b""
