@@ -44,6 +44,9 @@ hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
 `--phase_indels` (with --phase_output) hands hap_vcf --indels: heterozygous insertions, deletions and rows with two ALT alleles are phased too,
 by CIGAR-position alleles (no realignment, no left-alignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)); without it both files are what they were.
+`--hap_realign [W]` (with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin; excludes --left_align_indels) lifts "no realignment" for every
+step that holds reads against a site table: the flag and --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h:
+c3r_set_hap_realign); the unphased pass holds its reads against no table and does not get it.  Unit costs, no quality weights; a window stops at a splice junction.
 `--left_align_indels` (with one of --phase_indels, --haplotag_indels, --phasing_indels) lifts "no left-alignment" for every step that reads indels: the flag and
 --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h: c3r_set_hap_left_align).  A shift stops at a read's M run's
 start, at an N or another indel; there is still no realignment and there are no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap is not measured.
@@ -196,6 +199,8 @@ def build_parser():
            "every read's inside its own M run, on the device (include/c3r.h: c3r_set_hap_left_align) — so that a read whose aligner placed an "
            "indel elsewhere in a homopolymer or short tandem repeat shows the allele and not the reference; the flag is handed to every such "
            "step.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)")
+    from . import phasing as _phasing
+    _phasing.add_hap_realign_flag(a)
     a("--hap_min_bq", type=int, default=0, metavar="N",
       help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: a base whose quality is below N does not vote — every step that "
            "holds reads against a site table (phase_vcf between the passes, the 30-channel pass's haplotagging, hap_vcf, haplotag_bam) gets the flag, "
@@ -436,6 +441,10 @@ def _plan(args):
     min_bq = phasing.hap_min_bq_arg(args, bool(phased and (builtin or args.phased_vcf_fn)),
                                     "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step holds the reads against one")
     bq = ["--hap_min_bq", str(min_bq)] if min_bq else []
+    # (--hap_realign goes to every step that holds reads against a table: phase_vcf, the 30-channel pass, hap_vcf and haplotag_bam)
+    realign, _ = phasing.hap_realign_arg(args, bool(phased and (builtin or args.phased_vcf_fn)),
+                                         "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step holds the reads against one")
+    ra = ["--hap_realign", str(realign), "--ref_fn", args.ref_fn] if realign else []
     ext = ".vcf" if args.no_compress else ".vcf.gz"
     phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
     ctg = ["--ctg_name", args.ctg_name] if args.ctg_name else []
@@ -463,6 +472,7 @@ def _plan(args):
         first, second = copy.copy(args), copy.copy(args)
         first.phasing, first.enable_phasing_model = None, False
         first.hap_min_bq = 0                                  # (the unphased pass holds its reads against no site table: phase_vcf loads them itself)
+        first.hap_realign = 0
         second.phasing, second.phased_vcf_fn = None, phased_dir
         if args.phasing_indels:
             second.haplotag_indels = True                     # (the table of c3r_set_phase_alleles, as --phased_vcf_fn DIR --haplotag_indels)
@@ -472,7 +482,7 @@ def _plan(args):
         steps = [_Step("pass", first, None),
                  _Step("clear", (phased_dir, lambda name: name.startswith("phased_") and name.endswith(".vcf.gz")), None),
                  _Step("phase_vcf", ["--vcf_fn", unphased, "--output_dir", phased_dir, "--min_mq", str(args.min_mq), "--merge_levels", str(args.phase_merge_levels)]
-                       + (["--indels"] + la if args.phasing_indels else []) + bq + ctg + gpu, unphased),
+                       + (["--indels"] + la if args.phasing_indels else []) + bq + ra + ctg + gpu, unphased),
                  _Step("pass", second, None)]
     stem = os.path.join(args.output_dir, args.output_prefix + "_enable_phasing")
     source = phased_dir if builtin else args.phased_vcf_fn
@@ -482,14 +492,14 @@ def _plan(args):
     if args.phase_output:
         steps.append(_Step("hap_vcf", ["--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext, "--hap_counts_fn",
                                        stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if args.phase_indels else []) + tag_indels
-                           + (la if args.phase_indels or tag_indels else []) + bq + ctg + gpu,
+                           + (la if args.phase_indels or tag_indels else []) + bq + ra + ctg + gpu,
                            stem + ext))
     if args.haplotagged_bam:
         # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed (--ctg_name: added when the step runs); an
         # earlier run's files in this directory, for contigs this run did not process, go first
         bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
         steps += [_Step("clear", (bam_dir, lambda name: name.endswith(".bam") or name.endswith(".bam.bai")), stem + ext),
-                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + gpu, stem + ext)]
+                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + ra + gpu, stem + ext)]
     return steps
 
 
@@ -607,6 +617,7 @@ def _set_up(args, log, t_all):
     p.merger = sort_vcf.SampleMerger(p.out_fn, header, p.qual_merge, args.print_ref_calls, p.table, p.out_nt_fn, stream_gz=not args.no_compress,
                                      edits=p.edits) if p.rank == 0 else None
     p.hap_min_bq = int(getattr(args, "hap_min_bq", 0) or 0) if args.phased_vcf_fn else 0       # (only a pass with a phase table tags reads)
+    p.hap_realign = int(getattr(args, "hap_realign", 0) or 0) if args.phased_vcf_fn else 0     # (--hap_realign, likewise)
     p.fetcher = _Fetcher(p.bam_fn, args.ref_fn, want_quals=bool(p.hap_min_bq))
     p.phase_source = None                                              # --phased_vcf_fn: every contig's table is read on a fetch thread
     if args.phased_vcf_fn:
@@ -614,7 +625,8 @@ def _set_up(args, log, t_all):
         ref_of = None
         if getattr(args, "left_align_indels", False) and args.haplotag_indels:         # (asked from the fetch threads: nothing shared)
             ref_of = lambda c: (1, io.fetch_reference(args.ref_fn, c, 1, 2 ** 31, raw=True))
-        p.phase_source = phasedvcf.PhaseSource(args.phased_vcf_fn, args.haplotag_indels, *(() if ref_of is None else (None, ref_of)))
+        p.phase_source = phasedvcf.PhaseSource(args.phased_vcf_fn, args.haplotag_indels, *(() if ref_of is None else (None, ref_of)),
+                                               **(dict(realign=p.hap_realign) if p.hap_realign else {}))
     return p
 
 
@@ -830,6 +842,9 @@ def _device_stage(p, eng, ctg, rs, ref, phase):
         eng.load_reads(_empty_reads())               # (the previous contig's reads are done with: a new table would tag them again first)
         if p.phase_source.left_align is not None:    # (--left_align_indels: the tagging reads the whole contig's reference, set below again for the scan)
             eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str)))
+        if p.hap_realign:                            # (--hap_realign: the whole contig's reference likewise, then the switch)
+            from . import phasing
+            phasing.apply_hap_realign(eng, p.hap_realign, (1, ref), upper_view=not isinstance(ref, (bytes, str)))
         p.phase_source.apply(eng, phase)             # before the reads: they are tagged while they are prepared
         note = p.phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
         if note:

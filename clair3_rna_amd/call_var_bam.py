@@ -120,6 +120,8 @@ def build_parser():
            "too, not from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows `--phase_output --phase_indels` and "
            "`whatshap phase --indels` write.  Alleles are read off the CIGAR position: no realignment, no left-alignment (--left_align_indels lifts it), no base qualities "
            "(`--hap_min_bq` lifts it: a threshold, not weights)")
+    from . import phasing as _phasing
+    _phasing.add_hap_realign_flag(a)
     a('--left_align_indels', action='store_true',
       help="with --haplotag_indels: left-align the table's indels against the reference and every read's indel inside its own M run, on the "
            "device (include/c3r.h: c3r_set_hap_left_align), which lifts \"no left-alignment\"; the reference is then fetched for the whole "
@@ -182,6 +184,8 @@ def Run(args, engine=None):
         sys.exit("[ERROR] --left_align_indels needs --haplotag_indels (it left-aligns the indels the reads are haplotagged from)")
     from . import phasing
     min_bq = phasing.hap_min_bq_arg(args, bool(phased_vcf_fn), "--phased_vcf_fn: without a phase table no step holds the reads against one")
+    realign, _ = phasing.hap_realign_arg(args, bool(phased_vcf_fn), "--phased_vcf_fn: without a phase table no step holds the reads against one")
+    whole_contig = left_align or bool(realign)                # (the slice must cover every loaded read: the tagging reads it)
     for need in (args.bam_fn, args.ref_fn):
         if not os.path.isfile(need):
             sys.exit("[ERROR] file %s not found" % need)
@@ -197,8 +201,8 @@ def Run(args, engine=None):
         return 0
     extend_start, extend_end = max(1, ctg_start - 33), ctg_end + 33
     # (--left_align_indels: the whole contig — the table is the whole contig's, and the slice must cover every loaded read)
-    ref_start = 1 if left_align else max(1, ctg_start - 1000)
-    ref_seq = io.fetch_reference(args.ref_fn, ctg, ref_start, 2 ** 31 if left_align else ctg_end + 1000)
+    ref_start = 1 if whole_contig else max(1, ctg_start - 1000)
+    ref_seq = io.fetch_reference(args.ref_fn, ctg, ref_start, 2 ** 31 if whole_contig else ctg_end + 1000)
     if not ref_seq:
         sys.exit("[ERROR] Failed to load reference sequence from file (%s)." % args.ref_fn)
 
@@ -217,7 +221,8 @@ def Run(args, engine=None):
     phase = phase_source = None
     if phased_vcf_fn:
         from . import phasedvcf
-        phase_source = phasedvcf.PhaseSource(phased_vcf_fn, haplotag_indels, only=ctg, **(dict(left_align=lambda c: (ref_start, ref_seq)) if left_align else {}))
+        phase_source = phasedvcf.PhaseSource(phased_vcf_fn, haplotag_indels, only=ctg, **(dict(left_align=lambda c: (ref_start, ref_seq)) if left_align else {}),
+                                             **(dict(realign=realign) if realign else {}))
         phase = phase_source.table(ctg)
         note = phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
         if note:
@@ -227,6 +232,8 @@ def Run(args, engine=None):
             engine.load_reads(ReadSet.from_records([]))      # (a caller's engine may still hold a chunk's reads: a new table would tag them again first)
         if left_align:
             eng.set_reference(ref_start, ref_seq)            # (before the reads: they are tagged against it while they are prepared)
+        if realign:
+            phasing.apply_hap_realign(eng, realign, (ref_start, ref_seq))
         phase_source.apply(eng, phase)
     else:
         eng.set_phase_sites(None)                            # (a caller's engine may hold the table of an earlier chunk)

@@ -73,7 +73,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
            "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links",
            "c3r_set_hap_left_align", "c3r_hap_left_align_sites",
-           "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq"]
+           "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq",
+           "c3r_set_hap_realign", "c3r_get_hap_realign", "c3r_hap_realign_column"]
 
 _lib = None
 
@@ -129,6 +130,9 @@ def load_library():
     L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
     L.c3r_hap_assign.argtypes = [vp, i64, vp, C.POINTER(PhaseParams), vp, C.POINTER(HapAssignStats)]
     L.c3r_set_hap_left_align.argtypes = [vp, i32]
+    L.c3r_set_hap_realign.argtypes = [vp, i32]
+    L.c3r_get_hap_realign.argtypes = [vp, C.POINTER(i32)]
+    L.c3r_hap_realign_column.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.c3r_hap_left_align_sites.argtypes = [vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(LeftAlignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
@@ -340,6 +344,20 @@ class Engine(object):
         place inside its M run before they compare it with the table — which the caller normalises with hap_left_align_sites — and need a
         reference (set_reference) that covers the loaded reads.  With an allele table set and reads loaded the reads are tagged again."""
         self._chk(self.L.c3r_set_hap_left_align(self.h, 1 if on else 0))
+
+    def set_hap_realign(self, overhang):
+        """The opt-in switch of --hap_realign (c3r_set_hap_realign, overhang 0 .. 16, default 0 = off): while above 0, hap_allele_counts,
+        phase_allele_links, phase_allele_unit_links and the tagging of set_phase_alleles / load_reads compare each read's window of
+        `overhang` reference bases around a site with the site's two haplotypes (the rule `realign` of include/c3r.h) where the read can be
+        realigned there, and need a reference (set_reference).  It excludes set_hap_left_align.  With an allele table set and reads loaded
+        the reads are tagged again."""
+        self._chk(self.L.c3r_set_hap_realign(self.h, int(overhang)))
+
+    def hap_realign(self):
+        """The overhang of set_hap_realign (c3r_get_hap_realign; 0: off)."""
+        w = C.c_int32(0)
+        self._chk(self.L.c3r_get_hap_realign(self.h, C.byref(w)))
+        return int(w.value)
 
     def set_hap_min_bq(self, q):
         """The opt-in threshold of --hap_min_bq (c3r_set_hap_min_bq, 0 .. 93, default 0 = off): while above 0, every call that holds the
@@ -748,6 +766,28 @@ def hap_left_align_sites(sites, pool, ref_start, ref, pool_bases=None):
         raise C3RError(rc, "c3r_hap_left_align_sites: pos >= 1, flags 0 / 1, kinds 0 .. 2, an indel has a length and every insertion lies inside the pool")
     return (np.ascontiguousarray(out[:m.value]), np.ascontiguousarray(out_pool[:(ob.value + 1) // 2]), int(ob.value), np.ascontiguousarray(src[:m.value]),
             {k: int(getattr(st, k)) for k, _ in LeftAlignStats._fields_})
+
+
+def hap_realign_column(site, pool, ref_start, ref, read, cigars, seq4, overhang):
+    """The rule `realign` of include/c3r.h for one read at one site on the host (c3r_hap_realign_column; no GPU, no engine): one
+    HAP_SITE_DTYPE record, the packed pool, a reference slice (`ref`: str / bytes whose first letter is 1-based `ref_start`), one READ_DTYPE
+    record and the uint32 CIGAR and packed sequence arrays its offsets index -> (column 0 / 1 / 2, or 3 for no observation; whether the
+    read was realigned at the site)."""
+    L = load_library()
+    a = _hap_site_array(np.asarray(site).reshape(1))
+    pl, nb = _pool_args(pool, None)
+    r = np.frombuffer(ref.encode() if isinstance(ref, str) else bytes(ref), dtype=np.uint8)
+    for k in "ab":                                            # (the C entry carries no pool length: checked here)
+        if int(a[0][k + "_kind"]) == HAP_EV_INS and int(a[0][k + "_ins_off"]) + int(a[0][k + "_len"]) > nb:
+            raise ValueError("allele %s: the insertion runs past the pool of %d bases" % (k.upper(), nb))
+    rd = np.ascontiguousarray(np.asarray(read, dtype=READ_DTYPE).reshape(1))
+    cg, sq = np.ascontiguousarray(cigars, dtype=np.uint32), np.ascontiguousarray(seq4, dtype=np.uint8)
+    col, ra = C.c_int32(0), C.c_int32(0)
+    rc = L.c3r_hap_realign_column(_ptr(a), _ptr(pl) if nb else None, int(ref_start), _ptr(r) if len(r) else None, len(r), _ptr(rd), _ptr(cg) if len(cg) else None,
+                                  _ptr(sq) if len(sq) else None, int(overhang), C.byref(col), C.byref(ra))
+    if rc != 0:
+        raise C3RError(rc, "c3r_hap_realign_column: overhang 0 .. 16, pos >= 1, kinds 0 .. 2, an indel has a length, and a CIGAR that a load accepts")
+    return int(col.value), bool(ra.value)
 
 
 def phase_resolve(sites, links, min_reads=2, min_agree_pct=75):

@@ -165,6 +165,7 @@ struct c3r_ctx {
     int64_t n_phase = 0;
     bool phase_alleles = false;
     bool hap_la = false;                      // c3r_set_hap_left_align: the four allele kernels run their _la instantiation against d_ref
+    int hap_ra = 0;                           // c3r_set_hap_realign: the overhang W; above 0 they run their _ra instantiation against d_ref (never with hap_la)
     DevBuf d_phase, d_hptag, d_hpps, d_phasea, d_phasepool;
     // c3r_set_hap_min_bq: the threshold; whether the loaded reads came with qualities (c3r_load_reads_q); the qualities (2 n_seq_bytes, then
     // 32 bytes of 0xff), the masked copy of d_seq that read_args hands out while the threshold is above 0 (n_seq_bytes, then 16 zeroed bytes,
@@ -485,14 +486,16 @@ int mask_low_bq(c3r_ctx *ctx) {
     HIPCHK(ctx, hipGetLastError());
     return C3R_OK;
 }
-// The reference slice as the left-aligned observation reads it (c3r_set_hap_left_align), and the refusal of its four calls without one.
+// The reference slice as the left-aligned and the realigned observation read it (c3r_set_hap_left_align, c3r_set_hap_realign), and the refusal
+// of their four calls without one.
 HapRef hap_ref(const c3r_ctx *ctx) {
     HapRef r;
     r.ref = (const uint8_t *)ctx->d_ref.p; r.beg0 = (int32_t)(ctx->ref_start1 - 1); r.len = (int32_t)ctx->ref_len;
     return r;
 }
-int hap_la_needs_ref(c3r_ctx *ctx, const char *call) {
+int hap_needs_ref(c3r_ctx *ctx, const char *call) {
     if (ctx->hap_la && ctx->ref_len == 0) return fail(ctx, C3R_EINVAL, "%s: c3r_set_hap_left_align is on and no reference is set (c3r_set_reference)", call);
+    if (ctx->hap_ra > 0 && ctx->ref_len == 0) return fail(ctx, C3R_EINVAL, "%s: c3r_set_hap_realign is on and no reference is set (c3r_set_reference)", call);
     return C3R_OK;
 }
 // One launch of such a kernel: a group of PREP_GRP lanes per read.
@@ -695,10 +698,11 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
             h.sites = (const c3r_phase_site_t *)ctx->d_phase.p;
             launch_per_read(ctx, "k_haplotag", k_haplotag, h);
         } else {
-            if ((rc = hap_la_needs_ref(ctx, "c3r_load_reads"))) return rc;
-            HapAlleleTagLaArgs h = tag_args(read_args<HapAlleleTagLaArgs>(ctx, n));
+            if ((rc = hap_needs_ref(ctx, "c3r_load_reads"))) return rc;
+            HapAlleleTagRaArgs h = tag_args(read_args<HapAlleleTagRaArgs>(ctx, n));
             h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.pool = (const uint8_t *)ctx->d_phasepool.p;
-            if (ctx->hap_la) { h.ref = hap_ref(ctx); launch_per_read(ctx, "k_haplotag_alleles_la", k_haplotag_alleles_la, h); }
+            if (ctx->hap_ra > 0) { h.ref = hap_ref(ctx); h.overhang = (uint32_t)ctx->hap_ra; launch_per_read(ctx, "k_haplotag_alleles_ra", k_haplotag_alleles_ra, h); }
+            else if (ctx->hap_la) { h.ref = hap_ref(ctx); launch_per_read<HapAlleleTagLaArgs>(ctx, "k_haplotag_alleles_la", k_haplotag_alleles_la, h); }
             else launch_per_read<HapAlleleTagArgs>(ctx, "k_haplotag_alleles", k_haplotag_alleles, h);
         }
     }
@@ -957,7 +961,7 @@ int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, con
         return fail(ctx, C3R_EINVAL, "c3r_load_reads: c3r_set_hap_min_bq is %d and the reads come without qualities (c3r_load_reads_q)", ctx->hap_min_bq);
     if (n_reads >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many reads");
     if (n_cigar_ops >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many CIGAR ops");
-    if (ctx->phase_alleles) if (int rc0 = hap_la_needs_ref(ctx, "c3r_load_reads")) return rc0;       // (before anything of the previous load is given up)
+    if (ctx->phase_alleles) if (int rc0 = hap_needs_ref(ctx, "c3r_load_reads")) return rc0;       // (before anything of the previous load is given up)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool timing = getenv("C3R_TIMING") != nullptr;
     // whatever happens below, the previous contig's tables are gone
@@ -1374,7 +1378,7 @@ static int check_hap_sites(c3r_ctx *ctx, const char *what, const c3r_hap_site_t 
 int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8_t *h1, int64_t n, const uint8_t *ins_pool, int64_t pool_bases) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !h1)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "phase allele site", sites, n, ins_pool, pool_bases, h1)) return rc;
-    if (n) if (int rc = hap_la_needs_ref(ctx, "c3r_set_phase_alleles")) return rc;
+    if (n) if (int rc = hap_needs_ref(ctx, "c3r_set_phase_alleles")) return rc;
     if (n == 0 && ctx->n_phase == 0) return C3R_OK;               // (nothing set, nothing to clear: no copy, no wait, no rebuild)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (n) {
@@ -1393,13 +1397,15 @@ int c3r_set_phase_alleles(c3r_ctx *ctx, const c3r_hap_site_t *sites, const uint8
 int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *counts) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !counts)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "query site", sites, n, ins_pool, pool_bases, nullptr)) return rc;
-    if (int rc = hap_la_needs_ref(ctx, "c3r_hap_allele_counts")) return rc;
+    if (int rc = hap_needs_ref(ctx, "c3r_hap_allele_counts")) return rc;
     auto upload_sites = [&](HapAlleleArgs &a) {
         int rc;
         if ((rc = upload(ctx, ctx->d_hasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_hapool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
         a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.pool = (const uint8_t *)ctx->d_hapool.p;
         return (int)C3R_OK;
     };
+    if (ctx->hap_ra > 0)
+        return hap_count_table(ctx, "k_hap_allele_counts_ra", k_hap_allele_counts_ra, n, counts, [&](HapAlleleRaArgs &a) { a.ref = hap_ref(ctx); a.overhang = (uint32_t)ctx->hap_ra; return upload_sites(a); });
     if (ctx->hap_la) return hap_count_table(ctx, "k_hap_allele_counts_la", k_hap_allele_counts_la, n, counts, [&](HapAlleleLaArgs &a) { a.ref = hap_ref(ctx); return upload_sites(a); });
     return hap_count_table(ctx, "k_hap_allele_counts", k_hap_allele_counts, n, counts, upload_sites);
 }
@@ -1407,20 +1413,22 @@ int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, 
 int c3r_phase_allele_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, uint32_t *links) {
     if (!ctx || n < 0 || pool_bases < 0 || (n && (!sites || !links)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "candidate site", sites, n, ins_pool, pool_bases, nullptr, true)) return rc;
-    if (int rc = hap_la_needs_ref(ctx, "c3r_phase_allele_links")) return rc;
+    if (int rc = hap_needs_ref(ctx, "c3r_phase_allele_links")) return rc;
     if (n == 0) return C3R_OK;
     const size_t words = (size_t)n * C3R_PHASE_LINKS * 2;
     if (ctx->n_reads == 0) { memset(links, 0, words * 4); return C3R_OK; }               // (no voters: nothing to launch)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = upload(ctx, ctx->d_pasites, sites, (size_t)n)) || (rc = upload(ctx, ctx->d_papool, ins_pool, (size_t)((pool_bases + 1) / 2)))) return rc;
-    AlleleLinkLaArgs a = read_args<AlleleLinkLaArgs>(ctx, ctx->n_reads);
+    AlleleLinkRaArgs a = read_args<AlleleLinkRaArgs>(ctx, ctx->n_reads);
     a.sites = (const c3r_hap_site_t *)ctx->d_pasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_papool.p;
     a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
-    if (ctx->hap_la) a.ref = hap_ref(ctx);
+    if (ctx->hap_la || ctx->hap_ra > 0) a.ref = hap_ref(ctx);
+    a.overhang = (uint32_t)ctx->hap_ra;
     return counter_table(ctx, ctx->d_links, words, links, [&](uint32_t *t) {
         a.links = t;
-        if (ctx->hap_la) launch_per_read(ctx, "k_phase_allele_links_la", k_phase_allele_links_la, a);
+        if (ctx->hap_ra > 0) launch_per_read(ctx, "k_phase_allele_links_ra", k_phase_allele_links_ra, a);
+        else if (ctx->hap_la) launch_per_read<AlleleLinkLaArgs>(ctx, "k_phase_allele_links_la", k_phase_allele_links_la, a);
         else launch_per_read<AlleleLinkArgs>(ctx, "k_phase_allele_links", k_phase_allele_links, a);
     });
 }
@@ -1429,7 +1437,7 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
                                 int64_t cap_units, int64_t *n_units) {
     if (!ctx || n < 0 || pool_bases < 0 || cap_units < 0 || (n && (!sites || !h1)) || (pool_bases && !ins_pool)) return C3R_EINVAL;
     if (int rc = check_hap_sites(ctx, "unit site", sites, n, ins_pool, pool_bases, h1, true)) return rc;
-    if (int rc = hap_la_needs_ref(ctx, "c3r_phase_allele_unit_links")) return rc;
+    if (int rc = hap_needs_ref(ctx, "c3r_phase_allele_unit_links")) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (sites[i].ps != -1 && sites[i].ps < 1) return fail(ctx, C3R_EINVAL, "unit site %lld: ps %d is neither -1 (no block) nor a 1-based position", (long long)i, sites[i].ps);
     std::vector<int32_t> unit_ps, unit_of;
@@ -1450,14 +1458,16 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
     int rc;
     if ((rc = upload(ctx, ctx->d_pasites, t.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_papool, ins_pool, (size_t)((pool_bases + 1) / 2))) ||
         (rc = upload(ctx, ctx->d_unitof, unit_of.data(), (size_t)n))) return rc;
-    AlleleUnitLinkLaArgs a = read_args<AlleleUnitLinkLaArgs>(ctx, ctx->n_reads);
+    AlleleUnitLinkRaArgs a = read_args<AlleleUnitLinkRaArgs>(ctx, ctx->n_reads);
     a.sites = (const c3r_hap_site_t *)ctx->d_pasites.p; a.n_sites = (int32_t)n; a.pool = (const uint8_t *)ctx->d_papool.p;
     a.unit_of = (const int32_t *)ctx->d_unitof.p; a.n_units = (int32_t)U;
     a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
-    if (ctx->hap_la) a.ref = hap_ref(ctx);
+    if (ctx->hap_la || ctx->hap_ra > 0) a.ref = hap_ref(ctx);
+    a.overhang = (uint32_t)ctx->hap_ra;
     return counter_table(ctx, ctx->d_links, words, ulinks, [&](uint32_t *t2) {                                  // (t and unit_of live until it returns)
         a.ulinks = t2;
-        if (ctx->hap_la) launch_per_read(ctx, "k_phase_allele_unit_links_la", k_phase_allele_unit_links_la, a);
+        if (ctx->hap_ra > 0) launch_per_read(ctx, "k_phase_allele_unit_links_ra", k_phase_allele_unit_links_ra, a);
+        else if (ctx->hap_la) launch_per_read<AlleleUnitLinkLaArgs>(ctx, "k_phase_allele_unit_links_la", k_phase_allele_unit_links_la, a);
         else launch_per_read<AlleleUnitLinkArgs>(ctx, "k_phase_allele_unit_links", k_phase_allele_unit_links, a);
     });
 }
@@ -1466,6 +1476,7 @@ int c3r_set_hap_left_align(c3r_ctx *ctx, int on) {
     if (!ctx) return C3R_EINVAL;
     const bool want = on != 0;
     if (want == ctx->hap_la) return C3R_OK;
+    if (want && ctx->hap_ra > 0) return fail(ctx, C3R_EINVAL, "c3r_set_hap_left_align: c3r_set_hap_realign is on (%d); the two exclude each other", ctx->hap_ra);
     const bool retag = ctx->phase_alleles && ctx->n_reads > 0;    // the tags on the device are those of the other observation
     if (retag && want && ctx->ref_len == 0)
         return fail(ctx, C3R_EINVAL, "c3r_set_hap_left_align: an allele table is set and reads are loaded, and no reference is set (c3r_set_reference)");
@@ -1474,6 +1485,67 @@ int c3r_set_hap_left_align(c3r_ctx *ctx, int on) {
     ctx->last_scan_pruned = false;
     ctx->host_cache.reset();
     return ::refilter(ctx);
+}
+
+int c3r_set_hap_realign(c3r_ctx *ctx, int overhang) {
+    if (!ctx) return C3R_EINVAL;
+    if (overhang < 0 || overhang > (int)RA_MAX_W) return fail(ctx, C3R_EINVAL, "c3r_set_hap_realign: overhang %d is outside 0 .. %d", overhang, (int)RA_MAX_W);
+    if (overhang == ctx->hap_ra) return C3R_OK;
+    if (overhang > 0 && ctx->hap_la) return fail(ctx, C3R_EINVAL, "c3r_set_hap_realign: c3r_set_hap_left_align is on; the two exclude each other");
+    const bool retag = ctx->phase_alleles && ctx->n_reads > 0;    // the tags on the device are those of another observation
+    if (retag && overhang > 0 && ctx->ref_len == 0)
+        return fail(ctx, C3R_EINVAL, "c3r_set_hap_realign: an allele table is set and reads are loaded, and no reference is set (c3r_set_reference)");
+    ctx->hap_ra = overhang;
+    if (!retag) return C3R_OK;
+    ctx->last_scan_pruned = false;
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
+int c3r_get_hap_realign(c3r_ctx *ctx, int *overhang) {
+    if (!ctx) return C3R_EINVAL;
+    if (overhang) *overhang = ctx->hap_ra;
+    return C3R_OK;
+}
+
+// The rule `realign` of include/c3r.h for one read at one site on the host: the serial walk finds the M op of the normalised CIGAR that
+// holds the anchor, as walk_sites does, and hap_observe_ra — the function the four _ra kernels call — decides there.
+int c3r_hap_realign_column(const c3r_hap_site_t *site, const uint8_t *ins_pool, int64_t ref_start, const char *ref, int64_t ref_len, const c3r_read_t *read,
+                           const uint32_t *cigars, const uint8_t *seq4, int overhang, int *column, int *realigned) {
+    if (!site || !read || !column || ref_len < 0 || ref_start < 1 || (ref_len && !ref) || (read->n_cigar && !cigars) || (read->l_seq && !seq4) || overhang < 0 ||
+        overhang > (int)RA_MAX_W || site->pos < 1)
+        return C3R_EINVAL;
+    const c3r_hap_allele_t *al[2] = {&site->a, &site->b};
+    for (int w = 0; w < 2; ++w)
+        if (al[w]->kind > C3R_HAP_EV_DEL || (al[w]->kind == C3R_HAP_EV_NONE ? al[w]->len != 0 : al[w]->len == 0) || (al[w]->kind == C3R_HAP_EV_INS && !ins_pool)) return C3R_EINVAL;
+    struct HostRef {                                               // HapRef on the caller's letters, any case
+        const char *ref; int64_t beg0, len;
+        uint32_t code(long long p) const {
+            const long long o = p - beg0;
+            if (o < 0 || o >= len) return 0u;
+            switch (ref[o]) { case 'A': case 'a': return 1u; case 'C': case 'c': return 2u; case 'G': case 'g': return 4u; case 'T': case 't': return 8u; default: return 0u; }
+        }
+    };
+    const HostRef R{ref, ref_start - 1, ref_len};
+    ReadInfo ri;
+    ri.cig = cigars ? cigars + read->cigar_off : nullptr; ri.pos = read->pos; ri.n_cig = read->n_cigar; ri.l_seq = read->l_seq; ri.read_idx = 0; ri.wbits = 0;
+    ri.seq_off = read->seq_off; ri.compat = 0; ri.padbit = 0;
+    const uint8_t *rseq = seq4 ? seq4 + read->seq_off : nullptr;
+    uint32_t col = HAP_NOTHING;
+    bool ra = false;
+    const c3r_hap_site_t e = *site;
+    const int err = walk_serial_ops(ri, [&](uint32_t op, uint32_t len, long long x, uint32_t y, const OpCtx &cx) {
+        if (op != C3R_CIG_M) return;
+        const long long dd = (long long)e.pos - 1 - x;
+        if (dd < 0 || dd >= (long long)len) return;
+        const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
+        if (q >= ri.l_seq) return;
+        col = hap_observe_ra(e, ri, rseq, ins_pool, R, (uint32_t)overhang, q, dd == (long long)len - 1, (unsigned long long)y + len, cx, &ra);
+    });
+    if (err) return C3R_EINVAL;
+    *column = (int)col;
+    if (realigned) *realigned = ra ? 1 : 0;
+    return C3R_OK;
 }
 
 int c3r_set_hap_min_bq(c3r_ctx *ctx, int min_bq) {

@@ -89,4 +89,13 @@ __global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts_la(const Hap
     });
 }
 
+// The same with the realigned observation (c3r_set_hap_realign): hap_observe_ra against the reference slice, with the switch's overhang.
+struct HapAlleleRaArgs : HapAlleleLaArgs { uint32_t overhang; };
+
+__global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts_ra(const HapAlleleRaArgs a) {
+    hap_count_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_observe_ra(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
+    });
+}
+
 }  // namespace c3r

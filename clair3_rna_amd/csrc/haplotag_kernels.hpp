@@ -22,12 +22,14 @@
 // the sites of that set.
 //
 // The pieces that every kernel which holds reads against a sorted site table shares are here as well (hapcount_kernels.hpp and
-// phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe, hap_observe_la.
+// phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe, hap_observe_la,
+// hap_observe_ra.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "reads_kernels.hpp"
+#include "realign.hpp"
 
 namespace c3r {
 
@@ -83,10 +85,7 @@ __device__ __forceinline__ SiteRange read_sites(const Site *sites, int n_sites, 
     return r;
 }
 
-__device__ __forceinline__ uint32_t hap_nibble(const uint8_t *p, unsigned long long q) {
-    const uint32_t byte = p[q >> 1];
-    return (q & 1) ? (byte & 15u) : (byte >> 4);
-}
+__host__ __device__ __forceinline__ uint32_t hap_nibble(const uint8_t *p, unsigned long long q) { return ra_nibble(p, q); }      // (realign.hpp owns it)
 
 // One walk of a read over the sites [lo, hi) (k_phase_links: a window of them) that its M ops cover: every M op searches its own stretch once.
 // on_site(site index, site, query offset of the read's base there, is it the op's first base, is it the op's last base, query offset behind
@@ -110,7 +109,7 @@ __device__ __forceinline__ void walk_sites(const ReadInfo &R, int gl, bool seria
 
 // The column of a biallelic SNV that base b shows: 0 ref, 1 alt, 2 neither (k_hap_counts: `other` for A, C, G, T; the others: nothing).
 __device__ __forceinline__ uint32_t snv_column(const c3r_phase_site_t &e, uint32_t b) { return b == e.ref ? 0u : b == e.alt ? 1u : 2u; }
-__device__ __forceinline__ bool hap_is_acgt(uint32_t b) { return b == 1u || b == 2u || b == 4u || b == 8u; }      // (not =, N, IUPAC)
+__host__ __device__ __forceinline__ bool hap_is_acgt(uint32_t b) { return b == 1u || b == 2u || b == 4u || b == 8u; }      // (not =, N, IUPAC)
 
 // The column of an allele site (SNV, insertion, deletion, two-ALT; the rule of include/c3r.h) that the read shows: 0 allele A, 1 allele B,
 // 2 another allele, HAP_NOTHING no observation.  The lane that holds the M op decides: the read's base on the anchor and — on the op's LAST
@@ -123,8 +122,8 @@ __device__ __forceinline__ bool hap_is_acgt(uint32_t b) { return b == 1u || b ==
 // reads of the plain walk (there it costs the loads of two more neighbours next to an insertion and nothing else) and leave it 0 for
 // the serial walk, where compat would also run mpileup_compat's scan of the pads inside insertions, which this rule does not know.
 constexpr uint32_t HAP_EV_OTHER = 3u;         // an insertion with a deletion at once behind it: equals no allele's kind
-constexpr uint32_t HAP_NOTHING = 3u;
-__device__ __forceinline__ uint32_t hap_observe(const c3r_hap_site_t &e, const uint8_t *rseq, uint32_t l_seq, const uint8_t *pool, unsigned long long q, bool last,
+constexpr uint32_t HAP_NOTHING = RA_NOTHING;  // no observation (realign.hpp owns the value)
+__host__ __device__ __forceinline__ uint32_t hap_observe(const c3r_hap_site_t &e, const uint8_t *rseq, uint32_t l_seq, const uint8_t *pool, unsigned long long q, bool last,
                                                 unsigned long long iq, const OpCtx &cx) {
     const uint32_t b = hap_nibble(rseq, q);
     if (e.base_matters && !hap_is_acgt(b)) return HAP_NOTHING;
@@ -221,6 +220,21 @@ __device__ __forceinline__ uint32_t hap_observe_la(const c3r_hap_site_t &e, cons
         return true;
     };
     return shows(e.a) ? 0u : shows(e.b) ? 1u : 2u;
+}
+
+// ---- the realigned observation (c3r_set_hap_realign; the rule `realign` of include/c3r.h, restated by tests/realignref.py) --------------------
+// hap_observe where the read is not realigned at the site, else the column of the smaller edit distance of the read's window to the two
+// haplotype strings (realign.hpp: ra_column; a tie is no observation).  In the lane that holds the M op, like its two siblings; q(s) and q(t)
+// lie under other ops, so that lane scans the read's raw CIGAR from its first op (ra_query_span) — the simple form: a read pays its ops
+// once per site it covers.  Nothing of the walk is looked at before the fallback, so the result does not depend on the walk, and reads
+// with adjacent M-like ops keep the plain walk.  __host__ too: c3r_hap_realign_column (c3r_lib.hip) is this function behind the serial walk.
+template <class Ref>
+__host__ __device__ __forceinline__ uint32_t hap_observe_ra(const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, const uint8_t *pool, const Ref &ref, uint32_t overhang,
+                                                            unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx, bool *realigned = nullptr) {
+    bool ra;
+    const uint32_t col = ra_column(e, pool, ref, R.cig, R.n_cig, (long long)R.pos, R.l_seq, rseq, overhang, ra);
+    if (realigned) *realigned = ra;
+    return ra ? col : hap_observe(e, rseq, R.l_seq, pool, q, last, iq, cx);
 }
 
 // ---- the tags ---------------------------------------------------------------------------------------------------------------------------------
@@ -362,6 +376,18 @@ __global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles_la(const HapA
         const uint8_t *rseq = a.seq + R.seq_off;
         return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
             return hap_observe_la(e, rseq, R.l_seq, a.pool, a.ref, q, first, iq, cx);
+        });
+    });
+}
+
+// The same with the realigned observation (c3r_set_hap_realign): hap_observe_ra against the reference slice, with the switch's overhang.
+struct HapAlleleTagRaArgs : HapAlleleTagLaArgs { uint32_t overhang; };
+
+__global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles_ra(const HapAlleleTagRaArgs a) {
+    hap_tag_read(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+        const uint8_t *rseq = a.seq + R.seq_off;
+        return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+            return hap_observe_ra(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
         });
     });
 }

@@ -50,7 +50,7 @@ __device__ __forceinline__ void load_fail(LoadStats *st, int read, int code) {
 // finalised op in order.  Returns LD_OK or the error code.  Serial: one lane walks one read.  The parallel walk of k_prep handles
 // the reads whose CIGAR needs none of this (every op kept as it is); the others come here.
 template <class Emit>
-__device__ __forceinline__ int walk_norm(const uint32_t *cig, uint32_t n, Emit &&emit) {
+__host__ __device__ __forceinline__ int walk_norm(const uint32_t *cig, uint32_t n, Emit &&emit) {
     bool have = false;
     uint32_t cop = 0;
     unsigned long long clen = 0;
@@ -102,9 +102,9 @@ struct SegWalk {
     long long x0;
     bool open, useful, after_n;
     int bad;              // LD_SEG_OPS when a segment holds more than 65535 ops
-    __device__ __forceinline__ void begin(int32_t pos) { x = pos; y = 0; k = 0; open = false; useful = false; after_n = false; bad = 0; first_op = 15; k0 = 0; q0 = 0; x0 = pos; }
+    __host__ __device__ __forceinline__ void begin(int32_t pos) { x = pos; y = 0; k = 0; open = false; useful = false; after_n = false; bad = 0; first_op = 15; k0 = 0; q0 = 0; x0 = pos; }
     template <class Seg>
-    __device__ __forceinline__ void close(Seg &&seg) {
+    __host__ __device__ __forceinline__ void close(Seg &&seg) {
         if (!open) return;
         const bool lead_indel = after_n && (first_op == C3R_CIG_I || first_op == C3R_CIG_D);
         if (useful || lead_indel) {
@@ -114,7 +114,7 @@ struct SegWalk {
         open = false;
     }
     template <class Seg>
-    __device__ __forceinline__ void op(uint32_t o, uint32_t len, Seg &&seg) {
+    __host__ __device__ __forceinline__ void op(uint32_t o, uint32_t len, Seg &&seg) {
         if (o == C3R_CIG_N) {
             close(seg);
             x += len; after_n = true; ++k;
@@ -189,9 +189,9 @@ __device__ __forceinline__ void op_records(const ReadInfo &R, uint32_t op, uint3
     }
 }
 
-__device__ __forceinline__ uint32_t fold_op(uint32_t c) { const uint32_t op = c & 15u; return (op == C3R_CIG_EQ || op == C3R_CIG_X) ? (uint32_t)C3R_CIG_M : op; }
-__device__ __forceinline__ bool op_ref(uint32_t op) { return op == C3R_CIG_M || op == C3R_CIG_D || op == C3R_CIG_N; }
-__device__ __forceinline__ bool op_qry(uint32_t op) { return op == C3R_CIG_M || op == C3R_CIG_I || op == C3R_CIG_S; }
+__host__ __device__ __forceinline__ uint32_t fold_op(uint32_t c) { const uint32_t op = c & 15u; return (op == C3R_CIG_EQ || op == C3R_CIG_X) ? (uint32_t)C3R_CIG_M : op; }
+__host__ __device__ __forceinline__ bool op_ref(uint32_t op) { return op == C3R_CIG_M || op == C3R_CIG_D || op == C3R_CIG_N; }
+__host__ __device__ __forceinline__ bool op_qry(uint32_t op) { return op == C3R_CIG_M || op == C3R_CIG_I || op == C3R_CIG_S; }
 
 // A first look at a read's CIGAR by its 16 lanes: total reference length (normalisation never changes it), the I / D ops, and whether
 // the parallel walk may take it as it is — every op kept (H only as the first or last op), no zero-length op, no pad, no equal
@@ -267,7 +267,7 @@ __device__ __forceinline__ void walk_plain(const ReadInfo &R, int gl, Emit &&emi
 // decoder look up.  A run of more than 64 characters is refused (LD_PAD_INS): the table describes the pads by a 64-bit mask.
 // on_op(op, len, x, y, neighbours) receives every op of the NORMALISED form (walk_serial_ops); walk_serial turns them into pile records.
 template <class OnOp>
-__device__ __forceinline__ int walk_serial_ops(const ReadInfo &R, OnOp &&on_op, bool *pads = nullptr) {
+__host__ __device__ __forceinline__ int walk_serial_ops(const ReadInfo &R, OnOp &&on_op, bool *pads = nullptr) {
     if (R.compat) {
         uint32_t run_i = 0, run_p = 0;
         bool any = false;

@@ -32,6 +32,10 @@ agreement with whatshap is not measured.
 
     python -m clair3_rna_amd.hap_vcf --bam_fn x.bam --vcf_fn out/output_enable_phasing.vcf.gz \\
         --phased_vcf_fn out/tmp/phased_output/phased_vcf --output_fn out/phased.vcf.gz --hap_counts_fn out/hap_counts.tsv
+
+--hap_realign [W] (off by default; needs --ref_fn; excludes --left_align_indels) lifts "no realignment", as in phase_vcf: the reads are realigned
+against the two alleles of every site of the phase table and of every candidate (include/c3r.h: c3r_set_hap_realign); without --indels /
+--haplotag_indels the SNV tables go through the allele calls, which give the SNV calls' results bit for bit with the switch off.
 """
 import argparse
 import os
@@ -143,7 +147,8 @@ def build_parser():
     a("--left_align_indels", action="store_true",
       help="with --indels: left-align the candidates' indels (and, with --haplotag_indels, the phase table's) against --ref_fn and every read's "
            "indel inside its M run, on the device (default: the alleles are read off the CIGAR position as they stand)")
-    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
+    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels and --hap_realign only")
+    phasing.add_hap_realign_flag(a)
     a("--hap_min_bq", type=int, default=0, metavar="N",
       help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
@@ -160,7 +165,8 @@ def Run(args, log=None):
     indels = bool(getattr(args, "indels", False))
     tag_indels = bool(getattr(args, "haplotag_indels", False))
     ref_of = left_align_reference(args, "--indels", indels or tag_indels)     # (or --haplotag_indels alone: then only the tags' table is left-aligned)
-    source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None or not tag_indels else (None, ref_of)))
+    realign, realign_ref = phasing.hap_realign_arg(args)
+    source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None or not tag_indels else (None, ref_of)), **(dict(realign=realign) if realign else {}))
     min_bq = phasing.hap_min_bq_arg(args, True, "")
     if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
         sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
@@ -188,6 +194,8 @@ def Run(args, log=None):
             if ref_of is not None:                            # (the whole contig: it covers every read)
                 eng.set_reference(*ref_of(ctg))
                 eng.set_hap_left_align(True)
+            if realign:
+                phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
             source.apply(eng, table)
             phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
             if indels:
@@ -195,6 +203,10 @@ def Run(args, log=None):
                 out, st = capi.hap_assign(capi.hap_site_keys(query), counts, args.min_reads, args.min_agree_pct)
                 strings[ctg] = per[ctg][2]
                 lines += allele_counts_lines(ctg, query, strings[ctg], out, counts)
+            elif realign:                                     # (the SNV queries through the allele call: only the observation changes)
+                counts = eng.hap_allele_counts(phasing.snv_sites_as_alleles(query)[0])
+                out, st = capi.hap_assign(query, counts, args.min_reads, args.min_agree_pct)
+                lines += counts_lines(ctg, query, out, counts)
             else:
                 counts = eng.hap_counts(query)
                 out, st = capi.hap_assign(query, counts, args.min_reads, args.min_agree_pct)

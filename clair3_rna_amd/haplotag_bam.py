@@ -26,6 +26,9 @@ phasedvcf.contig_alleles -> Engine.set_phase_alleles), still as CIGAR-position a
 
     python -m clair3_rna_amd.haplotag_bam --bam_fn x.bam --phased_vcf_fn out/tmp/phased_output/phased_vcf \\
         --output_dir out/tmp/phased_output/phased_bam
+
+--hap_realign [W] (default off; needs --ref_fn; excludes --left_align_indels): the reads are realigned against the two alleles of every site
+before they vote (include/c3r.h: c3r_set_hap_realign), as in phase_vcf; without --haplotag_indels the SNV table goes through the allele call.
 """
 import argparse
 import os
@@ -74,7 +77,9 @@ def build_parser():
       help="with --haplotag_indels: left-align the table's indels against --ref_fn and every read's indel inside its own M run, on the device "
            "(include/c3r.h: c3r_set_hap_left_align): the tags of a 30-channel pass that ran with this flag.  A shift stops at the M run's "
            "start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap is not measured")
-    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
+    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels and --hap_realign only")
+    from . import phasing
+    phasing.add_hap_realign_flag(a)
     a("--hap_min_bq", type=int, default=0, metavar="N",
       help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
@@ -96,7 +101,8 @@ def Run(args, log=None):
     from .phase_vcf import left_align_reference
     tag_indels = bool(getattr(args, "haplotag_indels", False))
     ref_of = left_align_reference(args, "--haplotag_indels", tag_indels)
-    source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None else (None, ref_of)))
+    realign, realign_ref = phasing.hap_realign_arg(args)
+    source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None else (None, ref_of)), **(dict(realign=realign) if realign else {}))
     min_bq = phasing.hap_min_bq_arg(args, True, "")
     threads = int(getattr(args, "threads", 0) or 0)
     command = getattr(args, "command", None) or " ".join(sys.argv)
@@ -121,6 +127,8 @@ def Run(args, log=None):
                         eng.set_params()
                     if ref_of is not None:                         # (the whole contig: it covers every read)
                         eng.set_reference(*ref_of(ctg))
+                    if realign:
+                        phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
                     source.apply(eng, table)
                     phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()

@@ -27,6 +27,11 @@ The rule (include/c3r.h: c3r_phase_links / c3r_phase_resolve) is a greedy linkag
 not been measured.
 
     python -m clair3_rna_amd.phase_vcf --bam_fn x.bam --vcf_fn out/output.vcf.gz --output_dir out/tmp/phased_output/phased_vcf
+
+--hap_realign [W] (default off; needs --ref_fn; excludes --left_align_indels) lifts "no realignment": every read's window of W reference bases
+around a site is compared with the site's two alleles and the smaller unit-cost edit distance decides (include/c3r.h: c3r_set_hap_realign;
+phasing.apply_hap_realign).  Without --indels the SNV candidates go through the allele calls, which give the SNV calls' results bit for bit
+with the switch off, so only the observation changes.  No quality weights, no affine gaps; a window stops at a splice junction.
 """
 import argparse
 import os
@@ -53,7 +58,8 @@ def build_parser():
     a("--left_align_indels", action="store_true",
       help="with --indels: left-align the candidates' indels against --ref_fn and every read's indel inside its M run, on the device "
            "(default: the alleles are read off the CIGAR position as they stand)")
-    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels only")
+    a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels and --hap_realign only")
+    phasing.add_hap_realign_flag(a)
     a("--hap_min_bq", type=int, default=0, metavar="N",
       help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
@@ -89,6 +95,7 @@ def Run(args, log=None):
     indels = bool(getattr(args, "indels", False))
     ref_of = left_align_reference(args, "--indels", indels)
     min_bq = phasing.hap_min_bq_arg(args, True, "")
+    realign, realign_ref = phasing.hap_realign_arg(args)
     per = phasing.allele_candidates_from_vcf(args.vcf_fn, None, *(() if ref_of is None else (ref_of,))) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
     what = "heterozygous SNV / indel / two-ALT" if indels else "heterozygous SNV"
     contigs = args.ctg_name.split(",") if args.ctg_name else list(per)
@@ -111,12 +118,18 @@ def Run(args, log=None):
             if ref_of is not None:                            # (the whole contig: it covers every read)
                 eng.set_reference(*ref_of(ctg))
                 eng.set_hap_left_align(True)
+            if realign:
+                phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
             phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
             fn = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
             if indels:
                 pool, strings = rest[0], rest[1]
                 ps, h1, st = eng.phase_allele_sites(sites, pool, args.min_reads, args.min_agree_pct, merge_levels)
                 phasing.write_allele_phased_vcf(args.vcf_fn, ctg, sites, strings, ps, h1, fn)
+            elif realign:                                     # (the SNV table through the allele calls: only the observation changes)
+                out = sites.copy()
+                out["ps"], out["h1"], st = eng.phase_allele_sites(phasing.snv_sites_as_alleles(sites)[0], None, args.min_reads, args.min_agree_pct, merge_levels)
+                phasing.write_phased_vcf(args.vcf_fn, ctg, out, fn)
             else:
                 out, st = eng.phase_sites(sites, args.min_reads, args.min_agree_pct, merge_levels)
                 phasing.write_phased_vcf(args.vcf_fn, ctg, out, fn)

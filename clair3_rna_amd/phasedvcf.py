@@ -189,7 +189,7 @@ class PhaseSource(object):
     whichever thread asks first (call_sample asks from its fetch threads) — or, with `only`, for that one contig alone (the per-chunk
     driver never asks for another).  A contig without a file or without a row gets the empty table of the source's kind."""
 
-    def __init__(self, path, tag_indels=False, only=None, left_align=None):
+    def __init__(self, path, tag_indels=False, only=None, left_align=None, realign=0):
         """left_align (--left_align_indels, with tag_indels only; None: off): a function contig -> (1-based start, reference slice).  The
         allele table is left-aligned against it where it is read, and `apply` switches the engine's observation to match."""
         import os
@@ -200,6 +200,7 @@ class PhaseSource(object):
         if left_align is not None and not tag_indels:
             sys.exit("[ERROR] --left_align_indels needs --haplotag_indels")
         self.path, self.tag_indels, self.only, self.left_align = path, bool(tag_indels), only, left_align
+        self.realign = int(realign)                           # --hap_realign (0: off): apply hands an SNV table to the allele call
         self.per_contig = os.path.isdir(path) or only is not None
         self.all, self.lock = None, threading.Lock()
 
@@ -226,6 +227,10 @@ class PhaseSource(object):
             if self.left_align is not None:
                 engine.set_hap_left_align(True)
             engine.set_phase_alleles(table.sites, *table._rest)
+        elif self.realign and len(table):
+            from . import phasing
+            sites, h1 = phasing.snv_sites_as_alleles(table.sites)
+            engine.set_phase_alleles(sites, h1)
         else:
             engine.set_phase_sites(table.sites)
 

@@ -268,6 +268,64 @@ def load_reads_min_bq(eng, rs, q, ctg, log):
         log("[WARNING] %s: %d of %d reads carry no base qualities: --hap_min_bq masks none of their bases" % (ctg, without, len(rs.reads)))
 
 
+HAP_REALIGN_DEFAULT = 10      # --hap_realign without a value (recalled as whatshap's default overhang, not checked)
+
+
+def add_hap_realign_flag(add):
+    """--hap_realign [W] on a driver's parser (`add`: its add_argument)."""
+    add("--hap_realign", type=int, nargs="?", const=HAP_REALIGN_DEFAULT, default=0, metavar="W",
+        help="realign every read's window of W reference bases around a site against the site's two alleles before deciding which one the read "
+             "shows (include/c3r.h: c3r_set_hap_realign; W = 1 .. 16, %d without a value, default off; needs --ref_fn, excludes "
+             "--left_align_indels).  Unit costs, no quality weights, no affine gaps; a window stops at a splice junction; agreement with "
+             "whatshap is not measured" % HAP_REALIGN_DEFAULT)
+
+
+def hap_realign_arg(args, has_consumer=True, needs=""):
+    """A driver's --hap_realign: (W, contig -> (1-based start, reference slice)), or (0, None) without the flag (also when the parser has
+    none).  Refuses a value outside 1 .. 16, the flag beside --left_align_indels, without a step that holds reads against a table
+    (`needs` names it) and without --ref_fn."""
+    import os
+    import sys
+    from . import io
+    w = getattr(args, "hap_realign", 0)
+    w = 0 if w is None else int(w)
+    if w == 0:
+        return 0, None
+    if not 1 <= w <= 16:
+        sys.exit("[ERROR] --hap_realign must lie between 1 and 16 (the overhang in reference bases; without a value: %d)" % HAP_REALIGN_DEFAULT)
+    if getattr(args, "left_align_indels", False):
+        sys.exit("[ERROR] --hap_realign and --left_align_indels exclude each other (include/c3r.h: c3r_set_hap_realign)")
+    if not has_consumer:
+        sys.exit("[ERROR] --hap_realign needs %s (it realigns reads for the steps that hold them against a site table)" % needs)
+    ref_fn = getattr(args, "ref_fn", None)
+    if not ref_fn:
+        sys.exit("[ERROR] --hap_realign needs --ref_fn")
+    if not os.path.isfile(ref_fn):
+        sys.exit("[ERROR] file %s not found" % ref_fn)
+    return w, io.contig_reference(ref_fn)
+
+
+def snv_sites_as_alleles(sites):
+    """A PHASE_SITE_DTYPE table as the allele table that says the same (include/c3r.h: on REF-and-one-SNV sites the allele calls give the
+    SNV calls' results bit for bit with the switches off): (HAP_SITE_DTYPE array with A = REF and B = ALT, uint8 h1).  Under --hap_realign
+    a step that would use the SNV table goes through this, so that only the observation changes."""
+    import numpy as np
+    from .capi import HAP_SITE_DTYPE
+    out = np.zeros(len(sites), dtype=HAP_SITE_DTYPE)
+    out["pos"], out["ps"], out["base_matters"] = sites["pos"], sites["ps"], 1
+    out["a_base"], out["b_base"] = sites["ref"], sites["alt"]
+    return out, np.ascontiguousarray(sites["h1"], dtype=np.uint8)
+
+
+def apply_hap_realign(eng, w, ref, **how):
+    """The one place where a driver's engine meets --hap_realign (include/c3r.h: c3r_set_hap_realign), before the contig's table and
+    reads: the reference slice that covers every read of the contig (`ref`: (1-based start, letters); `how`: Engine.set_reference's
+    options), then the switch."""
+    if w:
+        eng.set_reference(*ref, **how)
+        eng.set_hap_realign(w)
+
+
 def _left_aligned_candidates(table, ref):
     """_allele_table's tuple after left_align_table; a row's strings get a third element, the row's own POS (the site may have moved)."""
     sites, pool, strings, skipped = table

@@ -124,7 +124,7 @@ int c3r_set_sites(c3r_ctx *ctx, const int32_t *sites, int64_t n);
  * the read's base there is the site's ref (allele 0) or alt (allele 1) — for haplotype 1 when allele == h1, else for haplotype 2; votes
  * are counted per phase set as (c1, c2); the read's phase set is the one with the most votes (equal: the one whose first voting site on
  * the read comes first); hp = 1 if c1 > c2, 2 if c2 > c1, else 0.  This is whatshap's per-phase-set majority with unit weights and the
- * allele read off the CIGAR position: no realignment, and no base-quality weights (c3r_set_hap_min_bq, below, lifts it as far as a threshold does:
+ * allele read off the CIGAR position: no realignment (c3r_set_hap_realign lifts it), and no base-quality weights (c3r_set_hap_min_bq, below, lifts it as far as a threshold does:
  * a threshold, not weights).
  * n = 0 clears the table: nothing is launched then and the records' own hp count again.  C3R_EINVAL, naming the first bad index, for an
  * unsorted or repeated position, pos < 1, a base code other than 1, 2, 4, 8, ref == alt, h1 > 1 or ps < 0.  Valid before or after c3r_load_reads
@@ -140,7 +140,7 @@ int c3r_get_haplotags(c3r_ctx *ctx, uint8_t *hp, int64_t cap, c3r_haplotag_stats
 int c3r_get_read_phase_sets(c3r_ctx *ctx, int32_t *ps, int64_t cap);
 /* Per-haplotype allele counts at called sites, and the phase of a heterozygous call from them: what phases the FINAL VCF once the reads are
  * tagged, and, written out, the haplotype support of every call.  c3r_hap_counts: biallelic SNVs only; c3r_hap_allele_counts (below):
- * SNVs, insertions, deletions and sites with two ALT alleles.  Both are a majority rule over CIGAR-position alleles (no realignment, no
+ * SNVs, insertions, deletions and sites with two ALT alleles.  Both are a majority rule over CIGAR-position alleles (no realignment (c3r_set_hap_realign lifts it), no
  * base qualities).
  *
  * Query sites (c3r_hap_counts): sorted by strictly increasing pos; ref and alt are valid; ps >= 0 is the phase set to count against; h1 is
@@ -212,7 +212,7 @@ int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, 
  *   comes first in the table), hp = 1 / 2 / 0 from c1 against c2; the winning set is kept for c3r_get_read_phase_sets.
  * On a table whose sites are all REF-and-one-SNV this IS c3r_set_phase_sites' rule, bit for bit (tags, sets and statistics): there the
  * column is 0 for ref, 1 for alt, and 2 or nothing for every other code.
- * Limits, as for both parents: the alleles are read off the CIGAR position — no realignment, no left-alignment of the reads' indels, no
+ * Limits, as for both parents: the alleles are read off the CIGAR position — no realignment (c3r_set_hap_realign lifts it), no left-alignment of the reads' indels, no
  * base qualities; a read whose aligner placed an indel one repeat unit away from the VCF's anchor shows "another allele" and does not
  * vote.  Agreement with `whatshap haplotag` (which, as far as we recall and have not checked, reads indel rows of a phased VCF too) is
  * not measured.
@@ -308,7 +308,7 @@ int c3r_phase_merge(const c3r_phase_site_t *in, int64_t n, const uint32_t *ulink
  *   c3r_phase_resolve and c3r_phase_merge read pos, ps and h1 only: the caller hands them a pseudo-table (pos, ref = 1, alt = 2, ps, h1),
  *   as c3r_phase_merge itself does for the units.  h1 = 0: allele A lies on haplotype 1 (GT 0|1, 1|2); h1 = 1: allele B (GT 1|0, 2|1).
  * On a table whose sites are all REF-and-one-SNV both calls give the words of c3r_phase_links / c3r_phase_unit_links.
- * Limits, as for both parents: the alleles are read off the CIGAR position — no realignment, no left-alignment of the reads' indels, no
+ * Limits, as for both parents: the alleles are read off the CIGAR position — no realignment (c3r_set_hap_realign lifts it), no left-alignment of the reads' indels, no
  * base qualities; the chain is greedy, not wMEC; agreement with `whatshap phase --indels` is not measured.
  *
  * c3r_phase_allele_links: links [n][K][2] cis / trans.  ps is IGNORED (a negative one is accepted); every other validation is
@@ -360,7 +360,7 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
  * no event.  The read's base on a site is the one the CIGAR puts there, and everything else of the observation is unchanged.  The result
  * does not depend on the walk a read takes: a read whose CIGAR holds two M-like ops in a row takes the serial walk while the switch is on
  * (the plain walk hands them out one by one; aligners that write = / X pay one lane per read there).
- * What remains: a shift stops at the M run's start, at an N or another indel, and at the slice's edge; there is no realignment and there
+ * What remains: a shift stops at the M run's start, at an N or another indel, and at the slice's edge; there is no realignment (c3r_set_hap_realign lifts it) and there
  * are no base qualities (c3r_set_hap_min_bq lifts it: a threshold, not weights); agreement with whatshap is not measured.
  *
  * c3r_set_hap_left_align(ctx, on): default 0.  While on, the four calls above run k_*_la (the same launches, one kernel each, with
@@ -376,6 +376,57 @@ int c3r_set_hap_left_align(c3r_ctx *ctx, int on);
 int c3r_hap_left_align_sites(const c3r_hap_site_t *sites, int64_t n, const uint8_t *ins_pool, int64_t pool_bases, int64_t ref_start, const char *ref,
                              int64_t ref_len, c3r_hap_site_t *out_sites, uint8_t *out_pool, int64_t out_pool_cap, int64_t *out_pool_bases,
                              int64_t *src_index, int64_t *n_out, c3r_left_align_stats_t *stats);
+/* Allele realignment for the same four calls (c3r_hap_allele_counts, c3r_phase_allele_links, c3r_phase_allele_unit_links and the tagging of
+ * c3r_set_phase_alleles / c3r_load_reads).  Opt-in (--hap_realign [W]); switched off, every path, launch and output byte is what the
+ * contracts above say.  It lifts their "no realignment": where the aligner wrote a substitution as `1D1I` beside the site, or put an indel a
+ * few bases from an SNV, the CIGAR-position allele is wrong although the read's bases are right.  Switched on, the read's local window is
+ * compared with the two haplotypes of the site — the step that stands behind `whatshap phase` and `whatshap haplotag` in the reference flow
+ * (run_clair3_rna:749-794) — with unit costs.  This is where the rule is stated; csrc/realign.hpp with csrc/haplotag_kernels.hpp
+ * (hap_observe_ra), c3r_hap_realign_column and tests/realignref.py restate it.
+ *
+ * realign, with overhang W: W = 0 is off, the legal range is 1 .. 16.  The drivers' default for the flag without a value is 10, which we
+ * recall as whatshap's default and have not checked.
+ * Site and window.  Site e (c3r_hap_site_t) has the 0-based anchor p0 = pos - 1.  D = the larger DEL length of its two alleles (0 if
+ *  neither is a deletion), I = the larger INS length.  Reference interval [s, t): s = p0 - W, t = p0 + 1 + D + W.  Haplotype string of
+ *  allele X = ref[s, p0) + X.base + X.ins + ref[p0 + 1 + X.del, t): both strings cover the same reference interval.
+ * A site is realignable when [s, t) lies inside the slice of c3r_set_reference and every reference base in it is A, C, G or T, and
+ *  2W + 1 + D + I <= 64.
+ * Query offset q(p) of a reference position p in a read: p is covered by the CIGAR op with first reference base x and first query base y
+ *  (soft clips count in y, as everywhere else); q(p) = y + (p - x) under an M-like op, q(p) = y under a D; under an N the window is not
+ *  usable.  H, P and empty ops consume nothing, = and X are M: the raw CIGAR and the normalised one give the same answer.  Hence an
+ *  insertion directly before s is outside the window and one directly before t is inside.
+ * A read is realigned at the site when the site is realignable, read.pos <= s and t < read.end, no N op holds a position of [s, t],
+ *  q(t) <= l_seq and m = q(t) - q(s) <= 64.
+ * Observation of a realigned read: the window is the m codes at q(s) .. q(t) - 1 of the sequence the kernels read (the masked copy under
+ *  c3r_set_hap_min_bq); dA, dB = the global unit-cost edit distances (Levenshtein) of the window to the two haplotype strings, where a read
+ *  code other than 1, 2, 4, 8 (N, a masked base) equals no base.  Column 0 when dA < dB, column 1 when dB < dA, NO OBSERVATION when
+ *  dA == dB: the realigned observation never yields column 2.  base_matters and event_matters are not looked at.
+ * Unchanged: the anchor must lie under an M op of the normalised CIGAR at a query offset below l_seq (an anchor under D or N: nothing), as
+ *  c3r_hap_allele_counts says.  Where the read is NOT realigned at the site the observation is c3r_hap_allele_counts', unchanged (a read's
+ *  ends, a splice junction within W, a long allele, a site near the slice's edge): the set of observed (read, site) pairs never shrinks
+ *  by anything but ties.
+ * The result depends neither on the walk a read takes nor on where inside (s, t) the CIGAR places its indels.
+ * What remains: the window stops at an N; there are no quality weights (c3r_set_hap_min_bq composes by construction: a masked base matches
+ *  nothing) and no affine gaps; agreement with whatshap is not measured.  A table row at a different but equivalent placement has another
+ *  window: c3r_hap_left_align_sites stays useful for rows (it does not look at reads or at this switch).
+ *
+ * c3r_set_hap_realign(ctx, overhang): default 0; C3R_EINVAL outside 0 .. 16.  While above 0 the four calls run k_*_ra (the same launches,
+ * one kernel each, hap_observe_ra in hap_observe's place, no atomics of their own) against the slice of c3r_set_reference that is current
+ * when they run, and return C3R_EINVAL with a message when no reference is set (c3r_set_phase_alleles with n = 0 still clears).  Changing
+ * the value with an allele table set and reads loaded tags the reads again (C3R_EINVAL, and the value stays, when that needs a reference
+ * and none is set); a later c3r_set_reference does NOT tag again.  Realign and left-align exclude each other: turning one on while the
+ * other is on is C3R_EINVAL and changes nothing.  The table of c3r_set_phase_sites and the four SNV kernels never look at the switch.
+ * c3r_get_hap_realign: the value.
+ * c3r_hap_realign_column is host code (no context, no device), compiled from the header the kernels use: the column (0, 1, 2, or 3 = no
+ * observation) of ONE read at ONE site and whether the read was realigned there (0: the column is c3r_hap_allele_counts').  site and
+ * ins_pool as in c3r_hap_allele_counts; the slice as in c3r_hap_left_align_sites (any letter case); read, cigars and seq4 as c3r_load_reads
+ * takes them (cigars and seq4 are the arrays that read->cigar_off and read->seq_off index).  The call carries no pool length: the CALLER
+ * guarantees that an insertion allele's ins_off + len lies inside ins_pool, as c3r_hap_allele_counts checks it (capi.hap_realign_column does).  overhang 0: the observation with the switch
+ * off.  C3R_EINVAL for a NULL it needs, an overhang outside 0 .. 16, pos < 1, a malformed allele or a CIGAR the load would refuse. */
+int c3r_set_hap_realign(c3r_ctx *ctx, int overhang);
+int c3r_get_hap_realign(c3r_ctx *ctx, int *overhang);
+int c3r_hap_realign_column(const c3r_hap_site_t *site, const uint8_t *ins_pool, int64_t ref_start, const char *ref, int64_t ref_len, const c3r_read_t *read,
+                           const uint32_t *cigars, const uint8_t *seq4, int overhang, int *column, int *realigned);
 /* A base-quality threshold for the twelve kernels that hold the loaded reads against a site table: k_haplotag, k_hap_counts, k_phase_links,
  * k_phase_unit_links, k_haplotag_alleles, k_hap_allele_counts, k_phase_allele_links, k_phase_allele_unit_links and the four _la
  * instantiations — the tagging of c3r_set_phase_sites / c3r_set_phase_alleles / c3r_load_reads, c3r_hap_counts, c3r_hap_allele_counts,
