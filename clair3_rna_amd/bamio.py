@@ -10,7 +10,7 @@ import numpy as np
 from .reads import READ_DTYPE, ReadSet
 
 EXPORTS = ["c3r_bam_open", "c3r_bam_close", "c3r_bam_last_error", "c3r_bam_n_contigs", "c3r_bam_contig", "c3r_bam_has_index", "c3r_bam_contig_weight",
-           "c3r_bam_fetch", "c3r_bam_copy", "c3r_bam_want_quals", "c3r_bam_copy_quals", "c3r_bam_index_build", "c3r_bam_header_text", "c3r_bam_write_haplotagged", "c3r_vcf_merge", "c3r_vcf_compress", "c3r_vcfz_open", "c3r_vcfz_write",
+           "c3r_bam_fetch", "c3r_bam_copy", "c3r_bam_want_quals", "c3r_bam_copy_quals", "c3r_bam_index_build", "c3r_bam_header_text", "c3r_bam_write_haplotagged", "c3r_bam_write_haplotagged_pc", "c3r_vcf_merge", "c3r_vcf_compress", "c3r_vcfz_open", "c3r_vcfz_write",
            "c3r_vcfz_close", "c3r_vcfz_piece_make", "c3r_vcfz_append", "c3r_vcfz_piece_free", "c3r_fasta_fetch", "c3r_io_alloc", "c3r_io_free"]
 _LIB = None
 
@@ -39,6 +39,8 @@ def load_library():
         L.c3r_bam_header_text.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int64)]
         L.c3r_bam_write_haplotagged.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int,
                                                 C.POINTER(C.c_int64)]
+        L.c3r_bam_write_haplotagged_pc.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int,
+                                                   C.POINTER(C.c_int64)]
         L.c3r_vcf_merge.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int64,
                                     C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.c3r_vcf_compress.argtypes = [C.c_char_p, C.c_int]
@@ -136,15 +138,16 @@ class BamFile:
         self.L.c3r_bam_header_text(self.h, C.byref(text), C.byref(n))
         return C.string_at(text, n.value) if n.value else b""
 
-    def write_haplotagged(self, contig, out_path, rs=None, hp=None, ps=None, pg_line=None, threads=0):
+    def write_haplotagged(self, contig, out_path, rs=None, hp=None, ps=None, pg_line=None, threads=0, pc=None):
         """c3r_bam_write_haplotagged: every record of `contig` to the BAM `out_path`, old HP / PS / PC aux fields removed, `HP:C` and PS
         appended where hp[k] is 1 or 2.  rs: the ReadSet fetch(contig) returned; hp / ps: Engine.haplotags() / read_phase_sets() of it.
         rs None: nothing is paired, every record goes out untagged.  pg_line: one "@PG\t..." line added to the header.
+        pc (c3r_bam_write_haplotagged_pc): one uint32 per read, written as PC behind PS where hp[k] is 1 or 2; None: no PC, the bytes of before.
         -> dict(records, tagged, stripped, unpaired).  IOError with the library's message (it names the read index) and no file when the
         arrays do not fit the contig's records."""
         if rs is None:
-            if hp is not None or ps is not None:
-                raise ValueError("hp / ps without the reads they belong to")
+            if hp is not None or ps is not None or pc is not None:
+                raise ValueError("hp / ps / pc without the reads they belong to")
             reads_p = hp_p = ps_p = None
             n = 0
         else:
@@ -156,8 +159,14 @@ class BamFile:
             # (an empty numpy array still has an address: the library then checks that the contig holds no read record)
             reads_p, hp_p, ps_p = reads.ctypes.data, hp_a.ctypes.data, ps_a.ctypes.data
         counts = (C.c_int64 * 4)()
-        rc = self.L.c3r_bam_write_haplotagged(self.h, contig.encode(), reads_p, hp_p, ps_p, n, os.fsencode(out_path),
-                                              pg_line.encode() if isinstance(pg_line, str) else pg_line, int(threads), counts)
+        pg = pg_line.encode() if isinstance(pg_line, str) else pg_line
+        if pc is None:
+            rc = self.L.c3r_bam_write_haplotagged(self.h, contig.encode(), reads_p, hp_p, ps_p, n, os.fsencode(out_path), pg, int(threads), counts)
+        else:
+            pc_a = np.ascontiguousarray(pc, dtype=np.uint32)
+            if len(pc_a) != n:
+                raise ValueError("%d reads, %d PC values" % (n, len(pc_a)))
+            rc = self.L.c3r_bam_write_haplotagged_pc(self.h, contig.encode(), reads_p, hp_p, ps_p, pc_a.ctypes.data, n, os.fsencode(out_path), pg, int(threads), counts)
         if rc != 0:
             raise IOError("c3r_bam_write_haplotagged: %s" % self.L.c3r_bam_last_error(self.h).decode())
         return dict(zip(("records", "tagged", "stripped", "unpaired"), (int(c) for c in counts)))

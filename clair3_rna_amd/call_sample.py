@@ -43,13 +43,13 @@ only: under torch.distributed.run (WORLD_SIZE > 1) it exits with an [ERROR] line
 hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-haplotype allele counts on the GPU into
 <prefix>_enable_phasing_phased.vcf.gz and writes the counts to <prefix>_enable_phasing_hap_counts.tsv; without the flag nothing changes.
 `--phase_indels` (with --phase_output) hands hap_vcf --indels: heterozygous insertions, deletions and rows with two ALT alleles are phased too,
-by CIGAR-position alleles (no realignment, no left-alignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)); without it both files are what they were.
+by CIGAR-position alleles (no realignment, no left-alignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes)); without it both files are what they were.
 `--hap_realign [W]` (with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin; excludes --left_align_indels) lifts "no realignment" for every
 step that holds reads against a site table: the flag and --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h:
 c3r_set_hap_realign); the unphased pass holds its reads against no table and does not get it.  Unit costs, no quality weights; a window stops at a splice junction.
 `--left_align_indels` (with one of --phase_indels, --haplotag_indels, --phasing_indels) lifts "no left-alignment" for every step that reads indels: the flag and
 --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h: c3r_set_hap_left_align).  A shift stops at a read's M run's
-start, at an N or another indel; there is still no realignment and there are no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap is not measured.
+start, at an N or another indel; there is still no realignment and there are no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); agreement with whatshap is not measured.
 `--haplotagged_bam` (same conditions as --phase_output, and combinable with it) adds the step the reference's "Haplotag the BAM" commands stand
 for: haplotag_bam writes <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai for the contigs the run processed — every record of the
 contig, with the HP / PS tags the GPU computed from the phase table the second pass read; without the flag nothing changes.
@@ -198,19 +198,22 @@ def build_parser():
       help="with --phase_indels, --haplotag_indels or --phasing_indels: left-align the indels those steps read — the tables' against --ref_fn, "
            "every read's inside its own M run, on the device (include/c3r.h: c3r_set_hap_left_align) — so that a read whose aligner placed an "
            "indel elsewhere in a homopolymer or short tandem repeat shows the allele and not the reference; the flag is handed to every such "
-           "step.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)")
+           "step.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes)")
     from . import phasing as _phasing
     _phasing.add_hap_realign_flag(a)
+    _phasing.add_hap_bq_weights_flag(a, "with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: handed to the 30-channel pass, to hap_vcf (--phase_output) "
+                                        "and to haplotag_bam (--haplotagged_bam, which then writes PC); not to the unphased pass, which haplotags nothing, and not to "
+                                        "phase_vcf, whose links stay unweighted.  ")
     a("--hap_min_bq", type=int, default=0, metavar="N",
       help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: a base whose quality is below N does not vote — every step that "
            "holds reads against a site table (phase_vcf between the passes, the 30-channel pass's haplotagging, hap_vcf, haplotag_bam) gets the flag, "
            "fetches the qualities and reads such a base as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  The tensor build and "
-           "the unphased pass never look at it.  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads "
+           "the unphased pass never look at it.  A threshold, not whatshap's quality weights (--hap_bq_weights are those); an indel's own quality is not modelled; reads "
            "without qualities are never masked; agreement with whatshap is not measured")
     a("--phase_indels", action="store_true",
       help="with --phase_output: handed to hap_vcf as --indels — heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2) are "
            "phased too, by CIGAR-position alleles (no realignment, no left-alignment of the reads' indels unless --left_align_indels is given, no base qualities "
-           "(`--hap_min_bq` lifts it: a threshold, not weights)), and the counts "
+           "(`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes)), and the counts "
            "file gets the column ALLELES")
     a("-c", "--ctg_name", type=str, default=None)
     a("--bed_fn", type=str, default=None)
@@ -441,6 +444,9 @@ def _plan(args):
     min_bq = phasing.hap_min_bq_arg(args, bool(phased and (builtin or args.phased_vcf_fn)),
                                     "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step holds the reads against one")
     bq = ["--hap_min_bq", str(min_bq)] if min_bq else []
+    # (--hap_bq_weights goes to the steps that haplotag reads: the 30-channel pass, hap_vcf and haplotag_bam; phase_vcf's links stay unweighted)
+    weights = phasing.hap_bq_weights_arg(args, bool(phased and (builtin or args.phased_vcf_fn)), "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step haplotags the reads")
+    bw = ["--hap_bq_weights"] if weights else []
     # (--hap_realign goes to every step that holds reads against a table: phase_vcf, the 30-channel pass, hap_vcf and haplotag_bam)
     realign, _ = phasing.hap_realign_arg(args, bool(phased and (builtin or args.phased_vcf_fn)),
                                          "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step holds the reads against one")
@@ -473,6 +479,7 @@ def _plan(args):
         first.phasing, first.enable_phasing_model = None, False
         first.hap_min_bq = 0                                  # (the unphased pass holds its reads against no site table: phase_vcf loads them itself)
         first.hap_realign = 0
+        first.hap_bq_weights = False
         second.phasing, second.phased_vcf_fn = None, phased_dir
         if args.phasing_indels:
             second.haplotag_indels = True                     # (the table of c3r_set_phase_alleles, as --phased_vcf_fn DIR --haplotag_indels)
@@ -492,14 +499,14 @@ def _plan(args):
     if args.phase_output:
         steps.append(_Step("hap_vcf", ["--vcf_fn", stem + ext, "--phased_vcf_fn", source, "--output_fn", stem + "_phased" + ext, "--hap_counts_fn",
                                        stem + "_hap_counts.tsv", "--min_mq", str(args.min_mq)] + (["--indels"] if args.phase_indels else []) + tag_indels
-                           + (la if args.phase_indels or tag_indels else []) + bq + ra + ctg + gpu,
+                           + (la if args.phase_indels or tag_indels else []) + bq + bw + ra + ctg + gpu,
                            stem + ext))
     if args.haplotagged_bam:
         # the reference's names (run_clair3_rna:787,799), for the contigs the passes processed (--ctg_name: added when the step runs); an
         # earlier run's files in this directory, for contigs this run did not process, go first
         bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
         steps += [_Step("clear", (bam_dir, lambda name: name.endswith(".bam") or name.endswith(".bam.bai")), stem + ext),
-                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + ra + gpu, stem + ext)]
+                  _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext)]
     return steps
 
 
@@ -530,7 +537,7 @@ def Run(args, log=None):
 class _Pass(object):
     """What set-up (_set_up) leaves for the other stages of a pass, as plain attributes; nothing is added to it afterwards:
         the run        args, log, t_all, timeline, compat (which samtools' column text), channels, qual_rows, qual_merge, weights,
-                       hap_min_bq (--hap_min_bq of a pass with a phase table, else 0)
+                       hap_min_bq (--hap_min_bq of a pass with a phase table, else 0), hap_bq_weights (--hap_bq_weights, likewise)
         the ranks      rank, world, dist (torch.distributed or None), n_thr (the threads this process may count on)
         the paths      out_dir, out_fn, out_nt_fn, parts_dir, split_dir, cmd_fn, bed_fn, vcf_fn (genotyping mode), bam_fn (the one fetched from)
         the plan       all_contigs and chunk_nums (plan_chunks), contigs (this rank's, in calling order), fai ({contig: length})
@@ -618,7 +625,8 @@ def _set_up(args, log, t_all):
                                      edits=p.edits) if p.rank == 0 else None
     p.hap_min_bq = int(getattr(args, "hap_min_bq", 0) or 0) if args.phased_vcf_fn else 0       # (only a pass with a phase table tags reads)
     p.hap_realign = int(getattr(args, "hap_realign", 0) or 0) if args.phased_vcf_fn else 0     # (--hap_realign, likewise)
-    p.fetcher = _Fetcher(p.bam_fn, args.ref_fn, want_quals=bool(p.hap_min_bq))
+    p.hap_bq_weights = bool(getattr(args, "hap_bq_weights", False)) and bool(args.phased_vcf_fn)   # (--hap_bq_weights, likewise)
+    p.fetcher = _Fetcher(p.bam_fn, args.ref_fn, want_quals=bool(p.hap_min_bq or p.hap_bq_weights))
     p.phase_source = None                                              # --phased_vcf_fn: every contig's table is read on a fetch thread
     if args.phased_vcf_fn:
         from . import phasedvcf
@@ -853,7 +861,7 @@ def _device_stage(p, eng, ctg, rs, ref, phase):
             rs.reads["hp"] = 0                       # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
     t = [time()]
     from . import phasing
-    phasing.load_reads_min_bq(eng, rs, p.hap_min_bq if phase is not None else 0, ctg, p.log); t.append(time())
+    phasing.load_reads_min_bq(eng, rs, p.hap_min_bq if phase is not None else 0, ctg, p.log, **(dict(weights=True) if p.hap_bq_weights and phase is not None else {})); t.append(time())
     eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str))); t.append(time())      # (the fetcher's array: upper-cased, used in place)
     if p.vcf_fn is not None:
         return ContigResult(ContigResult.CHUNKS, list(zip(regions, site_sets)))                   # genotyping mode: one scan per chunk (its own site list)

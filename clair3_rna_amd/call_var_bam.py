@@ -119,15 +119,16 @@ def build_parser():
       help="with --phased_vcf_fn: the reads are haplotagged from the phased insertions, deletions and two-ALT rows (`1|2`) of the phased VCF "
            "too, not from its biallelic SNVs alone (include/c3r.h: c3r_set_phase_alleles) — the rows `--phase_output --phase_indels` and "
            "`whatshap phase --indels` write.  Alleles are read off the CIGAR position: no realignment, no left-alignment (--left_align_indels lifts it), no base qualities "
-           "(`--hap_min_bq` lifts it: a threshold, not weights)")
+           "(`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes)")
     from . import phasing as _phasing
     _phasing.add_hap_realign_flag(a)
     a('--left_align_indels', action='store_true',
       help="with --haplotag_indels: left-align the table's indels against the reference and every read's indel inside its own M run, on the "
            "device (include/c3r.h: c3r_set_hap_left_align), which lifts \"no left-alignment\"; the reference is then fetched for the whole "
-           "contig.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights)")
+           "contig.  A shift stops at the M run's start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes)")
+    _phasing.add_hap_bq_weights_flag(a, "with --phased_vcf_fn: ")
     a('--hap_min_bq', type=int, default=0, metavar="N",
-      help="with --phased_vcf_fn: a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
+      help="with --phased_vcf_fn: a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights (--hap_bq_weights are those); an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a('--minCoverage', type=int, default=4)
     a('--minMQ', type=int, default=5)
     a('--minBQ', type=int, default=0)
@@ -184,6 +185,7 @@ def Run(args, engine=None):
         sys.exit("[ERROR] --left_align_indels needs --haplotag_indels (it left-aligns the indels the reads are haplotagged from)")
     from . import phasing
     min_bq = phasing.hap_min_bq_arg(args, bool(phased_vcf_fn), "--phased_vcf_fn: without a phase table no step holds the reads against one")
+    weights = phasing.hap_bq_weights_arg(args, bool(phased_vcf_fn), "--phased_vcf_fn: without a phase table no step haplotags the reads")
     realign, _ = phasing.hap_realign_arg(args, bool(phased_vcf_fn), "--phased_vcf_fn: without a phase table no step holds the reads against one")
     whole_contig = left_align or bool(realign)                # (the slice must cover every loaded read: the tagging reads it)
     for need in (args.bam_fn, args.ref_fn):
@@ -241,10 +243,10 @@ def Run(args, engine=None):
                    indel_min_af=args.indel_min_af, head_tail=int(args.enable_variant_calling_at_sequence_head_and_tail),
                    splice_padding=int(args.enable_padding_in_splice_junction_regions), genotyping_mode=int(sites is not None),
                    mpileup_compat=compat)
-    rs = io.load_reads(args.bam_fn, ctg, extend_start - 1, extend_end, **(dict(want_quals=True) if min_bq else {}))      # mpileup -r ctg:extend_start-extend_end
+    rs = io.load_reads(args.bam_fn, ctg, extend_start - 1, extend_end, **(dict(want_quals=True) if min_bq or weights else {}))      # mpileup -r ctg:extend_start-extend_end
     if phase is not None and not len(phase):
         rs.reads["hp"] = 0                  # nothing phased on this contig: every read untagged (the BAM's own HP tags do not count beside a phased VCF)
-    phasing.load_reads_min_bq(eng, rs, min_bq, ctg, lambda m: print(m, file=sys.stderr))
+    phasing.load_reads_min_bq(eng, rs, min_bq, ctg, lambda m: print(m, file=sys.stderr), **(dict(weights=True) if weights else {}))
     eng.set_reference(ref_start, ref_seq)
     eng.load_weights(io.load_weights(args.chkpnt_fn, channels), channels)
     eng.set_precision(getattr(args, "gpu_precision", "f16x3"))

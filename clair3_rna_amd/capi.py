@@ -74,7 +74,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links",
            "c3r_set_hap_left_align", "c3r_hap_left_align_sites",
            "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq",
-           "c3r_set_hap_realign", "c3r_get_hap_realign", "c3r_hap_realign_column"]
+           "c3r_set_hap_realign", "c3r_get_hap_realign", "c3r_hap_realign_column",
+           "c3r_set_hap_bq_weights", "c3r_get_hap_bq_weights", "c3r_get_haplotag_weights", "c3r_get_haplotag_words"]
 
 _lib = None
 
@@ -108,6 +109,10 @@ def load_library():
     L.c3r_set_hap_min_bq.argtypes = [vp, i32]
     L.c3r_get_hap_min_bq.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.c3r_get_hap_seq.argtypes = [vp, vp, i64]
+    L.c3r_set_hap_bq_weights.argtypes = [vp, i32]
+    L.c3r_get_hap_bq_weights.argtypes = [vp, C.POINTER(i32)]
+    L.c3r_get_haplotag_weights.argtypes = [vp, vp, i64]
+    L.c3r_get_haplotag_words.argtypes = [vp, vp, i64]
     L.c3r_host_alloc.argtypes = [C.c_size_t]
     L.c3r_host_alloc.restype = vp
     L.c3r_host_free.argtypes = [vp]
@@ -364,7 +369,7 @@ class Engine(object):
         loaded reads against a site table — the tagging of set_phase_sites / set_phase_alleles / load_reads, hap_counts, hap_allele_counts,
         phase_links, phase_unit_links and their allele forms — reads a base whose quality is below q as N (a base without a quality, 0xff,
         never).  Needs reads loaded with qualities (a ReadSet with `qual`); valid before or after load_reads with the same result; with a
-        phase table set and reads loaded the reads are tagged again.  A threshold, not quality weights."""
+        phase table set and reads loaded the reads are tagged again.  A threshold, not quality weights (set_hap_bq_weights are those)."""
         self._chk(self.L.c3r_set_hap_min_bq(self.h, int(q)))
 
     def hap_min_bq(self):
@@ -372,6 +377,39 @@ class Engine(object):
         q, n = C.c_int(), C.c_int64()
         self._chk(self.L.c3r_get_hap_min_bq(self.h, C.byref(q), C.byref(n)))
         return int(q.value), int(n.value)
+
+    def set_hap_bq_weights(self, on):
+        """The opt-in switch of --hap_bq_weights (c3r_set_hap_bq_weights, default off): while on, the tagging of set_phase_sites /
+        set_phase_alleles / load_reads weighs every vote by the quality of the read's base on the site (the rule `bq_weights` of
+        include/c3r.h; a base without a quality, 0xff, weighs 1) where it otherwise counts 1.  The count tables and the links do not look
+        at it.  Needs reads loaded with qualities (a ReadSet with `qual`); valid before or after load_reads with the same result; with a
+        phase table set and reads loaded the reads are tagged again."""
+        self._chk(self.L.c3r_set_hap_bq_weights(self.h, 1 if on else 0))
+
+    def hap_bq_weights(self):
+        """The switch of set_hap_bq_weights (c3r_get_hap_bq_weights)."""
+        on = C.c_int(0)
+        self._chk(self.L.c3r_get_hap_bq_weights(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def haplotag_weights(self):
+        """uint32 (n, 2): (w1, w2), the weight sums of the phase set every loaded read's tag was decided in, in load order; a tie's pair
+        where the tag is 0, (0, 0) for a read without an observation (c3r_get_haplotag_weights).  An error while no phase sites are set
+        or set_hap_bq_weights is off."""
+        st = HaplotagStats()
+        self._chk(self.L.c3r_get_haplotags(self.h, None, 0, C.byref(st)))
+        w = np.zeros((st.n_reads, 2), dtype=np.uint32)
+        self._chk(self.L.c3r_get_haplotag_weights(self.h, _ptr(w) if len(w) else None, len(w)))
+        return w
+
+    def haplotag_words(self):
+        """uint32[n]: the tag word of every loaded read, in load order: tag | observations on all phase sets << 2 (c3r_get_haplotag_words).
+        An error while no phase sites are set."""
+        st = HaplotagStats()
+        self._chk(self.L.c3r_get_haplotags(self.h, None, 0, C.byref(st)))
+        w = np.zeros(st.n_reads, dtype=np.uint32)
+        self._chk(self.L.c3r_get_haplotag_words(self.h, _ptr(w) if len(w) else None, len(w)))
+        return w
 
     def hap_seq(self):
         """uint8[n_seq_bytes]: the packed bases that the site-table kernels read — the masked copy, or with q = 0 the loaded sequence

@@ -878,6 +878,12 @@ namespace {
 
 inline void put16(std::vector<uint8_t> &v, uint32_t x) { v.push_back((uint8_t)x); v.push_back((uint8_t)(x >> 8)); }
 inline void put32(std::vector<uint8_t> &v, uint32_t x) { put16(v, x & 0xffff); put16(v, x >> 16); }
+// an aux field's type and value in the smallest unsigned type that holds x (PS, PC)
+inline void put_aux_uint(std::vector<uint8_t> &v, uint32_t x) {
+    if (x < 256) { v.push_back('C'); v.push_back((uint8_t)x); }
+    else if (x < 65536) { v.push_back('S'); put16(v, x); }
+    else { v.push_back('I'); put32(v, x); }
+}
 
 // One alignment (the block_size bytes after the length field) appended to `out` without its HP / PS / PC aux fields, whatever their
 // type; every other byte in place.  Strict where the keep rule is lenient, since what it cannot walk it cannot copy faithfully: an aux
@@ -951,6 +957,11 @@ extern "C" int c3r_bam_header_text(c3r_bam *b, const char **text, int64_t *n_byt
 
 extern "C" int c3r_bam_write_haplotagged(c3r_bam *b, const char *contig, const c3r_read_t *reads, const uint8_t *hp, const int32_t *ps,
                                          int64_t n_reads, const char *out_path, const char *pg_line, int threads, int64_t *counts) {
+    return c3r_bam_write_haplotagged_pc(b, contig, reads, hp, ps, nullptr, n_reads, out_path, pg_line, threads, counts);
+}
+
+extern "C" int c3r_bam_write_haplotagged_pc(c3r_bam *b, const char *contig, const c3r_read_t *reads, const uint8_t *hp, const int32_t *ps, const uint32_t *pc,
+                                            int64_t n_reads, const char *out_path, const char *pg_line, int threads, int64_t *counts) {
     if (!b) return C3R_EINVAL;
     if (!contig || !out_path || n_reads < 0) return failb(b, C3R_EINVAL, "c3r_bam_write_haplotagged: null contig / output path or negative n_reads");
     const bool paired = !(n_reads == 0 && !reads && !hp && !ps);       // (no arrays at all: the records go out untagged, nothing is checked)
@@ -1017,11 +1028,9 @@ extern "C" int c3r_bam_write_haplotagged(c3r_bam *b, const char *contig, const c
             }
             tag = hp[k];
             if (tag) {
-                const uint32_t set = (uint32_t)ps[k];
                 rec.insert(rec.end(), {'H', 'P', 'C', (uint8_t)tag, 'P', 'S'});
-                if (set < 256) { rec.push_back('C'); rec.push_back((uint8_t)set); }
-                else if (set < 65536) { rec.push_back('S'); put16(rec, set); }
-                else { rec.push_back('I'); put32(rec, set); }
+                put_aux_uint(rec, (uint32_t)ps[k]);
+                if (pc) { rec.insert(rec.end(), {'P', 'C'}); put_aux_uint(rec, pc[k]); }
             }
             ++k;
         }

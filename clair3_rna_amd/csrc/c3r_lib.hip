@@ -173,6 +173,10 @@ struct c3r_ctx {
     int hap_min_bq = 0;
     bool has_qual = false;
     DevBuf d_qual, d_hapseq, d_nmasked;
+    // c3r_set_hap_bq_weights: the tagging kernels run their _w instantiation, which weighs a vote by d_qual's byte and stores the chosen
+    // set's (w1, w2) per read in d_hpw ([n_reads][2]; allocated by the first tagging launch under the switch, never without it)
+    bool hap_w = false;
+    DevBuf d_hpw;
     // phasing (c3r_phase_links): the candidate sites and their link table, allocated by the first call and kept
     DevBuf d_plsites, d_links, d_unitof;  // (d_unitof: c3r_phase_unit_links, which shares the two others)
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
@@ -504,6 +508,38 @@ void launch_per_read(c3r_ctx *ctx, const char *label, void (*kernel)(Args), cons
     Launch L(ctx, label);
     hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_reads + PREP_READS - 1) / PREP_READS)), dim3(PREP_THREADS), 0, ctx->stream, a);
 }
+// The launch of a tagging kernel: `kernel`, or under c3r_set_hap_bq_weights its _w sibling with the qualities and the pair buffer behind
+// the same arguments.
+template <class Args>
+int launch_tagger(c3r_ctx *ctx, const char *label, void (*kernel)(Args), const char *label_w, void (*kernel_w)(HapWeighted<Args>), const Args &a) {
+    if (!ctx->hap_w) { launch_per_read<Args>(ctx, label, kernel, a); return C3R_OK; }
+    if (!ctx->has_qual) return fail(ctx, C3R_EINVAL, "internal: c3r_set_hap_bq_weights is on and the loaded reads have no qualities");
+    if (int rc = ensure(ctx, ctx->d_hpw, (size_t)a.n_reads * 8 + 16)) return rc;
+    HapWeighted<Args> w;
+    memset(&w, 0, sizeof w);
+    static_cast<Args &>(w) = a;
+    w.qual = (const uint8_t *)ctx->d_qual.p; w.w12 = (uint32_t *)ctx->d_hpw.p;
+    launch_per_read(ctx, label_w, kernel_w, w);
+    return C3R_OK;
+}
+// The tags of the n reads from the phase table that is set (k_haplotag*): the one choice of the kernel, from the table's kind, the
+// observation (c3r_set_hap_left_align, c3r_set_hap_realign) and the weights (c3r_set_hap_bq_weights).  Nothing here waits for the device.
+int launch_haplotag(c3r_ctx *ctx, int n) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16)) || (rc = ensure(ctx, ctx->d_hpps, (size_t)n * 4 + 16))) return rc;
+    auto tag_args = [&](auto h) { h.hp_reads = (DevRead *)ctx->d_reads.p; h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p; h.n_sites = (int32_t)ctx->n_phase; return h; };
+    if (!ctx->phase_alleles) {
+        HapArgs h = tag_args(read_args<HapArgs>(ctx, n));
+        h.sites = (const c3r_phase_site_t *)ctx->d_phase.p;
+        return launch_tagger<HapArgs>(ctx, "k_haplotag", k_haplotag, "k_haplotag_w", k_haplotag_w, h);
+    }
+    if ((rc = hap_needs_ref(ctx, "c3r_load_reads"))) return rc;
+    HapAlleleTagRaArgs h = tag_args(read_args<HapAlleleTagRaArgs>(ctx, n));
+    h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.pool = (const uint8_t *)ctx->d_phasepool.p;
+    if (ctx->hap_ra > 0) { h.ref = hap_ref(ctx); h.overhang = (uint32_t)ctx->hap_ra; return launch_tagger<HapAlleleTagRaArgs>(ctx, "k_haplotag_alleles_ra", k_haplotag_alleles_ra, "k_haplotag_alleles_ra_w", k_haplotag_alleles_ra_w, h); }
+    if (ctx->hap_la) { h.ref = hap_ref(ctx); return launch_tagger<HapAlleleTagLaArgs>(ctx, "k_haplotag_alleles_la", k_haplotag_alleles_la, "k_haplotag_alleles_la_w", k_haplotag_alleles_la_w, h); }
+    return launch_tagger<HapAlleleTagArgs>(ctx, "k_haplotag_alleles", k_haplotag_alleles, "k_haplotag_alleles_w", k_haplotag_alleles_w, h);
+}
 // A table of `words` 32-bit counters that one such launch adds to: zeroed in `buf`, filled by launch(the table on the device), copied to
 // `out`.  Waits for the device: the arrays the caller handed in may go once this returns, and the table is there.
 template <class LaunchOn>
@@ -690,22 +726,7 @@ int prepare_tables(c3r_ctx *ctx, int n, int64_t last_pos, bool timing, std::uniq
     const auto t_sync = std::chrono::steady_clock::now();
     // ---- haplotags from the phase sites, if the caller has set any: the records have passed the range checks above, and the second pass
     // takes every read's hp from the header this kernel writes it to (nothing here waits for the device)
-    if (ctx->n_phase > 0) {
-        if ((rc = ensure(ctx, ctx->d_hptag, (size_t)n * 4 + 16)) || (rc = ensure(ctx, ctx->d_hpps, (size_t)n * 4 + 16))) return rc;
-        auto tag_args = [&](auto h) { h.hp_reads = (DevRead *)ctx->d_reads.p; h.tags = (uint32_t *)ctx->d_hptag.p; h.read_ps = (int32_t *)ctx->d_hpps.p; h.n_sites = (int32_t)ctx->n_phase; return h; };
-        if (!ctx->phase_alleles) {
-            HapArgs h = tag_args(read_args<HapArgs>(ctx, n));
-            h.sites = (const c3r_phase_site_t *)ctx->d_phase.p;
-            launch_per_read(ctx, "k_haplotag", k_haplotag, h);
-        } else {
-            if ((rc = hap_needs_ref(ctx, "c3r_load_reads"))) return rc;
-            HapAlleleTagRaArgs h = tag_args(read_args<HapAlleleTagRaArgs>(ctx, n));
-            h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.pool = (const uint8_t *)ctx->d_phasepool.p;
-            if (ctx->hap_ra > 0) { h.ref = hap_ref(ctx); h.overhang = (uint32_t)ctx->hap_ra; launch_per_read(ctx, "k_haplotag_alleles_ra", k_haplotag_alleles_ra, h); }
-            else if (ctx->hap_la) { h.ref = hap_ref(ctx); launch_per_read<HapAlleleTagLaArgs>(ctx, "k_haplotag_alleles_la", k_haplotag_alleles_la, h); }
-            else launch_per_read<HapAlleleTagArgs>(ctx, "k_haplotag_alleles", k_haplotag_alleles, h);
-        }
-    }
+    if (ctx->n_phase > 0 && (rc = launch_haplotag(ctx, n))) return rc;
     // ---- second pass (nothing below waits for the device): every record into its bin
     if ((rc = ensure(ctx, ctx->d_recs, (size_t)hs.n_rec * sizeof(PileRec) + 64))) return rc;
     {
@@ -888,7 +909,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_rowctl, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0, cap = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -959,6 +980,8 @@ int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, con
     if (!qual && n_qual_bytes != 0) return fail(ctx, C3R_EINVAL, "c3r_load_reads_q: %lld quality bytes and no array", (long long)n_qual_bytes);
     if (!qual && n_reads > 0 && ctx->hap_min_bq > 0)               // (before anything of the previous load is given up)
         return fail(ctx, C3R_EINVAL, "c3r_load_reads: c3r_set_hap_min_bq is %d and the reads come without qualities (c3r_load_reads_q)", ctx->hap_min_bq);
+    if (!qual && n_reads > 0 && ctx->hap_w)
+        return fail(ctx, C3R_EINVAL, "c3r_load_reads: c3r_set_hap_bq_weights is on and the reads come without qualities (c3r_load_reads_q)");
     if (n_reads >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many reads");
     if (n_cigar_ops >= INT32_MAX) return fail(ctx, C3R_EINVAL, "too many CIGAR ops");
     if (ctx->phase_alleles) if (int rc0 = hap_needs_ref(ctx, "c3r_load_reads")) return rc0;       // (before anything of the previous load is given up)
@@ -1580,6 +1603,57 @@ int c3r_get_hap_min_bq(c3r_ctx *ctx, int *min_bq, int64_t *n_masked) {
         }
         *n_masked = (int64_t)m;
     }
+    return C3R_OK;
+}
+
+int c3r_set_hap_bq_weights(c3r_ctx *ctx, int on) {
+    if (!ctx) return C3R_EINVAL;
+    if (on != 0 && on != 1) return fail(ctx, C3R_EINVAL, "c3r_set_hap_bq_weights: %d is neither 0 nor 1", on);
+    const bool want = on != 0;
+    if (want == ctx->hap_w) return C3R_OK;
+    if (want && ctx->n_reads > 0 && !ctx->has_qual)
+        return fail(ctx, C3R_EINVAL, "c3r_set_hap_bq_weights: the loaded reads came without qualities (c3r_load_reads_q)");
+    ctx->hap_w = want;
+    if (!(ctx->n_phase > 0 && ctx->n_reads > 0)) return C3R_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->last_scan_pruned = false;                                 // the tags on the device are those of the other weights
+    ctx->host_cache.reset();
+    // the pair buffer first: while it cannot be had the old switch stays, and with it the tags on the device (a failure of the tagging
+    // that follows loses the loaded reads' tables, as a failed c3r_set_params does, and the switch goes back all the same)
+    if (want) if (int rc = ensure(ctx, ctx->d_hpw, (size_t)ctx->n_reads * 8 + 16)) { ctx->hap_w = false; return rc; }
+    const int rc = ::refilter(ctx);
+    if (rc) ctx->hap_w = !want;
+    return rc;
+}
+
+int c3r_get_hap_bq_weights(c3r_ctx *ctx, int *on) {
+    if (!ctx) return C3R_EINVAL;
+    if (on) *on = ctx->hap_w ? 1 : 0;
+    return C3R_OK;
+}
+
+int c3r_get_haplotag_weights(c3r_ctx *ctx, uint32_t *w12, int64_t cap) {
+    if (!ctx || cap < 0) return C3R_EINVAL;
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads have no weights");
+    if (!ctx->hap_w) return fail(ctx, C3R_EINVAL, "c3r_get_haplotag_weights: c3r_set_hap_bq_weights is off: the tags were decided by unit weights");
+    const int64_t n = ctx->n_reads;
+    if (n && (!w12 || cap < n)) return fail(ctx, C3R_EOVERFLOW, "weight pairs of %lld reads do not fit %lld slots", (long long)n, (long long)cap);
+    if (n == 0) return C3R_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(w12, ctx->d_hpw.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return C3R_OK;
+}
+
+int c3r_get_haplotag_words(c3r_ctx *ctx, uint32_t *words, int64_t cap) {
+    if (!ctx || cap < 0) return C3R_EINVAL;
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads have no tag words");
+    const int64_t n = ctx->n_reads;
+    if (n && (!words || cap < n)) return fail(ctx, C3R_EOVERFLOW, "tag words of %lld reads do not fit %lld slots", (long long)n, (long long)cap);
+    if (n == 0) return C3R_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(words, ctx->d_hptag.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return C3R_OK;
 }
 

@@ -20,6 +20,8 @@
 //      number above it, so any number of sets — interleaved as they may be — is exact in P + 1 walks with no storage.
 // The set the tag was decided in is kept beside the tag (read_ps): k_hap_counts (hapcount_kernels.hpp) counts a read on a haplotype only at
 // the sites of that set.
+// Each tagging kernel has a _w sibling (c3r_set_hap_bq_weights): the same body with HapTallyW, which weighs a vote by the quality byte of
+// the read's base on the site and stores the chosen set's (w1, w2) per read.
 //
 // The pieces that every kernel which holds reads against a sorted site table shares are here as well (hapcount_kernels.hpp and
 // phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe, hap_observe_la,
@@ -27,6 +29,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "reads_kernels.hpp"
 #include "realign.hpp"
@@ -269,18 +273,59 @@ struct HapTally {
     }
 };
 
+// The tally of quality-weighted votes (c3r_set_hap_bq_weights; the rule `bq_weights` of include/c3r.h, restated by tests/hapweightref.py):
+// c1 / c2 are sums of the quality bytes of the read's bases on the voting sites, n counts the observations (a Q0 base is one and adds
+// nothing), and everything else — the sets, the first site, the shuffles — is HapTally's.
+struct HapTallyW : HapTally {
+    uint32_t n;               // observations that counted (a read's sum fits: l_seq x 254)
+    __device__ __forceinline__ void clear() { HapTally::clear(); n = 0; }
+    // HapTally::vote with the weight in the place of 1; qual[at] = 0xff — a record without qualities — weighs 1
+    __device__ __forceinline__ void vote(uint32_t cur, uint32_t ps, bool hap1, int s, const uint8_t *qual, unsigned long long at) {
+        if (cur == HAP_NONE) { ps_min = min(ps_min, ps); ps_max = max(ps_max, ps); }
+        else {
+            if (ps > cur) ps_min = min(ps_min, ps);
+            if (ps != cur) return;
+        }
+        const uint32_t b = qual[at], w = b == 0xffu ? 1u : b;
+        if (hap1) c1 += w; else c2 += w;
+        n += 1;
+        first = min(first, (uint32_t)s);
+    }
+    __device__ __forceinline__ void reduce() {
+        HapTally::reduce();
+#pragma unroll
+        for (int off = PREP_GRP / 2; off > 0; off >>= 1) n += __shfl_xor(n, off, PREP_GRP);
+    }
+};
+
 // What the two tagging kernels take beside their table.
 struct HapTagArgs : ReadArgs {
     DevRead *hp_reads;                        // the same headers as `reads`, to write: hp is overwritten
     uint32_t *tags;                           // [n_reads] tag | votes of the read on all phase sets << 2
     int32_t *read_ps;                         // [n_reads] the phase set the tag was decided in, -1 when the tag is 0
 };
+// What a _w kernel takes beside its sibling's arguments.
+template <class Base>
+struct HapWeighted : Base {
+    const uint8_t *qual;                      // one quality byte per base of `seq`: the base at query offset q of a read is qual[2 * seq_off + q]
+    uint32_t *w12;                            // [n_reads][2] the weight sums (w1, w2) of the set the tag was decided in; a tie's pair when the tag is 0
+};
+// A tagging kernel and its _w sibling (HapWeighted<ARGS>) from one body, which names its arguments `a`, its tally `Tally` and the quality
+// bytes `qual` (null in the unit form, which never reads them): the one place where the two forms part.  The body stands in the kernel
+// itself: behind a function template of its own the compiler schedules the four kernels that were there before the weights differently
+// (tools/device_asm_diff.py), and they are held to their code byte for byte.
+#define C3R_HAPLOTAG_KERNELS(NAME, ARGS, ...)                                                                                            \
+    __global__ __launch_bounds__(PREP_THREADS) void NAME(const ARGS a) { using Tally = HapTally; const uint8_t *const qual = nullptr; __VA_ARGS__ }      \
+    __global__ __launch_bounds__(PREP_THREADS) void NAME##_w(const HapWeighted<ARGS> a) { using Tally = HapTallyW; const uint8_t *const qual = a.qual; __VA_ARGS__ }
 
 // The tag of the group's read from walk(R, gl, serial, lo, hi, cur) -> HapTally, the reduced votes of one walk (steps 1 to 3 above), and
 // lane 0's three stores.  compat_plain: ReadInfo::compat of a read of the plain walk.  LA: the left-aligned observation (cigar_has_m_neighbours).  The body of k_haplotag and k_haplotag_alleles; all
 // lanes of a group take the same way through it (whole groups leave: the shuffles stay inside a group).
-template <bool LA = false, class Args, class Walk>
+// With Tally = HapTallyW (the _w kernels, whose Args are HapWeighted) the sets are compared by weight, the tag word still holds the observations, and lane 0 stores the
+// chosen set's (w1, w2) as well.
+template <class Tally, bool LA = false, class Args, class Walk>
 __device__ __forceinline__ void hap_tag_read(const Args &a, bool compat_plain, Walk &&walk) {
+    constexpr bool weighted = !std::is_same<Tally, HapTally>::value;
     const GroupAt g;
     const int gl = g.gl, i = g.i;
     if (i >= a.n_reads) return;
@@ -290,14 +335,14 @@ __device__ __forceinline__ void hap_tag_read(const Args &a, bool compat_plain, W
     if (r.lo < r.hi) {
         const bool serial = a.serial[i] != 0 || (LA && cigar_has_m_neighbours(ReadInfo(d, i, a.cigars, 0), gl));
         const ReadInfo R(d, i, a.cigars, compat_plain && !serial ? 1 : 0);
-        HapTally t = walk(R, gl, serial, r.lo, r.hi, HAP_NONE);
-        votes = t.c1 + t.c2;
+        Tally t = walk(R, gl, serial, r.lo, r.hi, HAP_NONE);
+        if constexpr (weighted) votes = t.n; else votes = t.c1 + t.c2;        // (the observations behind c1 / c2)
         set = t.ps_min;                                                // (one set, or no vote: HAP_NONE)
         if (votes && t.ps_min != t.ps_max) {
             // several phase sets: one walk each, in the order of their numbers; the set with the most votes wins, the earlier first site among equals
             uint32_t best_n = 0, best_first = HAP_NONE, b1 = 0, b2 = 0;
             for (uint32_t cur = t.ps_min; cur != HAP_NONE;) {
-                const HapTally u = walk(R, gl, serial, r.lo, r.hi, cur);
+                const Tally u = walk(R, gl, serial, r.lo, r.hi, cur);
                 const uint32_t n = u.c1 + u.c2;
                 if (n > best_n || (n == best_n && u.first < best_first)) { best_n = n; best_first = u.first; b1 = u.c1; b2 = u.c2; set = cur; }
                 cur = u.ps_min;
@@ -305,6 +350,9 @@ __device__ __forceinline__ void hap_tag_read(const Args &a, bool compat_plain, W
             t.c1 = b1; t.c2 = b2;
         }
         tag = t.c1 > t.c2 ? 1u : t.c2 > t.c1 ? 2u : 0u;
+        if constexpr (weighted) { if (gl == 0) *(uint2 *)(a.w12 + 2 * (size_t)i) = make_uint2(t.c1, t.c2); }      // (a tie's pair too)
+    } else if constexpr (weighted) {
+        if (gl == 0) *(uint2 *)(a.w12 + 2 * (size_t)i) = make_uint2(0u, 0u);
     }
     if (gl == 0) {
         a.hp_reads[i].hp = (uint8_t)tag;
@@ -318,21 +366,26 @@ struct HapArgs : HapTagArgs {
 };
 
 // One walk: the votes of the sites [lo, hi) that the read's M ops cover.  All lanes of the group come here together.
-__device__ __forceinline__ HapTally hap_walk(const ReadInfo &R, int gl, bool serial, const HapArgs &a, int lo, int hi, uint32_t cur) {
-    HapTally t;
+// qual: the quality bytes of HapWeighted, read by HapTallyW only.
+template <class Tally>
+__device__ __forceinline__ Tally hap_walk(const ReadInfo &R, int gl, bool serial, const HapArgs &a, int lo, int hi, uint32_t cur, const uint8_t *qual) {
+    Tally t;
     t.clear();
     const uint8_t *rseq = a.seq + R.seq_off;
     walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_phase_site_t &e, unsigned long long q, bool, bool, unsigned long long, const OpCtx &) __attribute__((always_inline)) {
         const uint32_t al = snv_column(e, hap_nibble(rseq, q));
-        if (al != 2u) t.vote(cur, (uint32_t)e.ps, al == e.h1, s);
+        if (al != 2u) {
+            if constexpr (std::is_same<Tally, HapTally>::value) t.vote(cur, (uint32_t)e.ps, al == e.h1, s);
+            else t.vote(cur, (uint32_t)e.ps, al == e.h1, s, qual, 2ull * R.seq_off + q);
+        }
     });
     t.reduce();
     return t;
 }
 
-__global__ __launch_bounds__(PREP_THREADS) void k_haplotag(const HapArgs a) {
-    hap_tag_read(a, false, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) { return hap_walk(R, gl, serial, a, lo, hi, cur); });
-}
+C3R_HAPLOTAG_KERNELS(k_haplotag, HapArgs,
+    hap_tag_read<Tally>(a, false, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) { return hap_walk<Tally>(R, gl, serial, a, lo, hi, cur, qual); });
+)
 
 // ---- k_haplotag_alleles: the same tags from a table whose sites may be SNVs, insertions, deletions and two-ALT sites (c3r_set_phase_alleles) --
 // The rule is stated in include/c3r.h and restated, independently of this file, by tests/hapindelref.py.  k_haplotag's shape — 16 lanes per
@@ -347,49 +400,53 @@ struct HapAlleleTagArgs : HapTagArgs {
 };
 
 // hap_walk for the allele table; observe(site, walk_sites' arguments) -> hap_observe's column
-template <class Observe>
-__device__ __forceinline__ HapTally hap_walk_alleles(const ReadInfo &R, int gl, bool serial, const HapAlleleTagArgs &a, int lo, int hi, uint32_t cur, Observe &&observe) {
-    HapTally t;
+template <class Tally, class Observe>
+__device__ __forceinline__ Tally hap_walk_alleles(const ReadInfo &R, int gl, bool serial, const HapAlleleTagArgs &a, int lo, int hi, uint32_t cur, const uint8_t *qual, Observe &&observe) {
+    Tally t;
     t.clear();
     walk_sites(R, gl, serial, a.sites, lo, hi, [&](int s, const c3r_hap_site_t &e, unsigned long long q, bool first, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         const uint32_t al = observe(e, q, first, last, iq, cx);
-        if (al < 2u) t.vote(cur, (uint32_t)e.ps, al == e.reserved[0], s);
+        if (al < 2u) {
+            if constexpr (std::is_same<Tally, HapTally>::value) t.vote(cur, (uint32_t)e.ps, al == e.reserved[0], s);
+            else t.vote(cur, (uint32_t)e.ps, al == e.reserved[0], s, qual, 2ull * R.seq_off + q);
+        }
     });
     t.reduce();
     return t;
 }
 
-__global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles(const HapAlleleTagArgs a) {
-    hap_tag_read(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+C3R_HAPLOTAG_KERNELS(k_haplotag_alleles, HapAlleleTagArgs,
+    hap_tag_read<Tally>(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
         const uint8_t *rseq = a.seq + R.seq_off;
-        return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_walk_alleles<Tally>(R, gl, serial, a, lo, hi, cur, qual, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
             return hap_observe(e, rseq, R.l_seq, a.pool, q, last, iq, cx);
         });
     });
-}
+)
 
 // The same with the left-aligned observation (c3r_set_hap_left_align): hap_observe_la against the reference slice.
 struct HapAlleleTagLaArgs : HapAlleleTagArgs { HapRef ref; };
 
-__global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles_la(const HapAlleleTagLaArgs a) {
-    hap_tag_read<true>(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+C3R_HAPLOTAG_KERNELS(k_haplotag_alleles_la, HapAlleleTagLaArgs,
+    hap_tag_read<Tally, true>(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
         const uint8_t *rseq = a.seq + R.seq_off;
-        return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_walk_alleles<Tally>(R, gl, serial, a, lo, hi, cur, qual, [&](const c3r_hap_site_t &e, unsigned long long q, bool first, bool, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
             return hap_observe_la(e, rseq, R.l_seq, a.pool, a.ref, q, first, iq, cx);
         });
     });
-}
+)
 
 // The same with the realigned observation (c3r_set_hap_realign): hap_observe_ra against the reference slice, with the switch's overhang.
 struct HapAlleleTagRaArgs : HapAlleleTagLaArgs { uint32_t overhang; };
 
-__global__ __launch_bounds__(PREP_THREADS) void k_haplotag_alleles_ra(const HapAlleleTagRaArgs a) {
-    hap_tag_read(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+C3R_HAPLOTAG_KERNELS(k_haplotag_alleles_ra, HapAlleleTagRaArgs,
+    hap_tag_read<Tally>(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
         const uint8_t *rseq = a.seq + R.seq_off;
-        return hap_walk_alleles(R, gl, serial, a, lo, hi, cur, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_walk_alleles<Tally>(R, gl, serial, a, lo, hi, cur, qual, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
             return hap_observe_ra(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
         });
     });
-}
+)
+#undef C3R_HAPLOTAG_KERNELS
 
 }  // namespace c3r

@@ -14,20 +14,20 @@ says whether the candidate was phased in it; HP1 / HP2 / NONE are the reads tagg
 another set), REF / ALT / OTHER the allele the read shows.
 
 By default it covers SNVs only and is a majority rule over CIGAR-position alleles: no indels, no multi-allelic or homozygous rows, no
-realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights).  Agreement with `whatshap` has not been measured.
+realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes).  Agreement with `whatshap` has not been measured.
 
 --indels (off by default, like `whatshap phase --indels`): the candidates are phasing.allele_candidates_from_vcf's — heterozygous rows whose
 alleles are SNVs, insertions or deletions, GT `0/1` with one ALT or `1/2` with two (`C  T,CGG`, `ACC  A,TCC`) — counted by
 Engine.hap_allele_counts (include/c3r.h: c3r_hap_allele_counts) and written as `0|1` / `1|0` / `1|2` / `2|1`.  The nearest-set rule and the
 assignment are the same.  The counts file's REF / ALT columns then hold the row's strings, its REF / ALT count columns stand for allele A /
 allele B, and one more column ALLELES says which they are: `0,1` or `1,2`.  The alleles are read off the CIGAR position: no realignment, no
-left-alignment of the reads' indels, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); a homozygous row or one with three or more ALTs stays as it is.  Agreement with
+left-alignment of the reads' indels, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); a homozygous row or one with three or more ALTs stays as it is.  Agreement with
 `whatshap --indels` has not been measured.  Without --indels both files are what they were.
 
 --left_align_indels (off by default; needs --indels and --ref_fn) lifts "no left-alignment", as in phase_vcf: the candidates' indels are
 left-aligned against the reference, each read's indel inside its own M run on the device (include/c3r.h: c3r_set_hap_left_align); with
 --haplotag_indels the phase table is left-aligned too and the reads are tagged by the same observation.  Rows keep their POS, REF and ALT
-in both files.  A shift stops at the M run's start, at an N or another indel and at the contig's ends; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights);
+in both files.  A shift stops at the M run's start, at an N or another indel and at the contig's ends; no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes);
 agreement with whatshap is not measured.
 
     python -m clair3_rna_amd.hap_vcf --bam_fn x.bam --vcf_fn out/output_enable_phasing.vcf.gz \\
@@ -140,7 +140,7 @@ def build_parser():
     a("--min_agree_pct", type=int, default=75, help="fewest per cent of them that agree on the orientation")
     a("--indels", action="store_true",
       help="also phase heterozygous insertions, deletions and rows with two ALT alleles (GT 1/2), by CIGAR-position alleles: no realignment, no "
-           "left-alignment (--left_align_indels lifts it), no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); the counts file gets the column ALLELES.  Off: SNVs only, both files as they were")
+           "left-alignment (--left_align_indels lifts it), no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); the counts file gets the column ALLELES.  Off: SNVs only, both files as they were")
     a("--haplotag_indels", action="store_true",
       help="tag the reads from the phased insertions, deletions and two-ALT rows of --phased_vcf_fn too, not from its biallelic SNVs alone "
            "(what the 30-channel pass did when it ran with this flag; include/c3r.h: c3r_set_phase_alleles)")
@@ -149,8 +149,9 @@ def build_parser():
            "indel inside its M run, on the device (default: the alleles are read off the CIGAR position as they stand)")
     a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels and --hap_realign only")
     phasing.add_hap_realign_flag(a)
+    phasing.add_hap_bq_weights_flag(a, "the reads' tags — by which the counts are split — come from quality-weighted votes; the counts themselves stay counts of reads: ")
     a("--hap_min_bq", type=int, default=0, metavar="N",
-      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
+      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights (--hap_bq_weights are those); an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 
@@ -168,6 +169,7 @@ def Run(args, log=None):
     realign, realign_ref = phasing.hap_realign_arg(args)
     source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None or not tag_indels else (None, ref_of)), **(dict(realign=realign) if realign else {}))
     min_bq = phasing.hap_min_bq_arg(args, True, "")
+    weights = phasing.hap_bq_weights_arg(args)
     if args.min_reads < 0 or not 0 <= args.min_agree_pct <= 100:
         sys.exit("[ERROR] --min_reads must be >= 0 and --min_agree_pct between 0 and 100")
     per = phasing.allele_candidates_from_vcf(args.vcf_fn, None, *(() if ref_of is None else (ref_of,))) if indels else phasing.candidates_from_vcf(args.vcf_fn, None)
@@ -190,14 +192,14 @@ def Run(args, log=None):
                 eng = capi.Engine(gpu_id)
                 eng.set_params(min_mq=args.min_mq)
             query = nearest_sets(cands, table.sites)
-            rs = io.load_reads(args.bam_fn, ctg, **(dict(want_quals=True) if min_bq else {}))
+            rs = io.load_reads(args.bam_fn, ctg, **(dict(want_quals=True) if min_bq or weights else {}))
             if ref_of is not None:                            # (the whole contig: it covers every read)
                 eng.set_reference(*ref_of(ctg))
                 eng.set_hap_left_align(True)
             if realign:
                 phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
             source.apply(eng, table)
-            phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
+            phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log, **(dict(weights=True) if weights else {}))
             if indels:
                 counts = eng.hap_allele_counts(query, per[ctg][1])
                 out, st = capi.hap_assign(capi.hap_site_keys(query), counts, args.min_reads, args.min_agree_pct)

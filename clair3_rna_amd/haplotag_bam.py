@@ -17,12 +17,12 @@ Contigs: --ctg_name, else every contig of the BAM header; a contig without a rec
 The tag rule is the one of include/c3r.h (c3r_set_phase_sites): ALL loaded reads are tagged, whatever excl_flags / min_mq say (secondary and
 supplementary alignments and MAPQ 0 included); every phased heterozygous SNV a read covers is one vote of unit weight for the haplotype
 whose allele the read shows at the CIGAR position; the read's set is the one with the most votes.  No realignment, no base qualities
-(`--hap_min_bq` lifts it: a threshold, not weights), no
+(`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes), no
 indels, no tagging of a supplementary alignment after its primary.  Agreement with `whatshap haplotag` / `longphase haplotag` has not been
 measured.  --haplotag_indels: the phased insertions, deletions and two-ALT rows of the phased VCF vote too (c3r_set_phase_alleles:
 phasedvcf.contig_alleles -> Engine.set_phase_alleles), still as CIGAR-position alleles without left-alignment — unless --left_align_indels (with
 --ref_fn) is given: then the table's indels are left-aligned against the reference and every read's indel inside its own M run, on the device
-(include/c3r.h: c3r_set_hap_left_align); a shift stops at the run's start, at an N or another indel; still no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights).
+(include/c3r.h: c3r_set_hap_left_align); a shift stops at the run's start, at an N or another indel; still no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes).
 
     python -m clair3_rna_amd.haplotag_bam --bam_fn x.bam --phased_vcf_fn out/tmp/phased_output/phased_vcf \\
         --output_dir out/tmp/phased_output/phased_bam
@@ -63,7 +63,7 @@ def build_parser():
     p = argparse.ArgumentParser(
         description="Write the haplotagged BAM of a phased run (one indexed <ctg>.bam per contig) with the HP / PS tags MI355X computes from the phased "
                     "VCF: all loaded reads are tagged whatever their flags or MAPQ, unit-weight votes of CIGAR-position alleles at phased "
-                    "heterozygous SNVs, no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights).  Agreement with whatshap / longphase haplotag has not been measured")
+                    "heterozygous SNVs, no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes).  Agreement with whatshap / longphase haplotag has not been measured")
     a = p.add_argument
     a("-b", "--bam_fn", type=str, required=True, help="the BAM the phased VCF was made from (coordinate-sorted; an index beside it keeps every contig's pass short)")
     a("--phased_vcf_fn", type=str, required=True,
@@ -76,12 +76,14 @@ def build_parser():
     a("--left_align_indels", action="store_true",
       help="with --haplotag_indels: left-align the table's indels against --ref_fn and every read's indel inside its own M run, on the device "
            "(include/c3r.h: c3r_set_hap_left_align): the tags of a 30-channel pass that ran with this flag.  A shift stops at the M run's "
-           "start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap is not measured")
+           "start, at an N or another indel; no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); agreement with whatshap is not measured")
     a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels and --hap_realign only")
     from . import phasing
     phasing.add_hap_realign_flag(a)
     a("--hap_min_bq", type=int, default=0, metavar="N",
-      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
+      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights (--hap_bq_weights are those); an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
+    phasing.add_hap_bq_weights_flag(a, "the tags of a 30-channel pass that ran with this flag, and PC (the difference of the two haplotypes' weight sums, "
+                                       "in the smallest unsigned type) behind PS of every tagged record: ")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     a("--threads", type=int, default=0, help="BGZF inflate / deflate threads; default: the CPUs this process may run on, 32 at the most")
     return p
@@ -104,6 +106,7 @@ def Run(args, log=None):
     realign, realign_ref = phasing.hap_realign_arg(args)
     source = phasedvcf.PhaseSource(args.phased_vcf_fn, tag_indels, *(() if ref_of is None else (None, ref_of)), **(dict(realign=realign) if realign else {}))
     min_bq = phasing.hap_min_bq_arg(args, True, "")
+    weights = phasing.hap_bq_weights_arg(args)
     threads = int(getattr(args, "threads", 0) or 0)
     command = getattr(args, "command", None) or " ".join(sys.argv)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -118,9 +121,9 @@ def Run(args, log=None):
                     log("[INFO] %s: not in the header of %s: no file" % (ctg, args.bam_fn))
                     continue
                 table = source.table(ctg)
-                rs = hp = ps = None
+                rs = hp = ps = pc = None
                 if len(table):
-                    rs = bf.fetch(ctg, **(dict(want_quals=True) if min_bq else {}))                             # io.load_reads(bam, ctg) on the handle that is open already (--threads)
+                    rs = bf.fetch(ctg, **(dict(want_quals=True) if min_bq or weights else {}))                             # io.load_reads(bam, ctg) on the handle that is open already (--threads)
                 if rs is not None and len(rs):
                     if eng is None:
                         eng = capi.Engine(gpu_id)
@@ -130,14 +133,18 @@ def Run(args, log=None):
                     if realign:
                         phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
                     source.apply(eng, table)
-                    phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
+                    phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log, **(dict(weights=True) if weights else {}))
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()
+                    if weights:                                    # (PC: |w1 - w2| of the set the tag was decided in)
+                        w = eng.haplotag_weights().astype(np.int64)
+                        pc = np.abs(w[:, 0] - w[:, 1]).astype(np.uint32)
                 elif rs is not None:                               # (no read record: nothing to launch; the contig's other records still go out)
                     hp, ps = np.zeros(0, np.uint8), np.zeros(0, np.int32)
+                    pc = np.zeros(0, np.uint32) if weights else None
                 out = os.path.join(args.output_dir, ctg + ".bam")
                 tmp, tmp_bai = out + ".tmp", out + ".bai.tmp"
                 try:
-                    st = bf.write_haplotagged(ctg, tmp, rs, hp, ps, pg_line=line, threads=threads)
+                    st = bf.write_haplotagged(ctg, tmp, rs, hp, ps, pg_line=line, threads=threads, **(dict(pc=pc) if pc is not None else {}))
                     if st["records"] == 0:                         # (header + EOF: through an index that costs nothing)
                         os.remove(tmp)
                         log("[INFO] %s: no record in %s: no file" % (ctg, args.bam_fn))

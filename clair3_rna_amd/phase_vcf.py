@@ -12,7 +12,7 @@ then also says how many units joined in how many levels.
 --indels (default off, as `whatshap phase --indels` is): the candidates are every heterozygous row whose alleles are SNVs, insertions or
 deletions — `0/1` with one ALT, `1/2` with two (phasing.allele_candidates_from_vcf) —, phased by Engine.phase_allele_sites (include/c3r.h:
 c3r_phase_allele_links) and written as `0|1` / `1|0` / `1|2` / `2|1` + PS.  The alleles are read off the CIGAR position: no realignment,
-no left-alignment of the reads' indels, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); homozygous rows and rows with three or more ALTs are not candidates.  The
+no left-alignment of the reads' indels, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); homozygous rows and rows with three or more ALTs are not candidates.  The
 second pass reads such a directory with `--haplotag_indels`.
 
 --left_align_indels (default off; needs --indels and --ref_fn) lifts "no left-alignment": the candidates' indels are brought to their
@@ -20,7 +20,7 @@ left-most form against the reference (phasing.left_align_table) and each read's 
 device (include/c3r.h: c3r_set_hap_left_align), so that a read whose aligner placed the indel elsewhere in a homopolymer or a short tandem
 repeat shows the allele and not the reference.  A row whose alleles cannot move together is no candidate (`not_left_alignable`), nor is the
 later of two that land on one position (`same_pos_after_left_align`).  Written rows keep their POS, REF and ALT.  What remains: a shift
-stops at the M run's start, at an N or another indel, and at the contig's ends; no realignment, no base qualities (`--hap_min_bq` lifts it: a threshold, not weights); agreement with whatshap
+stops at the M run's start, at an N or another indel, and at the contig's ends; no realignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); agreement with whatshap
 is not measured.
 
 The rule (include/c3r.h: c3r_phase_links / c3r_phase_resolve) is a greedy linkage chain, not whatshap's wMEC: agreement with whatshap has
@@ -61,7 +61,7 @@ def build_parser():
     a("--ref_fn", type=str, default=None, help="the reference FASTA with its .fai: needed by --left_align_indels and --hap_realign only")
     phasing.add_hap_realign_flag(a)
     a("--hap_min_bq", type=int, default=0, metavar="N",
-      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights; an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
+      help="a base whose quality is below N does not vote: the steps that hold reads against a site table read it as N (include/c3r.h: c3r_set_hap_min_bq; 0 .. 93, default 0: off).  A threshold, not whatshap's quality weights (--hap_bq_weights are those); an indel's own quality is not modelled; reads without qualities are never masked; agreement with whatshap is not measured")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else 0")
     return p
 

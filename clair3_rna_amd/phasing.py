@@ -249,11 +249,13 @@ def reads_without_quals(rs):
     return int((rs.qual[2 * r["seq_off"].astype(np.int64)] == 0xff).sum()) if len(r) else 0
 
 
-def load_reads_min_bq(eng, rs, q, ctg, log):
+def load_reads_min_bq(eng, rs, q, ctg, log, weights=False):
     """The one place where a driver's engine meets --hap_min_bq (include/c3r.h: c3r_set_hap_min_bq): Engine.load_reads under the
     threshold q.  q = 0: the plain load, nothing else.  Otherwise `rs` must carry qualities (io.load_reads(..., want_quals=True)); the
     threshold is set before the load, one [INFO] line gives masked / total bases, and one [WARNING] line counts the reads without
-    qualities when there are any — they are not refused: none of their bases is masked."""
+    qualities when there are any — they are not refused: none of their bases is masked.
+    weights: --hap_bq_weights, which needs the same qualities on the same way (apply_hap_bq_weights, before the load)."""
+    apply_hap_bq_weights(eng, weights, rs, ctg, log)
     if not q:
         eng.load_reads(rs)
         return
@@ -266,6 +268,41 @@ def load_reads_min_bq(eng, rs, q, ctg, log):
     without = reads_without_quals(rs)
     if without:
         log("[WARNING] %s: %d of %d reads carry no base qualities: --hap_min_bq masks none of their bases" % (ctg, without, len(rs.reads)))
+
+
+def add_hap_bq_weights_flag(add, where=""):
+    """--hap_bq_weights on a driver's parser (`add`: its add_argument; `where`: what the driver has to say about its own steps)."""
+    add("--hap_bq_weights", action="store_true",
+        help="%sweigh every haplotag vote by the quality of the read's base on the site where it otherwise counts 1 (include/c3r.h: "
+             "c3r_set_hap_bq_weights; default off): one Q30 base outvotes two Q5 bases, a base without a quality weighs 1.  The tagging only: "
+             "the count tables and the links of the built-in phasing stay unweighted.  An indel's own quality and the inserted bases' are "
+             "not modelled; under --hap_realign the weight is still the anchor base's; that whatshap weights by phred is recalled, not "
+             "checked; agreement with whatshap is not measured" % where)
+
+
+def hap_bq_weights_arg(args, has_consumer=True, needs=""):
+    """A driver's --hap_bq_weights (False also when the parser has no such flag); refuses the flag without a step that tags reads
+    (`has_consumer`; `needs`: what the message asks for)."""
+    import sys
+    if not getattr(args, "hap_bq_weights", False):
+        return False
+    if not has_consumer:
+        sys.exit("[ERROR] --hap_bq_weights needs %s (it weighs the votes of the step that haplotags the reads from a site table)" % needs)
+    return True
+
+
+def apply_hap_bq_weights(eng, on, rs, ctg, log):
+    """The one place where a driver's engine meets --hap_bq_weights (include/c3r.h: c3r_set_hap_bq_weights), before the contig's reads
+    are loaded: `rs` must carry qualities (io.load_reads(..., want_quals=True)); one [WARNING] line counts the reads without qualities
+    when there are any — they are not refused: their votes weigh 1."""
+    if not on:
+        return
+    if getattr(rs, "qual", None) is None:
+        raise ValueError("--hap_bq_weights: the reads of %s were fetched without their qualities" % ctg)
+    eng.set_hap_bq_weights(True)
+    without = reads_without_quals(rs)
+    if without:
+        log("[WARNING] %s: %d of %d reads carry no base qualities: under --hap_bq_weights each of their votes weighs 1" % (ctg, without, len(rs.reads)))
 
 
 HAP_REALIGN_DEFAULT = 10      # --hap_realign without a value (recalled as whatshap's default overhang, not checked)

@@ -124,8 +124,8 @@ int c3r_set_sites(c3r_ctx *ctx, const int32_t *sites, int64_t n);
  * the read's base there is the site's ref (allele 0) or alt (allele 1) — for haplotype 1 when allele == h1, else for haplotype 2; votes
  * are counted per phase set as (c1, c2); the read's phase set is the one with the most votes (equal: the one whose first voting site on
  * the read comes first); hp = 1 if c1 > c2, 2 if c2 > c1, else 0.  This is whatshap's per-phase-set majority with unit weights and the
- * allele read off the CIGAR position: no realignment (c3r_set_hap_realign lifts it), and no base-quality weights (c3r_set_hap_min_bq, below, lifts it as far as a threshold does:
- * a threshold, not weights).
+ * allele read off the CIGAR position: no realignment (c3r_set_hap_realign lifts it), and no base-quality weights (c3r_set_hap_min_bq, below, lifts it as far as a threshold does,
+ * c3r_set_hap_bq_weights, below, with the weights themselves).
  * n = 0 clears the table: nothing is launched then and the records' own hp count again.  C3R_EINVAL, naming the first bad index, for an
  * unsorted or repeated position, pos < 1, a base code other than 1, 2, 4, 8, ref == alt, h1 > 1 or ps < 0.  Valid before or after c3r_load_reads
  * with the same result: when reads are loaded their tables are rebuilt from the records the device holds (as c3r_set_params does for new
@@ -169,7 +169,7 @@ int c3r_hap_assign(const c3r_phase_site_t *in, int64_t n, const uint32_t *counts
                    c3r_hap_assign_stats_t *stats);
 /* The same counts for a heterozygous call whose two alleles may be SNVs, insertions or deletions: `0/1` rows with an indel ALT and `1/2` rows
  * (`C  T,CGG`, `ACC  A,TCC`).  Opt-in (hap_vcf --indels), like `whatshap phase --indels`.  The alleles are read off the CIGAR position: no
- * realignment, no left-alignment of the reads' indels, no base qualities (c3r_set_hap_min_bq lifts it: a threshold, not weights); agreement with `whatshap --indels` is not measured.  This is where
+ * realignment, no left-alignment of the reads' indels, no base qualities (c3r_set_hap_min_bq lifts it as a threshold, c3r_set_hap_bq_weights as weights of the tagging's votes); agreement with `whatshap --indels` is not measured.  This is where
  * the rule is stated; phasing.allele_candidates_from_vcf, csrc/hapcount_kernels.hpp and tests/hapalleleref.py restate it.
  *
  * Alleles of a VCF row: REF r and an ALT a, upper-cased, letters of ACGT only; the common SUFFIX is stripped while both are longer than one
@@ -361,7 +361,7 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
  * does not depend on the walk a read takes: a read whose CIGAR holds two M-like ops in a row takes the serial walk while the switch is on
  * (the plain walk hands them out one by one; aligners that write = / X pay one lane per read there).
  * What remains: a shift stops at the M run's start, at an N or another indel, and at the slice's edge; there is no realignment (c3r_set_hap_realign lifts it) and there
- * are no base qualities (c3r_set_hap_min_bq lifts it: a threshold, not weights); agreement with whatshap is not measured.
+ * are no base qualities (c3r_set_hap_min_bq lifts it as a threshold, c3r_set_hap_bq_weights as weights of the tagging's votes); agreement with whatshap is not measured.
  *
  * c3r_set_hap_left_align(ctx, on): default 0.  While on, the four calls above run k_*_la (the same launches, one kernel each, with
  * hap_observe_la in hap_observe's place) against the slice of c3r_set_reference that is current when they run, and return C3R_EINVAL with a
@@ -447,7 +447,7 @@ int c3r_hap_realign_column(const c3r_hap_site_t *site, const uint8_t *ins_pool, 
  * (an N never equals a reference code).  Hence the results with (qualities, Q) equal, element for element,
  * the results with Q = 0 on reads whose masked bases the caller replaced by N.  Everything else reads the sequence as it was loaded: the
  * tensor build and its tokens, the ordered recompute, the decoder's copy of the bases, c3r_rows_begin_ex.
- * What remains: it is a threshold, not whatshap's quality-weighted votes; an indel's own quality is not modelled (an indel carries none in
+ * What remains: it is a threshold, not whatshap's quality-weighted votes (c3r_set_hap_bq_weights, below, are those); an indel's own quality is not modelled (an indel carries none in
  * BAM); agreement with whatshap is not measured; the default is 0.
  *
  * c3r_load_reads_q is c3r_load_reads plus the qualities (c3r_load_reads is this call with qual = NULL, n_qual_bytes = 0).
@@ -469,6 +469,44 @@ int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, con
 int c3r_set_hap_min_bq(c3r_ctx *ctx, int min_bq);
 int c3r_get_hap_min_bq(c3r_ctx *ctx, int *min_bq, int64_t *n_masked);
 int c3r_get_hap_seq(c3r_ctx *ctx, uint8_t *seq4, int64_t cap);
+/* Quality-weighted votes for the tagging — the decision of c3r_set_phase_sites / c3r_set_phase_alleles inside c3r_load_reads* — and for
+ * nothing else.  Opt-in (--hap_bq_weights); switched off, every launch, upload and output byte is what the contracts above say.  Whatshap
+ * sums the phred quality of the read's base on each phased site where the rule above counts 1; this switch is that weighting.  This is
+ * where the rule `bq_weights` is stated; csrc/haplotag_kernels.hpp (HapTallyW, the four _w kernels) and tests/hapweightref.py restate it.
+ *
+ * Rule: hap_bq_weights is 0 or 1.  Voters, the observation (also under c3r_set_hap_left_align / c3r_set_hap_realign, where only the
+ * observation differs) and the membership of a site in a phase set are the contracts above.  The WEIGHT of a vote is the quality byte of
+ * the read's base on the site's position, qual[2 * seq_off + q], q being the query offset of that base: the anchor base of an indel or
+ * two-ALT site.  A byte 0xff (no quality; such a record is 0xff throughout) weighs 1, so a read without qualities gets its unit-weight
+ * result.  Weight 0 is legal: the observation counts as one and adds nothing.  No cap, no rescaling: a read's sum is at most l_seq x 254.
+ * Per phase set the read has (w1, w2), the weight sums for haplotype 1 and 2, n, the number of observations, and the first voting site.
+ * The read's phase set is the one with the largest w1 + w2 (equal: the one whose first voting site on the read comes first);
+ * hp = 1 if w1 > w2, 2 if w2 > w1, else 0.  The tag word and c3r_haplotag_stats_t keep their meaning: n_votes sums the observations of
+ * all sets, n_no_vote counts reads with no observation, n_tie reads with w1 == w2 in the chosen set.  With c3r_set_hap_min_bq a masked
+ * base is an N and no observation, as there; the weight of an unmasked base is its own quality.
+ * The count tables (c3r_hap_counts, c3r_hap_allele_counts) and the four link calls do not look at the switch: they count reads, by the
+ * tags and sets this rule decided.
+ * What remains: an indel's own quality and the inserted bases' qualities are not modelled; under c3r_set_hap_realign the weight is still
+ * the anchor's quality, not a difference of alignment costs; the links of the built-in phasing stay unweighted; that whatshap weights by
+ * phred and writes PC is recalled, not checked; agreement with whatshap is not measured; the default is off.
+ *
+ * c3r_set_hap_bq_weights: C3R_EINVAL for a value other than 0 or 1, and for 1 while reads are loaded that came without a quality array
+ * (c3r_load_reads); the context stays as it was.  While the switch is on, a c3r_load_reads of n_reads > 0 without qualities is C3R_EINVAL
+ * before anything of the previous load is given up: a weight that silently does not apply is refused.  Valid before or after the load with
+ * the same result: with reads loaded and a table set the reads are tagged again, as c3r_set_hap_min_bq does.
+ * c3r_get_hap_bq_weights: the switch.
+ * c3r_get_haplotag_weights: (w1, w2) of the set every loaded read's tag was decided in, in load order (w12: [cap][2], cap >= the number
+ * of loaded reads): a tie's pair for a read tagged 0 with observations, (0, 0) without one.  Their difference is what
+ * the BAM writer of include/c3r_io.h writes as PC.  C3R_EINVAL when no phase sites are set or the switch is off;
+ * C3R_EOVERFLOW when cap is smaller.  The pairs' buffer on the device exists only once the switch was on.
+ * c3r_get_haplotag_words: the tag word of every loaded read, in load order (words: [cap], cap >= the number of loaded reads): tag | n << 2
+ * with n the read's observations on all phase sets — what c3r_get_haplotags sums into n_votes —, with the switch on or off.  C3R_EINVAL
+ * when no phase sites are set; C3R_EOVERFLOW when cap is smaller.
+ * A re-tag that fails inside c3r_set_hap_bq_weights leaves the switch as it was before the call. */
+int c3r_set_hap_bq_weights(c3r_ctx *ctx, int on);
+int c3r_get_hap_bq_weights(c3r_ctx *ctx, int *on);
+int c3r_get_haplotag_weights(c3r_ctx *ctx, uint32_t *w12, int64_t cap);
+int c3r_get_haplotag_words(c3r_ctx *ctx, uint32_t *words, int64_t cap);
 
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped

@@ -94,6 +94,12 @@ int c3r_bam_header_text(c3r_bam *b, const char **text, int64_t *n_bytes);
  * unpaired (the ones the keep rule skips). */
 int c3r_bam_write_haplotagged(c3r_bam *b, const char *contig, const c3r_read_t *reads, const uint8_t *hp, const int32_t *ps, int64_t n_reads,
                               const char *out_path, const char *pg_line, int threads, int64_t *counts);
+/* c3r_bam_write_haplotagged plus PC, the phase confidence whatshap writes beside HP and PS: pc is [n_reads] or NULL.  Where hp[k] is 1
+ * or 2 and pc is given, PC follows PS in the smallest unsigned type that holds pc[k] (C / S / I); the caller hands in |w1 - w2| of
+ * c3r_get_haplotag_weights (include/c3r.h: c3r_set_hap_bq_weights).  Everything else — pairing, refusals, counts, threading — is the
+ * call above, which is this one with pc = NULL and writes the bytes it always wrote. */
+int c3r_bam_write_haplotagged_pc(c3r_bam *b, const char *contig, const c3r_read_t *reads, const uint8_t *hp, const int32_t *ps, const uint32_t *pc,
+                                 int64_t n_reads, const char *out_path, const char *pg_line, int threads, int64_t *counts);
 
 /* ---- output side (csrc/vcfio.cpp): what `sort_vcf` does after the per-chunk calls (src/sort_vcf.py:123-292).
  *
