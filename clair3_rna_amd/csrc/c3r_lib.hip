@@ -2241,7 +2241,7 @@ static int scan_fused(c3r_ctx *ctx, const ScanKnobs &kn, int32_t n_regions, cons
         if ((rc = ensure(ctx, ctx->d_evwg, (size_t)deep_grid * DEEP_EVG_CAP * sizeof(EvRec)))) return rc;
         a.ev_wg = (EvRec *)ctx->d_evwg.p; a.ev_wg_cap = DEEP_EVG_CAP;
     }
-    // giant spans (k_deep_walk, k_deep_alleles): 64 accumulator slots + the slice list (2 MB), a pool of 12 M events (288 MB) and their allele table
+    // giant spans (k_deep_walk, k_deep_alleles): GIANT_SLOTS = 256 accumulator slots + the slice list (8.5 MB), a pool of 12 M events (288 MB) and their allele table
     // (192 MB), for a context that has met one
     const size_t giant_acc_bytes = (size_t)GIANT_SLOTS * GIANT_STRIDE * 4 + 16;          // (+ the pool's cursor: cleared with the slots)
     a.n_giant = &ctl->n_giant; a.n_help = &ctl->n_help;

@@ -1119,3 +1119,163 @@ def build_row_export_check(exe, timeout=None):
                          os.path.join(root, "tests", "c", "row_export_check.hip"), "-o", exe], capture_output=True, text=True, timeout=timeout)
     assert cc.returncode == 0 and "warning:" not in cc.stderr, cc.stderr[-3000:]
     return exe
+
+
+# ---- scans at the fused scan's allocator switch (tests/test_scan_shards_ref.py holds every input on its floor with the oracle alone,
+# tests/test_gpu_scan_shards.py runs the engine).  A scan of SHARD_TILES tiles or more hands rows and token slots out through ALLOC_SHARDS
+# sub-allocators whose sizes come from what the context's previous sharded scan needed (c3r_lib.hip, scan_fused: hint_rows / hint_toks);
+# the numbers below are that code's constants.
+SPAN, SHARD_TILES, ALLOC_SHARDS = 224, 4096, 16
+FRESH_ROWS, FRESH_TOKS = 4096, 131072           # per shard, a context that has made no sharded scan yet
+PRIMED_ROWS, PRIMED_TOKS = 64, 2048             # per shard, after a sharded scan that found nothing: 1.25 x 0 + 64 rows / 2048 token slots
+DENSE_END, SHARD_END = 917247, 917248           # ctg_end of a scan from 1 with 4095 / 4096 tiles
+SHARD_REF_LEN = 1920000                         # the reference slice of every case: the reads lie in its first 918 kb, the rest is `A`
+PRIME_REGION = (1000001, 1000001 + 917300)      # 4096 tiles or more and no read: a scan of it leaves the hints at PRIMED_ROWS / PRIMED_TOKS
+
+
+def scan_tiles(regions):
+    """The tiles of a scan of `regions` ((ctg_start, ctg_end) pairs): every region with its 33-position halo, in spans of 224."""
+    return sum(-(-(b + 33 - (max(1, a - 33) - 1)) // SPAN) for a, b in regions)
+
+
+def edge_regions(n_last):
+    """64 adjacent regions: 63 of 64 tiles and a last one of n_last."""
+    regs = [(100 + 14270 * k, 100 + 14270 * k + 14269) for k in range(64)]
+    a, _b = regs[-1]
+    regs[-1] = (a, a + 14269 - SPAN * (64 - n_last))
+    return regs
+
+
+def padded_reference(parts):
+    """SHARD_REF_LEN bases: `A` everywhere but on the (0-based offset, bases) parts."""
+    buf = bytearray(b"A" * SHARD_REF_LEN)
+    for off, s in parts:
+        buf[off:off + len(s)] = s.encode()
+    return buf.decode()
+
+
+_burst_cache = {}
+
+
+def burst_case(channels, offset, seed=77, iupac=False):
+    """(ref, ReadSet): synth.small_case(seed, 9 kb, 3 genes, depth 30, reads of ~500) moved `offset` positions into the padded reference
+    — with snp_min_af = 0 and min_coverage = 2 more than 1200 candidates within 9 kb (about 41 spans, 130 reads).  iupac: one read shows an
+    `M` on a covered column (30 channels: the ordered recompute, which a context builds its tables for only after meeting such a column)."""
+    from clair3_rna_amd import synth
+    from clair3_rna_amd.reads import ReadSet
+    key = (channels, seed)
+    if key not in _burst_cache:
+        _burst_cache[key] = synth.small_case(seed=seed, ref_len=9000, n_genes=3, depth=30, mean_len=500, phased=(channels == 30),
+                                             platform="hifi" if channels == 30 else "ont")[:2]
+    ref, rs = _burst_cache[key]
+    if iupac:
+        seq = rs.seq.copy()
+        r = rs.reads[len(rs.reads) // 2]
+        q = 0                                                       # a query position well inside the read's first long match
+        for c in rs.cigar[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["n_cigar"])]:
+            op, ln = int(c) & 15, int(c) >> 4
+            if op in (0, 7, 8) and ln >= 12:
+                q += 6
+                break
+            if op in (0, 1, 4, 7, 8):
+                q += ln
+        byte, hi = int(r["seq_off"]) + q // 2, q % 2 == 0
+        seq[byte] = ((3 << 4) | (seq[byte] & 15)) if hi else ((seq[byte] & 0xf0) | 3)       # 'M' (A or C) there
+        rs = ReadSet(rs.reads, rs.cigar, seq)
+    return padded_reference([(offset, ref)]), shift_readset(rs, offset)
+
+
+DEEP_PILE_RLEN, DEEP_PILE_COLS = 60, 28         # reads of 60 M: two records each; the 28 columns that have 16 covered positions on either side
+
+
+def deep_piles(depth, n_piles, offset, pitch=1000, seed=5):
+    """(ref, ReadSet, records): n_piles piles `pitch` apart, each `depth` reads `60M` on one position, nine in ten with a substitution on
+    each of the pile's 28 central columns (the only ones with a whole window), alternating strands.  Default gates: 28 candidates per pile
+    and 0.9 x depth tokens per candidate; a span holds at most one pile, 2 x depth records.
+    Two piles, not three: a regrowth sizes the shards by the fullest one of the attempt that failed, and the scan gives up after two, so k
+    equally heavy spans that happen to land 1, then 2, then 3 in one shard would end it with an error; with two the third attempt fits
+    wherever they land."""
+    from clair3_rna_amd.reads import ReadSet
+    ref = random_reference(n_piles * pitch + 200, seed)
+    recs = []
+    for k in range(n_piles):
+        p0 = 100 + k * pitch
+        alt = _with_subs(ref, p0, DEEP_PILE_RLEN, range(p0 + 16, p0 + 16 + DEEP_PILE_COLS))
+        recs += [dict(pos=offset + p0, cigar="%dM" % DEEP_PILE_RLEN, seq=ref[p0:p0 + DEEP_PILE_RLEN] if i % 10 == 9 else alt, flag=16 * (i % 2), hp=i % 3)
+                 for i in range(depth)]
+    return padded_reference([(offset, ref)]), ReadSet.from_records(recs), recs
+
+
+WIDE_RLEN, WIDE_DEPTH, WIDE_AT = 500, 6200, 224 * 1000 - 16      # (its first candidate column is the first position of a span)
+
+
+def wide_pile(seed=9):
+    """(ref, ReadSet): WIDE_DEPTH reads `500M` on one position, nine in ten with a substitution on each of the 468 columns that have a whole
+    window — 2.6 M tokens, more than the 16 x 131072 slots of a context that has made no sharded scan, in spans of 224, 224 and 20 candidates
+    (the first of them alone is more than a fresh shard holds, and 1.25 x the two large ones hold all three: the third attempt always fits)."""
+    from clair3_rna_amd.reads import ReadSet
+    ref = random_reference(WIDE_RLEN + 100, seed)
+    alt = _with_subs(ref, 0, WIDE_RLEN, range(16, WIDE_RLEN - 16))
+    recs = [dict(pos=WIDE_AT, cigar="%dM" % WIDE_RLEN, seq=ref[:WIDE_RLEN] if i % 10 == 9 else alt, flag=16 * (i % 2), hp=i % 3) for i in range(WIDE_DEPTH)]
+    return padded_reference([(WIDE_AT, ref)]), ReadSet.from_records(recs)
+
+
+def oracle_regions(rs, ref, regions, channels=18, **pk):
+    """The oracle's result for a scan of several regions: dict(lines, X) of the regions one after the other."""
+    parts = [oracle_chunk(rs, ref, 1, a, b, channels=channels, **pk) for a, b in regions]
+    return dict(lines=[l for p in parts for l in p["lines"]], X=np.concatenate([p["X"].reshape(-1, 33, channels) for p in parts]),
+                rows=[r for p in parts for r in p["rows"]], depth=np.concatenate([np.asarray(p["depth"]).reshape(-1) for p in parts]))
+
+
+def alt_tokens(lines):
+    """A lower bound of the tokens behind the lines: the counts of their alt_info fields (`<depth>-<allele> <count> ...`) without the
+    reference's (`R<base>`) — every such count is one read's token; reads inside a deletion have tokens that alt_info does not count."""
+    n = 0
+    for l in lines:
+        f = l.split("\t")[4].split("-", 1)[1].split()
+        n += sum(int(v) for k, v in zip(f[0::2], f[1::2]) if not k.startswith("R"))
+    return n
+
+
+def max_span_candidates(lines, ctg_start=1):
+    """The most candidates that one span of a scan from ctg_start holds: a span is one workgroup's and takes its rows from one shard."""
+    first = max(1, ctg_start - 33)
+    return int(np.bincount([(p - first) // SPAN for p in line_positions(lines)]).max())
+
+
+BURST_AT, BURST_AT2, PILES_AT = 400000, 123457, 600000            # offsets of the inputs in the padded reference (0-based)
+BURST_KW = dict(snp_min_af=0.0, min_coverage=2)
+
+
+def shard_case(name, channels=18):
+    """The inputs of tests/test_gpu_scan_shards.py by name -> dict(ref, rs, kw: engine parameters, okw: the oracle's).
+    burst / burst2: burst_case at BURST_AT / BURST_AT2; burst_iupac: with the IUPAC base; piles_tile / piles_deep: deep_piles of 2 x 1000 and
+    2 x 2600 reads (2000 and 5200 records in a span: k_fused_tiles' and k_fused_deep's at the natural thresholds); batch: the burst at 20000
+    and piles_deep at PILES_AT in one read set, gates of the burst; wide: wide_pile."""
+    okw = dict(channels=channels)
+    kw = dict(channels=channels)
+    if name.startswith("burst"):
+        ref, rs = burst_case(channels, BURST_AT2 if name == "burst2" else BURST_AT, iupac=(name == "burst_iupac"))
+    elif name == "piles_tile":
+        ref, rs, _ = deep_piles(1000, 2, PILES_AT)
+    elif name == "piles_deep":
+        ref, rs, _ = deep_piles(2600, 2, PILES_AT)
+    elif name == "wide":
+        ref, rs = wide_pile()
+    elif name == "batch":
+        ref_b, rs_b = burst_case(channels, 20000)
+        ref_p, rs_p, _ = deep_piles(2600, 2, PILES_AT)
+        ref = padded_reference([(20000, ref_b[20000:29000]), (PILES_AT, ref_p[PILES_AT:PILES_AT + 2200])])
+        rs = merge_readsets(rs_b, rs_p)
+    else:
+        raise KeyError(name)
+    if name.startswith("burst") or name == "batch":
+        kw.update(BURST_KW)
+        okw.update(snp_af=0.0, min_coverage=2)
+    return dict(ref=ref, rs=rs, kw=kw, okw=okw)
+
+
+# the batch of tests/test_gpu_scan_shards.py on shard_case("batch"): (region, kind) in scan order — `prime` scans find nothing and leave the
+# hints at their floor, so that the sharded scan behind each must grow and repeat
+BATCH_SCANS = [((20001, 23000), "dense"), (PRIME_REGION, "prime"), ((1, SHARD_END), "sharded"), ((23000, 29500), "dense"), (PRIME_REGION, "prime"),
+               ((30001, 30001 + 917300), "sharded"), ((PILES_AT, PILES_AT + 600), "dense")]
