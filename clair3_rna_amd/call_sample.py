@@ -46,7 +46,8 @@ hap_vcf phases the heterozygous SNVs of <prefix>_enable_phasing.vcf.gz from per-
 by CIGAR-position alleles (no realignment, no left-alignment, no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes)); without it both files are what they were.
 `--hap_realign [W]` (with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin; excludes --left_align_indels) lifts "no realignment" for every
 step that holds reads against a site table: the flag and --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h:
-c3r_set_hap_realign); the unphased pass holds its reads against no table and does not get it.  Unit costs, no quality weights; a window stops at a splice junction.
+c3r_set_hap_realign); the unphased pass holds its reads against no table and does not get it.  Unit costs, no quality weights; a window stops at a splice junction
+unless `--hap_realign_spliced` is given, which goes to exactly the steps that get `--hap_realign` (include/c3r.h: c3r_set_hap_realign_spliced).
 `--left_align_indels` (with one of --phase_indels, --haplotag_indels, --phasing_indels) lifts "no left-alignment" for every step that reads indels: the flag and
 --ref_fn are handed to phase_vcf, to the 30-channel pass, to hap_vcf and to haplotag_bam (include/c3r.h: c3r_set_hap_left_align).  A shift stops at a read's M run's
 start, at an N or another indel; there is still no realignment and there are no base qualities (`--hap_min_bq` lifts it as a threshold, `--hap_bq_weights` as weights of the haplotag votes); agreement with whatshap is not measured.
@@ -450,7 +451,7 @@ def _plan(args):
     # (--hap_realign goes to every step that holds reads against a table: phase_vcf, the 30-channel pass, hap_vcf and haplotag_bam)
     realign, _ = phasing.hap_realign_arg(args, bool(phased and (builtin or args.phased_vcf_fn)),
                                          "--enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: without a phase table no step holds the reads against one")
-    ra = ["--hap_realign", str(realign), "--ref_fn", args.ref_fn] if realign else []
+    ra = ["--hap_realign", str(realign), "--ref_fn", args.ref_fn] + (["--hap_realign_spliced"] if phasing.hap_realign_spliced_arg(args) else []) if realign else []
     ext = ".vcf" if args.no_compress else ".vcf.gz"
     phased_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_vcf")
     ctg = ["--ctg_name", args.ctg_name] if args.ctg_name else []
@@ -479,6 +480,7 @@ def _plan(args):
         first.phasing, first.enable_phasing_model = None, False
         first.hap_min_bq = 0                                  # (the unphased pass holds its reads against no site table: phase_vcf loads them itself)
         first.hap_realign = 0
+        first.hap_realign_spliced = False
         first.hap_bq_weights = False
         second.phasing, second.phased_vcf_fn = None, phased_dir
         if args.phasing_indels:
@@ -625,6 +627,7 @@ def _set_up(args, log, t_all):
                                      edits=p.edits) if p.rank == 0 else None
     p.hap_min_bq = int(getattr(args, "hap_min_bq", 0) or 0) if args.phased_vcf_fn else 0       # (only a pass with a phase table tags reads)
     p.hap_realign = int(getattr(args, "hap_realign", 0) or 0) if args.phased_vcf_fn else 0     # (--hap_realign, likewise)
+    p.hap_realign_spliced = bool(getattr(args, "hap_realign_spliced", False)) and bool(p.hap_realign)      # (--hap_realign_spliced goes where it goes)
     p.hap_bq_weights = bool(getattr(args, "hap_bq_weights", False)) and bool(args.phased_vcf_fn)   # (--hap_bq_weights, likewise)
     p.fetcher = _Fetcher(p.bam_fn, args.ref_fn, want_quals=bool(p.hap_min_bq or p.hap_bq_weights))
     p.phase_source = None                                              # --phased_vcf_fn: every contig's table is read on a fetch thread
@@ -852,7 +855,7 @@ def _device_stage(p, eng, ctg, rs, ref, phase):
             eng.set_reference(1, ref, upper_view=not isinstance(ref, (bytes, str)))
         if p.hap_realign:                            # (--hap_realign: the whole contig's reference likewise, then the switch)
             from . import phasing
-            phasing.apply_hap_realign(eng, p.hap_realign, (1, ref), upper_view=not isinstance(ref, (bytes, str)))
+            phasing.apply_hap_realign(eng, p.hap_realign, (1, ref), p.hap_realign_spliced, upper_view=not isinstance(ref, (bytes, str)))
         p.phase_source.apply(eng, phase)             # before the reads: they are tagged while they are prepared
         note = p.phase_source.indel_note(phase, "[INFO] %s: %d phased sites in the table of --haplotag_indels, " % (ctg, len(phase)))
         if note:

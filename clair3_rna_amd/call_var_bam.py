@@ -235,7 +235,7 @@ def Run(args, engine=None):
         if left_align:
             eng.set_reference(ref_start, ref_seq)            # (before the reads: they are tagged against it while they are prepared)
         if realign:
-            phasing.apply_hap_realign(eng, realign, (ref_start, ref_seq))
+            phasing.apply_hap_realign(eng, realign, (ref_start, ref_seq), phasing.hap_realign_spliced_arg(args))
         phase_source.apply(eng, phase)
     else:
         eng.set_phase_sites(None)                            # (a caller's engine may hold the table of an earlier chunk)

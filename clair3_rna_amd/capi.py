@@ -75,6 +75,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_set_hap_left_align", "c3r_hap_left_align_sites",
            "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq",
            "c3r_set_hap_realign", "c3r_get_hap_realign", "c3r_hap_realign_column",
+           "c3r_set_hap_realign_spliced", "c3r_get_hap_realign_spliced", "c3r_hap_realign_column_spliced",
            "c3r_set_hap_bq_weights", "c3r_get_hap_bq_weights", "c3r_get_haplotag_weights", "c3r_get_haplotag_words"]
 
 _lib = None
@@ -138,6 +139,9 @@ def load_library():
     L.c3r_set_hap_realign.argtypes = [vp, i32]
     L.c3r_get_hap_realign.argtypes = [vp, C.POINTER(i32)]
     L.c3r_hap_realign_column.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.c3r_set_hap_realign_spliced.argtypes = [vp, i32]
+    L.c3r_get_hap_realign_spliced.argtypes = [vp, C.POINTER(i32)]
+    L.c3r_hap_realign_column_spliced.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.c3r_hap_left_align_sites.argtypes = [vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(LeftAlignStats)]
     L.c3r_pileup_scan.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.c3r_pileup_scan_regions.argtypes = [vp, C.c_int32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
@@ -363,6 +367,19 @@ class Engine(object):
         w = C.c_int32(0)
         self._chk(self.L.c3r_get_hap_realign(self.h, C.byref(w)))
         return int(w.value)
+
+    def set_hap_realign_spliced(self, on):
+        """The opt-in switch of --hap_realign_spliced (c3r_set_hap_realign_spliced, default off): while it is on AND set_hap_realign is
+        above 0, a read's window is counted in the read's own spliced positions and so crosses an N op (the rule `realign_spliced` of
+        include/c3r.h).  It may be set at any time; with the overhang above 0, an allele table set and reads loaded the reads are tagged
+        again."""
+        self._chk(self.L.c3r_set_hap_realign_spliced(self.h, 1 if on is True else 0 if on is False else int(on)))
+
+    def hap_realign_spliced(self):
+        """The value of set_hap_realign_spliced (c3r_get_hap_realign_spliced)."""
+        on = C.c_int32(0)
+        self._chk(self.L.c3r_get_hap_realign_spliced(self.h, C.byref(on)))
+        return bool(on.value)
 
     def set_hap_min_bq(self, q):
         """The opt-in threshold of --hap_min_bq (c3r_set_hap_min_bq, 0 .. 93, default 0 = off): while above 0, every call that holds the
@@ -806,8 +823,9 @@ def hap_left_align_sites(sites, pool, ref_start, ref, pool_bases=None):
             {k: int(getattr(st, k)) for k, _ in LeftAlignStats._fields_})
 
 
-def hap_realign_column(site, pool, ref_start, ref, read, cigars, seq4, overhang):
-    """The rule `realign` of include/c3r.h for one read at one site on the host (c3r_hap_realign_column; no GPU, no engine): one
+def hap_realign_column(site, pool, ref_start, ref, read, cigars, seq4, overhang, spliced=False):
+    """The rule `realign` of include/c3r.h — with spliced=True the rule `realign_spliced` — for one read at one site on the host
+    (c3r_hap_realign_column / c3r_hap_realign_column_spliced; no GPU, no engine): one
     HAP_SITE_DTYPE record, the packed pool, a reference slice (`ref`: str / bytes whose first letter is 1-based `ref_start`), one READ_DTYPE
     record and the uint32 CIGAR and packed sequence arrays its offsets index -> (column 0 / 1 / 2, or 3 for no observation; whether the
     read was realigned at the site)."""
@@ -821,8 +839,9 @@ def hap_realign_column(site, pool, ref_start, ref, read, cigars, seq4, overhang)
     rd = np.ascontiguousarray(np.asarray(read, dtype=READ_DTYPE).reshape(1))
     cg, sq = np.ascontiguousarray(cigars, dtype=np.uint32), np.ascontiguousarray(seq4, dtype=np.uint8)
     col, ra = C.c_int32(0), C.c_int32(0)
-    rc = L.c3r_hap_realign_column(_ptr(a), _ptr(pl) if nb else None, int(ref_start), _ptr(r) if len(r) else None, len(r), _ptr(rd), _ptr(cg) if len(cg) else None,
-                                  _ptr(sq) if len(sq) else None, int(overhang), C.byref(col), C.byref(ra))
+    where = (_ptr(a), _ptr(pl) if nb else None, int(ref_start), _ptr(r) if len(r) else None, len(r), _ptr(rd), _ptr(cg) if len(cg) else None, _ptr(sq) if len(sq) else None,
+             int(overhang))
+    rc = L.c3r_hap_realign_column_spliced(*where, 1, C.byref(col), C.byref(ra)) if spliced else L.c3r_hap_realign_column(*where, C.byref(col), C.byref(ra))
     if rc != 0:
         raise C3RError(rc, "c3r_hap_realign_column: overhang 0 .. 16, pos >= 1, kinds 0 .. 2, an indel has a length, and a CIGAR that a load accepts")
     return int(col.value), bool(ra.value)

@@ -166,6 +166,7 @@ struct c3r_ctx {
     bool phase_alleles = false;
     bool hap_la = false;                      // c3r_set_hap_left_align: the four allele kernels run their _la instantiation against d_ref
     int hap_ra = 0;                           // c3r_set_hap_realign: the overhang W; above 0 they run their _ra instantiation against d_ref (never with hap_la)
+    bool hap_rs = false;                      // c3r_set_hap_realign_spliced: while hap_ra is above 0 they run their _rs instantiation in the _ra one's place
     DevBuf d_phase, d_hptag, d_hpps, d_phasea, d_phasepool;
     // c3r_set_hap_min_bq: the threshold; whether the loaded reads came with qualities (c3r_load_reads_q); the qualities (2 n_seq_bytes, then
     // 32 bytes of 0xff), the masked copy of d_seq that read_args hands out while the threshold is above 0 (n_seq_bytes, then 16 zeroed bytes,
@@ -536,6 +537,7 @@ int launch_haplotag(c3r_ctx *ctx, int n) {
     if ((rc = hap_needs_ref(ctx, "c3r_load_reads"))) return rc;
     HapAlleleTagRaArgs h = tag_args(read_args<HapAlleleTagRaArgs>(ctx, n));
     h.sites = (const c3r_hap_site_t *)ctx->d_phasea.p; h.pool = (const uint8_t *)ctx->d_phasepool.p;
+    if (ctx->hap_ra > 0 && ctx->hap_rs) { h.ref = hap_ref(ctx); h.overhang = (uint32_t)ctx->hap_ra; return launch_tagger<HapAlleleTagRaArgs>(ctx, "k_haplotag_alleles_rs", k_haplotag_alleles_rs, "k_haplotag_alleles_rs_w", k_haplotag_alleles_rs_w, h); }
     if (ctx->hap_ra > 0) { h.ref = hap_ref(ctx); h.overhang = (uint32_t)ctx->hap_ra; return launch_tagger<HapAlleleTagRaArgs>(ctx, "k_haplotag_alleles_ra", k_haplotag_alleles_ra, "k_haplotag_alleles_ra_w", k_haplotag_alleles_ra_w, h); }
     if (ctx->hap_la) { h.ref = hap_ref(ctx); return launch_tagger<HapAlleleTagLaArgs>(ctx, "k_haplotag_alleles_la", k_haplotag_alleles_la, "k_haplotag_alleles_la_w", k_haplotag_alleles_la_w, h); }
     return launch_tagger<HapAlleleTagArgs>(ctx, "k_haplotag_alleles", k_haplotag_alleles, "k_haplotag_alleles_w", k_haplotag_alleles_w, h);
@@ -1427,6 +1429,8 @@ int c3r_hap_allele_counts(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n, 
         a.sites = (const c3r_hap_site_t *)ctx->d_hasites.p; a.pool = (const uint8_t *)ctx->d_hapool.p;
         return (int)C3R_OK;
     };
+    if (ctx->hap_ra > 0 && ctx->hap_rs)
+        return hap_count_table(ctx, "k_hap_allele_counts_rs", k_hap_allele_counts_rs, n, counts, [&](HapAlleleRaArgs &a) { a.ref = hap_ref(ctx); a.overhang = (uint32_t)ctx->hap_ra; return upload_sites(a); });
     if (ctx->hap_ra > 0)
         return hap_count_table(ctx, "k_hap_allele_counts_ra", k_hap_allele_counts_ra, n, counts, [&](HapAlleleRaArgs &a) { a.ref = hap_ref(ctx); a.overhang = (uint32_t)ctx->hap_ra; return upload_sites(a); });
     if (ctx->hap_la) return hap_count_table(ctx, "k_hap_allele_counts_la", k_hap_allele_counts_la, n, counts, [&](HapAlleleLaArgs &a) { a.ref = hap_ref(ctx); return upload_sites(a); });
@@ -1450,7 +1454,8 @@ int c3r_phase_allele_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, int64_t n,
     a.overhang = (uint32_t)ctx->hap_ra;
     return counter_table(ctx, ctx->d_links, words, links, [&](uint32_t *t) {
         a.links = t;
-        if (ctx->hap_ra > 0) launch_per_read(ctx, "k_phase_allele_links_ra", k_phase_allele_links_ra, a);
+        if (ctx->hap_ra > 0 && ctx->hap_rs) launch_per_read(ctx, "k_phase_allele_links_rs", k_phase_allele_links_rs, a);
+        else if (ctx->hap_ra > 0) launch_per_read(ctx, "k_phase_allele_links_ra", k_phase_allele_links_ra, a);
         else if (ctx->hap_la) launch_per_read<AlleleLinkLaArgs>(ctx, "k_phase_allele_links_la", k_phase_allele_links_la, a);
         else launch_per_read<AlleleLinkArgs>(ctx, "k_phase_allele_links", k_phase_allele_links, a);
     });
@@ -1489,7 +1494,8 @@ int c3r_phase_allele_unit_links(c3r_ctx *ctx, const c3r_hap_site_t *sites, const
     a.overhang = (uint32_t)ctx->hap_ra;
     return counter_table(ctx, ctx->d_links, words, ulinks, [&](uint32_t *t2) {                                  // (t and unit_of live until it returns)
         a.ulinks = t2;
-        if (ctx->hap_ra > 0) launch_per_read(ctx, "k_phase_allele_unit_links_ra", k_phase_allele_unit_links_ra, a);
+        if (ctx->hap_ra > 0 && ctx->hap_rs) launch_per_read(ctx, "k_phase_allele_unit_links_rs", k_phase_allele_unit_links_rs, a);
+        else if (ctx->hap_ra > 0) launch_per_read(ctx, "k_phase_allele_unit_links_ra", k_phase_allele_unit_links_ra, a);
         else if (ctx->hap_la) launch_per_read<AlleleUnitLinkLaArgs>(ctx, "k_phase_allele_unit_links_la", k_phase_allele_unit_links_la, a);
         else launch_per_read<AlleleUnitLinkArgs>(ctx, "k_phase_allele_unit_links", k_phase_allele_unit_links, a);
     });
@@ -1531,11 +1537,38 @@ int c3r_get_hap_realign(c3r_ctx *ctx, int *overhang) {
     return C3R_OK;
 }
 
-// The rule `realign` of include/c3r.h for one read at one site on the host: the serial walk finds the M op of the normalised CIGAR that
-// holds the anchor, as walk_sites does, and hap_observe_ra — the function the four _ra kernels call — decides there.
+int c3r_set_hap_realign_spliced(c3r_ctx *ctx, int on) {
+    if (!ctx) return C3R_EINVAL;
+    if (on != 0 && on != 1) return fail(ctx, C3R_EINVAL, "c3r_set_hap_realign_spliced: %d is neither 0 nor 1", on);
+    const bool want = on != 0;
+    if (want == ctx->hap_rs) return C3R_OK;
+    const bool retag = ctx->hap_ra > 0 && ctx->phase_alleles && ctx->n_reads > 0;       // the tags on the device are those of the other window
+    if (retag && ctx->ref_len == 0)
+        return fail(ctx, C3R_EINVAL, "c3r_set_hap_realign_spliced: an allele table is set and reads are loaded, and no reference is set (c3r_set_reference)");
+    ctx->hap_rs = want;
+    if (!retag) return C3R_OK;
+    ctx->last_scan_pruned = false;
+    ctx->host_cache.reset();
+    return ::refilter(ctx);
+}
+
+int c3r_get_hap_realign_spliced(c3r_ctx *ctx, int *on) {
+    if (!ctx) return C3R_EINVAL;
+    if (on) *on = ctx->hap_rs ? 1 : 0;
+    return C3R_OK;
+}
+
+// The rules `realign` and `realign_spliced` of include/c3r.h for one read at one site on the host: the serial walk finds the M op of the
+// normalised CIGAR that holds the anchor, as walk_sites does, and hap_observe_ra / hap_observe_rs — the functions the _ra and the _rs
+// kernels call — decide there.
 int c3r_hap_realign_column(const c3r_hap_site_t *site, const uint8_t *ins_pool, int64_t ref_start, const char *ref, int64_t ref_len, const c3r_read_t *read,
                            const uint32_t *cigars, const uint8_t *seq4, int overhang, int *column, int *realigned) {
-    if (!site || !read || !column || ref_len < 0 || ref_start < 1 || (ref_len && !ref) || (read->n_cigar && !cigars) || (read->l_seq && !seq4) || overhang < 0 ||
+    return c3r_hap_realign_column_spliced(site, ins_pool, ref_start, ref, ref_len, read, cigars, seq4, overhang, 0, column, realigned);
+}
+
+int c3r_hap_realign_column_spliced(const c3r_hap_site_t *site, const uint8_t *ins_pool, int64_t ref_start, const char *ref, int64_t ref_len, const c3r_read_t *read,
+                                   const uint32_t *cigars, const uint8_t *seq4, int overhang, int spliced, int *column, int *realigned) {
+    if (!site || (spliced != 0 && spliced != 1) || !read || !column || ref_len < 0 || ref_start < 1 || (ref_len && !ref) || (read->n_cigar && !cigars) || (read->l_seq && !seq4) || overhang < 0 ||
         overhang > (int)RA_MAX_W || site->pos < 1)
         return C3R_EINVAL;
     const c3r_hap_allele_t *al[2] = {&site->a, &site->b};
@@ -1563,7 +1596,8 @@ int c3r_hap_realign_column(const c3r_hap_site_t *site, const uint8_t *ins_pool, 
         if (dd < 0 || dd >= (long long)len) return;
         const unsigned long long q = (unsigned long long)y + (unsigned long long)dd;
         if (q >= ri.l_seq) return;
-        col = hap_observe_ra(e, ri, rseq, ins_pool, R, (uint32_t)overhang, q, dd == (long long)len - 1, (unsigned long long)y + len, cx, &ra);
+        col = spliced ? hap_observe_rs(e, ri, rseq, ins_pool, R, (uint32_t)overhang, q, dd == (long long)len - 1, (unsigned long long)y + len, cx, &ra)
+                      : hap_observe_ra(e, ri, rseq, ins_pool, R, (uint32_t)overhang, q, dd == (long long)len - 1, (unsigned long long)y + len, cx, &ra);
     });
     if (err) return C3R_EINVAL;
     *column = (int)col;

@@ -98,4 +98,11 @@ __global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts_ra(const Hap
     });
 }
 
+// The same across splice junctions (c3r_set_hap_realign_spliced): hap_observe_rs, the _ra kernel's arguments.
+__global__ __launch_bounds__(PREP_THREADS) void k_hap_allele_counts_rs(const HapAlleleRaArgs a) {
+    hap_count_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        return hap_observe_rs(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
+    });
+}
+
 }  // namespace c3r

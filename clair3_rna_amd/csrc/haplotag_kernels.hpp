@@ -25,7 +25,7 @@
 //
 // The pieces that every kernel which holds reads against a sorted site table shares are here as well (hapcount_kernels.hpp and
 // phase_kernels.hpp include this file): ReadArgs, GroupAt, read_sites, walk_sites, hap_nibble, snv_column, hap_observe, hap_observe_la,
-// hap_observe_ra.
+// hap_observe_ra, hap_observe_rs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -240,6 +240,16 @@ __host__ __device__ __forceinline__ uint32_t hap_observe_ra(const c3r_hap_site_t
     if (realigned) *realigned = ra;
     return ra ? col : hap_observe(e, rseq, R.l_seq, pool, q, last, iq, cx);
 }
+// The same across splice junctions (c3r_set_hap_realign_spliced; the rule `realign_spliced` of include/c3r.h, restated by
+// tests/realignspliceref.py): ra_column_spliced in ra_column's place — two scans of the raw CIGAR per site in the place of one.
+template <class Ref>
+__host__ __device__ __forceinline__ uint32_t hap_observe_rs(const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, const uint8_t *pool, const Ref &ref, uint32_t overhang,
+                                                            unsigned long long q, bool last, unsigned long long iq, const OpCtx &cx, bool *realigned = nullptr) {
+    bool ra;
+    const uint32_t col = ra_column_spliced(e, pool, ref, R.cig, R.n_cig, (long long)R.pos, R.l_seq, rseq, overhang, ra);
+    if (realigned) *realigned = ra;
+    return ra ? col : hap_observe(e, rseq, R.l_seq, pool, q, last, iq, cx);
+}
 
 // ---- the tags ---------------------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t HAP_NONE = 0xffffffffu;    // no phase set (ps is an int32 >= 0)
@@ -444,6 +454,16 @@ C3R_HAPLOTAG_KERNELS(k_haplotag_alleles_ra, HapAlleleTagRaArgs,
         const uint8_t *rseq = a.seq + R.seq_off;
         return hap_walk_alleles<Tally>(R, gl, serial, a, lo, hi, cur, qual, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
             return hap_observe_ra(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
+        });
+    });
+)
+
+// The same across splice junctions (c3r_set_hap_realign_spliced): hap_observe_rs, the _ra kernels' arguments.
+C3R_HAPLOTAG_KERNELS(k_haplotag_alleles_rs, HapAlleleTagRaArgs,
+    hap_tag_read<Tally>(a, true, [&](const ReadInfo &R, int gl, bool serial, int lo, int hi, uint32_t cur) __attribute__((always_inline)) {
+        const uint8_t *rseq = a.seq + R.seq_off;
+        return hap_walk_alleles<Tally>(R, gl, serial, a, lo, hi, cur, qual, [&](const c3r_hap_site_t &e, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+            return hap_observe_rs(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
         });
     });
 )

@@ -141,6 +141,14 @@ __global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_links_ra(const Al
     });
 }
 
+// The same across splice junctions (c3r_set_hap_realign_spliced): hap_observe_rs, the _ra kernel's arguments.
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_links_rs(const AlleleLinkRaArgs a) {
+    phase_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe_rs(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
+        return al < 2u ? al : 2u;
+    });
+}
+
 // ---- k_phase_unit_links: the link table of the block-merge stage (c3r_phase_unit_links; the rule is in include/c3r.h, restated by
 // tests/phasemergeref.py).  The units are the blocks the chain left (unit_of[s]: the unit of table site s, -1 for a singleton), and a read
 // observes a unit with the majority of its sites' votes there: haplotype 1 / 2, nothing on a tie.
@@ -275,6 +283,14 @@ struct AlleleUnitLinkRaArgs : AlleleUnitLinkLaArgs { uint32_t overhang; };
 __global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_unit_links_ra(const AlleleUnitLinkRaArgs a) {
     phase_unit_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
         const uint32_t al = hap_observe_ra(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
+        return al < 2u ? al : 2u;
+    }, [](const c3r_hap_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.reserved[0]; });
+}
+
+// The same across splice junctions (c3r_set_hap_realign_spliced).
+__global__ __launch_bounds__(PREP_THREADS) void k_phase_allele_unit_links_rs(const AlleleUnitLinkRaArgs a) {
+    phase_unit_links_read(a, true, [&](const c3r_hap_site_t &e, const ReadInfo &R, const uint8_t *rseq, unsigned long long q, bool, bool last, unsigned long long iq, const OpCtx &cx) __attribute__((always_inline)) {
+        const uint32_t al = hap_observe_rs(e, R, rseq, a.pool, a.ref, a.overhang, q, last, iq, cx);
         return al < 2u ? al : 2u;
     }, [](const c3r_hap_site_t &e) __attribute__((always_inline)) { return (uint32_t)e.reserved[0]; });
 }

@@ -2,7 +2,9 @@
 // reference position to a query offset of a read, the two haplotype strings of a site, and the global unit-cost edit distance of the read's
 // window to each.  Included by haplotag_kernels.hpp (hap_observe_ra: the four _ra kernels) and, through it, by c3r_lib.hip
 // (c3r_hap_realign_column: the same functions on the host, no context and no device).  tests/realignref.py restates the rule on its own:
-// a textbook DP and a CIGAR map of its own.
+// a textbook DP and a CIGAR map of its own.  At the end of the file: the rule `realign_spliced` (c3r_set_hap_realign_spliced), whose window
+// crosses an N op — new functions beside the old ones (hap_observe_rs: the five _rs kernels; c3r_hap_realign_column_spliced), which keep
+// their code; tests/realignspliceref.py restates it.
 //
 // What it replaces: the realignment of a read's local window against the two alleles that stands behind `whatshap phase` and `whatshap
 // haplotag` in the reference flow (run_clair3_rna:749-794) — here with unit costs, no quality weights and no affine gaps.
@@ -154,6 +156,114 @@ C3R_RA_FN uint32_t ra_column(const c3r_hap_site_t &e, const uint8_t *pool, const
     const RaHap ha = ra_haplotype(ref, e.a, pool, s, p0, t), hb = ra_haplotype(ref, e.b, pool, s, p0, t);
     uint32_t dA, dB;
     ra_distances(ha, hb, rseq, sp.qs, (uint32_t)(sp.qt - sp.qs), dA, dB);
+    return dA < dB ? 0u : dB < dA ? 1u : RA_NOTHING;
+}
+
+// ---- the same across splice junctions (the rule `realign_spliced` of include/c3r.h; c3r_set_hap_realign_spliced) -------------------------
+// The window is counted in the read's SPLICED positions x_0 < x_1 < ... — the reference positions under its M-like and D ops, never those
+// under an N — and not in reference positions: ks = k0 - W and kt = k0 + 1 + D + W around the anchor's index k0.  An N consumes no query
+// base, so the read's window stays one stretch of SEQ; only the reference side follows the read's own splicing, for both strings alike.
+// tests/realignspliceref.py restates the rule on its own.  The simple form: two forward scans of the raw CIGAR in the lane that holds the
+// M op — the first for k0, the read's number of spliced positions and the core test, the second for q(x_ks), q(x_kt) and the flank letters.
+
+// Scan 1.  k0: the spliced index of p0; n: the spliced positions of the whole read; ok: p0 lies under an M or a D and no N op holds a
+// position of the core [p0, p0 + D] (what the read has of it: that it reaches p0 + D is kt < n's to say).
+struct RaAnchor { unsigned long long k0, n; bool ok; };
+C3R_RA_FN RaAnchor ra_spliced_anchor(const uint32_t *cig, uint32_t n_cig, long long pos, long long p0, uint32_t D) {
+    RaAnchor r;
+    r.k0 = 0; r.n = 0; r.ok = false;
+    if (pos > p0) return r;
+    long long x = pos;
+    unsigned long long c = 0;
+    bool have = false, cut = false;
+    for (uint32_t k = 0; k < n_cig; ++k) {
+        const uint32_t w = cig[k], raw = w & 15u, len = w >> 4;
+        if (len == 0) continue;
+        if (raw == C3R_CIG_N) {
+            cut = cut || (x <= p0 + (long long)D && x + (long long)len > p0);      // an N op touches the core
+            x += len;
+        } else if (raw == C3R_CIG_M || raw == C3R_CIG_D || raw == C3R_CIG_EQ || raw == C3R_CIG_X) {
+            const long long xe = x + (long long)len;
+            if (!have && p0 < xe) { r.k0 = c + (unsigned long long)(p0 - x); have = true; }
+            x = xe;
+            c += len;
+        }
+    }
+    r.n = c;
+    r.ok = have && !cut;
+    return r;
+}
+
+// Scan 2.  q(x_ks) and q(x_kt), the letters of the left flank x_ks .. x_(k0-1) and of the tail x_kd .. x_(kt-1) (kd = k0 + 1 + D: what both
+// strings share behind the core), and whether all those letters are A, C, G or T of the slice.  Introns are never read.  ks < k0 < kd <= kt
+// and kt is an index of the read (the caller has tested it), so both offsets are found.
+struct RaFlanks { RaHap left, tail; unsigned long long qs, qt; bool ref_ok; };
+template <class Ref>
+C3R_RA_FN RaFlanks ra_spliced_flanks(const Ref &ref, const uint32_t *cig, uint32_t n_cig, long long pos, unsigned long long ks, unsigned long long k0, unsigned long long kd,
+                                     unsigned long long kt) {
+    RaFlanks f;
+    f.left.clear(); f.tail.clear(); f.qs = 0; f.qt = 0; f.ref_ok = true;
+    long long x = pos;
+    unsigned long long y = 0, c = 0;
+    for (uint32_t k = 0; k < n_cig; ++k) {
+        const uint32_t w = cig[k], raw = w & 15u, len = w >> 4;
+        const bool m = raw == C3R_CIG_M || raw == C3R_CIG_EQ || raw == C3R_CIG_X;
+        if (len == 0) continue;
+        if (raw == C3R_CIG_N) x += len;
+        else if (m || raw == C3R_CIG_D) {
+            const unsigned long long ce = c + len;
+            if (ks >= c && ks < ce) f.qs = m ? y + (ks - c) : y;
+            for (unsigned long long i = ks > c ? ks : c; i < (k0 < ce ? k0 : ce); ++i) {
+                const uint32_t code = ref.code(x + (long long)(i - c));
+                f.ref_ok = f.ref_ok && code != 0u;
+                f.left.push(code);
+            }
+            for (unsigned long long i = kd > c ? kd : c; i < (kt < ce ? kt : ce); ++i) {
+                const uint32_t code = ref.code(x + (long long)(i - c));
+                f.ref_ok = f.ref_ok && code != 0u;
+                f.tail.push(code);
+            }
+            if (kt < ce) { f.qt = m ? y + (kt - c) : y; return f; }
+            x += len;
+            c = ce;
+            if (m) y += len;
+        } else if (raw == C3R_CIG_I || raw == C3R_CIG_S) y += len;
+    }
+    return f;
+}
+
+// left + X.base + X.ins + ref[p0 + 1 + X.del, p0 + 1 + D) + tail: the core holds no N, so its positions are consecutive
+template <class Ref>
+C3R_RA_FN RaHap ra_haplotype_spliced(const Ref &ref, const c3r_hap_allele_t &al, const uint8_t *pool, const RaHap &left, const RaHap &tail, long long p0, uint32_t D) {
+    RaHap h = left;
+    h.push(al.base);
+    if (al.kind == C3R_HAP_EV_INS)
+        for (uint32_t j = 0; j < al.len; ++j) h.push(ra_nibble(pool, (unsigned long long)al.ins_off + j));
+    for (long long p = p0 + 1 + (al.kind == C3R_HAP_EV_DEL ? (long long)al.len : 0ll); p < p0 + 1 + (long long)D; ++p) h.push(ref.code(p));
+    const uint32_t sh = h.n & 63u;                                      // (tail.n = W >= 1 and the whole fits: h.n <= 63 here)
+    h.ma |= tail.ma << sh; h.mc |= tail.mc << sh; h.mg |= tail.mg << sh; h.mt |= tail.mt << sh;
+    h.n += tail.n;
+    return h;
+}
+
+// ra_column under realign_spliced: the same three results.
+template <class Ref>
+C3R_RA_FN uint32_t ra_column_spliced(const c3r_hap_site_t &e, const uint8_t *pool, const Ref &ref, const uint32_t *cig, uint32_t n_cig, long long read_pos, uint32_t l_seq,
+                                     const uint8_t *rseq, uint32_t W, bool &realigned) {
+    realigned = false;
+    const RaWindow w = ra_window(e, W);
+    if (W == 0u || !w.fits) return RA_NOTHING;
+    const long long p0 = (long long)e.pos - 1;
+    const RaAnchor an = ra_spliced_anchor(cig, n_cig, read_pos, p0, w.D);
+    const unsigned long long kd = an.k0 + 1ull + w.D, kt = kd + W;
+    if (!an.ok || an.k0 < (unsigned long long)W || kt >= an.n) return RA_NOTHING;
+    if (!ra_ref_ok(ref, p0, p0 + 1 + (long long)w.D)) return RA_NOTHING;
+    const RaFlanks f = ra_spliced_flanks(ref, cig, n_cig, read_pos, an.k0 - W, an.k0, kd, kt);
+    if (!f.ref_ok || f.qt > (unsigned long long)l_seq || f.qt - f.qs > (unsigned long long)RA_MAX_LEN) return RA_NOTHING;
+    realigned = true;
+    const RaHap ha = ra_haplotype_spliced(ref, e.a, pool, f.left, f.tail, p0, w.D), hb = ra_haplotype_spliced(ref, e.b, pool, f.left, f.tail, p0, w.D);
+    uint32_t dA, dB;
+    ra_distances(ha, hb, rseq, f.qs, (uint32_t)(f.qt - f.qs), dA, dB);
     return dA < dB ? 0u : dB < dA ? 1u : RA_NOTHING;
 }
 

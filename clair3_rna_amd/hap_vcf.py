@@ -197,7 +197,7 @@ def Run(args, log=None):
                 eng.set_reference(*ref_of(ctg))
                 eng.set_hap_left_align(True)
             if realign:
-                phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
+                phasing.apply_hap_realign(eng, realign, realign_ref(ctg), phasing.hap_realign_spliced_arg(args))
             source.apply(eng, table)
             phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log, **(dict(weights=True) if weights else {}))
             if indels:

@@ -131,7 +131,7 @@ def Run(args, log=None):
                     if ref_of is not None:                         # (the whole contig: it covers every read)
                         eng.set_reference(*ref_of(ctg))
                     if realign:
-                        phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
+                        phasing.apply_hap_realign(eng, realign, realign_ref(ctg), phasing.hap_realign_spliced_arg(args))
                     source.apply(eng, table)
                     phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log, **(dict(weights=True) if weights else {}))
                     hp, ps = eng.haplotags()[0], eng.read_phase_sets()

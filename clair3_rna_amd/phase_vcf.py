@@ -31,7 +31,8 @@ not been measured.
 --hap_realign [W] (default off; needs --ref_fn; excludes --left_align_indels) lifts "no realignment": every read's window of W reference bases
 around a site is compared with the site's two alleles and the smaller unit-cost edit distance decides (include/c3r.h: c3r_set_hap_realign;
 phasing.apply_hap_realign).  Without --indels the SNV candidates go through the allele calls, which give the SNV calls' results bit for bit
-with the switch off, so only the observation changes.  No quality weights, no affine gaps; a window stops at a splice junction.
+with the switch off, so only the observation changes.  No quality weights, no affine gaps; a window stops at a splice junction
+unless --hap_realign_spliced is given (include/c3r.h: c3r_set_hap_realign_spliced): then it is counted in the read's own spliced positions.
 """
 import argparse
 import os
@@ -119,7 +120,7 @@ def Run(args, log=None):
                 eng.set_reference(*ref_of(ctg))
                 eng.set_hap_left_align(True)
             if realign:
-                phasing.apply_hap_realign(eng, realign, realign_ref(ctg))
+                phasing.apply_hap_realign(eng, realign, realign_ref(ctg), phasing.hap_realign_spliced_arg(args))
             phasing.load_reads_min_bq(eng, rs, min_bq, ctg, log)
             fn = os.path.join(args.output_dir, "phased_%s.vcf.gz" % ctg)
             if indels:

@@ -313,8 +313,12 @@ def add_hap_realign_flag(add):
     add("--hap_realign", type=int, nargs="?", const=HAP_REALIGN_DEFAULT, default=0, metavar="W",
         help="realign every read's window of W reference bases around a site against the site's two alleles before deciding which one the read "
              "shows (include/c3r.h: c3r_set_hap_realign; W = 1 .. 16, %d without a value, default off; needs --ref_fn, excludes "
-             "--left_align_indels).  Unit costs, no quality weights, no affine gaps; a window stops at a splice junction; agreement with "
-             "whatshap is not measured" % HAP_REALIGN_DEFAULT)
+             "--left_align_indels).  Unit costs, no quality weights, no affine gaps; a window stops at a splice junction unless "
+             "--hap_realign_spliced is given; agreement with whatshap is not measured" % HAP_REALIGN_DEFAULT)
+    add("--hap_realign_spliced", action="store_true",
+        help="with --hap_realign: count a read's window in the read's own spliced positions, so that it crosses an N op and follows the read's "
+             "splicing on the reference side (include/c3r.h: c3r_set_hap_realign_spliced; default off).  A junction inside a site's core "
+             "still falls back to the CIGAR-position allele")
 
 
 def hap_realign_arg(args, has_consumer=True, needs=""):
@@ -326,6 +330,8 @@ def hap_realign_arg(args, has_consumer=True, needs=""):
     from . import io
     w = getattr(args, "hap_realign", 0)
     w = 0 if w is None else int(w)
+    if w == 0 and hap_realign_spliced_arg(args):
+        sys.exit("[ERROR] --hap_realign_spliced needs --hap_realign (it says how the window of --hap_realign is counted)")
     if w == 0:
         return 0, None
     if not 1 <= w <= 16:
@@ -342,6 +348,11 @@ def hap_realign_arg(args, has_consumer=True, needs=""):
     return w, io.contig_reference(ref_fn)
 
 
+def hap_realign_spliced_arg(args):
+    """A driver's --hap_realign_spliced (False when the parser has none); hap_realign_arg refuses it without --hap_realign."""
+    return bool(getattr(args, "hap_realign_spliced", False))
+
+
 def snv_sites_as_alleles(sites):
     """A PHASE_SITE_DTYPE table as the allele table that says the same (include/c3r.h: on REF-and-one-SNV sites the allele calls give the
     SNV calls' results bit for bit with the switches off): (HAP_SITE_DTYPE array with A = REF and B = ALT, uint8 h1).  Under --hap_realign
@@ -354,12 +365,15 @@ def snv_sites_as_alleles(sites):
     return out, np.ascontiguousarray(sites["h1"], dtype=np.uint8)
 
 
-def apply_hap_realign(eng, w, ref, **how):
-    """The one place where a driver's engine meets --hap_realign (include/c3r.h: c3r_set_hap_realign), before the contig's table and
-    reads: the reference slice that covers every read of the contig (`ref`: (1-based start, letters); `how`: Engine.set_reference's
-    options), then the switch."""
+def apply_hap_realign(eng, w, ref, spliced=False, **how):
+    """The one place where a driver's engine meets --hap_realign and --hap_realign_spliced (include/c3r.h: c3r_set_hap_realign,
+    c3r_set_hap_realign_spliced), before the contig's table and reads: the reference slice that covers every read of the contig (`ref`:
+    (1-based start, letters); `how`: Engine.set_reference's options), then the switches.  Without --hap_realign_spliced the engine's
+    second switch is never touched."""
     if w:
         eng.set_reference(*ref, **how)
+        if spliced:
+            eng.set_hap_realign_spliced(True)
         eng.set_hap_realign(w)
 
 

@@ -406,11 +406,11 @@ int c3r_hap_left_align_sites(const c3r_hap_site_t *sites, int64_t n, const uint8
  *  ends, a splice junction within W, a long allele, a site near the slice's edge): the set of observed (read, site) pairs never shrinks
  *  by anything but ties.
  * The result depends neither on the walk a read takes nor on where inside (s, t) the CIGAR places its indels.
- * What remains: the window stops at an N; there are no quality weights (c3r_set_hap_min_bq composes by construction: a masked base matches
+ * What remains: the window stops at an N (c3r_set_hap_realign_spliced, below, lifts it); there are no quality weights (c3r_set_hap_min_bq composes by construction: a masked base matches
  *  nothing) and no affine gaps; agreement with whatshap is not measured.  A table row at a different but equivalent placement has another
  *  window: c3r_hap_left_align_sites stays useful for rows (it does not look at reads or at this switch).
  *
- * c3r_set_hap_realign(ctx, overhang): default 0; C3R_EINVAL outside 0 .. 16.  While above 0 the four calls run k_*_ra (the same launches,
+ * c3r_set_hap_realign(ctx, overhang): default 0; C3R_EINVAL outside 0 .. 16.  While above 0 the four calls run k_*_ra — k_*_rs under c3r_set_hap_realign_spliced, below — (the same launches,
  * one kernel each, hap_observe_ra in hap_observe's place, no atomics of their own) against the slice of c3r_set_reference that is current
  * when they run, and return C3R_EINVAL with a message when no reference is set (c3r_set_phase_alleles with n = 0 still clears).  Changing
  * the value with an allele table set and reads loaded tags the reads again (C3R_EINVAL, and the value stays, when that needs a reference
@@ -427,6 +427,49 @@ int c3r_set_hap_realign(c3r_ctx *ctx, int overhang);
 int c3r_get_hap_realign(c3r_ctx *ctx, int *overhang);
 int c3r_hap_realign_column(const c3r_hap_site_t *site, const uint8_t *ins_pool, int64_t ref_start, const char *ref, int64_t ref_len, const c3r_read_t *read,
                            const uint32_t *cigars, const uint8_t *seq4, int overhang, int *column, int *realigned);
+/* Allele realignment across splice junctions, for the same four calls.  Opt-in (--hap_realign_spliced beside --hap_realign [W]); switched
+ * off, every path, launch and output byte is what the contracts above say.  It lifts `realign`'s "the window stops at an N": exons are
+ * short, so a site within W bases of an exon's edge is seen by every spliced read through the CIGAR-position rule — just where aligners
+ * misplace bases most often.  An N op consumes no query base, so the read's window stays one stretch of SEQ across a junction; only the
+ * reference side has to follow the read's own splicing.  Both haplotype strings follow the same splicing, so a junction the aligner put a
+ * base or two off costs both strings the same and cancels in dA against dB.  This is where the rule is stated; csrc/realign.hpp
+ * (ra_column_spliced) with csrc/haplotag_kernels.hpp (hap_observe_rs), c3r_hap_realign_column_spliced and tests/realignspliceref.py
+ * restate it.
+ *
+ * realign_spliced, in force only while this switch is on AND c3r_set_hap_realign is above 0.  W, D, I, p0 and q(p) are `realign`'s.
+ * Spliced positions of a read: the reference positions under an M-like or a D op of its raw CIGAR, in increasing order x_0 < x_1 < ...
+ *  Positions under an N are not among them.  H, P and empty ops consume nothing, = and X are M.
+ * Window.  k0 is the index with x_k0 = p0 (the anchor must lie under an M op at a query offset below l_seq, as ever: otherwise there is
+ *  nothing to observe).  The read is realigned at the site when all of these hold:
+ *   x_(k0+j) = p0 + j for j = 0 .. D: no N holds a position of the site's core [p0, p0 + D];
+ *   ks = k0 - W >= 0;
+ *   kt = k0 + 1 + D + W is an index of the read (`realign`'s t < read.end);
+ *   2W + 1 + D + I <= 64;
+ *   every reference base that the strings use — the positions x_ks .. x_(kt-1), core included as in `realign` — lies inside the slice of
+ *    c3r_set_reference and is A, C, G or T.  Introns are never read, so only those positions need the slice;
+ *   q(x_kt) <= l_seq and m = q(x_kt) - q(x_ks) <= 64.
+ *  Haplotype string of allele X = ref[x_ks .. x_(k0-1)] + X.base + X.ins + ref[x_(k0+1+X.del) .. x_(kt-1)].
+ *  The read's window is the m codes at q(x_ks) .. q(x_kt) - 1.  The distances, the tie (no observation, never column 2) and the masked
+ *  base that equals nothing are `realign`'s.  An insertion directly before x_ks is outside the window; one directly before x_kt is inside,
+ *  on whichever side of an N the CIGAR lists it.
+ * Otherwise: where the read is not realigned at the site the observation is c3r_hap_allele_counts', unchanged.
+ * Consequences.  A read with no N in [s, t] gets exactly `realign`'s result (x_ks = s and x_kt = t).  The set of realigned (read, site)
+ *  pairs never shrinks against `realign`.  The result depends neither on the walk a read takes nor on where inside the window the CIGAR
+ *  places its indels, nor on the introns' lengths or letters: cut the introns out of reference, sites and reads and `realign` gives the
+ *  same columns.
+ * What remains: an N inside the core falls back; left-align does not cross an N; the rest of `realign`'s list.
+ *
+ * c3r_set_hap_realign_spliced(ctx, on): default 0; anything but 0 or 1 is C3R_EINVAL.  It may be set at any time and has effect only
+ * while the overhang is above 0: then the four calls run k_*_rs (the same launches and arguments as k_*_ra, hap_observe_rs in
+ * hap_observe_ra's place, no atomics of their own).  Flipping it with the overhang above 0, an allele table set and reads loaded tags the
+ * reads again, as a new overhang does.  A refusal leaves the context as it was.  Left-align keeps excluding realign.
+ * c3r_get_hap_realign_spliced: the value.
+ * c3r_hap_realign_column_spliced: c3r_hap_realign_column with `spliced` (0 or 1, else C3R_EINVAL) choosing the rule; host code, no
+ * context and no device.  c3r_hap_realign_column is this call with spliced = 0 and returns what it returned. */
+int c3r_set_hap_realign_spliced(c3r_ctx *ctx, int on);
+int c3r_get_hap_realign_spliced(c3r_ctx *ctx, int *on);
+int c3r_hap_realign_column_spliced(const c3r_hap_site_t *site, const uint8_t *ins_pool, int64_t ref_start, const char *ref, int64_t ref_len, const c3r_read_t *read,
+                                   const uint32_t *cigars, const uint8_t *seq4, int overhang, int spliced, int *column, int *realigned);
 /* A base-quality threshold for the twelve kernels that hold the loaded reads against a site table: k_haplotag, k_hap_counts, k_phase_links,
  * k_phase_unit_links, k_haplotag_alleles, k_hap_allele_counts, k_phase_allele_links, k_phase_allele_unit_links and the four _la
  * instantiations — the tagging of c3r_set_phase_sites / c3r_set_phase_alleles / c3r_load_reads, c3r_hap_counts, c3r_hap_allele_counts,
