@@ -54,6 +54,9 @@ start, at an N or another indel; there is still no realignment and there are no 
 `--haplotagged_bam` (same conditions as --phase_output, and combinable with it) adds the step the reference's "Haplotag the BAM" commands stand
 for: haplotag_bam writes <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai for the contigs the run processed — every record of the
 contig, with the HP / PS tags the GPU computed from the phase table the second pass read; without the flag nothing changes.
+`--hap_expression_bed BED` (same conditions, combinable with both) adds one more step behind them: hap_expr counts the reads of each haplotype
+and phase set over every interval of BED on the GPU (include/c3r.h: the rule `hap_regions`) into <prefix>_enable_phasing_hap_expression.tsv,
+with the tagging flags haplotag_bam gets; `--hap_expression_stranded same|reverse` is handed over as --stranded; without the flag nothing changes.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
@@ -244,6 +247,13 @@ def build_parser():
       help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin: after the passes, write the haplotagged BAM of every "
            "processed contig with the tags the GPU computed to <output_dir>/tmp/phased_output/phased_bam/<ctg>.bam + .bai (haplotag_bam: the "
            "files the reference's `whatshap haplotag` + `samtools index` step leaves).  One process only.  Off: no file more and no byte different")
+    a("--hap_expression_bed", type=str, default=None, metavar="BED",
+      help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin (combinable with --phase_output and --haplotagged_bam): after "
+           "the passes, count the reads of each haplotype and phase set over every interval of BED (exons, genes) on the GPU, with the tags the "
+           "30-channel pass called with, into <prefix>_enable_phasing_hap_expression.tsv (hap_expr: allele-specific expression; a read counts in "
+           "every region it overlaps, no gene-level union, no statistics).  One process only.  Off: no file more and no byte different")
+    from . import hap_expr as _hap_expr
+    _hap_expr.add_stranded_flag(a, "--hap_expression_stranded")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else LOCAL_RANK under torch.distributed.run, else 0")
     a("--gpu_precision", type=str, default=_env_precision(), choices=["f32", "f16x3", "f16+f8", "auto"],
       help="network arithmetic (c3r_set_precision): f16x3 = fp32-equivalent split-f16 (default); auto = the faster fp8-corrected path where a "
@@ -430,14 +440,21 @@ def _plan(args):
              "--phased_vcf_fn ... --output_fn ...`"),
             ("--haplotagged_bam", args.haplotagged_bam, "it writes the tags the 30-channel pass called with",
              "run the pass without it and then `python -m clair3_rna_amd.haplotag_bam --bam_fn ... --phased_vcf_fn ... --output_dir "
-             "<output_dir>/tmp/phased_output/phased_bam`")):
+             "<output_dir>/tmp/phased_output/phased_bam`"),
+            ("--hap_expression_bed", bool(getattr(args, "hap_expression_bed", None)), "it counts reads by the tags the 30-channel pass called with",
+             "run the pass without it and then `python -m clair3_rna_amd.hap_expr --bam_fn ... --phased_vcf_fn ... --regions_bed_fn ... "
+             "--output_fn ...`")):
         if on:
             if not phased:
                 sys.exit("[ERROR] %s needs --enable_phasing_model (%s)" % (flag, why))
             if not builtin and not args.phased_vcf_fn:
                 sys.exit("[ERROR] %s needs a phased VCF to haplotag the reads from: --phased_vcf_fn or --phasing builtin" % flag)
             one_process(flag, instead)
-    left_align = bool(getattr(args, "left_align_indels", False))
+    if getattr(args, "hap_expression_bed", None) and not os.path.isfile(args.hap_expression_bed):
+        sys.exit("[ERROR] file %s not found" % args.hap_expression_bed)
+    if getattr(args, "hap_expression_stranded", "no") != "no" and not getattr(args, "hap_expression_bed", None):
+        sys.exit("[ERROR] --hap_expression_stranded belongs to --hap_expression_bed (it chooses the strand of the reads counted there): it needs --hap_expression_bed")
+    left_align =bool(getattr(args, "left_align_indels", False))
     if left_align and not (args.phase_indels or args.haplotag_indels or args.phasing_indels):
         sys.exit("[ERROR] --left_align_indels needs one of --phase_indels, --haplotag_indels, --phasing_indels (it left-aligns the indels those steps read)")
     la = ["--left_align_indels", "--ref_fn", args.ref_fn] if left_align else []
@@ -509,6 +526,11 @@ def _plan(args):
         bam_dir = os.path.join(args.output_dir, "tmp", "phased_output", "phased_bam")
         steps += [_Step("clear", (bam_dir, lambda name: name.endswith(".bam") or name.endswith(".bam.bai")), stem + ext),
                   _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext)]
+    if getattr(args, "hap_expression_bed", None):
+        # the tagging flags haplotag_bam gets: the counts are by the tags of the pass; the contigs the passes processed are added when the step runs
+        steps.append(_Step("hap_expr", ["--phased_vcf_fn", source, "--regions_bed_fn", args.hap_expression_bed, "--output_fn", stem + "_hap_expression.tsv",
+                                        "--min_mq", str(args.min_mq), "--stranded", args.hap_expression_stranded]
+                           + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext))
     return steps
 
 
@@ -526,7 +548,7 @@ def Run(args, log=None):
             os.makedirs(step.handed[0], exist_ok=True)
         else:
             argv = ["--bam_fn", _indexed_bam(args)] + step.handed
-            if step.name == "haplotag_bam":
+            if step.name in ("haplotag_bam", "hap_expr"):
                 contigs, _ = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn),
                                          args.chunk_size, args.chunk_num)
                 argv += ["--ctg_name", ",".join(contigs)]

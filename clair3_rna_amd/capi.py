@@ -23,6 +23,10 @@ HAP_EV_NONE, HAP_EV_INS, HAP_EV_DEL = 0, 1, 2
 HAP_SITE_DTYPE = np.dtype([("pos", "<i4"), ("ps", "<i4"), ("base_matters", "u1"), ("event_matters", "u1"), ("reserved", "u1", (6,)),
                            ("a_base", "u1"), ("a_kind", "u1"), ("a_len", "<u2"), ("a_ins_off", "<u4"),
                            ("b_base", "u1"), ("b_kind", "u1"), ("b_len", "<u2"), ("b_ins_off", "<u4")], align=True)
+# c3r_hap_region_t: one interval of c3r_hap_region_counts (0-based, half-open; strand 0 none, 1 +, 2 -) and where its rows start
+HAP_REGION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("row_off", "<i4"), ("strand", "u1"), ("reserved", "u1", (3,))], align=True)
+HAP_REGION_MAX_BACK = 4096
+assert HAP_REGION_DTYPE.itemsize == 16
 assert SITE_DTYPE.itemsize == 52 and TOKEN_DTYPE.itemsize == 16 and PADINS_DTYPE.itemsize == 24 and PHASE_SITE_DTYPE.itemsize == 12
 assert HAP_SITE_DTYPE.itemsize == 32 and HAP_SITE_DTYPE.fields["a_base"][1] == 16 and HAP_SITE_DTYPE.fields["b_ins_off"][1] == 28
 
@@ -70,7 +74,7 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_pileup_scan", "c3r_pileup_scan_regions", "c3r_batch_begin", "c3r_batch_end", "c3r_batch_count", "c3r_get_tensors", "c3r_get_sites", "c3r_token_count", "c3r_get_tokens", "c3r_get_pad_insertions", "c3r_get_columns",
            "c3r_weight_count", "c3r_load_weights", "c3r_set_precision", "c3r_get_precision", "c3r_get_precision_guard", "c3r_reserve", "c3r_infer", "c3r_get_probs", "c3r_call_rows", "c3r_get_rows", "c3r_rows_begin", "c3r_rows_begin_ex", "c3r_rows_decode", "c3r_rows_get", "c3r_rows_info", "c3r_rows_free", "c3r_decode_text", "c3r_set_profiling", "c3r_reset_kernel_stats",
            "c3r_get_kernel_stats", "c3r_get_scan_counts", "c3r_set_phase_sites", "c3r_get_haplotags", "c3r_phase_links", "c3r_phase_resolve",
-           "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign",
+           "c3r_phase_unit_links", "c3r_phase_merge", "c3r_get_read_phase_sets", "c3r_hap_counts", "c3r_hap_assign", "c3r_hap_region_counts",
            "c3r_hap_allele_counts", "c3r_set_phase_alleles", "c3r_phase_allele_links", "c3r_phase_allele_unit_links",
            "c3r_set_hap_left_align", "c3r_hap_left_align_sites",
            "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq",
@@ -131,6 +135,7 @@ def load_library():
     L.c3r_get_read_phase_sets.argtypes = [vp, vp, i64]
     L.c3r_hap_counts.argtypes = [vp, vp, i64, vp]
     L.c3r_hap_allele_counts.argtypes = [vp, vp, i64, vp, i64, vp]
+    L.c3r_hap_region_counts.argtypes = [vp, vp, i64, vp, i64, C.c_int32, vp, vp]
     L.c3r_phase_allele_links.argtypes = [vp, vp, i64, vp, i64, vp]
     L.c3r_phase_allele_unit_links.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
@@ -468,6 +473,25 @@ class Engine(object):
         counts = np.zeros((len(a), 3, 3), dtype=np.uint32)
         self._chk(self.L.c3r_hap_counts(self.h, _ptr(a), len(a), _ptr(counts)))
         return counts
+
+    def hap_region_counts(self, regions, row_ps, stranded=0):
+        """(region_counts uint32 (n, 2), row_counts uint32 (n_rows, 2)): the loaded reads that pass the current filters, per interval of
+        `regions` (a HAP_REGION_DTYPE array sorted by (start, end); region j's rows are row_ps[row_off[j] : row_off[j + 1]], phase-set numbers
+        strictly increasing inside a region) — region_counts: untagged reads, reads tagged in a set that is none of the region's rows;
+        row_counts: haplotype 1, haplotype 2 of the row's set (c3r_hap_region_counts, the rule `hap_regions`).  A read counts once in every
+        region that one of its M / = / X / D ops overlaps.  stranded: 0 off, 1 same, 2 reverse.  Needs a phase table; leaves tags, table
+        and scans as they are."""
+        a = np.zeros(0, HAP_REGION_DTYPE) if regions is None else np.asarray(regions)
+        if a.dtype != HAP_REGION_DTYPE:
+            raise TypeError("regions must be a capi.HAP_REGION_DTYPE array, got %r" % (a.dtype,))
+        a = np.ascontiguousarray(a)
+        ps = np.ascontiguousarray(np.zeros(0, np.int32) if row_ps is None else row_ps, dtype=np.int32)
+        if ps.ndim != 1:
+            raise TypeError("row_ps must be one-dimensional")
+        region_counts, row_counts = np.zeros((len(a), 2), dtype=np.uint32), np.zeros((len(ps), 2), dtype=np.uint32)
+        self._chk(self.L.c3r_hap_region_counts(self.h, _ptr(a) if len(a) else None, len(a), _ptr(ps) if len(ps) else None, len(ps), int(stranded),
+                                               _ptr(region_counts) if len(a) else None, _ptr(row_counts) if len(ps) else None))
+        return region_counts, row_counts
 
     def hap_allele_counts(self, sites, ins_pool=None):
         """uint32 (n, 3, 3) like hap_counts, for query sites whose two alleles may be SNVs, insertions or deletions (a HAP_SITE_DTYPE array

@@ -29,6 +29,7 @@
 #include "haplotag_kernels.hpp"
 #include "phase_kernels.hpp"
 #include "hapcount_kernels.hpp"
+#include "hapregion_kernels.hpp"
 #include "qual_kernels.hpp"
 #include <sched.h>
 
@@ -183,6 +184,7 @@ struct c3r_ctx {
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
     DevBuf d_hcsites, d_hcounts;
     DevBuf d_hasites, d_hapool;               // c3r_hap_allele_counts: its query sites and the pool of inserted bases (the counts share d_hcounts)
+    DevBuf d_hrregions, d_hrfirst, d_hrps, d_hrcounts;      // c3r_hap_region_counts: its regions, first_open, row_ps and count table, allocated by the first call and kept
     DevBuf d_pasites, d_papool;               // c3r_phase_allele_links / c3r_phase_allele_unit_links: their candidate sites and pool (the links share d_links, the units d_unitof)
 
     // ---- scan state
@@ -911,7 +913,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hrregions, &ctx->d_hrfirst, &ctx->d_hrps, &ctx->d_hrcounts, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_rowctl, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0, cap = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1363,6 +1365,69 @@ int c3r_hap_counts(c3r_ctx *ctx, const c3r_phase_site_t *sites, int64_t n, uint3
         a.sites = (const c3r_phase_site_t *)ctx->d_hcsites.p;
         return (int)C3R_OK;
     });
+}
+
+// The rule `hap_regions` of include/c3r.h: the table's checks, first_open and the bound on the host, then one launch of k_hap_region_counts.
+int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t n, const int32_t *row_ps, int64_t n_rows, int32_t stranded,
+                          uint32_t *region_counts, uint32_t *row_counts) {
+    if (!ctx || n < 0 || n_rows < 0 || (n && (!regions || !region_counts)) || (n_rows && (!row_ps || !row_counts))) return C3R_EINVAL;
+    if (stranded < 0 || stranded > 2) return fail(ctx, C3R_EINVAL, "c3r_hap_region_counts: stranded %d is not 0 (off), 1 (same) or 2 (reverse)", stranded);
+    if (n >= INT32_MAX / 2 || n_rows >= INT32_MAX / 2) return fail(ctx, C3R_EINVAL, "c3r_hap_region_counts: too many regions or rows");
+    if (n == 0 && n_rows != 0) return fail(ctx, C3R_EINVAL, "c3r_hap_region_counts: %lld rows and no region", (long long)n_rows);
+    std::vector<DevHapRegion> dev((size_t)n);
+    std::vector<int32_t> first_open((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+        const c3r_hap_region_t &e = regions[j];
+        if (e.start < 0 || e.start >= e.end) return fail(ctx, C3R_EINVAL, "region %lld: [%d, %d) is not a 0-based half-open interval with start < end", (long long)j, e.start, e.end);
+        if (j > 0 && (e.start < regions[j - 1].start || (e.start == regions[j - 1].start && e.end < regions[j - 1].end)))
+            return fail(ctx, C3R_EINVAL, "region %lld: the table must be sorted by (start, end) ([%d, %d) after [%d, %d))", (long long)j, e.start, e.end, regions[j - 1].start, regions[j - 1].end);
+        if (e.strand > 2 || e.reserved[0] || e.reserved[1] || e.reserved[2]) return fail(ctx, C3R_EINVAL, "region %lld: strand must be 0, 1 or 2 and the reserved bytes 0", (long long)j);
+        if ((j == 0 ? e.row_off != 0 : e.row_off < regions[j - 1].row_off) || (int64_t)e.row_off > n_rows)
+            return fail(ctx, C3R_EINVAL, "region %lld: row_off %d must start at 0, never decrease and stay within the %lld rows", (long long)j, e.row_off, (long long)n_rows);
+        // (the next region's row_off is checked when its turn comes: until then only its use as this region's end has to be safe)
+        const int64_t row_end = j + 1 < n ? std::min<int64_t>(std::max<int64_t>(regions[j + 1].row_off, e.row_off), n_rows) : n_rows;
+        if (row_end - e.row_off >= (1 << 24)) return fail(ctx, C3R_EINVAL, "region %lld: %lld rows are more than a region takes (2^24 - 1)", (long long)j, (long long)(row_end - e.row_off));
+        for (int64_t r = e.row_off; r < row_end; ++r) {
+            if (row_ps[r] < 0) return fail(ctx, C3R_EINVAL, "row %lld (region %lld): phase set %d is negative", (long long)r, (long long)j, row_ps[r]);
+            if (r > e.row_off && row_ps[r] <= row_ps[r - 1])
+                return fail(ctx, C3R_EINVAL, "row %lld (region %lld): phase sets must be strictly increasing inside a region (%d after %d)", (long long)r, (long long)j, row_ps[r], row_ps[r - 1]);
+        }
+        // first_open[j]: starts never decrease, so a region closed at start_(j - 1) stays closed and first_open never decreases either:
+        // on from first_open[j - 1] to the first region whose end lies behind this start (n + the table's length steps in all)
+        int64_t f = j > 0 ? first_open[(size_t)j - 1] : 0;
+        while (f < j && regions[f].end <= e.start) ++f;
+        first_open[(size_t)j] = (int32_t)f;
+        if (j - f > C3R_HAP_REGION_MAX_BACK)
+            return fail(ctx, C3R_EINVAL, "region %lld: [%d, %d) starts while region %lld, %lld entries before it, is still open ([%d, %d)): more than C3R_HAP_REGION_MAX_BACK = %d; "
+                        "count long and short regions (genes and exons) in separate calls", (long long)j, e.start, e.end, (long long)f, (long long)(j - f), regions[f].start, regions[f].end, C3R_HAP_REGION_MAX_BACK);
+        DevHapRegion &o = dev[(size_t)j];
+        o.start = e.start; o.end = e.end; o.row_off = e.row_off; o.strand_rows = (uint32_t)e.strand | ((uint32_t)(row_end - e.row_off) << 8);
+    }
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
+    if (n == 0) return C3R_OK;
+    const size_t words = 2 * (size_t)n + 2 * (size_t)n_rows;
+    if (ctx->n_reads == 0) {                                           // (no voters: nothing to launch)
+        memset(region_counts, 0, 2 * (size_t)n * 4);
+        if (n_rows) memset(row_counts, 0, 2 * (size_t)n_rows * 4);
+        return C3R_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HapRegionArgs a = read_args<HapRegionArgs>(ctx, ctx->n_reads);
+    int rc;
+    if ((rc = upload(ctx, ctx->d_hrregions, dev.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_hrfirst, first_open.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_hrps, row_ps, (size_t)n_rows))) return rc;
+    a.regions = (const DevHapRegion *)ctx->d_hrregions.p; a.n_regions = (int32_t)n; a.first_open = (const int32_t *)ctx->d_hrfirst.p; a.row_ps = (const int32_t *)ctx->d_hrps.p;
+    a.stranded = stranded;
+    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    std::vector<uint32_t> table(words);
+    rc = counter_table(ctx, ctx->d_hrcounts, words, table.data(), [&](uint32_t *t) {
+        a.region_counts = t; a.row_counts = t + 2 * (size_t)n;
+        launch_per_read(ctx, "k_hap_region_counts", k_hap_region_counts, a);
+    });
+    if (rc) return rc;
+    memcpy(region_counts, table.data(), 2 * (size_t)n * 4);
+    if (n_rows) memcpy(row_counts, table.data() + 2 * (size_t)n, 2 * (size_t)n_rows * 4);
+    return C3R_OK;
 }
 
 // The checks of a table of c3r_hap_site_t: c3r_hap_allele_counts' (h1 = NULL) and c3r_set_phase_alleles' (the same and h1 <= 1).  any_ps:

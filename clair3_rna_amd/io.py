@@ -110,6 +110,35 @@ def read_bed(bed_fn, contig, keep_start=None, keep_end=None):
     return iv, (None if not iv else bed_start), (None if not iv else bed_end)
 
 
+class BedRegions(list):
+    """read_bed_regions' list, with the number of lines it skipped."""
+    n_skipped = 0
+
+
+def read_bed_regions(bed_fn, contig):
+    """-> [(start, end, name, strand)] of one contig in file order, 0-based half-open: the named intervals of hap_expr.  name: column 4, or
+    "."; strand: "+" or "-" from column 6, else None.  Unlike read_bed nothing is widened: a line with end <= start is skipped and counted
+    (the list's n_skipped).  Columns are split at tabs where the line holds one, else at white space; `#`, `track` and `browser` lines are
+    not data."""
+    out = BedRegions()
+    with _open_text(bed_fn) as f:
+        for row in f:
+            row = row.rstrip("\r\n")
+            if not row.strip() or row[0] == "#" or row.startswith(("track", "browser")):
+                continue
+            c = row.split("\t") if "\t" in row else row.split()
+            if c[0] != contig:
+                continue
+            s, e = int(c[1]), int(c[2])
+            if e <= s or s < 0:
+                out.n_skipped += 1
+                continue
+            name = c[3].strip() if len(c) > 3 and c[3].strip() else "."
+            strand = c[5].strip() if len(c) > 5 and c[5].strip() in ("+", "-") else None
+            out.append((s, e, name, strand))
+    return out
+
+
 def read_vcf_sites(vcf_fn, contig):
     sites = set()
     with _open_text(vcf_fn) as f:

@@ -551,6 +551,47 @@ int c3r_get_hap_bq_weights(c3r_ctx *ctx, int *on);
 int c3r_get_haplotag_weights(c3r_ctx *ctx, uint32_t *w12, int64_t cap);
 int c3r_get_haplotag_words(c3r_ctx *ctx, uint32_t *words, int64_t cap);
 
+/* Haplotype-resolved read counts per interval (the rule `hap_regions`): how many loaded reads of each haplotype, per phase set, overlap each
+ * interval of a table — the exons or genes of a BED file.  Allele-specific expression from the tags the device already holds, without the
+ * haplotagged BAM.  Opt-in: nothing calls it unless asked (hap_expr, call_sample --hap_expression_bed).
+ *
+ * Inputs.  regions[n]: start, end 0-based half-open with start < end; sorted by (start, end), equal and nested regions allowed; strand 0 none,
+ * 1 `+`, 2 `-`; reserved = 0.  The rows of region j are [row_off[j], row_off[j + 1]), the last region's end at n_rows; row_off is
+ * non-decreasing, row_off[0] = 0 and no row_off exceeds n_rows.  row_ps[n_rows]: phase-set numbers >= 0, strictly increasing inside one
+ * region.  stranded: 0 off, 1 same, 2 reverse.
+ * Voters: the loaded reads that the tensor build keeps under the current parameters (read_kept with min_mq / excl_flags: the voters of
+ * c3r_hap_counts) and that have end > pos.  No depth cap.
+ * Overlap: a read overlaps a region iff at least one reference position under one of its M-like (M, =, X) or D ops of the normalised CIGAR
+ * lies in [start, end).  Introns (N) do not count; I, S, H and P consume no reference.  A read counts once per region, however many of its
+ * ops overlap it, and in every region it overlaps.
+ * Strand: with stranded != 0 and region.strand != 0 the read counts only if its strand (flag & 16: `-`) equals the region's (stranded = 1)
+ * or is the opposite (stranded = 2).  A region with strand = 0 always counts.
+ * Where the one count goes: (tag, set) are those of c3r_get_haplotags / c3r_get_read_phase_sets.  Tag 0: region_counts[j][0] (untagged).
+ * Tag 1 or 2 and the set is row r of region j: row_counts[r][tag - 1].  Tag 1 or 2 and the set is none of the region's rows:
+ * region_counts[j][1] (tagged in another set).
+ * Output: region_counts uint32 [n][2], row_counts uint32 [n_rows][2].  All sums are integers: neither read order nor arrival order shows.
+ *
+ * The bound.  first_open[j] is the smallest i <= j with end_i > start_j (the library computes it): the regions an op [x, x + len) can
+ * overlap lie from first_open[k], k the last region with start <= x, up to the first region with start >= x + len.  A table with
+ * max_j (j - first_open[j]) > C3R_HAP_REGION_MAX_BACK is refused (C3R_EINVAL naming the region): one long region lying over thousands of
+ * short ones makes every op scan them all.  It is a safety condition that bounds one op's scan to 4096 loads, not a tuned number; count long
+ * and short regions (genes and exons) in separate calls then.  That gene annotations stay far below it — a few thousand genes per
+ * chromosome, the longest spanning well under a hundred others — is recalled, not checked.
+ *
+ * c3r_hap_region_counts needs a phase table (C3R_EINVAL without one, whatever n is); n = 0 succeeds and launches nothing; no reads loaded:
+ * every count is 0 and nothing is launched.  C3R_EINVAL, naming the first bad region or row, for start >= end, start < 0, an unsorted table,
+ * a strand above 2, a non-zero reserved byte, a row_off that is not 0 at region 0, decreases or exceeds n_rows, a region of 2^24 rows or
+ * more, a negative ps, ps not strictly increasing inside a region, stranded outside 0 .. 2 and a table over the bound.  It uploads regions,
+ * first_open and row_ps into buffers of its own, clears one device table of 2 n + 2 n_rows words, runs k_hap_region_counts
+ * (csrc/hapregion_kernels.hpp) on the context's stream and reads the table back.  It changes neither the reads' haplotags and phase sets,
+ * nor the phase table, nor anything a scan or another count table reads.  Its device buffers are allocated at the first call and kept.
+ * Not done: no union of a gene's exon rows (a read over two exons of one gene counts in both), no fractional assignment of a read that
+ * overlaps several regions, no statistics (no test of allelic imbalance); agreement with featureCounts / htseq-count is not measured. */
+#define C3R_HAP_REGION_MAX_BACK 4096
+typedef struct { int32_t start, end, row_off; uint8_t strand, reserved[3]; } c3r_hap_region_t;
+int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t n, const int32_t *row_ps, int64_t n_rows, int32_t stranded,
+                          uint32_t *region_counts, uint32_t *row_counts);
+
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped
  * at 1; src/create_tensor_pileup.py:411-415), per-position channel counts, candidate gates, window
