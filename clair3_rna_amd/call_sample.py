@@ -57,6 +57,9 @@ contig, with the HP / PS tags the GPU computed from the phase table the second p
 `--hap_expression_bed BED` (same conditions, combinable with both) adds one more step behind them: hap_expr counts the reads of each haplotype
 and phase set over every interval of BED on the GPU (include/c3r.h: the rule `hap_regions`) into <prefix>_enable_phasing_hap_expression.tsv,
 with the tagging flags haplotag_bam gets; `--hap_expression_stranded same|reverse` is handed over as --stranded; without the flag nothing changes.
+`--hap_junctions` (same conditions, combinable with all three) adds one more step behind them: hap_junctions counts, on the GPU, the reads of
+each haplotype and phase set per splice junction the reads hold (include/c3r.h: the rule `hap_junctions`) into
+<prefix>_enable_phasing_hap_junctions.tsv, with the tagging flags hap_expr gets and --ref_fn for MOTIF / STRAND; without the flag nothing changes.
 
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --output_dir out
     python -m clair3_rna_amd.call_sample --bam_fn x.bam --ref_fn ref.fa --pileup_model_path W --phased_pileup_model_path W30 \
@@ -254,6 +257,12 @@ def build_parser():
            "every region it overlaps, no gene-level union, no statistics).  One process only.  Off: no file more and no byte different")
     from . import hap_expr as _hap_expr
     _hap_expr.add_stranded_flag(a, "--hap_expression_stranded")
+    a("--hap_junctions", action="store_true",
+      help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin (combinable with --phase_output, --haplotagged_bam and "
+           "--hap_expression_bed): after the passes, count on the GPU the reads of each haplotype and phase set per splice junction (every N op of a "
+           "counted read), with the tags the 30-channel pass called with, into <prefix>_enable_phasing_hap_junctions.tsv (hap_junctions: "
+           "allele-specific splicing; no minimum intron or anchor length, no annotation, no statistics; agreement with an external junction "
+           "counter is not measured).  One process only.  Off: no file more and no byte different")
     a("--gpu_id", type=int, default=None, help="default: $C3R_DEVICE, else LOCAL_RANK under torch.distributed.run, else 0")
     a("--gpu_precision", type=str, default=_env_precision(), choices=["f32", "f16x3", "f16+f8", "auto"],
       help="network arithmetic (c3r_set_precision): f16x3 = fp32-equivalent split-f16 (default); auto = the faster fp8-corrected path where a "
@@ -443,7 +452,9 @@ def _plan(args):
              "<output_dir>/tmp/phased_output/phased_bam`"),
             ("--hap_expression_bed", bool(getattr(args, "hap_expression_bed", None)), "it counts reads by the tags the 30-channel pass called with",
              "run the pass without it and then `python -m clair3_rna_amd.hap_expr --bam_fn ... --phased_vcf_fn ... --regions_bed_fn ... "
-             "--output_fn ...`")):
+             "--output_fn ...`"),
+            ("--hap_junctions", bool(getattr(args, "hap_junctions", False)), "it counts junction reads by the tags the 30-channel pass called with",
+             "run the pass without it and then `python -m clair3_rna_amd.hap_junctions --bam_fn ... --phased_vcf_fn ... --ref_fn ... --output_fn ...`")):
         if on:
             if not phased:
                 sys.exit("[ERROR] %s needs --enable_phasing_model (%s)" % (flag, why))
@@ -531,6 +542,10 @@ def _plan(args):
         steps.append(_Step("hap_expr", ["--phased_vcf_fn", source, "--regions_bed_fn", args.hap_expression_bed, "--output_fn", stem + "_hap_expression.tsv",
                                         "--min_mq", str(args.min_mq), "--stranded", args.hap_expression_stranded]
                            + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext))
+    if getattr(args, "hap_junctions", False):
+        # the tagging flags hap_expr gets, and the reference for MOTIF / STRAND (argparse keeps the one --ref_fn, whoever names it again)
+        steps.append(_Step("hap_junctions", ["--phased_vcf_fn", source, "--output_fn", stem + "_hap_junctions.tsv", "--min_mq", str(args.min_mq), "--ref_fn", args.ref_fn]
+                           + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext))
     return steps
 
 
@@ -548,7 +563,7 @@ def Run(args, log=None):
             os.makedirs(step.handed[0], exist_ok=True)
         else:
             argv = ["--bam_fn", _indexed_bam(args)] + step.handed
-            if step.name in ("haplotag_bam", "hap_expr"):
+            if step.name in ("haplotag_bam", "hap_expr", "hap_junctions"):
                 contigs, _ = plan_chunks(args.ref_fn, args.ctg_name, args.include_all_ctgs, existing(args.bed_fn), existing(args.genotyping_mode_vcf_fn),
                                          args.chunk_size, args.chunk_num)
                 argv += ["--ctg_name", ",".join(contigs)]

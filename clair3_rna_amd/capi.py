@@ -27,6 +27,11 @@ HAP_SITE_DTYPE = np.dtype([("pos", "<i4"), ("ps", "<i4"), ("base_matters", "u1")
 HAP_REGION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("row_off", "<i4"), ("strand", "u1"), ("reserved", "u1", (3,))], align=True)
 HAP_REGION_MAX_BACK = 4096
 assert HAP_REGION_DTYPE.itemsize == 16
+# c3r_hap_junction_t / c3r_hap_junction_row_t: one splice junction of c3r_hap_junction_counts (0-based, half-open; its rows are
+# rows[row_off : the next junction's row_off]) and one phase set of a junction
+HAP_JUNCTION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("reads", "<u4"), ("reverse", "<u4"), ("untagged", "<u4"), ("row_off", "<i4")], align=True)
+HAP_JUNCTION_ROW_DTYPE = np.dtype([("ps", "<i4"), ("hp1", "<u4"), ("hp2", "<u4")], align=True)
+assert HAP_JUNCTION_DTYPE.itemsize == 24 and HAP_JUNCTION_ROW_DTYPE.itemsize == 12
 assert SITE_DTYPE.itemsize == 52 and TOKEN_DTYPE.itemsize == 16 and PADINS_DTYPE.itemsize == 24 and PHASE_SITE_DTYPE.itemsize == 12
 assert HAP_SITE_DTYPE.itemsize == 32 and HAP_SITE_DTYPE.fields["a_base"][1] == 16 and HAP_SITE_DTYPE.fields["b_ins_off"][1] == 28
 
@@ -80,7 +85,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_load_reads_q", "c3r_set_hap_min_bq", "c3r_get_hap_min_bq", "c3r_get_hap_seq",
            "c3r_set_hap_realign", "c3r_get_hap_realign", "c3r_hap_realign_column",
            "c3r_set_hap_realign_spliced", "c3r_get_hap_realign_spliced", "c3r_hap_realign_column_spliced",
-           "c3r_set_hap_bq_weights", "c3r_get_hap_bq_weights", "c3r_get_haplotag_weights", "c3r_get_haplotag_words"]
+           "c3r_set_hap_bq_weights", "c3r_get_hap_bq_weights", "c3r_get_haplotag_weights", "c3r_get_haplotag_words",
+           "c3r_hap_junction_counts", "c3r_get_hap_junctions", "c3r_set_hap_junction_direct"]
 
 _lib = None
 
@@ -136,6 +142,9 @@ def load_library():
     L.c3r_hap_counts.argtypes = [vp, vp, i64, vp]
     L.c3r_hap_allele_counts.argtypes = [vp, vp, i64, vp, i64, vp]
     L.c3r_hap_region_counts.argtypes = [vp, vp, i64, vp, i64, C.c_int32, vp, vp]
+    L.c3r_hap_junction_counts.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.c3r_get_hap_junctions.argtypes = [vp, vp, i64, vp, i64]
+    L.c3r_set_hap_junction_direct.argtypes = [vp, i32]
     L.c3r_phase_allele_links.argtypes = [vp, vp, i64, vp, i64, vp]
     L.c3r_phase_allele_unit_links.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
@@ -492,6 +501,24 @@ class Engine(object):
         self._chk(self.L.c3r_hap_region_counts(self.h, _ptr(a) if len(a) else None, len(a), _ptr(ps) if len(ps) else None, len(ps), int(stranded),
                                                _ptr(region_counts) if len(a) else None, _ptr(row_counts) if len(ps) else None))
         return region_counts, row_counts
+
+    def hap_junction_counts(self, slots_hint=0):
+        """(junctions, rows): every splice junction that a loaded read which passes the current filters holds — an N op [start, end) of its
+        normalised CIGAR — as a HAP_JUNCTION_DTYPE array sorted by (start, end) with reads / reverse / untagged, and per junction and phase set
+        in which one of its reads was tagged a HAP_JUNCTION_ROW_DTYPE row (ps, hp1, hp2), junction j's rows at rows[row_off[j] :
+        row_off[j + 1]] in ps order (c3r_hap_junction_counts, the rule `hap_junctions`).  No phase table: every read is untagged and there
+        are no rows.  slots_hint: the initial size of the device's hash tables (0: the library's default); the result does not depend on
+        it.  Leaves tags, table and scans as they are."""
+        nj, nr = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.c3r_hap_junction_counts(self.h, int(slots_hint), C.byref(nj), C.byref(nr)))
+        junctions, rows = np.zeros(nj.value, dtype=HAP_JUNCTION_DTYPE), np.zeros(nr.value, dtype=HAP_JUNCTION_ROW_DTYPE)
+        self._chk(self.L.c3r_get_hap_junctions(self.h, _ptr(junctions) if len(junctions) else None, len(junctions), _ptr(rows) if len(rows) else None, len(rows)))
+        return junctions, rows
+
+    def set_hap_junction_direct(self, on):
+        """c3r_set_hap_junction_direct (default off): hap_junction_counts runs its kernel without the per-workgroup LDS stage.  Same
+        result; a switch for measurements."""
+        self._chk(self.L.c3r_set_hap_junction_direct(self.h, 1 if on else 0))
 
     def hap_allele_counts(self, sites, ins_pool=None):
         """uint32 (n, 3, 3) like hap_counts, for query sites whose two alleles may be SNVs, insertions or deletions (a HAP_SITE_DTYPE array

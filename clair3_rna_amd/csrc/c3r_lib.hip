@@ -19,6 +19,7 @@
 #include <thread>
 #include <type_traits>
 #include <vector>
+#include <new>
 
 #include "../../include/c3r.h"
 #include "decode.hpp"
@@ -30,6 +31,7 @@
 #include "phase_kernels.hpp"
 #include "hapcount_kernels.hpp"
 #include "hapregion_kernels.hpp"
+#include "hapjunction_kernels.hpp"
 #include "qual_kernels.hpp"
 #include <sched.h>
 
@@ -185,6 +187,13 @@ struct c3r_ctx {
     DevBuf d_hcsites, d_hcounts;
     DevBuf d_hasites, d_hapool;               // c3r_hap_allele_counts: its query sites and the pool of inserted bases (the counts share d_hcounts)
     DevBuf d_hrregions, d_hrfirst, d_hrps, d_hrcounts;      // c3r_hap_region_counts: its regions, first_open, row_ps and count table, allocated by the first call and kept
+    // c3r_hap_junction_counts: the junction table (keys, then [slots][3] counters), the row table (keys, then [slots][2] counters) and the
+    // overflow word, allocated by the first call and kept; the compacted, sorted result of the last call (hj_valid: there is one — until the
+    // next c3r_load_reads); c3r_set_hap_junction_direct
+    DevBuf d_hjtab, d_hjrows, d_hjover;
+    std::vector<c3r_hap_junction_t> hj_junctions;
+    std::vector<c3r_hap_junction_row_t> hj_rows;
+    bool hj_valid = false, hj_direct = false;
     DevBuf d_pasites, d_papool;               // c3r_phase_allele_links / c3r_phase_allele_unit_links: their candidate sites and pool (the links share d_links, the units d_unitof)
 
     // ---- scan state
@@ -913,7 +922,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hrregions, &ctx->d_hrfirst, &ctx->d_hrps, &ctx->d_hrcounts, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hrregions, &ctx->d_hrfirst, &ctx->d_hrps, &ctx->d_hrcounts, &ctx->d_hjtab, &ctx->d_hjrows, &ctx->d_hjover, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_rowctl, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0, cap = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -994,6 +1003,7 @@ int c3r_load_reads_q(c3r_ctx *ctx, const c3r_read_t *reads, int64_t n_reads, con
     // whatever happens below, the previous contig's tables are gone
     ctx->n_reads = 0; ctx->n_indel_ops = 0; ctx->n_seq_bytes = 0; ctx->n_cigar_ops = 0; ctx->max_cover = 0;
     ctx->host_reads_valid = false; ctx->last_scan_pruned = false; ctx->legacy_valid = false;
+    ctx->hj_valid = false; ctx->hj_junctions.clear(); ctx->hj_rows.clear();
     ctx->host_cache.reset();              // (snapshots of the previous contig keep their copy alive)
     ctx->padins.reset();
     const int n = (int)n_reads;
@@ -1427,6 +1437,112 @@ int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t
     if (rc) return rc;
     memcpy(region_counts, table.data(), 2 * (size_t)n * 4);
     if (n_rows) memcpy(row_counts, table.data() + 2 * (size_t)n, 2 * (size_t)n_rows * 4);
+    return C3R_OK;
+}
+
+// The rule `hap_junctions` of include/c3r.h: k_hap_junction_counts into the two hash tables, the scan allocator's grow-and-repeat when one
+// of them had no place for a key, then the tables compacted and sorted on the host into the context.
+int c3r_hap_junction_counts(c3r_ctx *ctx, int64_t slots_hint, int64_t *n_junctions, int64_t *n_rows) {
+    if (!ctx || !n_junctions || !n_rows) return C3R_EINVAL;
+    if (slots_hint < 0) return fail(ctx, C3R_EINVAL, "c3r_hap_junction_counts: slots_hint %lld is negative", (long long)slots_hint);
+    ctx->hj_valid = false; ctx->hj_junctions.clear(); ctx->hj_rows.clear();
+    *n_junctions = 0; *n_rows = 0;
+    if (ctx->n_reads == 0) { ctx->hj_valid = true; return C3R_OK; }              // (no reads: nothing to launch)
+    uint32_t jlog = HJ_MIN_LOG;
+    while (jlog < (uint32_t)HJ_MAX_LOG && ((int64_t)1 << jlog) < (slots_hint ? slots_hint : (int64_t)C3R_HAP_JUNCTION_SLOTS)) ++jlog;
+    uint32_t rlog = jlog;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HapJunctionArgs a = read_args<HapJunctionArgs>(ctx, ctx->n_reads);
+    if (ctx->n_phase > 0) { a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p; }       // (else null: every read is untagged)
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    int rc;
+    if ((rc = ensure(ctx, ctx->d_hjover, 16))) return rc;
+    for (int round = 0;; ++round) {
+        const size_t js = (size_t)1 << jlog, rs = (size_t)1 << rlog;
+        if ((rc = ensure(ctx, ctx->d_hjtab, js * 20)) || (rc = ensure(ctx, ctx->d_hjrows, rs * 16))) return rc;
+        a.jkeys = (unsigned long long *)ctx->d_hjtab.p; a.jcounts = (uint32_t *)((char *)ctx->d_hjtab.p + js * 8); a.jlog = jlog;
+        a.rkeys = (unsigned long long *)ctx->d_hjrows.p; a.rcounts = (uint32_t *)((char *)ctx->d_hjrows.p + rs * 8); a.rlog = rlog;
+        a.overflow = (uint32_t *)ctx->d_hjover.p;
+        HIPCHK(ctx, hipMemsetAsync(a.jkeys, 0xff, js * 8, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(a.jcounts, 0, js * 12, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(a.rkeys, 0xff, rs * 8, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(a.rcounts, 0, rs * 8, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(a.overflow, 0, 4, ctx->stream));
+        if (ctx->hj_direct) launch_per_read(ctx, "k_hap_junction_counts_direct", k_hap_junction_counts<false>, a);
+        else launch_per_read(ctx, "k_hap_junction_counts", k_hap_junction_counts<true>, a);
+        HIPCHK(ctx, hipGetLastError());
+        uint32_t over = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&over, a.overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (!over) break;
+        if (over & HJ_OVER_JUNCTIONS) ++jlog;
+        if (over & HJ_OVER_ROWS) ++rlog;
+        if (round + 1 >= C3R_HAP_JUNCTION_MAX_ROUNDS || jlog > (uint32_t)HJ_MAX_LOG || rlog > (uint32_t)HJ_MAX_LOG)
+            return fail(ctx, C3R_EOVERFLOW, "c3r_hap_junction_counts: the tables still had no place for a key after %d launches (2^%u junction slots, 2^%u row slots)",
+                        round + 1, jlog, rlog);
+    }
+    // the tables as they are, then: occupied slots in key order — (start << 32) | end of non-negative positions orders by (start, end).
+    // (The host's copies are as large as the tables: one that does not fit the host's memory is C3R_ENOMEM, not an exception through the C ABI.)
+    try {
+    const size_t js = (size_t)1 << jlog, rs = (size_t)1 << rlog;
+    std::vector<unsigned long long> jt(js * 5 / 2 + 1), rt(rs * 2);
+    HIPCHK(ctx, hipMemcpyAsync(jt.data(), ctx->d_hjtab.p, js * 20, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(rt.data(), ctx->d_hjrows.p, rs * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t *jc = (const uint32_t *)(jt.data() + js), *rcn = (const uint32_t *)(rt.data() + rs);
+    std::vector<std::pair<unsigned long long, uint32_t>> order;                 // (key, slot)
+    for (size_t s = 0; s < js; ++s) if (jt[s] != HJ_EMPTY) order.push_back({jt[s], (uint32_t)s});
+    std::sort(order.begin(), order.end());
+    std::vector<int32_t> rank(js, -1);
+    ctx->hj_junctions.resize(order.size());
+    for (size_t j = 0; j < order.size(); ++j) {
+        const uint32_t s = order[j].second;
+        rank[s] = (int32_t)j;
+        c3r_hap_junction_t &o = ctx->hj_junctions[j];
+        o.start = (int32_t)(order[j].first >> 32); o.end = (int32_t)(uint32_t)order[j].first;
+        o.reads = jc[3 * (size_t)s]; o.reverse = jc[3 * (size_t)s + 1]; o.untagged = jc[3 * (size_t)s + 2]; o.row_off = 0;
+    }
+    std::vector<std::pair<std::pair<int32_t, int32_t>, uint32_t>> rows;        // ((junction, ps), slot)
+    for (size_t s = 0; s < rs; ++s) {
+        if (rt[s] == HJ_EMPTY) continue;
+        const uint64_t slot = rt[s] >> 32;
+        if (slot >= js || rank[slot] < 0) return fail(ctx, C3R_EHIP, "internal: a row of the junction table names slot %llu, which holds no junction", (unsigned long long)slot);
+        rows.push_back({{rank[slot], (int32_t)(uint32_t)rt[s]}, (uint32_t)s});
+    }
+    std::sort(rows.begin(), rows.end());
+    ctx->hj_rows.resize(rows.size());
+    size_t r = 0;
+    for (size_t j = 0; j < order.size(); ++j) {
+        ctx->hj_junctions[j].row_off = (int32_t)r;
+        for (; r < rows.size() && (size_t)rows[r].first.first == j; ++r) {
+            c3r_hap_junction_row_t &o = ctx->hj_rows[r];
+            o.ps = rows[r].first.second; o.hp1 = rcn[2 * (size_t)rows[r].second]; o.hp2 = rcn[2 * (size_t)rows[r].second + 1];
+        }
+    }
+    } catch (const std::bad_alloc &) {
+        ctx->hj_junctions.clear(); ctx->hj_rows.clear();
+        return fail(ctx, C3R_ENOMEM, "c3r_hap_junction_counts: no host memory for the copies of the tables (2^%u junction slots, 2^%u row slots)", jlog, rlog);
+    }
+    ctx->hj_valid = true;
+    *n_junctions = (int64_t)ctx->hj_junctions.size(); *n_rows = (int64_t)ctx->hj_rows.size();
+    return C3R_OK;
+}
+
+int c3r_get_hap_junctions(c3r_ctx *ctx, c3r_hap_junction_t *junctions, int64_t cap_j, c3r_hap_junction_row_t *rows, int64_t cap_r) {
+    if (!ctx || cap_j < 0 || cap_r < 0) return C3R_EINVAL;
+    if (!ctx->hj_valid) return fail(ctx, C3R_EINVAL, "c3r_get_hap_junctions: nothing has been counted since the last c3r_load_reads (c3r_hap_junction_counts)");
+    const size_t nj = ctx->hj_junctions.size(), nr = ctx->hj_rows.size();
+    if ((nj && (!junctions || (size_t)cap_j < nj)) || (nr && (!rows || (size_t)cap_r < nr)))
+        return fail(ctx, C3R_EINVAL, "c3r_get_hap_junctions: %zu junctions and %zu rows do not fit %lld and %lld slots", nj, nr, (long long)cap_j, (long long)cap_r);
+    if (nj) memcpy(junctions, ctx->hj_junctions.data(), nj * sizeof(c3r_hap_junction_t));
+    if (nr) memcpy(rows, ctx->hj_rows.data(), nr * sizeof(c3r_hap_junction_row_t));
+    return C3R_OK;
+}
+
+int c3r_set_hap_junction_direct(c3r_ctx *ctx, int on) {
+    if (!ctx) return C3R_EINVAL;
+    if (on != 0 && on != 1) return fail(ctx, C3R_EINVAL, "c3r_set_hap_junction_direct: %d is neither 0 nor 1", on);
+    ctx->hj_direct = on != 0;
     return C3R_OK;
 }
 

@@ -592,6 +592,49 @@ typedef struct { int32_t start, end, row_off; uint8_t strand, reserved[3]; } c3r
 int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t n, const int32_t *row_ps, int64_t n_rows, int32_t stranded,
                           uint32_t *region_counts, uint32_t *row_counts);
 
+/* Haplotype-resolved splice-junction counts (the rule `hap_junctions`): which haplotype uses which intron — per junction that the loaded
+ * reads hold, how many reads hold it, and per phase set how many of them carry each haplotype.  Allele-specific splicing from the tags the
+ * device already holds, without the haplotagged BAM.  Opt-in: nothing calls it unless asked (hap_junctions, call_sample --hap_junctions).
+ *
+ * Counted reads: the loaded reads that the tensor build keeps under the current parameters (read_kept with min_mq / excl_flags: the
+ * voters of `hap_regions`) and that have end > pos.  No depth cap.
+ * A junction of a read: every N op of length >= 1 of its NORMALISED CIGAR (zero-length ops, H and P dropped, = and X folded into M, equal
+ * neighbours merged — the form both walks of the device deliver, so adjacent N ops are one junction and `0N` is none).  An op at reference
+ * position x (0-based) of length len is the junction [x, x + len), 0-based half-open.  What lies on either side does not matter:
+ * `5M3I10N5M` and `10M2D100N10M` count as written.  Reference positions increase along a read, so a read holds a junction at most once.
+ * Per junction: reads — the counted reads that hold it; reverse — those with flag bit 16; untagged — those whose tag is 0; and one row
+ * per phase set in which at least one of them was tagged, with hp1 / hp2, the reads tagged 1 / 2 in that set ((tag, set) are those of
+ * c3r_get_haplotags / c3r_get_read_phase_sets).  reads == untagged + the sum of hp1 + hp2 over the junction's rows.
+ * No phase table is needed: without one, or with a table under which no read was tagged, every counted read is untagged and there are no
+ * rows — a plain junction counter.
+ * Output order: junctions by (start, end), a junction's rows by ps; rows of junction j are [row_off_j, row_off_(j + 1)), the last
+ * junction's end at the number of rows.  All sums are integers: neither read order, arrival order nor the hash shows.
+ *
+ * c3r_hap_junction_counts runs k_hap_junction_counts (csrc/hapjunction_kernels.hpp) on the context's stream: two insert-only hash tables
+ * on the device (junctions; rows), counted into per-workgroup tables in LDS first.  slots_hint: the initial number of junction slots (the
+ * row table starts with as many); 0: the library's default, C3R_HAP_JUNCTION_SLOTS; rounded up to a power of two and clamped to
+ * 16 .. 2^28; negative: C3R_EINVAL.  A table without a place for a key within 256 probes (or its size, if smaller: linear probing, so a
+ * table grows at a load factor near 0.9, before probing degenerates) is doubled, both are cleared and the launch is repeated — exact,
+ * the counts being sums —, at most C3R_HAP_JUNCTION_MAX_ROUNDS times, then C3R_EOVERFLOW with a message.  The host reads both whole
+ * tables back (20 and 16 bytes per slot; C3R_ENOMEM when its copies do not fit).  Measured at load factors of 0.16 and 0.04 only: a
+ * contig whose distinct junctions come near the table's size costs more probes per claim and one or more repeated launches, neither measured.  The host compacts and sorts, and
+ * the context keeps the result until the next call or the next c3r_load_reads.  *n_junctions / *n_rows (both required) receive the sizes.
+ * No reads loaded: both are 0 and nothing is launched.  It changes neither the reads' haplotags and phase sets, nor the phase table, nor
+ * anything a scan or another count table reads.  Its device buffers are allocated at the first call and kept.
+ * c3r_get_hap_junctions copies the kept result (either array may be NULL when its count is 0); C3R_EINVAL when a capacity is smaller than
+ * the count or nothing has been counted since the last c3r_load_reads.
+ * c3r_set_hap_junction_direct(ctx, on): default 0; anything but 0 or 1 is C3R_EINVAL.  1: the same kernel body without its LDS stage —
+ * every count goes to the global tables directly.  The results are identical; the switch exists to measure what the aggregation buys.
+ * Not done: no minimum intron length or anchor length; no annotation; no statistics (no test of imbalance); a read tagged in a set counts
+ * in that set's row even where the set has no site near the junction; agreement with any external junction counter is not measured. */
+#define C3R_HAP_JUNCTION_SLOTS 65536
+#define C3R_HAP_JUNCTION_MAX_ROUNDS 48
+typedef struct { int32_t start, end; uint32_t reads, reverse, untagged; int32_t row_off; } c3r_hap_junction_t;   /* 24 bytes */
+typedef struct { int32_t ps; uint32_t hp1, hp2; } c3r_hap_junction_row_t;                                        /* 12 bytes */
+int c3r_hap_junction_counts(c3r_ctx *ctx, int64_t slots_hint, int64_t *n_junctions, int64_t *n_rows);
+int c3r_get_hap_junctions(c3r_ctx *ctx, c3r_hap_junction_t *junctions, int64_t cap_j, c3r_hap_junction_row_t *rows, int64_t cap_r);
+int c3r_set_hap_junction_direct(c3r_ctx *ctx, int on);
+
 /* ---- tensor build (A1-A5) ------------------------------------------------------------------ */
 /* Phase 1+2: CIGAR walk over the reads overlapping [ctg_start-33, ctg_end+33] (1-based, clamped
  * at 1; src/create_tensor_pileup.py:411-415), per-position channel counts, candidate gates, window
