@@ -57,6 +57,8 @@ contig, with the HP / PS tags the GPU computed from the phase table the second p
 `--hap_expression_bed BED` (same conditions, combinable with both) adds one more step behind them: hap_expr counts the reads of each haplotype
 and phase set over every interval of BED on the GPU (include/c3r.h: the rule `hap_regions`) into <prefix>_enable_phasing_hap_expression.tsv,
 with the tagging flags haplotag_bam gets; `--hap_expression_stranded same|reverse` is handed over as --stranded; without the flag nothing changes.
+`--hap_expression_group_by_name` (needs --hap_expression_bed) hands hap_expr --group_by_name: the gene-level count, the BED lines of one name one
+group and a read counted once per group (include/c3r.h: the rule `hap_groups`), into <prefix>_enable_phasing_hap_expression_by_name.tsv instead.
 `--hap_junctions` (same conditions, combinable with all three) adds one more step behind them: hap_junctions counts, on the GPU, the reads of
 each haplotype and phase set per splice junction the reads hold (include/c3r.h: the rule `hap_junctions`) into
 <prefix>_enable_phasing_hap_junctions.tsv, with the tagging flags hap_expr gets and --ref_fn for MOTIF / STRAND; without the flag nothing changes.
@@ -257,6 +259,10 @@ def build_parser():
            "every region it overlaps, no gene-level union, no statistics).  One process only.  Off: no file more and no byte different")
     from . import hap_expr as _hap_expr
     _hap_expr.add_stranded_flag(a, "--hap_expression_stranded")
+    a("--hap_expression_group_by_name", action="store_true",
+      help="with --hap_expression_bed: the gene-level count — the BED lines with the same name (column 4) are one group and a read counts once per "
+           "group, however many of its intervals it overlaps (hap_expr --group_by_name) — into <prefix>_enable_phasing_hap_expression_by_name.tsv "
+           "in place of <prefix>_enable_phasing_hap_expression.tsv.  No GTF reader, no fractional assignment, no statistics")
     a("--hap_junctions", action="store_true",
       help="with --enable_phasing_model and one of --phased_vcf_fn / --phasing builtin (combinable with --phase_output, --haplotagged_bam and "
            "--hap_expression_bed): after the passes, count on the GPU the reads of each haplotype and phase set per splice junction (every N op of a "
@@ -463,6 +469,8 @@ def _plan(args):
             one_process(flag, instead)
     if getattr(args, "hap_expression_bed", None) and not os.path.isfile(args.hap_expression_bed):
         sys.exit("[ERROR] file %s not found" % args.hap_expression_bed)
+    if getattr(args, "hap_expression_group_by_name", False) and not getattr(args, "hap_expression_bed", None):
+        sys.exit("[ERROR] --hap_expression_group_by_name belongs to --hap_expression_bed (it groups the lines of that BED by their name): it needs --hap_expression_bed")
     if getattr(args, "hap_expression_stranded", "no") != "no" and not getattr(args, "hap_expression_bed", None):
         sys.exit("[ERROR] --hap_expression_stranded belongs to --hap_expression_bed (it chooses the strand of the reads counted there): it needs --hap_expression_bed")
     left_align =bool(getattr(args, "left_align_indels", False))
@@ -539,8 +547,10 @@ def _plan(args):
                   _Step("haplotag_bam", ["--phased_vcf_fn", source, "--output_dir", bam_dir] + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext)]
     if getattr(args, "hap_expression_bed", None):
         # the tagging flags haplotag_bam gets: the counts are by the tags of the pass; the contigs the passes processed are added when the step runs
-        steps.append(_Step("hap_expr", ["--phased_vcf_fn", source, "--regions_bed_fn", args.hap_expression_bed, "--output_fn", stem + "_hap_expression.tsv",
-                                        "--min_mq", str(args.min_mq), "--stranded", args.hap_expression_stranded]
+        by_name = bool(getattr(args, "hap_expression_group_by_name", False))
+        steps.append(_Step("hap_expr", ["--phased_vcf_fn", source, "--regions_bed_fn", args.hap_expression_bed,
+                                        "--output_fn", stem + ("_hap_expression_by_name.tsv" if by_name else "_hap_expression.tsv"),
+                                        "--min_mq", str(args.min_mq), "--stranded", args.hap_expression_stranded] + (["--group_by_name"] if by_name else [])
                            + tag_indels + (la if tag_indels else []) + bq + bw + ra + gpu, stem + ext))
     if getattr(args, "hap_junctions", False):
         # the tagging flags hap_expr gets, and the reference for MOTIF / STRAND (argparse keeps the one --ref_fn, whoever names it again)

@@ -27,6 +27,9 @@ HAP_SITE_DTYPE = np.dtype([("pos", "<i4"), ("ps", "<i4"), ("base_matters", "u1")
 HAP_REGION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("row_off", "<i4"), ("strand", "u1"), ("reserved", "u1", (3,))], align=True)
 HAP_REGION_MAX_BACK = 4096
 assert HAP_REGION_DTYPE.itemsize == 16
+# c3r_hap_interval_t: one interval of c3r_hap_group_counts (0-based, half-open; strand 0 none, 1 +, 2 -) and the group it belongs to
+HAP_INTERVAL_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("group", "<i4"), ("strand", "u1"), ("reserved", "u1", (3,))], align=True)
+assert HAP_INTERVAL_DTYPE.itemsize == 16
 # c3r_hap_junction_t / c3r_hap_junction_row_t: one splice junction of c3r_hap_junction_counts (0-based, half-open; its rows are
 # rows[row_off : the next junction's row_off]) and one phase set of a junction
 HAP_JUNCTION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("reads", "<u4"), ("reverse", "<u4"), ("untagged", "<u4"), ("row_off", "<i4")], align=True)
@@ -86,7 +89,8 @@ EXPORTS = ["c3r_version", "c3r_create", "c3r_destroy", "c3r_trim", "c3r_last_err
            "c3r_set_hap_realign", "c3r_get_hap_realign", "c3r_hap_realign_column",
            "c3r_set_hap_realign_spliced", "c3r_get_hap_realign_spliced", "c3r_hap_realign_column_spliced",
            "c3r_set_hap_bq_weights", "c3r_get_hap_bq_weights", "c3r_get_haplotag_weights", "c3r_get_haplotag_words",
-           "c3r_hap_junction_counts", "c3r_get_hap_junctions", "c3r_set_hap_junction_direct"]
+           "c3r_hap_junction_counts", "c3r_get_hap_junctions", "c3r_set_hap_junction_direct",
+           "c3r_hap_group_counts", "c3r_set_hap_group_direct", "c3r_get_hap_group_direct"]
 
 _lib = None
 
@@ -145,6 +149,9 @@ def load_library():
     L.c3r_hap_junction_counts.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.c3r_get_hap_junctions.argtypes = [vp, vp, i64, vp, i64]
     L.c3r_set_hap_junction_direct.argtypes = [vp, i32]
+    L.c3r_hap_group_counts.argtypes = [vp, vp, i64, i64, vp, vp, i64, C.c_int32, vp, vp]
+    L.c3r_set_hap_group_direct.argtypes = [vp, i32]
+    L.c3r_get_hap_group_direct.argtypes = [vp, C.POINTER(i32)]
     L.c3r_phase_allele_links.argtypes = [vp, vp, i64, vp, i64, vp]
     L.c3r_phase_allele_unit_links.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.c3r_set_phase_alleles.argtypes = [vp, vp, vp, i64, vp, i64]
@@ -501,6 +508,39 @@ class Engine(object):
         self._chk(self.L.c3r_hap_region_counts(self.h, _ptr(a) if len(a) else None, len(a), _ptr(ps) if len(ps) else None, len(ps), int(stranded),
                                                _ptr(region_counts) if len(a) else None, _ptr(row_counts) if len(ps) else None))
         return region_counts, row_counts
+
+    def hap_group_counts(self, intervals, n_groups, group_row_off, row_ps, stranded=0):
+        """(group_counts uint32 (n_groups, 2), row_counts uint32 (n_rows, 2)): the loaded reads that pass the current filters, per GROUP of
+        `intervals` (a HAP_INTERVAL_DTYPE array sorted by (start, end); the intervals of one group disjoint and of one strand; group g's rows
+        are row_ps[group_row_off[g] : group_row_off[g + 1]], the last group's end at len(row_ps), phase-set numbers strictly increasing inside
+        a group) — group_counts: untagged reads, reads tagged in a set that is none of the group's rows; row_counts: haplotype 1, haplotype 2
+        of the row's set (c3r_hap_group_counts, the rule `hap_groups`).  A read counts once in every group of which it covers a position of
+        an interval, however many intervals: the gene-level count, a gene being the group of its exons.  stranded: 0 off, 1 same, 2 reverse.
+        Needs a phase table; leaves tags, table and scans as they are."""
+        a = np.zeros(0, HAP_INTERVAL_DTYPE) if intervals is None else np.asarray(intervals)
+        if a.dtype != HAP_INTERVAL_DTYPE:
+            raise TypeError("intervals must be a capi.HAP_INTERVAL_DTYPE array, got %r" % (a.dtype,))
+        a = np.ascontiguousarray(a)
+        off = np.ascontiguousarray(np.zeros(0, np.int32) if group_row_off is None else group_row_off, dtype=np.int32)
+        ps = np.ascontiguousarray(np.zeros(0, np.int32) if row_ps is None else row_ps, dtype=np.int32)
+        n_groups = int(n_groups)
+        if off.ndim != 1 or ps.ndim != 1 or n_groups < 0 or len(off) != n_groups:
+            raise TypeError("group_row_off must be one-dimensional with one entry per group, row_ps one-dimensional")
+        group_counts, row_counts = np.zeros((n_groups, 2), dtype=np.uint32), np.zeros((len(ps), 2), dtype=np.uint32)
+        self._chk(self.L.c3r_hap_group_counts(self.h, _ptr(a) if len(a) else None, len(a), n_groups, _ptr(off) if n_groups else None,
+                                              _ptr(ps) if len(ps) else None, len(ps), int(stranded),
+                                              _ptr(group_counts) if n_groups else None, _ptr(row_counts) if len(ps) else None))
+        return group_counts, row_counts
+
+    def set_hap_group_direct(self, on):
+        """c3r_set_hap_group_direct (default off): hap_group_counts runs its kernel without the per-workgroup LDS stage.  Same result."""
+        self._chk(self.L.c3r_set_hap_group_direct(self.h, 1 if on else 0))
+
+    def hap_group_direct(self):
+        """c3r_get_hap_group_direct: whether hap_group_counts runs without its LDS stage."""
+        on = C.c_int(0)
+        self._chk(self.L.c3r_get_hap_group_direct(self.h, C.byref(on)))
+        return bool(on.value)
 
     def hap_junction_counts(self, slots_hint=0):
         """(junctions, rows): every splice junction that a loaded read which passes the current filters holds — an N op [start, end) of its

@@ -32,6 +32,7 @@
 #include "hapcount_kernels.hpp"
 #include "hapregion_kernels.hpp"
 #include "hapjunction_kernels.hpp"
+#include "hapgroup_kernels.hpp"
 #include "qual_kernels.hpp"
 #include <sched.h>
 
@@ -187,6 +188,10 @@ struct c3r_ctx {
     DevBuf d_hcsites, d_hcounts;
     DevBuf d_hasites, d_hapool;               // c3r_hap_allele_counts: its query sites and the pool of inserted bases (the counts share d_hcounts)
     DevBuf d_hrregions, d_hrfirst, d_hrps, d_hrcounts;      // c3r_hap_region_counts: its regions, first_open, row_ps and count table, allocated by the first call and kept
+    // c3r_hap_group_counts: its intervals, first_open, group_row_off, row_ps and count table, allocated by the first call and kept;
+    // c3r_set_hap_group_direct
+    DevBuf d_hgintervals, d_hgfirst, d_hgoff, d_hgps, d_hgcounts;
+    bool hg_direct = false;
     // c3r_hap_junction_counts: the junction table (keys, then [slots][3] counters), the row table (keys, then [slots][2] counters) and the
     // overflow word, allocated by the first call and kept; the compacted, sorted result of the last call (hj_valid: there is one — until the
     // next c3r_load_reads); c3r_set_hap_junction_direct
@@ -922,7 +927,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hrregions, &ctx->d_hrfirst, &ctx->d_hrps, &ctx->d_hrcounts, &ctx->d_hjtab, &ctx->d_hjrows, &ctx->d_hjover, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hrregions, &ctx->d_hrfirst, &ctx->d_hrps, &ctx->d_hrcounts, &ctx->d_hjtab, &ctx->d_hjrows, &ctx->d_hjover, &ctx->d_hgintervals, &ctx->d_hgfirst, &ctx->d_hgoff, &ctx->d_hgps, &ctx->d_hgcounts, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_rowctl, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0, cap = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1437,6 +1442,101 @@ int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t
     if (rc) return rc;
     memcpy(region_counts, table.data(), 2 * (size_t)n * 4);
     if (n_rows) memcpy(row_counts, table.data() + 2 * (size_t)n, 2 * (size_t)n_rows * 4);
+    return C3R_OK;
+}
+
+// The rule `hap_groups` of include/c3r.h: the table's checks, first_open, the bound and every interval's predecessor in its group on the
+// host, then one launch of k_hap_group_counts.
+int c3r_hap_group_counts(c3r_ctx *ctx, const c3r_hap_interval_t *intervals, int64_t n, int64_t n_groups, const int32_t *group_row_off,
+                         const int32_t *row_ps, int64_t n_rows, int32_t stranded, uint32_t *group_counts, uint32_t *row_counts) {
+    if (!ctx || n < 0 || n_groups < 0 || n_rows < 0 || (n && !intervals) || (n_groups && (!group_row_off || !group_counts)) || (n_rows && (!row_ps || !row_counts))) return C3R_EINVAL;
+    if (stranded < 0 || stranded > 2) return fail(ctx, C3R_EINVAL, "c3r_hap_group_counts: stranded %d is not 0 (off), 1 (same) or 2 (reverse)", stranded);
+    if (n >= INT32_MAX / 2 || n_groups >= INT32_MAX / 2 || n_rows >= INT32_MAX / 2) return fail(ctx, C3R_EINVAL, "c3r_hap_group_counts: too many intervals, groups or rows");
+    if (n == 0 && (n_groups != 0 || n_rows != 0)) return fail(ctx, C3R_EINVAL, "c3r_hap_group_counts: %lld groups, %lld rows and no interval", (long long)n_groups, (long long)n_rows);
+    std::vector<DevHapInterval> dev((size_t)n);
+    std::vector<int32_t> first_open((size_t)n), last_of((size_t)n_groups, -1), off((size_t)n_groups + 1);
+    for (int64_t j = 0; j < n; ++j) {
+        const c3r_hap_interval_t &e = intervals[j];
+        if (e.start < 0 || e.start >= e.end) return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) is not a 0-based half-open interval with start < end", (long long)j, e.start, e.end);
+        if (j > 0 && (e.start < intervals[j - 1].start || (e.start == intervals[j - 1].start && e.end < intervals[j - 1].end)))
+            return fail(ctx, C3R_EINVAL, "interval %lld: the table must be sorted by (start, end) ([%d, %d) after [%d, %d))", (long long)j, e.start, e.end, intervals[j - 1].start, intervals[j - 1].end);
+        if (e.strand > 2 || e.reserved[0] || e.reserved[1] || e.reserved[2]) return fail(ctx, C3R_EINVAL, "interval %lld: strand must be 0, 1 or 2 and the reserved bytes 0", (long long)j);
+        if (e.group < 0 || (int64_t)e.group >= n_groups) return fail(ctx, C3R_EINVAL, "interval %lld: group %d is not in [0, %lld)", (long long)j, e.group, (long long)n_groups);
+        // the group's previous interval in table order: starts never decrease and the group's earlier intervals are disjoint, so it holds the
+        // group's largest end, and this interval overlaps one of them iff it starts before that end
+        const int32_t prev = last_of[(size_t)e.group];
+        if (prev >= 0 && intervals[prev].end > e.start)
+            return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) overlaps interval %d, [%d, %d), of the same group %d: the intervals of a group must be disjoint (merge them)",
+                        (long long)j, e.start, e.end, prev, intervals[prev].start, intervals[prev].end, e.group);
+        if (prev >= 0 && intervals[prev].strand != e.strand)
+            return fail(ctx, C3R_EINVAL, "interval %lld: strand %d, and interval %d of the same group %d has strand %d: a group carries one strand", (long long)j, e.strand, prev, e.group, intervals[prev].strand);
+        last_of[(size_t)e.group] = (int32_t)j;
+        // first_open[j]: as c3r_hap_region_counts computes it
+        int64_t f = j > 0 ? first_open[(size_t)j - 1] : 0;
+        while (f < j && intervals[f].end <= e.start) ++f;
+        first_open[(size_t)j] = (int32_t)f;
+        if (j - f > C3R_HAP_REGION_MAX_BACK)
+            return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) starts while interval %lld, %lld entries before it, is still open ([%d, %d)): more than C3R_HAP_REGION_MAX_BACK = %d",
+                        (long long)j, e.start, e.end, (long long)f, (long long)(j - f), intervals[f].start, intervals[f].end, C3R_HAP_REGION_MAX_BACK);
+        DevHapInterval &o = dev[(size_t)j];
+        o.start = e.start; o.end = e.end; o.prev = prev; o.group_strand = ((uint32_t)e.group << 2) | (uint32_t)e.strand;
+    }
+    for (int64_t g = 0; g < n_groups; ++g) {
+        if (last_of[(size_t)g] < 0) return fail(ctx, C3R_EINVAL, "group %lld: no interval of the table belongs to it", (long long)g);
+        const int32_t lo = group_row_off[g];
+        if ((g == 0 ? lo != 0 : lo < group_row_off[g - 1]) || (int64_t)lo > n_rows)
+            return fail(ctx, C3R_EINVAL, "group %lld: group_row_off %d must start at 0, never decrease and stay within the %lld rows", (long long)g, lo, (long long)n_rows);
+        // (the next group's offset is checked when its turn comes: until then only its use as this group's end has to be safe)
+        const int64_t row_end = g + 1 < n_groups ? std::min<int64_t>(std::max<int64_t>(group_row_off[g + 1], lo), n_rows) : n_rows;
+        if (row_end - lo >= (1 << 24)) return fail(ctx, C3R_EINVAL, "group %lld: %lld rows are more than a group takes (2^24 - 1)", (long long)g, (long long)(row_end - lo));
+        for (int64_t r = lo; r < row_end; ++r) {
+            if (row_ps[r] < 0) return fail(ctx, C3R_EINVAL, "row %lld (group %lld): phase set %d is negative", (long long)r, (long long)g, row_ps[r]);
+            if (r > lo && row_ps[r] <= row_ps[r - 1])
+                return fail(ctx, C3R_EINVAL, "row %lld (group %lld): phase sets must be strictly increasing inside a group (%d after %d)", (long long)r, (long long)g, row_ps[r], row_ps[r - 1]);
+        }
+        off[(size_t)g] = lo;
+    }
+    off[(size_t)n_groups] = (int32_t)n_rows;
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
+    if (n == 0) return C3R_OK;
+    const size_t words = 2 * (size_t)n_groups + 2 * (size_t)n_rows;
+    if (ctx->n_reads == 0) {                                           // (no voters: nothing to launch)
+        memset(group_counts, 0, 2 * (size_t)n_groups * 4);
+        if (n_rows) memset(row_counts, 0, 2 * (size_t)n_rows * 4);
+        return C3R_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HapGroupArgs a = read_args<HapGroupArgs>(ctx, ctx->n_reads);
+    int rc;
+    if ((rc = upload(ctx, ctx->d_hgintervals, dev.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_hgfirst, first_open.data(), (size_t)n)) ||
+        (rc = upload(ctx, ctx->d_hgoff, off.data(), off.size())) || (rc = upload(ctx, ctx->d_hgps, row_ps, (size_t)n_rows))) return rc;
+    a.intervals = (const DevHapInterval *)ctx->d_hgintervals.p; a.n_intervals = (int32_t)n; a.first_open = (const int32_t *)ctx->d_hgfirst.p;
+    a.group_row_off = (const int32_t *)ctx->d_hgoff.p; a.row_ps = (const int32_t *)ctx->d_hgps.p; a.n_groups = (int32_t)n_groups;
+    a.stranded = stranded;
+    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    std::vector<uint32_t> table(words);
+    rc = counter_table(ctx, ctx->d_hgcounts, words, table.data(), [&](uint32_t *t) {
+        a.counts = t;
+        if (ctx->hg_direct) launch_per_read(ctx, "k_hap_group_counts_direct", k_hap_group_counts<false>, a);
+        else launch_per_read(ctx, "k_hap_group_counts", k_hap_group_counts<true>, a);
+    });
+    if (rc) return rc;
+    memcpy(group_counts, table.data(), 2 * (size_t)n_groups * 4);
+    if (n_rows) memcpy(row_counts, table.data() + 2 * (size_t)n_groups, 2 * (size_t)n_rows * 4);
+    return C3R_OK;
+}
+
+int c3r_set_hap_group_direct(c3r_ctx *ctx, int on) {
+    if (!ctx) return C3R_EINVAL;
+    if (on != 0 && on != 1) return fail(ctx, C3R_EINVAL, "c3r_set_hap_group_direct: %d is neither 0 nor 1", on);
+    ctx->hg_direct = on != 0;
+    return C3R_OK;
+}
+
+int c3r_get_hap_group_direct(c3r_ctx *ctx, int *on) {
+    if (!ctx || !on) return C3R_EINVAL;
+    *on = ctx->hg_direct ? 1 : 0;
     return C3R_OK;
 }
 

@@ -585,12 +585,52 @@ int c3r_get_haplotag_words(c3r_ctx *ctx, uint32_t *words, int64_t cap);
  * first_open and row_ps into buffers of its own, clears one device table of 2 n + 2 n_rows words, runs k_hap_region_counts
  * (csrc/hapregion_kernels.hpp) on the context's stream and reads the table back.  It changes neither the reads' haplotags and phase sets,
  * nor the phase table, nor anything a scan or another count table reads.  Its device buffers are allocated at the first call and kept.
- * Not done: no union of a gene's exon rows (a read over two exons of one gene counts in both), no fractional assignment of a read that
- * overlaps several regions, no statistics (no test of allelic imbalance); agreement with featureCounts / htseq-count is not measured. */
+ * Not done: no union of a gene's exon rows here (a read over two exons of one gene counts in both: the gene-level count is the rule
+ * `hap_groups` below, c3r_hap_group_counts), no fractional assignment of a read that overlaps several regions, no statistics (no test of
+ * allelic imbalance); agreement with featureCounts / htseq-count is not measured. */
 #define C3R_HAP_REGION_MAX_BACK 4096
 typedef struct { int32_t start, end, row_off; uint8_t strand, reserved[3]; } c3r_hap_region_t;
 int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t n, const int32_t *row_ps, int64_t n_rows, int32_t stranded,
                           uint32_t *region_counts, uint32_t *row_counts);
+
+/* Haplotype-resolved read counts per GROUP of intervals (the rule `hap_groups`): the gene-level count — a gene is the group of its exons,
+ * and a read counts once per gene it overlaps, however many of the gene's exons it lies over.  Voters, overlap, strand and (tag, set) are
+ * those of `hap_regions` above.  Opt-in: nothing calls it unless asked (hap_expr --group_by_name, call_sample
+ * --hap_expression_group_by_name).
+ *
+ * Inputs.  intervals[n]: start, end 0-based half-open with start < end, sorted by (start, end); group in [0, n_groups); strand 0 none,
+ * 1 `+`, 2 `-`; reserved = 0.  The intervals of one group are pairwise disjoint (abutting is allowed) and carry one strand; intervals of
+ * different groups may overlap, nest or be equal; every group has at least one interval.  The rows of group g are
+ * row_ps[group_row_off[g] .. group_row_off[g + 1]), the last group's end at n_rows (group_row_off: [n_groups], 0 at group 0, never
+ * decreasing, never above n_rows); phase-set numbers >= 0, strictly increasing inside one group.  stranded: 0 off, 1 same, 2 reverse.
+ * Counting.  A voter counts in group g exactly once iff at least one reference position under one of its M-like or D ops lies in at least
+ * one interval of g that the strand test of `hap_regions` admits (one strand per group: it admits all of g's intervals or none).  How many
+ * ops and how many of the group's intervals are involved does not matter; a read that lies only in the group's introns is not in it.
+ * Where the one count goes.  Tag 0: group_counts[g][0] (untagged).  Tag 1 or 2 and the set is row r of g: row_counts[r][tag - 1].  Tag 1
+ * or 2 and the set is none of g's rows: group_counts[g][1] (tagged in another set).
+ * Output: group_counts uint32 [n_groups][2], row_counts uint32 [n_rows][2]; integer sums, neither read order nor arrival order shows.
+ * With every interval a group of its own the two tables are c3r_hap_region_counts' tables element for element.
+ *
+ * c3r_hap_group_counts needs a phase table (C3R_EINVAL without one, whatever n is); n = 0 (then n_groups = 0 and n_rows = 0) succeeds and
+ * launches nothing; no reads loaded: every count is 0 and nothing is launched.  C3R_EINVAL, naming the first bad interval, group or row,
+ * for start >= end, start < 0, an unsorted table, a strand above 2, a non-zero reserved byte, a group id outside [0, n_groups), two
+ * intervals of one group that overlap, two strands in one group, a group without an interval, a group_row_off that is not 0 at group 0,
+ * decreases or exceeds n_rows, a group of 2^24 rows or more, a negative ps, ps not strictly increasing inside a group, stranded outside
+ * 0 .. 2 and an interval table over C3R_HAP_REGION_MAX_BACK (the bound of `hap_regions`, on the interval table).  The library computes
+ * first_open and, per interval, the previous interval of its group in table order; it uploads them with the rows into buffers of its own,
+ * clears one device table of 2 n_groups + 2 n_rows words, runs k_hap_group_counts (csrc/hapgroup_kernels.hpp) on the context's stream and
+ * reads the table back.  It changes neither the reads' haplotags and phase sets, nor the phase table, nor anything a scan or another count
+ * table reads.  Its device buffers are allocated at the first call and kept.
+ * c3r_set_hap_group_direct(ctx, on): default 0; anything but 0 or 1 is C3R_EINVAL.  0: the counts of a workgroup's reads are summed in LDS
+ * first and every touched word gets one global add per workgroup.  1: the same kernel body without the LDS stage, one global add per
+ * (read, group).  The results are identical.  c3r_get_hap_group_direct reads the switch.
+ * Not done: no GTF reader (the groups come from the caller), no fractional assignment of a read that lies in several genes (it counts once
+ * in each), no statistics (no test of allelic imbalance); agreement with featureCounts / htseq-count is not measured. */
+typedef struct { int32_t start, end, group; uint8_t strand, reserved[3]; } c3r_hap_interval_t;
+int c3r_hap_group_counts(c3r_ctx *ctx, const c3r_hap_interval_t *intervals, int64_t n, int64_t n_groups, const int32_t *group_row_off,
+                         const int32_t *row_ps, int64_t n_rows, int32_t stranded, uint32_t *group_counts, uint32_t *row_counts);
+int c3r_set_hap_group_direct(c3r_ctx *ctx, int on);
+int c3r_get_hap_group_direct(c3r_ctx *ctx, int *on);
 
 /* Haplotype-resolved splice-junction counts (the rule `hap_junctions`): which haplotype uses which intron — per junction that the loaded
  * reads hold, how many reads hold it, and per phase set how many of them carry each haplotype.  Allele-specific splicing from the tags the
