@@ -187,10 +187,9 @@ struct c3r_ctx {
     // per-haplotype allele counts (c3r_hap_counts): the query sites and their count table, allocated by the first call and kept
     DevBuf d_hcsites, d_hcounts;
     DevBuf d_hasites, d_hapool;               // c3r_hap_allele_counts: its query sites and the pool of inserted bases (the counts share d_hcounts)
-    DevBuf d_hrregions, d_hrfirst, d_hrps, d_hrcounts;      // c3r_hap_region_counts: its regions, first_open, row_ps and count table, allocated by the first call and kept
-    // c3r_hap_group_counts: its intervals, first_open, group_row_off, row_ps and count table, allocated by the first call and kept;
-    // c3r_set_hap_group_direct
-    DevBuf d_hgintervals, d_hgfirst, d_hgoff, d_hgps, d_hgcounts;
+    // c3r_hap_region_counts and c3r_hap_group_counts (hap_interval_table): the table's entries, first_open, the groups' row offsets, row_ps
+    // and the count table of whichever call came last, allocated by the first call and kept; c3r_set_hap_group_direct
+    DevBuf d_hientries, d_hifirst, d_hioff, d_hips, d_hicounts;
     bool hg_direct = false;
     // c3r_hap_junction_counts: the junction table (keys, then [slots][3] counters), the row table (keys, then [slots][2] counters) and the
     // overflow word, allocated by the first call and kept; the compacted, sorted result of the last call (hj_valid: there is one — until the
@@ -588,6 +587,81 @@ int hap_count_table(c3r_ctx *ctx, const char *label, void (*kernel)(Args), int64
     return counter_table(ctx, ctx->d_hcounts, words, counts, [&](uint32_t *t) { a.counts = t; launch_per_read(ctx, label, kernel, a); });
 }
 
+// ---- c3r_hap_region_counts and c3r_hap_group_counts: what the two calls check of a sorted interval table, and everything behind the checks
+// Entry j of the caller's table (`noun`: what a message calls an entry): a half-open interval, sorted by (start, end), a strand, reserved
+// bytes of 0; then own_checks(), what the call asks of the entry beyond that; then first_open[j] and its bound (`advice`: the end of that
+// refusal).
+template <class Entry, class Own>
+int check_interval(c3r_ctx *ctx, const char *noun, const char *advice, const Entry *v, int64_t j, std::vector<int32_t> &first_open, Own &&own_checks) {
+    const Entry &e = v[j];
+    if (e.start < 0 || e.start >= e.end) return fail(ctx, C3R_EINVAL, "%s %lld: [%d, %d) is not a 0-based half-open interval with start < end", noun, (long long)j, e.start, e.end);
+    if (j > 0 && (e.start < v[j - 1].start || (e.start == v[j - 1].start && e.end < v[j - 1].end)))
+        return fail(ctx, C3R_EINVAL, "%s %lld: the table must be sorted by (start, end) ([%d, %d) after [%d, %d))", noun, (long long)j, e.start, e.end, v[j - 1].start, v[j - 1].end);
+    if (e.strand > 2 || e.reserved[0] || e.reserved[1] || e.reserved[2]) return fail(ctx, C3R_EINVAL, "%s %lld: strand must be 0, 1 or 2 and the reserved bytes 0", noun, (long long)j);
+    if (int rc = own_checks()) return rc;
+    // first_open[j]: starts never decrease, so an entry closed at start_(j - 1) stays closed and first_open never decreases either: on from
+    // first_open[j - 1] to the first entry whose end lies behind this start (n + the table's length steps in all)
+    int64_t f = j > 0 ? first_open[(size_t)j - 1] : 0;
+    while (f < j && v[f].end <= e.start) ++f;
+    first_open[(size_t)j] = (int32_t)f;
+    if (j - f > C3R_HAP_REGION_MAX_BACK)
+        return fail(ctx, C3R_EINVAL, "%s %lld: [%d, %d) starts while %s %lld, %lld entries before it, is still open ([%d, %d)): more than C3R_HAP_REGION_MAX_BACK = %d%s",
+                    noun, (long long)j, e.start, e.end, noun, (long long)f, (long long)(j - f), v[f].start, v[f].end, C3R_HAP_REGION_MAX_BACK, advice);
+    return C3R_OK;
+}
+
+// The rows of owner g of n_owners (`noun`: a region or a group; `off_name`: what the caller calls off(g), the owner's first row): offsets
+// that start at 0 and never decrease, fewer than 2^24 rows, phase sets that are not negative and strictly increasing.  -> *row_end.
+template <class Off>
+int check_row_run(c3r_ctx *ctx, const char *noun, const char *off_name, Off &&off, int64_t g, int64_t n_owners, const int32_t *row_ps, int64_t n_rows, int64_t *row_end) {
+    const int32_t lo = off(g);
+    if ((g == 0 ? lo != 0 : lo < off(g - 1)) || (int64_t)lo > n_rows)
+        return fail(ctx, C3R_EINVAL, "%s %lld: %s %d must start at 0, never decrease and stay within the %lld rows", noun, (long long)g, off_name, lo, (long long)n_rows);
+    // (the next owner's offset is checked when its turn comes: until then only its use as this owner's end has to be safe)
+    const int64_t top = g + 1 < n_owners ? std::min<int64_t>(std::max<int64_t>(off(g + 1), lo), n_rows) : n_rows;
+    if (top - lo >= (1 << 24)) return fail(ctx, C3R_EINVAL, "%s %lld: %lld rows are more than a %s takes (2^24 - 1)", noun, (long long)g, (long long)(top - lo), noun);
+    for (int64_t r = lo; r < top; ++r) {
+        if (row_ps[r] < 0) return fail(ctx, C3R_EINVAL, "row %lld (%s %lld): phase set %d is negative", (long long)r, noun, (long long)g, row_ps[r]);
+        if (r > lo && row_ps[r] <= row_ps[r - 1])
+            return fail(ctx, C3R_EINVAL, "row %lld (%s %lld): phase sets must be strictly increasing inside a %s (%d after %d)", (long long)r, noun, (long long)g, noun, row_ps[r], row_ps[r - 1]);
+    }
+    *row_end = top;
+    return C3R_OK;
+}
+
+// Both calls once their table is checked: the counts of the n_owners owners and n_rows rows by the tags of the phase table that is set.
+// `dev`: the entries as the kernel loads them; `off`: the owners' row offsets where the kernel reads them from an array of their own
+// (d_hioff), else empty.  launch(args) sets what its kernel takes beyond HapIntervalArgs and launches it.  One set of buffers serves both
+// calls: each waits for the device before it returns (counter_table).
+template <class Args, class DevEntry, class LaunchOn>
+int hap_interval_table(c3r_ctx *ctx, const std::vector<DevEntry> &dev, const std::vector<int32_t> &first_open, const std::vector<int32_t> &off, const int32_t *row_ps,
+                       int64_t n_owners, int64_t n_rows, int32_t stranded, uint32_t *owner_counts, uint32_t *row_counts, LaunchOn &&launch) {
+    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
+    const size_t n = dev.size();
+    if (n == 0) return C3R_OK;
+    const size_t owner_words = 2 * (size_t)n_owners, row_words = 2 * (size_t)n_rows;
+    if (ctx->n_reads == 0) {                                           // (no voters: nothing to launch)
+        memset(owner_counts, 0, owner_words * 4);
+        if (n_rows) memset(row_counts, 0, row_words * 4);
+        return C3R_OK;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Args a = read_args<Args>(ctx, ctx->n_reads);
+    int rc;
+    if ((rc = upload(ctx, ctx->d_hientries, dev.data(), n)) || (rc = upload(ctx, ctx->d_hifirst, first_open.data(), n)) ||
+        (rc = upload(ctx, ctx->d_hioff, off.data(), off.size())) || (rc = upload(ctx, ctx->d_hips, row_ps, (size_t)n_rows))) return rc;
+    a.entries = (const DevEntry *)ctx->d_hientries.p; a.n_entries = (int32_t)n; a.first_open = (const int32_t *)ctx->d_hifirst.p;
+    a.row_ps = (const int32_t *)ctx->d_hips.p; a.n_owners = (int32_t)n_owners; a.stranded = stranded;
+    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
+    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
+    std::vector<uint32_t> table(owner_words + row_words);
+    rc = counter_table(ctx, ctx->d_hicounts, table.size(), table.data(), [&](uint32_t *t) { a.counts = t; launch(a); });
+    if (rc) return rc;
+    memcpy(owner_counts, table.data(), owner_words * 4);
+    if (n_rows) memcpy(row_counts, table.data() + owner_words, row_words * 4);
+    return C3R_OK;
+}
+
 }  // namespace
 static int device_excl_scan(c3r_ctx *ctx, int32_t *d, int n, int32_t *d_total);
 namespace {
@@ -927,7 +1001,7 @@ void c3r_destroy(c3r_ctx *ctx) {
     const auto t0 = std::chrono::steady_clock::now();
     DevBuf *bufs[] = {&ctx->d_wgtab, &ctx->d_rawreads, &ctx->d_rawcig, &ctx->d_bincnt, &ctx->d_binoff, &ctx->d_rtab, &ctx->d_recs, &ctx->d_serial, &ctx->d_nind, &ctx->d_lbk, &ctx->d_lcnt, &ctx->d_tokexp, &ctx->d_tokoff,
                       &ctx->d_stats, &ctx->d_lb, &ctx->d_regb, &ctx->d_span, &ctx->d_spanbase, &ctx->d_meta, &ctx->d_spanrec, &ctx->d_deep, &ctx->d_evwg, &ctx->d_giant, &ctx->d_giant_ev, &ctx->d_giant_tab, &ctx->d_winidx, &ctx->d_rawidx, &ctx->d_export, &ctx->d_dbg, &ctx->d_tile_cand, &ctx->d_reads, &ctx->d_cigar, &ctx->d_seq, &ctx->d_prefmax, &ctx->d_tile_cols, &ctx->d_tile_rng, &ctx->d_tile_list, &ctx->d_tile_list2, &ctx->d_rsegs, &ctx->d_rseg_first, &ctx->d_ref, &ctx->d_bed[0], &ctx->d_bed[1],
-                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hrregions, &ctx->d_hrfirst, &ctx->d_hrps, &ctx->d_hrcounts, &ctx->d_hjtab, &ctx->d_hjrows, &ctx->d_hjover, &ctx->d_hgintervals, &ctx->d_hgfirst, &ctx->d_hgoff, &ctx->d_hgps, &ctx->d_hgcounts, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
+                      &ctx->d_sites, &ctx->d_phase, &ctx->d_phasea, &ctx->d_phasepool, &ctx->d_qual, &ctx->d_hapseq, &ctx->d_nmasked, &ctx->d_hpw, &ctx->d_hptag, &ctx->d_hpps, &ctx->d_hcsites, &ctx->d_hcounts, &ctx->d_hasites, &ctx->d_hapool, &ctx->d_hientries, &ctx->d_hifirst, &ctx->d_hioff, &ctx->d_hips, &ctx->d_hicounts, &ctx->d_hjtab, &ctx->d_hjrows, &ctx->d_hjover, &ctx->d_pasites, &ctx->d_papool, &ctx->d_plsites, &ctx->d_links, &ctx->d_unitof, &ctx->d_cols, &ctx->d_depth, &ctx->d_ncov, &ctx->d_flags, &ctx->d_skipmax, &ctx->d_geo, &ctx->d_lastrow, &ctx->d_drop, &ctx->d_ev, &ctx->d_small,
                       &ctx->d_blockcnt, &ctx->d_scan_tops, &ctx->d_cand, &ctx->d_tensors, &ctx->d_raw, &ctx->d_sites_out, &ctx->d_tokcnt, &ctx->d_tok, &ctx->d_tokb, &ctx->d_tokrec, &ctx->d_recoff, &ctx->d_rowctl, &ctx->d_padins, &ctx->d_aftab, &ctx->d_keep, &ctx->d_sites_c, &ctx->d_probs_c};
     int n_dev = 0; size_t b_dev = 0, b_pin = 0, cap = 0;
     for (DevBuf *b : bufs) if (b->p) { (void)hipFree(b->p); ++n_dev; b_dev += b->cap; }
@@ -1393,56 +1467,15 @@ int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t
     std::vector<int32_t> first_open((size_t)n);
     for (int64_t j = 0; j < n; ++j) {
         const c3r_hap_region_t &e = regions[j];
-        if (e.start < 0 || e.start >= e.end) return fail(ctx, C3R_EINVAL, "region %lld: [%d, %d) is not a 0-based half-open interval with start < end", (long long)j, e.start, e.end);
-        if (j > 0 && (e.start < regions[j - 1].start || (e.start == regions[j - 1].start && e.end < regions[j - 1].end)))
-            return fail(ctx, C3R_EINVAL, "region %lld: the table must be sorted by (start, end) ([%d, %d) after [%d, %d))", (long long)j, e.start, e.end, regions[j - 1].start, regions[j - 1].end);
-        if (e.strand > 2 || e.reserved[0] || e.reserved[1] || e.reserved[2]) return fail(ctx, C3R_EINVAL, "region %lld: strand must be 0, 1 or 2 and the reserved bytes 0", (long long)j);
-        if ((j == 0 ? e.row_off != 0 : e.row_off < regions[j - 1].row_off) || (int64_t)e.row_off > n_rows)
-            return fail(ctx, C3R_EINVAL, "region %lld: row_off %d must start at 0, never decrease and stay within the %lld rows", (long long)j, e.row_off, (long long)n_rows);
-        // (the next region's row_off is checked when its turn comes: until then only its use as this region's end has to be safe)
-        const int64_t row_end = j + 1 < n ? std::min<int64_t>(std::max<int64_t>(regions[j + 1].row_off, e.row_off), n_rows) : n_rows;
-        if (row_end - e.row_off >= (1 << 24)) return fail(ctx, C3R_EINVAL, "region %lld: %lld rows are more than a region takes (2^24 - 1)", (long long)j, (long long)(row_end - e.row_off));
-        for (int64_t r = e.row_off; r < row_end; ++r) {
-            if (row_ps[r] < 0) return fail(ctx, C3R_EINVAL, "row %lld (region %lld): phase set %d is negative", (long long)r, (long long)j, row_ps[r]);
-            if (r > e.row_off && row_ps[r] <= row_ps[r - 1])
-                return fail(ctx, C3R_EINVAL, "row %lld (region %lld): phase sets must be strictly increasing inside a region (%d after %d)", (long long)r, (long long)j, row_ps[r], row_ps[r - 1]);
-        }
-        // first_open[j]: starts never decrease, so a region closed at start_(j - 1) stays closed and first_open never decreases either:
-        // on from first_open[j - 1] to the first region whose end lies behind this start (n + the table's length steps in all)
-        int64_t f = j > 0 ? first_open[(size_t)j - 1] : 0;
-        while (f < j && regions[f].end <= e.start) ++f;
-        first_open[(size_t)j] = (int32_t)f;
-        if (j - f > C3R_HAP_REGION_MAX_BACK)
-            return fail(ctx, C3R_EINVAL, "region %lld: [%d, %d) starts while region %lld, %lld entries before it, is still open ([%d, %d)): more than C3R_HAP_REGION_MAX_BACK = %d; "
-                        "count long and short regions (genes and exons) in separate calls", (long long)j, e.start, e.end, (long long)f, (long long)(j - f), regions[f].start, regions[f].end, C3R_HAP_REGION_MAX_BACK);
+        int64_t row_end = 0;
+        if (int rc = check_interval(ctx, "region", "; count long and short regions (genes and exons) in separate calls", regions, j, first_open, [&] {
+                return check_row_run(ctx, "region", "row_off", [&](int64_t g) { return regions[g].row_off; }, j, n, row_ps, n_rows, &row_end);
+            })) return rc;
         DevHapRegion &o = dev[(size_t)j];
         o.start = e.start; o.end = e.end; o.row_off = e.row_off; o.strand_rows = (uint32_t)e.strand | ((uint32_t)(row_end - e.row_off) << 8);
     }
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
-    if (n == 0) return C3R_OK;
-    const size_t words = 2 * (size_t)n + 2 * (size_t)n_rows;
-    if (ctx->n_reads == 0) {                                           // (no voters: nothing to launch)
-        memset(region_counts, 0, 2 * (size_t)n * 4);
-        if (n_rows) memset(row_counts, 0, 2 * (size_t)n_rows * 4);
-        return C3R_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HapRegionArgs a = read_args<HapRegionArgs>(ctx, ctx->n_reads);
-    int rc;
-    if ((rc = upload(ctx, ctx->d_hrregions, dev.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_hrfirst, first_open.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_hrps, row_ps, (size_t)n_rows))) return rc;
-    a.regions = (const DevHapRegion *)ctx->d_hrregions.p; a.n_regions = (int32_t)n; a.first_open = (const int32_t *)ctx->d_hrfirst.p; a.row_ps = (const int32_t *)ctx->d_hrps.p;
-    a.stranded = stranded;
-    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
-    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
-    std::vector<uint32_t> table(words);
-    rc = counter_table(ctx, ctx->d_hrcounts, words, table.data(), [&](uint32_t *t) {
-        a.region_counts = t; a.row_counts = t + 2 * (size_t)n;
-        launch_per_read(ctx, "k_hap_region_counts", k_hap_region_counts, a);
-    });
-    if (rc) return rc;
-    memcpy(region_counts, table.data(), 2 * (size_t)n * 4);
-    if (n_rows) memcpy(row_counts, table.data() + 2 * (size_t)n, 2 * (size_t)n_rows * 4);
-    return C3R_OK;
+    return hap_interval_table<HapRegionArgs>(ctx, dev, first_open, {}, row_ps, n, n_rows, stranded, region_counts, row_counts,
+                                             [&](const HapRegionArgs &a) { launch_per_read(ctx, "k_hap_region_counts", k_hap_region_counts, a); });
 }
 
 // The rule `hap_groups` of include/c3r.h: the table's checks, first_open, the bound and every interval's predecessor in its group on the
@@ -1457,74 +1490,35 @@ int c3r_hap_group_counts(c3r_ctx *ctx, const c3r_hap_interval_t *intervals, int6
     std::vector<int32_t> first_open((size_t)n), last_of((size_t)n_groups, -1), off((size_t)n_groups + 1);
     for (int64_t j = 0; j < n; ++j) {
         const c3r_hap_interval_t &e = intervals[j];
-        if (e.start < 0 || e.start >= e.end) return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) is not a 0-based half-open interval with start < end", (long long)j, e.start, e.end);
-        if (j > 0 && (e.start < intervals[j - 1].start || (e.start == intervals[j - 1].start && e.end < intervals[j - 1].end)))
-            return fail(ctx, C3R_EINVAL, "interval %lld: the table must be sorted by (start, end) ([%d, %d) after [%d, %d))", (long long)j, e.start, e.end, intervals[j - 1].start, intervals[j - 1].end);
-        if (e.strand > 2 || e.reserved[0] || e.reserved[1] || e.reserved[2]) return fail(ctx, C3R_EINVAL, "interval %lld: strand must be 0, 1 or 2 and the reserved bytes 0", (long long)j);
-        if (e.group < 0 || (int64_t)e.group >= n_groups) return fail(ctx, C3R_EINVAL, "interval %lld: group %d is not in [0, %lld)", (long long)j, e.group, (long long)n_groups);
-        // the group's previous interval in table order: starts never decrease and the group's earlier intervals are disjoint, so it holds the
-        // group's largest end, and this interval overlaps one of them iff it starts before that end
-        const int32_t prev = last_of[(size_t)e.group];
-        if (prev >= 0 && intervals[prev].end > e.start)
-            return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) overlaps interval %d, [%d, %d), of the same group %d: the intervals of a group must be disjoint (merge them)",
-                        (long long)j, e.start, e.end, prev, intervals[prev].start, intervals[prev].end, e.group);
-        if (prev >= 0 && intervals[prev].strand != e.strand)
-            return fail(ctx, C3R_EINVAL, "interval %lld: strand %d, and interval %d of the same group %d has strand %d: a group carries one strand", (long long)j, e.strand, prev, e.group, intervals[prev].strand);
-        last_of[(size_t)e.group] = (int32_t)j;
-        // first_open[j]: as c3r_hap_region_counts computes it
-        int64_t f = j > 0 ? first_open[(size_t)j - 1] : 0;
-        while (f < j && intervals[f].end <= e.start) ++f;
-        first_open[(size_t)j] = (int32_t)f;
-        if (j - f > C3R_HAP_REGION_MAX_BACK)
-            return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) starts while interval %lld, %lld entries before it, is still open ([%d, %d)): more than C3R_HAP_REGION_MAX_BACK = %d",
-                        (long long)j, e.start, e.end, (long long)f, (long long)(j - f), intervals[f].start, intervals[f].end, C3R_HAP_REGION_MAX_BACK);
+        int32_t prev = -1;
+        if (int rc = check_interval(ctx, "interval", "", intervals, j, first_open, [&] {
+                if (e.group < 0 || (int64_t)e.group >= n_groups) return fail(ctx, C3R_EINVAL, "interval %lld: group %d is not in [0, %lld)", (long long)j, e.group, (long long)n_groups);
+                // the group's previous interval in table order: starts never decrease and the group's earlier intervals are disjoint, so it
+                // holds the group's largest end, and this interval overlaps one of them iff it starts before that end
+                prev = last_of[(size_t)e.group];
+                if (prev >= 0 && intervals[prev].end > e.start)
+                    return fail(ctx, C3R_EINVAL, "interval %lld: [%d, %d) overlaps interval %d, [%d, %d), of the same group %d: the intervals of a group must be disjoint (merge them)",
+                                (long long)j, e.start, e.end, prev, intervals[prev].start, intervals[prev].end, e.group);
+                if (prev >= 0 && intervals[prev].strand != e.strand)
+                    return fail(ctx, C3R_EINVAL, "interval %lld: strand %d, and interval %d of the same group %d has strand %d: a group carries one strand", (long long)j, e.strand, prev, e.group, intervals[prev].strand);
+                last_of[(size_t)e.group] = (int32_t)j;
+                return (int)C3R_OK;
+            })) return rc;
         DevHapInterval &o = dev[(size_t)j];
         o.start = e.start; o.end = e.end; o.prev = prev; o.group_strand = ((uint32_t)e.group << 2) | (uint32_t)e.strand;
     }
     for (int64_t g = 0; g < n_groups; ++g) {
         if (last_of[(size_t)g] < 0) return fail(ctx, C3R_EINVAL, "group %lld: no interval of the table belongs to it", (long long)g);
-        const int32_t lo = group_row_off[g];
-        if ((g == 0 ? lo != 0 : lo < group_row_off[g - 1]) || (int64_t)lo > n_rows)
-            return fail(ctx, C3R_EINVAL, "group %lld: group_row_off %d must start at 0, never decrease and stay within the %lld rows", (long long)g, lo, (long long)n_rows);
-        // (the next group's offset is checked when its turn comes: until then only its use as this group's end has to be safe)
-        const int64_t row_end = g + 1 < n_groups ? std::min<int64_t>(std::max<int64_t>(group_row_off[g + 1], lo), n_rows) : n_rows;
-        if (row_end - lo >= (1 << 24)) return fail(ctx, C3R_EINVAL, "group %lld: %lld rows are more than a group takes (2^24 - 1)", (long long)g, (long long)(row_end - lo));
-        for (int64_t r = lo; r < row_end; ++r) {
-            if (row_ps[r] < 0) return fail(ctx, C3R_EINVAL, "row %lld (group %lld): phase set %d is negative", (long long)r, (long long)g, row_ps[r]);
-            if (r > lo && row_ps[r] <= row_ps[r - 1])
-                return fail(ctx, C3R_EINVAL, "row %lld (group %lld): phase sets must be strictly increasing inside a group (%d after %d)", (long long)r, (long long)g, row_ps[r], row_ps[r - 1]);
-        }
-        off[(size_t)g] = lo;
+        int64_t row_end;
+        if (int rc = check_row_run(ctx, "group", "group_row_off", [&](int64_t k) { return group_row_off[k]; }, g, n_groups, row_ps, n_rows, &row_end)) return rc;
+        off[(size_t)g] = group_row_off[g];
     }
     off[(size_t)n_groups] = (int32_t)n_rows;
-    if (ctx->n_phase == 0) return fail(ctx, C3R_EINVAL, "no phase sites are set (c3r_set_phase_sites / c3r_set_phase_alleles): the reads carry no tags to count by");
-    if (n == 0) return C3R_OK;
-    const size_t words = 2 * (size_t)n_groups + 2 * (size_t)n_rows;
-    if (ctx->n_reads == 0) {                                           // (no voters: nothing to launch)
-        memset(group_counts, 0, 2 * (size_t)n_groups * 4);
-        if (n_rows) memset(row_counts, 0, 2 * (size_t)n_rows * 4);
-        return C3R_OK;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HapGroupArgs a = read_args<HapGroupArgs>(ctx, ctx->n_reads);
-    int rc;
-    if ((rc = upload(ctx, ctx->d_hgintervals, dev.data(), (size_t)n)) || (rc = upload(ctx, ctx->d_hgfirst, first_open.data(), (size_t)n)) ||
-        (rc = upload(ctx, ctx->d_hgoff, off.data(), off.size())) || (rc = upload(ctx, ctx->d_hgps, row_ps, (size_t)n_rows))) return rc;
-    a.intervals = (const DevHapInterval *)ctx->d_hgintervals.p; a.n_intervals = (int32_t)n; a.first_open = (const int32_t *)ctx->d_hgfirst.p;
-    a.group_row_off = (const int32_t *)ctx->d_hgoff.p; a.row_ps = (const int32_t *)ctx->d_hgps.p; a.n_groups = (int32_t)n_groups;
-    a.stranded = stranded;
-    a.tags = (const uint32_t *)ctx->d_hptag.p; a.read_ps = (const int32_t *)ctx->d_hpps.p;
-    a.min_mq = ctx->prm.min_mq; a.excl_flags = ctx->prm.excl_flags;
-    std::vector<uint32_t> table(words);
-    rc = counter_table(ctx, ctx->d_hgcounts, words, table.data(), [&](uint32_t *t) {
-        a.counts = t;
+    return hap_interval_table<HapGroupArgs>(ctx, dev, first_open, off, row_ps, n_groups, n_rows, stranded, group_counts, row_counts, [&](HapGroupArgs &a) {
+        a.group_row_off = (const int32_t *)ctx->d_hioff.p;
         if (ctx->hg_direct) launch_per_read(ctx, "k_hap_group_counts_direct", k_hap_group_counts<false>, a);
         else launch_per_read(ctx, "k_hap_group_counts", k_hap_group_counts<true>, a);
     });
-    if (rc) return rc;
-    memcpy(group_counts, table.data(), 2 * (size_t)n_groups * 4);
-    if (n_rows) memcpy(row_counts, table.data() + 2 * (size_t)n_groups, 2 * (size_t)n_rows * 4);
-    return C3R_OK;
 }
 
 int c3r_set_hap_group_direct(c3r_ctx *ctx, int on) {

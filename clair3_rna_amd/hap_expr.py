@@ -115,16 +115,21 @@ def count_regions(eng, regions, pos, ps, stranded=0):
     return out
 
 
-def region_lines(ctg, regions, counted):
-    """The TSV lines of one contig; counted: count_regions' list, or None when nothing was launched."""
+def count_lines(heads, counted):
+    """The TSV lines of one contig from every owner's leading columns: per owner its summary line, then a line per row.  counted: the list
+    of count_regions or count_groups, or None when nothing was launched."""
     lines = []
-    for j, (start, end, name, strand) in enumerate(regions):
-        head = [ctg, str(start), str(end), name, strand or "."]
+    for j, head in enumerate(heads):
         (untagged, other), rows = counted[j] if counted is not None else ((".", "."), [])
         lines.append("\t".join(head + [".", ".", ".", str(untagged), str(other)]))
         for ps, h1, h2 in rows:
             lines.append("\t".join(head + [str(ps), str(h1), str(h2), ".", "."]))
     return lines
+
+
+def region_lines(ctg, regions, counted):
+    """The TSV lines of one contig; counted: count_regions' list, or None when nothing was launched."""
+    return count_lines([[ctg, str(start), str(end), name, strand or "."] for start, end, name, strand in regions], counted)
 
 
 def group_by_name(regions):
@@ -182,14 +187,8 @@ def count_groups(eng, groups, pos, ps, stranded=0):
 
 def group_lines(ctg, groups, counted):
     """The TSV lines of one contig under --group_by_name; counted: count_groups' list, or None when nothing was launched."""
-    lines = []
-    for g, (name, strand, merged) in enumerate(groups):
-        head = [ctg, str(merged[0][0]), str(merged[-1][1]), name, strand or ".", str(len(merged)), str(sum(end - start for start, end in merged))]
-        (untagged, other), rows = counted[g] if counted is not None else ((".", "."), [])
-        lines.append("\t".join(head + [".", ".", ".", str(untagged), str(other)]))
-        for ps, h1, h2 in rows:
-            lines.append("\t".join(head + [str(ps), str(h1), str(h2), ".", "."]))
-    return lines
+    return count_lines([[ctg, str(merged[0][0]), str(merged[-1][1]), name, strand or ".", str(len(merged)), str(sum(end - start for start, end in merged))]
+                        for name, strand, merged in groups], counted)
 
 
 def build_parser():

@@ -582,9 +582,10 @@ int c3r_get_haplotag_words(c3r_ctx *ctx, uint32_t *words, int64_t cap);
  * every count is 0 and nothing is launched.  C3R_EINVAL, naming the first bad region or row, for start >= end, start < 0, an unsorted table,
  * a strand above 2, a non-zero reserved byte, a row_off that is not 0 at region 0, decreases or exceeds n_rows, a region of 2^24 rows or
  * more, a negative ps, ps not strictly increasing inside a region, stranded outside 0 .. 2 and a table over the bound.  It uploads regions,
- * first_open and row_ps into buffers of its own, clears one device table of 2 n + 2 n_rows words, runs k_hap_region_counts
+ * first_open and row_ps into buffers that it shares with c3r_hap_group_counts (each call waits for the device before it returns, so
+ * neither call finds the other's table), clears one device table of 2 n + 2 n_rows words, runs k_hap_region_counts
  * (csrc/hapregion_kernels.hpp) on the context's stream and reads the table back.  It changes neither the reads' haplotags and phase sets,
- * nor the phase table, nor anything a scan or another count table reads.  Its device buffers are allocated at the first call and kept.
+ * nor the phase table, nor anything a scan or another count table reads.  The device buffers are allocated at the first call and kept.
  * Not done: no union of a gene's exon rows here (a read over two exons of one gene counts in both: the gene-level count is the rule
  * `hap_groups` below, c3r_hap_group_counts), no fractional assignment of a read that overlaps several regions, no statistics (no test of
  * allelic imbalance); agreement with featureCounts / htseq-count is not measured. */
@@ -617,8 +618,8 @@ int c3r_hap_region_counts(c3r_ctx *ctx, const c3r_hap_region_t *regions, int64_t
  * intervals of one group that overlap, two strands in one group, a group without an interval, a group_row_off that is not 0 at group 0,
  * decreases or exceeds n_rows, a group of 2^24 rows or more, a negative ps, ps not strictly increasing inside a group, stranded outside
  * 0 .. 2 and an interval table over C3R_HAP_REGION_MAX_BACK (the bound of `hap_regions`, on the interval table).  The library computes
- * first_open and, per interval, the previous interval of its group in table order; it uploads them with the rows into buffers of its own,
- * clears one device table of 2 n_groups + 2 n_rows words, runs k_hap_group_counts (csrc/hapgroup_kernels.hpp) on the context's stream and
+ * first_open and, per interval, the previous interval of its group in table order; it uploads them with the rows into the buffers of
+ * c3r_hap_region_counts, clears one device table of 2 n_groups + 2 n_rows words, runs k_hap_group_counts (csrc/hapgroup_kernels.hpp) on the context's stream and
  * reads the table back.  It changes neither the reads' haplotags and phase sets, nor the phase table, nor anything a scan or another count
  * table reads.  Its device buffers are allocated at the first call and kept.
  * c3r_set_hap_group_direct(ctx, on): default 0; anything but 0 or 1 is C3R_EINVAL.  0: the counts of a workgroup's reads are summed in LDS

@@ -1,5 +1,5 @@
 """One compact tour through every device entry point that holds the loaded reads against a site table — the base-quality mask, the
-haplotaggers and their _w siblings, the count tables, the link tables of phasing, region and junction counts — and through row export:
+haplotaggers and their _w siblings, the count tables, the link tables of phasing, region, gene and junction counts — and through row export:
 the inputs and, from the plain-Python restatements under tests/*ref.py, the expected arrays.  No GPU is touched here.
 
 tests/support/hap_tour_worker.py walks the tour on the device (`STOPS` names what it writes, in its order), tests/test_gpu_hap_poison.py
@@ -16,6 +16,7 @@ import numpy as np
 from clair3_rna_amd.reads import ReadSet
 from tests import hapalleleref as HA
 from tests import hapcountref as HC
+from tests import hapgroupref as HG
 from tests import hapindelref as HI
 from tests import hapjunctionref as HJ
 from tests import hapref
@@ -43,10 +44,10 @@ CTG = "chr20"
 SIZES = {
     "A": dict(snv=dict(n_reads=260, n_sites=120, n_ps=30), phase=dict(n_reads=203, n_sites=1400), frag=dict(n_reads=203),
               plain=dict(n_reads=203, n_snv=100, n_indel=30, n_two=8), la=dict(n_reads=203, n_snv=80, n_indel=24, n_two=5),
-              ra=dict(n_reads=150, step=15), rs=dict(n_reads=150, step=15), regions=1, rows=(1, 1500)),
+              ra=dict(n_reads=150, step=15), rs=dict(n_reads=150, step=15), regions=1, groups=9, rows=(1, 1500)),
     "B": dict(snv=dict(n_reads=90, n_sites=60, n_ps=12), phase=dict(n_reads=83, n_sites=70), frag=dict(n_reads=83, run=4),
               plain=dict(n_reads=83, n_snv=60, n_indel=16, n_two=4), la=dict(n_reads=83, n_snv=50, n_indel=12, n_two=3),
-              ra=dict(n_reads=70, step=30), rs=dict(n_reads=70, step=30), regions=2, rows=(1, 700)),
+              ra=dict(n_reads=70, step=30), rs=dict(n_reads=70, step=30), regions=2, groups=5, rows=(1, 700)),
 }
 SEED = {"A": 5, "B": 6}                                      # the generators' seed per set ...
 FUZZ_SEED = {"A": dict(ra=5, rs=4), "B": dict(ra=8, rs=4, plain=4)}      # ... but where another one is needed for tests/test_haptour_ref.py's conditions
@@ -122,7 +123,7 @@ def inputs(which):
         return _cache[("in", which)]
     sz, seed = SIZES[which], SEED[which]
     out = {}
-    # snv: hapref.gen_case (= hapjunctionref.distinct_case) — mask, SNV tags, hap_counts, regions, junctions, rows
+    # snv: hapref.gen_case (= hapjunctionref.distinct_case) — mask, SNV tags, hap_counts, regions, groups, junctions, rows
     ref, rs, table, _ = hapref.gen_case(seed, **sz["snv"])
     plain = with_quals(rs, seed + 100)
     rs = _finish(rs, which, seed + 100)
@@ -132,8 +133,12 @@ def inputs(which):
     regs, row_ps = HR.gen_regions(seed, table)
     keep = [(int(r["start"]), int(r["end"]), int(r["strand"])) for r in regs][::sz["regions"]]
     regs, row_ps = HR.pack(keep, HR.row_table(keep, table))
+    # the gene table: hapgroupref.fuzz_table's triples of exons and five single intervals (nine groups), cut to the first sz["groups"] groups
+    _, gtab, _, _ = HG.fuzz_table(seed, "triples", table, len(ref))
+    ivs = [(int(e["start"]), int(e["end"]), int(e["group"]), int(e["strand"])) for e in gtab if int(e["group"]) < sz["groups"]]
+    gtab, goff, grow_ps = HG.pack(ivs, HG.group_rows(ivs, sz["groups"], table))
     out["snv"] = dict(ref=ref, rs=rs, rs_plain=ragged(plain) if which == "B" else plain, table=table, query=query, regions=regs, row_ps=row_ps,
-                      rows=sz["rows"])
+                      intervals=gtab, n_groups=sz["groups"], group_row_off=goff, group_row_ps=grow_ps, rows=sz["rows"])
     # phase: phaseref.gen_case (= hapjunctionref.shared_case) — phase_links, junctions shared by many reads
     ref, rs, sites, truth, _ = P.gen_case(seed, **sz["phase"])
     jtable = sites.copy()
@@ -212,7 +217,7 @@ def _stops():
     s += [("links", ["k_phase_links"]), ("unit_links", ["k_phase_unit_links"])]
     for f in FORMS:
         s += [("allele_links_" + f, ["k_phase_allele_links" + SUFFIX[f]]), ("allele_unit_links_" + f, ["k_phase_allele_unit_links" + SUFFIX[f]])]
-    s.append(("regions", ["k_hap_region_counts"]))
+    s += [("regions", ["k_hap_region_counts"]), ("groups", ["k_hap_group_counts"])]
     for d in ("snv", "phase"):
         s += [("junctions_%s_lds" % d, ["k_hap_junction_counts"]), ("junctions_%s_direct" % d, ["k_hap_junction_counts_direct"])]
     s.append(("junctions_bare", ["k_hap_junction_counts"]))
@@ -283,6 +288,8 @@ def expected(which):
     for s in STRANDED:
         reg, row = HR.counts(rs, table, snv["regions"], snv["row_ps"], s)
         put("regions", {"region%d" % s: reg, "row%d" % s: row})
+        grp, row = HG.counts(rs, table, snv["intervals"], snv["n_groups"], snv["group_row_off"], snv["group_row_ps"], s)
+        put("groups", {"group%d" % s: grp, "row%d" % s: row})
     for name in ("snv", "phase"):
         fields = _junction_fields(HJ.counts(d[name]["rs"], d[name]["table"]))
         put("junctions_%s_lds" % name, fields)

@@ -20,6 +20,7 @@ def reset(e):
     e.set_hap_left_align(False)
     e.set_hap_min_bq(0)
     e.set_hap_junction_direct(False)
+    e.set_hap_group_direct(False)
     e.set_bed(0, None)
     e.set_bed(1, None)
     e.params = capi.default_params()
@@ -116,13 +117,19 @@ def tour(e, which, out, prefix):
         switch_on(e, f, a["ref"])
         e.load_reads(a["rs"])
         assert stop(dict(ulinks=e.phase_allele_unit_links(qu, uh1, pool))) == "allele_unit_links_" + f
-    # f. regions and junctions
+    # f. regions, groups and junctions
     e.load_reads(rs)
     e.set_phase_sites(table)
     fields = {}
     for s in T.STRANDED:
         fields["region%d" % s], fields["row%d" % s] = e.hap_region_counts(snv["regions"], snv["row_ps"], s)
     assert stop(fields) == "regions"
+    e.load_reads(rs)
+    e.set_phase_sites(table)
+    fields = {}
+    for s in T.STRANDED:
+        fields["group%d" % s], fields["row%d" % s] = e.hap_group_counts(snv["intervals"], snv["n_groups"], snv["group_row_off"], snv["group_row_ps"], s)
+    assert stop(fields) == "groups"
     for name in ("snv", "phase"):
         for direct in (False, True):
             e.load_reads(d[name]["rs"])

@@ -1,7 +1,7 @@
 """Uninitialised and stale device memory under the haplotype kernels and row export.  C3R_POISON=<byte> fills every FRESH allocation of
 libc3r (tests/test_gpu_poison.py); a buffer that a larger earlier call filled is neither fresh nor poisoned — it holds that call's data, and
 the drivers work exactly so: one context, contig after contig, large then small.  Both are covered here by one tour (tests/haptour.py)
-through the mask, every tagger and its _w sibling, the count tables, the link tables in their four observation forms, region and junction
+through the mask, every tagger and its _w sibling, the count tables, the link tables in their four observation forms, region, gene and junction
 counts (the tables grown from their smallest size) and row export, walked by a child process (tests/support/hap_tour_worker.py) per fill
 byte: context 1 runs set A, then the smaller set B; context 2 runs B alone.
 

@@ -226,6 +226,31 @@ def test_the_call_leaves_tags_sets_count_tables_and_a_scan_alone(eng):
     assert sum(int(x.sum()) for x in eng.hap_group_counts(c2["tab"], c2["n_groups"], c2["off"], c2["row_ps"])) == 0
 
 
+def test_region_and_group_calls_alternate_on_their_shared_buffers(eng):
+    """c3r_hap_region_counts and c3r_hap_group_counts upload into one set of device buffers.  On one engine and one loaded read set: a region
+    call on table A, a group call on a smaller table B — behind which A's entries, first_open, rows and counts still lie —, then A again;
+    each equals its restatement.  17 reads (a workgroup's 16 and one), every third through the serial walk."""
+    rs = _forced_serial(_readset([(100 + 2 * k, "10M40N10M", "ACG"[k % 3] * 20, 16 * (k % 4 == 0)) for k in range(17)]), 3)
+    table = hapref.make_sites([(105, "A", "C", 0, 1), (120, "A", "C", 1, 2), (158, "A", "C", 0, 3), (175, "A", "C", 0, 4), (186, "A", "C", 1, 5)])
+    regs = [(90, 105, 0), (100, 112, 1), (104, 130, 2), (110, 111, 0), (118, 150, 0), (125, 190, 1), (140, 156, 0), (150, 165, 2), (155, 158, 0), (160, 180, 0),
+            (170, 200, 1), (185, 186, 0)]
+    a_tab, a_rows = HR.pack(regs, HR.row_table(regs, table))
+    ivs = [(100, 110, 0, 1), (120, 135, 1, 2), (150, 160, 0, 1), (175, 192, 1, 2)]      # read 0 covers [100, 110) and [150, 160): both intervals of group 0
+    b_tab, b_off, b_rows = HG.pack(ivs, HG.group_rows(ivs, 2, table))
+    assert len(a_tab) == 12 and len(b_tab) < len(a_tab) and 0 < len(b_rows) < len(a_rows)
+    detail = {}
+    want_a = HR.counts(rs, table, a_tab, a_rows, 1)
+    want_b = HG.counts(rs, table, b_tab, 2, b_off, b_rows, 1, detail=detail)
+    assert detail["multi_interval_pairs"] >= 1 and all(int(w.sum()) > 0 for w in want_a + want_b)
+    eng.set_phase_sites(table)
+    eng.load_reads(rs)
+    for direct in (False, True):
+        eng.set_hap_group_direct(direct)
+        _same(eng.hap_region_counts(a_tab, a_rows, 1), want_a)
+        _same(eng.hap_group_counts(b_tab, 2, b_off, b_rows, 1), want_b)
+        _same(eng.hap_region_counts(a_tab, a_rows, 1), want_a)
+
+
 def test_no_intervals_no_reads_and_no_table(eng):
     from clair3_rna_amd import capi
     from clair3_rna_amd.reads import ReadSet

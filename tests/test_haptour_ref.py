@@ -48,7 +48,8 @@ def test_b_is_strictly_smaller_than_a_in_everything_a_buffer_is_sized_by():
         print("%s: inserted-base pool bytes A %d, B %d; units A %d, B %d" % (f, pools[0], pools[1], units[0], units[1]))
         assert pools[1] < pools[0] and pools[1] > 0 and units[1] < units[0]       # plain 37 / 6, la 31 / 12, ra 6 / 4, rs 10 / 4; units 46 / 27, 37 / 22, 8 / 4, 8 / 4
     other = dict(query=[len(d["snv"]["query"]) for d in (a, b)], regions=[len(d["snv"]["regions"]) for d in (a, b)],
-                 region_rows=[len(d["snv"]["row_ps"]) for d in (a, b)], chain_units=[len(T.expected(w)["unit_links/ulinks"]) for w in SETS],
+                 region_rows=[len(d["snv"]["row_ps"]) for d in (a, b)], group_intervals=[len(d["snv"]["intervals"]) for d in (a, b)],
+                 groups=[d["snv"]["n_groups"] for d in (a, b)], group_rows=[len(d["snv"]["group_row_ps"]) for d in (a, b)], chain_units=[len(T.expected(w)["unit_links/ulinks"]) for w in SETS],
                  junctions_snv=[len(_junctions(w, "snv")) for w in SETS], junctions_phase=[len(_junctions(w, "phase")) for w in SETS],
                  junction_rows_snv=[sum(len(e["rows"]) for e in _junctions(w, "snv").values()) for w in SETS],
                  candidate_rows=[len(T.oracle_rows(w)[0]) for w in SETS], scan_end=[T.inputs(w)["snv"]["rows"][1] for w in SETS])
@@ -125,6 +126,21 @@ def test_every_count_column_and_row_cis_and_trans(which):
         print(which, "stranded", s, "region columns", reg.sum(axis=0).tolist(), "row columns", row.sum(axis=0).tolist())
         assert reg.sum(axis=0).min() >= 5 and row.sum(axis=0).min() >= 50      # the least: A regions [24, 1342], B rows [141, 115]
     assert not np.array_equal(e["regions/region0"], e["regions/region1"]) and not np.array_equal(e["regions/row1"], e["regions/row2"])
+    for s in T.STRANDED:
+        grp, row = e["groups/group%d" % s], e["groups/row%d" % s]
+        print(which, "stranded", s, "group columns", grp.sum(axis=0).tolist(), "row columns", row.sum(axis=0).tolist())
+        assert grp.sum(axis=0).min() >= 1 and row.sum(axis=0).min() >= 1       # all four kinds of count word occur; the least: B stranded 1 groups [8, 49]
+    assert not np.array_equal(e["groups/group0"], e["groups/group1"]) and not np.array_equal(e["groups/row1"], e["groups/row2"])
+
+
+def test_the_group_tables_of_a_and_b_differ():
+    """What the groups stop of B finds behind its own table in the shared buffers is A's, and A's is something else."""
+    a, b = T.expected("A"), T.expected("B")
+    for s in T.STRANDED:
+        for k in ("groups/group%d" % s, "groups/row%d" % s):
+            n = min(len(a[k]), len(b[k]))
+            print(k, "A", a[k].shape, int(a[k].sum()), "B", b[k].shape, int(b[k].sum()))
+            assert len(b[k]) < len(a[k]) and a[k].sum() > 0 and b[k].sum() > 0 and not np.array_equal(a[k][:n], b[k][:n])
 
 
 def test_a_read_of_a_takes_a_second_window_of_the_link_kernels():
